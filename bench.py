@@ -579,6 +579,35 @@ def _timed(runner, eng, steps, dist, torch):
     return el
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(eng, out_dir, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step -- svils_get_state's gamma,
+    lambda and converged flags, and the held-out likelihood row of the last sweep -- as DIR/<name>.npy (float64; the
+    0/1 flags as float32).  At most `budget` bytes in all: a gamma larger than what is left keeps a fixed, seeded
+    sample of its rows (gamma_rows.npy holds their indices), so that two builds given the same arguments can be
+    compared array by array.  -> {name: shape}"""
+    import numpy as np
+    g, lam, conv = eng.state()
+    arrays = {"lambda": lam.astype(np.float64), "converged": (conv > 0).astype(np.float32)}
+    nrows = int(eng.control().rows)
+    if nrows:
+        arrays["heldout_row"] = eng.rows(nrows - 1, 1)[0]
+    left = budget - 4096 - sum(a.nbytes for a in arrays.values())     # (the .npy headers)
+    if g.nbytes <= left:
+        arrays["gamma"] = g
+    else:
+        keep = max(1, left // (g.shape[1] * 8 + 8))     # a row of gamma + its index
+        idx = np.sort(np.random.default_rng(20240517).choice(g.shape[0], size=min(keep, g.shape[0]), replace=False))
+        arrays["gamma"] = np.ascontiguousarray(g[idx])
+        arrays["gamma_rows"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def _spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: this process (which has not touched HIP or torch) becomes the
     launcher -- N children of the same command line, one per GPU, with the environment torch.distributed.run would
@@ -666,6 +695,9 @@ def main():
     ap.add_argument("--test-one-gpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-cli", action="store_true", help="N=1: skip the cli_end_to_end record (three runs of the svinet binary to its stop rule, ~5 s)")
     ap.add_argument("--cli-only", action="store_true", help="print the cli_end_to_end record alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what their last step computed (gamma, lambda, converged flags, held-out "
+                         "row; rank 0's replica for N > 1) as DIR/<name>.npy, at most 64 MB (a seeded row sample of a larger gamma)")
     ap.add_argument("--main-timeout", type=int, default=420,
                     help="N>1: seconds the communicator set-up + warm-up + timed sweeps may take before rank 0 prints "
                          "an error line and every rank exits")
@@ -818,6 +850,9 @@ def main():
         main_done.set()
     assert ctrl.sweeps_done >= args.warmup + args.steps, "sweeps were skipped"
     first_window_ms = elapsed / args.steps * 1e3
+    dumped = None
+    if multi and rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(eng, args.dump_outputs)     # rank 0's replica after the last repetition of the window
 
     same_window = None
     exch = None
@@ -830,6 +865,8 @@ def main():
             import numpy as np
             elapsed = float(np.median(np.asarray(times)))
             ctrl = eng.control()
+        if args.dump_outputs:
+            dumped = dump_outputs(eng, args.dump_outputs)     # the state after the last timed window, before the event pass
         # event pass of its own over the same window: every `period`-th sweep launches eagerly between hipEvents
         _reseed(eng, setup)
         eng.sweep(args.warmup)
@@ -925,6 +962,8 @@ def main():
             out["value_definition"] = ("median over %d repetitions of the timed window (each: exactly %d sweeps from the re-seeded "
                                        "state after %d warm-up sweeps, device sync on both sides, hipGraph replay, no events); "
                                        "first_window_ms_per_step is the single first window" % (repeat["reps"], args.steps, args.warmup))
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if args.test_one_gpu:
             out["test_mode"] = "all ranks on GPU 0 over the tests' transport: a code-path check, not a measurement"
         roof = {"bound": "hbm", "kernel": "k_phi_lpl (phi pass, A6)" if k <= 56 else "k_phi (phi pass, A6)"}

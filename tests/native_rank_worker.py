@@ -1,6 +1,7 @@
 """worker of tests/test_gpu_native_ranks.py -- ONE RANK of the library's own multi-rank drivers
 (svils_comm_init + svils_sweep_sharded / svils_step_sharded / svils_sweep_ksharded: the collectives are issued
-inside libsvils on the engine's stream).  Every rank is a separate process on GPU 0; the transport is
+inside libsvils on the engine's stream).  Every rank is a separate process, on GPU 0 or on a GPU of its own
+(NATIVE_RANK_DEVICE, set by the test); the transport is
 tests/fakerccl (SVILS_RCCL_LIBRARY, set by the test), because RCCL refuses two ranks on one device.  No
 torch.distributed here: the ranks only share the 128-byte communicator id, which rank 0 leaves in a file.
 
@@ -39,6 +40,7 @@ def comm_id(out, rank):
 def main():
     path, n, k, count, out = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
     rank, world, mode = int(sys.argv[6]), int(sys.argv[7]), sys.argv[8]
+    device = int(os.environ.get("NATIVE_RANK_DEVICE", "0"))     # the test's placement: GPU 0, or one GPU per rank
     assert os.environ.get("SVILS_RCCL_LIBRARY"), "the test names the transport"
     from svinet_amd import _svils
     from svinet_amd.host_api import Setup
@@ -49,7 +51,7 @@ def main():
         from svinet_amd.ksharded import column_slices
         k0, k1 = column_slices(k, world)[rank]
         eng = _svils.Engine(setup.n, setup.k, ones=setup.ones, ones_prob=setup.ones_prob, eta=setup.eta,
-                            link_thresh=setup.link_thresh, lt_min_deg=setup.lt_min_deg, device=0, k_slice=(k0, k1),
+                            link_thresh=setup.link_thresh, lt_min_deg=setup.lt_min_deg, device=device, k_slice=(k0, k1),
                             use_validation_stop=False)
         eng.set_graph(setup.links)
         eng.set_validation(setup.validation_sorted)
@@ -77,10 +79,10 @@ def main():
     else:
         B = block_size(n, world)
         if mode.startswith("step") or mode == "sweep-equal":   # mini-batch steps need the equal blocks svils_comm_init assumes
-            eng = setup.engine(device=0, node_block=node_block(n, world, rank), n_alloc=B * world, use_validation_stop=False)
+            eng = setup.engine(device=device, node_block=node_block(n, world, rank), n_alloc=B * world, use_validation_stop=False)
         else:                                                   # whole sweeps: the work-balanced blocks, declared before the communicator
             bounds = balanced_bounds(setup.links, n, world)
-            eng = setup.engine(device=0, node_block=(int(bounds[rank]), int(bounds[rank + 1])), use_validation_stop=(mode == "sweep-stop"))
+            eng = setup.engine(device=device, node_block=(int(bounds[rank]), int(bounds[rank + 1])), use_validation_stop=(mode == "sweep-stop"))
             eng.set_node_blocks(rank, world, bounds)
             extra_bounds = bounds
         eng.comm_init(comm_id(out, rank), rank, world)
@@ -106,7 +108,7 @@ def main():
         extra = dict(mphi=eng.aux(2), **early)
     eng.synchronize()
     ci = eng.comm_query()
-    assert ci["rank"] == rank and ci["nranks"] == world and ci["hip_device"] == 0
+    assert ci["rank"] == rank and ci["nranks"] == world and ci["hip_device"] == device
     extra.update(row_comm=ci["row_communicator"], comm_nranks=ci["nranks"])
     g, lam, conv = eng.state()
     c = eng.control()

@@ -9,6 +9,9 @@ the same kernels and layouts) against the oracle running live.
 """
 import numpy as np
 import pytest
+import torch  # noqa: F401  (the skip condition of one_rank_per_gpu)
+
+from test_gpu_native_ranks import one_rank_per_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -298,17 +301,13 @@ def test_hbm_bound_sweep_against_oracle(hbm_bound):
     eng.close()
 
 
-def test_hbm_bound_eight_node_blocks_chunked_exchange_against_oracle(hbm_bound, tmp_path):
-    """The node-block form of an HBM-bound K = 512 run as eight GPUs execute it: EIGHT native ranks (processes on this one
-    GPU over the tests' transport) on work-balanced blocks, the row exchange FORCED into its pipelined form (option xchunks:
-    chunks of every block on the communication stream and a second communicator, each expanded while the next travels --
-    the form config 5's 4.1 GB payload takes by itself) -- every rank's replicated state against the live oracle."""
+def _hbm_bound_node_blocks_chunked_exchange(hbm_bound, tmp_path, world):
     import test_gpu_native_ranks as T
     n, k, nsweeps, pairs, s, ref = hbm_bound
     path = str(tmp_path / "mmsb_n100k.txt")
     with open(path, "w") as f:
         f.write("".join("%d\t%d\n" % (a, b) for a, b in np.asarray(pairs).tolist()))
-    world, chunks = 8, 3
+    chunks = 3
     states, (calls, ncomm) = T._run_ranks(tmp_path, path, n, k, nsweeps, world, "sweep", {"SVILS_XCHUNKS": str(chunks)})
     for st in states:
         assert np.max(np.abs(st["gamma"] - ref.gamma) / ref.gamma) < 1e-9
@@ -321,6 +320,21 @@ def test_hbm_bound_eight_node_blocks_chunked_exchange_against_oracle(hbm_bound, 
     assert np.array_equal(states[0]["member"], ref.communities())
     # per sweep: all-reduce(sum) + chunks x world broadcasts + all-reduce(s1,s2,s3); + the tag gather and the second communicator's id
     assert ncomm == 2 and calls == (2 + chunks * world) * nsweeps + world + 1
+
+
+@one_rank_per_gpu(8)
+def test_hbm_bound_eight_node_blocks_chunked_exchange_against_oracle(hbm_bound, tmp_path):
+    """The node-block form of an HBM-bound K = 512 run as eight GPUs execute it: EIGHT native ranks (processes, one GPU each,
+    over the tests' transport) on work-balanced blocks, the row exchange FORCED into its pipelined form (option xchunks:
+    chunks of every block on the communication stream and a second communicator, each expanded while the next travels --
+    the form config 5's 4.1 GB payload takes by itself) -- every rank's replicated state against the live oracle."""
+    _hbm_bound_node_blocks_chunked_exchange(hbm_bound, tmp_path, 8)
+
+
+def test_hbm_bound_five_node_blocks_chunked_exchange_against_oracle(hbm_bound, tmp_path):
+    """The same on ONE GPU: five native ranks sharing it (with the pytest process, the six processes a test machine lets
+    hold a GPU at once)."""
+    _hbm_bound_node_blocks_chunked_exchange(hbm_bound, tmp_path, 5)
 
 
 @pytest.mark.parametrize("k", [20, 28])

@@ -12,7 +12,10 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("graph,world,k,sweeps", [("lfr", 2, 28, 70), ("lfr", 4, 100, 6), ("lfr", 3, 130, 5),
                                                    ("astroph", 4, 200, 3), ("lfr", 7, 28, 20),   # slices of <= 64 columns (down to 4): k_phi_ksh16
                                                    ("astroph", 2, 200, 3), ("lfr", 2, 300, 30),   # 100 / 150 columns: k_phi_ksh<2>, <4>
-                                                   ("lfr", 2, 600, 4)])         # 300 columns: k_phi_ksh<8>
+                                                   ("lfr", 2, 600, 4),          # 300 columns: k_phi_ksh<8>
+                                                   # eight K-shards in one process: slices of 3 and 4 columns, and BASELINE config 4
+                                                   # in its 8-GPU layout (ca-AstroPh, slices of 25 columns)
+                                                   ("lfr", 8, 28, 35), ("astroph", 8, 200, 3)])
 def test_ksharded_virtual_ranks_equal_oracle(graph_files, graph, world, k, sweeps):
     from svinet_amd.host_api import Setup
     from svinet_amd.ksharded import KShard, init_virtual, sweep_virtual

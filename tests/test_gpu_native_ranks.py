@@ -15,6 +15,7 @@ import sys
 
 import numpy as np
 import pytest
+import torch  # noqa: F401  (the skip condition of one_rank_per_gpu)
 
 from oracle import oracle as O
 
@@ -24,6 +25,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 FAKE = os.path.join(HERE, "fakerccl", "libfakerccl.so")
 SVINET = os.path.join(ROOT, "svinet_amd", "bin", "svinet")
+
+
+# A GPU test machine lets six processes hold a GPU at once (a run of the GPU tier with eight rank processes beside pytest was
+# stopped at nine: profiles/r08a_gpu_tier_process_limit.txt).  So a run of up to five ranks shares GPU 0; a larger world is the
+# multi-GPU layout itself -- one rank per GPU -- and needs that many GPUs.  The arithmetic of the eight-way layouts is held
+# against the oracle on one GPU by the virtual ranks of tests/test_gpu_sharded.py and tests/test_gpu_ksharded.py.
+MAX_RANKS_ONE_GPU = 5
+
+
+def one_rank_per_gpu(world):
+    """mark of a case whose `world` ranks run on a GPU each (world > MAX_RANKS_ONE_GPU): skipped where fewer GPUs are present.
+    The condition is evaluated when the test is set up, before its fixtures (the module needs `torch` in its globals)."""
+    return pytest.mark.skipif("torch.cuda.device_count() < %d" % world,
+                              reason="needs %d GPUs, one per rank: %d rank processes cannot share one GPU beside the test process"
+                                     % (world, world))
 
 
 def _env(tmp_path=None, sync=False):
@@ -64,8 +80,11 @@ def _run_ranks(tmp_path, path, n, k, count, world, mode, extra_env=None, sync=Fa
     worker = os.path.join(HERE, "native_rank_worker.py")
     env = _env(tmp_path, sync=sync)
     env.update(extra_env or {})
-    procs = [subprocess.Popen([sys.executable, worker, path, str(n), str(k), str(count), out, str(r), str(world), mode],
-                              env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(world)]
+    procs = []
+    for r in range(world):
+        env_r = dict(env, NATIVE_RANK_DEVICE=str(r if world > MAX_RANKS_ONE_GPU else 0))
+        procs.append(subprocess.Popen([sys.executable, worker, path, str(n), str(k), str(count), out, str(r), str(world), mode],
+                                      env=env_r, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     errs = []
     for p in procs:
         try:
@@ -123,13 +142,16 @@ def _check_node_block(states, ref, n, world, tags=True):
                                                                ("lfr", 3, 28, 35, 3, False), ("lfr", 2, 100, 8, 5, False), ("astroph", 3, 200, 3, 4, False),
                                                                # and once each on the synchronous transport
                                                                ("lfr", 2, 28, 40, 1, True), ("lfr", 3, 28, 35, 3, True),
-                                                               # the world sizes the driver's scaling run uses (2, 4, 8): four and
-                                                               # eight node blocks, the headline graph at its own K on eight
-                                                               ("lfr", 4, 28, 35, 1, False), ("lfr", 8, 28, 35, 3, False),
-                                                               ("astroph", 8, 20, 6, 1, False), ("astroph", 4, 200, 3, 2, False),
+                                                               # more node blocks than the cases above: four and five (every rank is a
+                                                               # process with the GPU open, and the test machines allow six such
+                                                               # processes at once, this one included), the headline graph at its own K
+                                                               ("lfr", 4, 28, 35, 1, False), ("lfr", 5, 28, 35, 3, False),
+                                                               ("astroph", 5, 20, 6, 1, False), ("astroph", 4, 200, 3, 2, False),
                                                                # BASELINE config 4 as its 8-GPU run executes it: ca-AstroPh K = 200 on
-                                                               # eight balanced node blocks (exact-count row exchange: 8 x bmax = 3.0 n)
-                                                               ("astroph", 8, 200, 3, 2, False)])
+                                                               # eight balanced node blocks, one GPU per rank (exact-count row exchange:
+                                                               # 8 x bmax = 3.0 n) -- and on five blocks sharing one GPU (2.5 n)
+                                                               pytest.param("astroph", 8, 200, 3, 2, False, marks=one_rank_per_gpu(8)),
+                                                               ("astroph", 5, 200, 3, 2, False)])
 def test_native_sweep_sharded_ranks(graph_files, tmp_path, graph, world, k, sweeps, chunks, sync):
     """svils_sweep_sharded in `world` processes on WORK-BALANCED node blocks (svils_balance_node_blocks: blocks of
     different sizes): per sweep one grouped {all-reduce of sum[k], in-place all-gather of the staged rows padded to the
@@ -240,10 +262,13 @@ def test_native_step_sharded_windows(graph_files, tmp_path, world):
 
 @pytest.mark.parametrize("world,k,sweeps,mode", [(2, 28, 40, "kshard"), (3, 100, 6, "kshard"), (3, 130, 5, "kshard-log"),
                                                   (2, 28, 40, "kshard-log"), (3, 28, 30, "kshard-lowt"),
-                                                  # four and eight column slices (K = 28 on eight ranks: slices of 3 and 4 columns)
-                                                  (4, 28, 35, "kshard"), (8, 28, 35, "kshard"), (8, 200, 4, "kshard"),
-                                                  # BASELINE config 4 K-sharded over eight ranks: ca-AstroPh, slices of 25 columns
-                                                  (8, 200, 3, "kshard-astroph")])
+                                                  # four and five column slices (K = 28 on five ranks: slices of 5 and 6 columns;
+                                                  # five ranks: see test_native_sweep_sharded_ranks)
+                                                  (4, 28, 35, "kshard"), (5, 28, 35, "kshard"), (5, 200, 4, "kshard"),
+                                                  # BASELINE config 4 K-sharded over eight ranks, one GPU each (ca-AstroPh, slices
+                                                  # of 25 columns), and over five ranks sharing one GPU (slices of 40 columns)
+                                                  pytest.param(8, 200, 3, "kshard-astroph", marks=one_rank_per_gpu(8)),
+                                                  (5, 200, 3, "kshard-astroph")])
 def test_native_sweep_ksharded_ranks(graph_files, tmp_path, world, k, sweeps, mode):
     """svils_ksh_init_state + svils_sweep_ksharded in `world` processes (uneven slices at K=100/3, 130/3): the column
     slices put together equal the oracle, flags / rows / counters replicated; svils_validation_row and

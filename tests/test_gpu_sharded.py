@@ -21,6 +21,7 @@ def _exchange_sum(ts):
 @pytest.mark.parametrize("graph,world,k,sweeps,balanced", [("lfr", 2, 28, 70, True), ("lfr", 3, 28, 12, True), ("lfr", 2, 100, 5, True),
                                                             ("astroph", 4, 200, 3, True),   # BASELINE config 4's shape, sharded
                                                             ("astroph", 8, 20, 8, True),    # the headline graph on eight work-balanced blocks
+                                                            ("astroph", 8, 200, 3, True),   # BASELINE config 4 in its 8-GPU layout, in one process
                                                             ("lfr", 3, 28, 12, False)])     # equal blocks (s3 by node block)
 def test_virtual_ranks_equal_oracle(graph_files, graph, world, k, sweeps, balanced):
     import torch
