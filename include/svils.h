@@ -38,7 +38,8 @@ extern "C" {
                                  7: k up to SVILS_MAX_K_TOTAL (column-tiled handles above SVILS_MAX_K; K-sharded k_total up to it),
                                     getters that do not wait behind a stop the caller has seen ("After the stop");
                                  8: svils_init_gamma (init_gamma2 on the device); svils_set_option / svils_get_option / svils_option_table (every tunable in one documented table; nothing
-                                    on a sweep path reads the environment); svils_gather_communities ends the no-wait window of "After the stop" */
+                                    on a sweep path reads the environment); svils_gather_communities ends the no-wait window of "After the stop";
+                                    (additive, same version) svils_link_prob / svils_predict_links: link prediction from the state */
 
 typedef enum {
   SVILS_OK = 0,
@@ -292,6 +293,33 @@ int svils_get_community_tags(svils_handle *h, uint32_t *tags, uint64_t cap, uint
  * which = 0 Elogpi [n][k], 1 Elogbeta [k][2], 2 mphi [n][k],
  *         3 active_comms [n] (uint32), 4 training_links [n] (double). */
 int svils_get_aux(svils_handle *h, int which, void *out);
+
+/* ---- link prediction from the current state (an ADDITION of ABI 8; nothing on the sweep path changes) --------------------
+ * link_prob(p, q) = sum_z pi_pz pi_qz beta_z, the reference's LinkSampling::link_prob (src/linksampling.hh:240-256) with
+ * pi_p = gamma_p / sum_k gamma_pk (estimate_pi, :205-214) and beta_z = lambda_z0 / (lambda_z0 + lambda_z1)
+ * (estimate_bernoulli_rate, :217-225; gsl_ran_bernoulli_pdf(1, u) = u).  The reference wires this quantity only to dead code:
+ * auc() / biased_auc() / uniform_auc() (src/linksampling.cc:855-877, 1185-1226) sit behind create_test_precision_sets, which
+ * its main.cc never sets, and behind load_test_sets(), which nothing calls.  For y = 1 the held-out likelihood already uses it:
+ * edge_likelihood (:259-294) is log(max(link_prob, 1e-30)).
+ * Both calls enqueue on the handle's stream behind the sweeps already enqueued and synchronise before returning; they read
+ * gamma, lambda and the training CSR and write nothing a sweep reads (a handle whose stop rule has fired and a mini-batch
+ * handle between steps work the same way).  Device scratch is allocated on first use and freed by svils_destroy: at most
+ * ~0.5 GB (queries go through in internal batches of 8192: 384 MB of partial top-k heaps, 64 MB of query rows, 24 MB of
+ * results; pairs in batches of 2^20: 24 MB) plus 8 bytes per node and 4 bytes per CSR entry (a copy of the training CSR
+ * with every row sorted, built on first use; the graph of a handle never changes).  Results are bitwise deterministic, and
+ * a query's row does not depend on which other nodes are in the same call.
+ * SVILS_ERR_ARG: no graph or state, a node id >= n, a pair with p == q, topk == 0 or > SVILS_PREDICT_MAX_TOPK.
+ * SVILS_ERR_UNSUPPORTED: column-tiled handles (k > SVILS_MAX_K), K-sharded handles (k_total != 0), node-block handles. */
+#define SVILS_PREDICT_MAX_TOPK 256
+/* link_prob of pairs[npairs][2] (p != q, both < n) -> prob[npairs], in the reference's order of operations */
+int svils_link_prob(svils_handle *h, const uint32_t *pairs, uint64_t npairs, double *prob);
+/* The top-k links of each query node: nodes[nnodes] (NULL = all n nodes; nnodes is then 0 or n) -> ids[nnodes][topk],
+ * scores[nnodes][topk].  Candidates of p: every node except p itself and p's training neighbours (held-out pairs ARE
+ * candidates: finding them is the point).  Order: score descending, ties by ascending node id.  A node with fewer than topk
+ * candidates has its remaining slots filled with id UINT32_MAX and score -1.0.  The scores are link_prob computed as
+ * (sum_z (gamma_pz / sum gamma_p) beta_z gamma_qz) / sum gamma_q on the matrix cores (fp64), within a few ulps of
+ * svils_link_prob's. */
+int svils_predict_links(svils_handle *h, const uint32_t *nodes, uint32_t nnodes, uint32_t topk, uint32_t *ids, double *scores);
 
 /* Evaluate the kernels' own special functions on a plain array (unit tests):
  * which = 0 digamma(x) [stands for gsl_sf_psi], 1 exp(x) for x <= 0, 2 1/x, 3 ln(x) for x >= 1. */

@@ -34,7 +34,9 @@ EXPORTS = (
     "svils_report_tag_count", "svils_report_fetch_tags", "svils_get_community_tags",
     "svils_set_node_blocks", "svils_balance_node_blocks", "svils_prepare_graphs",
     "svils_set_option", "svils_get_option", "svils_option_table", "svils_init_gamma",
+    "svils_link_prob", "svils_predict_links",
 )
+PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
 
 
 class SvilsError(RuntimeError):
@@ -149,6 +151,8 @@ def load():
     L.svils_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]
     L.svils_get_option.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t]
     L.svils_option_table.restype = C.c_char_p
+    L.svils_link_prob.argtypes = [vp, vp, C.c_uint64, vp]
+    L.svils_predict_links.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):
@@ -382,6 +386,27 @@ class Engine:
         out = np.zeros(shape, dtype=dt)
         _chk(load().svils_get_aux(self._h, which, out.ctypes.data))
         return out
+
+    def link_prob(self, pairs):
+        """link_prob (src/linksampling.hh:240-256) of node pairs [m][2] (p != q) -> float64[m] (svils_link_prob)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        out = np.zeros(pairs.shape[0], dtype=np.float64)
+        _chk(load().svils_link_prob(self._h, pairs.ctypes.data, pairs.shape[0], out.ctypes.data))
+        return out
+
+    def predict_links(self, topk, nodes=None):
+        """the top-k candidate links of each query node (all nodes when None) -> (ids uint32[nq, topk], scores float64[nq, topk]);
+        score descending, ties by ascending id; missing candidates are id 0xffffffff, score -1 (svils_predict_links)"""
+        if nodes is None:
+            nq, ptr = self.n, None
+        else:
+            nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1)
+            nq, ptr = nodes.shape[0], nodes.ctypes.data
+        ids = np.zeros((nq, max(int(topk), 1)), dtype=np.uint32)
+        scores = np.zeros((nq, max(int(topk), 1)), dtype=np.float64)
+        _chk(load().svils_predict_links(self._h, ptr, nq if nodes is not None else 0, int(topk), ids.ctypes.data,
+                                        scores.ctypes.data))
+        return ids, scores
 
     def debug_eval(self, which, x):
         x = np.ascontiguousarray(x, dtype=np.float64)

@@ -140,6 +140,24 @@ struct svils_handle {
   uint32_t *t_pairs = nullptr;
   double *t_uval = nullptr, *t_rows = nullptr;
   uint32_t nt = 0, t_cap = 0;
+  // link prediction (svils_link_prob / svils_predict_links, svils_predict.hip): device scratch allocated on first use and
+  // grown on demand, all of it dalloc()ed (freed by svils_destroy); nothing a sweep reads lives here
+  struct PredictScratch {
+    uint32_t *scol = nullptr;        // [2L] the CSR rows with every row sorted ascending (built once: the graph never changes)
+    double *inv = nullptr;           // [n] 1 / sum_k gamma_pk of the state of the current call
+    double *beta = nullptr;          // [K] lambda_k0 / (lambda_k0 + lambda_k1)
+    uint32_t *pairs = nullptr;       // [pair_cap][2]
+    double *prob = nullptr;          // [pair_cap]
+    uint64_t pair_cap = 0;
+    uint32_t *qnodes = nullptr;      // [q_cap] query nodes of a batch, UINT32_MAX past its end
+    double *aq = nullptr;            // [q_cap][k16] query rows gamma_p / sum gamma_p * beta, zero past column K
+    uint32_t *ids = nullptr;         // [q_cap][topk] results of a batch
+    double *scores = nullptr;
+    uint64_t q_cap = 0, aq_cap = 0, out_cap = 0;
+    double *hs = nullptr;            // per-thread partial top-k heaps of the candidate chunks (scores, ids)
+    uint32_t *hi = nullptr;
+    uint64_t heap_cap = 0;
+  } pred;
   ReportSlot rslot[SVILS_REPORT_SLOTS];
   ReportLayout rlay{};
   hipStream_t copy_stream = nullptr;

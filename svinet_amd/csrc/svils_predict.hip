@@ -1,0 +1,383 @@
+// svils_predict.hip -- link prediction from a fitted state: svils_link_prob (scores of given pairs) and svils_predict_links
+// (the top-k candidate links of query nodes).  The quantity is the reference's LinkSampling::link_prob
+// (src/linksampling.hh:240-256): sum_z pi_pz pi_qz beta_z with pi_p = gamma_p / sum gamma_p (estimate_pi, :205-214) and
+// beta_z = lambda_z0 / (lambda_z0 + lambda_z1) (estimate_bernoulli_rate, :217-225).
+//
+//   k_link_prob     one thread per pair, the reference's order of operations (row sums, pi = gamma / sum, sum of products)
+//   k_rowinv        1 / sum_k gamma_pk of every node (a sequential sum per thread)
+//   k_beta          beta_z
+//   k_build_aq      the query rows of a batch: gamma_p / sum gamma_p * beta, zero-padded to a multiple of 16 columns
+//   k_sort_rows     once per handle: every CSR row sorted ascending (the upper part of a row is in adjacency order)
+//   k_topk_tiles    grid (query tile of 64, candidate chunk): 64 x 64 score tiles from v_mfma_f64_16x16x4_f64, then every
+//                   query's four selector threads keep a top-k heap each over their quarter of the chunk's candidates
+//   k_topk_merge    one block per query: the 4 x chunks heaps sorted together (bitonic, in LDS), the first k kept
+//
+// Read-only: everything here reads gamma, lambda and the CSR, and writes the scratch of svils_handle::pred only.
+#include "svils_handle.h"
+
+namespace {
+
+constexpr uint32_t PQ = 64;               // query rows per tile (four wavefronts of 16)
+constexpr uint32_t PC = 64;               // candidates per tile (four 16-column MFMA blocks per wavefront)
+constexpr uint32_t Q_BATCH = 8192;        // query nodes per internal batch (bounds the scratch, see include/svils.h)
+constexpr uint32_t MERGE_MAX = 4096;      // entries one merge block sorts: 4 selectors x chunks x topk
+constexpr uint64_t PAIR_BATCH = 1u << 20; // pairs per internal batch of svils_link_prob
+constexpr uint32_t NONE = 0xffffffffu;
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void k_link_prob(uint64_t np, uint32_t K, uint32_t ld, const double *__restrict__ gamma,
+                                                   const double *__restrict__ lambda, const uint32_t *__restrict__ pairs,
+                                                   double *__restrict__ prob) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= np) return;
+  const double *gp = gamma + (size_t)pairs[2 * i] * ld, *gq = gamma + (size_t)pairs[2 * i + 1] * ld;
+  double sp = .0, sq = .0;
+  for (uint32_t k = 0; k < K; ++k) sp += gp[k];
+  for (uint32_t k = 0; k < K; ++k) sq += gq[k];
+  double s = .0;
+  for (uint32_t z = 0; z < K; ++z) {
+    const double u = lambda[2 * z] / (.0 + lambda[2 * z] + lambda[2 * z + 1]);
+    s += (gp[z] / sp) * (gq[z] / sq) * u;
+  }
+  prob[i] = s;
+}
+
+__global__ __launch_bounds__(256) void k_rowinv(uint32_t n, uint32_t K, uint32_t ld, const double *__restrict__ gamma,
+                                                double *__restrict__ inv) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  const double *g = gamma + (size_t)p * ld;
+  double s = .0;
+  for (uint32_t k = 0; k < K; ++k) s += g[k];
+  inv[p] = 1.0 / s;
+}
+
+__global__ __launch_bounds__(256) void k_beta(uint32_t K, const double *__restrict__ lambda, double *__restrict__ beta) {
+  const uint32_t z = blockIdx.x * 256 + threadIdx.x;
+  if (z < K) beta[z] = lambda[2 * z] / (.0 + lambda[2 * z] + lambda[2 * z + 1]);
+}
+
+// aq[i][k] for i < rows (a multiple of PQ), k < k16: rows past the batch (qnodes[i] == NONE) and columns past K are zero
+__global__ __launch_bounds__(256) void k_build_aq(uint32_t rows, uint32_t K, uint32_t ld, uint32_t k16, const double *__restrict__ gamma,
+                                                  const double *__restrict__ inv, const double *__restrict__ beta,
+                                                  const uint32_t *__restrict__ qnodes, double *__restrict__ aq) {
+  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (uint64_t)rows * k16) return;
+  const uint32_t i = (uint32_t)(e / k16), k = (uint32_t)(e % k16), p = qnodes[i];
+  aq[e] = (p != NONE && k < K) ? gamma[(size_t)p * ld + k] * inv[p] * beta[k] : 0.0;
+}
+
+// one wavefront per row: every entry's rank in its row (ties by position, so a repeated neighbour keeps both slots)
+__global__ __launch_bounds__(256) void k_sort_rows(uint32_t n, const uint64_t *__restrict__ rowptr, const uint32_t *__restrict__ col,
+                                                   uint32_t *__restrict__ scol) {
+  const uint32_t x = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (x >= n) return;
+  const uint64_t b = rowptr[x];
+  const uint32_t d = (uint32_t)(rowptr[x + 1] - b);
+  for (uint32_t i = lane; i < d; i += 64) {
+    const uint32_t v = col[b + i];
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < d; ++j) {
+      const uint32_t u = col[b + j];
+      r += (u < v || (u == v && j < i)) ? 1u : 0u;
+    }
+    scol[b + r] = v;
+  }
+}
+
+__device__ inline bool in_row(const uint32_t *__restrict__ s, uint64_t b, uint64_t e, uint32_t q) {
+  while (b < e) {
+    const uint64_t m = (b + e) >> 1;
+    const uint32_t v = s[m];
+    if (v == q) return true;
+    if (v < q) b = m + 1; else e = m;
+  }
+  return false;
+}
+
+// (as, ai) ranks below (bs, bi): lower score, or the same score and the higher id
+__device__ inline bool worse(double as, uint32_t ai, double bs, uint32_t bi) { return as < bs || (as == bs && ai > bi); }
+
+// row[col .. col + 3], zero at and past column K (row + col is 16-byte aligned: ld is even, col a multiple of 4)
+__device__ inline void load4(const double *__restrict__ row, uint32_t col, uint32_t K, double *o) {
+  if (col + 3 < K) {
+    const double2 x = *(const double2 *)(row + col), y = *(const double2 *)(row + col + 2);
+    o[0] = x.x; o[1] = x.y; o[2] = y.x; o[3] = y.y;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = col + e < K ? row[col + e] : 0.0;
+  }
+}
+
+// Block (qt, c): query rows [64 qt, 64 qt + 64) of the batch against the candidates of chunk c of nch.  Per tile of 64
+// candidates wavefront w computes the 16 x 64 scores of query rows 16 w .. 16 w + 15 as four 16 x 16 MFMA blocks, K in steps
+// of 4.  Operand map of v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k-slot l >> 4] and B[k-slot l >> 4][col l & 15];
+// the k column behind k-slot g in step s of a 16-column chunk is kc + 4 g + s (both operands use the same map, so every
+// lane reads four consecutive doubles of its row per chunk).  C/D: register r of lane l is row (l >> 4) + 4 r, col l & 15.
+// Selection: thread t serves query row t >> 2 over the candidates t & 3, t & 3 + 4, ... of every tile (ascending ids) with a
+// k-entry heap of its own in global scratch (slot i at stride 256: the block's heaps interleave), worst entry on top; a
+// candidate is looked at further only if it beats that entry.  (Heaps in LDS for k <= 10 measured no faster:
+// profiles/r09a_predict.md.)
+__global__ __launch_bounds__(256) void k_topk_tiles(uint32_t n, uint32_t K, uint32_t ld, uint32_t k16, uint32_t topk, uint32_t nch,
+                                                    const double *__restrict__ gamma, const double *__restrict__ inv,
+                                                    const double *__restrict__ aq, const uint32_t *__restrict__ qnodes,
+                                                    const uint64_t *__restrict__ rowptr, const uint32_t *__restrict__ scol,
+                                                    double *__restrict__ hs, uint32_t *__restrict__ hi) {
+  __shared__ double S[PQ][PC + 1];
+  const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63, g = l >> 4, r16 = l & 15;
+  const uint32_t qt = blockIdx.x, c = blockIdx.y;
+  uint32_t cb, ce;
+  chunk_range(n, c, nch, &cb, &ce);
+  const uint32_t qi = t >> 2, sub = t & 3;
+  const uint32_t p = qnodes[qt * PQ + qi];
+  uint64_t nb = 0, ne = 0;
+  if (p != NONE) { nb = rowptr[p]; ne = rowptr[p + 1]; }
+  const size_t hbase = ((size_t)qt * nch + c) * topk * 256 + t;
+  double *hsc = hs + hbase;
+  uint32_t *hid = hi + hbase;
+  for (uint32_t i = 0; i < topk; ++i) { hsc[(size_t)i * 256] = -1.0; hid[(size_t)i * 256] = NONE; }
+  double worst = -1.0;
+  const double *arow = aq + (size_t)(qt * PQ + 16 * w + r16) * k16;
+  for (uint32_t c0 = cb; c0 < ce; c0 += PC) {
+    d4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
+    for (uint32_t kc = 0; kc < k16; kc += 16) {
+      const uint32_t col = kc + 4 * g;
+      const double2 a01 = *(const double2 *)(arow + col), a23 = *(const double2 *)(arow + col + 2);
+      const double a[4] = {a01.x, a01.y, a23.x, a23.y};
+      double b[4][4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t cand = c0 + 16 * j + r16;
+        if (cand < ce) load4(gamma + (size_t)cand * ld, col, K, b[j]);
+        else b[j][0] = b[j][1] = b[j][2] = b[j][3] = 0.0;
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[j][s], acc[j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t cand = c0 + 16 * j + r16;
+      const double iq = cand < ce ? inv[cand] : 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) S[16 * w + g + 4 * r][16 * j + r16] = acc[j][r] * iq;
+    }
+    __syncthreads();
+    if (p != NONE) {
+      for (uint32_t i = 0; i < PC / 4; ++i) {
+        const uint32_t cc = sub + 4 * i, q = c0 + cc;
+        if (q >= ce) break;
+        const double s = S[qi][cc];
+        if (!(s > worst)) continue;
+        if (q == p || in_row(scol, nb, ne, q)) continue;
+        uint32_t pos = 0;
+        for (;;) {
+          uint32_t ch = 2 * pos + 1;
+          if (ch >= topk) break;
+          double cs = hsc[(size_t)ch * 256];
+          uint32_t ci = hid[(size_t)ch * 256];
+          if (ch + 1 < topk) {
+            const double ds = hsc[(size_t)(ch + 1) * 256];
+            const uint32_t di = hid[(size_t)(ch + 1) * 256];
+            if (worse(ds, di, cs, ci)) { ++ch; cs = ds; ci = di; }
+          }
+          if (!worse(cs, ci, s, q)) break;
+          hsc[(size_t)pos * 256] = cs;
+          hid[(size_t)pos * 256] = ci;
+          pos = ch;
+        }
+        hsc[(size_t)pos * 256] = s;
+        hid[(size_t)pos * 256] = q;
+        worst = hsc[0];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// query row i of the batch: its 4 x nch heaps (L entries, padded to lp = a power of two <= MERGE_MAX with the empty entry
+// (-1, NONE)) sorted best first -- score descending, id ascending -- and the first topk written out
+__global__ __launch_bounds__(256) void k_topk_merge(uint32_t topk, uint32_t nch, uint32_t lp, const double *__restrict__ hs,
+                                                    const uint32_t *__restrict__ hi, double *__restrict__ oscore,
+                                                    uint32_t *__restrict__ oid) {
+  __shared__ double ks[MERGE_MAX];
+  __shared__ uint32_t ki[MERGE_MAX];
+  const uint32_t i = blockIdx.x, qt = i / PQ, qi = i % PQ;
+  const uint32_t L = 4 * nch * topk;
+  for (uint32_t e = threadIdx.x; e < lp; e += 256) {
+    double s = -1.0;
+    uint32_t id = NONE;
+    if (e < L) {
+      const uint32_t c = e / (4 * topk), rem = e % (4 * topk), sub = rem / topk, slot = rem % topk;
+      const size_t idx = (((size_t)qt * nch + c) * topk + slot) * 256 + qi * 4 + sub;
+      s = hs[idx];
+      id = hi[idx];
+    }
+    ks[e] = s;
+    ki[e] = id;
+  }
+  __syncthreads();
+  for (uint32_t size = 2; size <= lp; size <<= 1)
+    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+      for (uint32_t x = threadIdx.x; x < lp / 2; x += 256) {
+        const uint32_t a = 2 * x - (x & (stride - 1)), b = a + stride;
+        const bool up = (a & size) == 0;   // this run ends best first
+        const bool b_better = worse(ks[a], ki[a], ks[b], ki[b]);
+        if (b_better == up) {
+          const double ts = ks[a]; ks[a] = ks[b]; ks[b] = ts;
+          const uint32_t ti = ki[a]; ki[a] = ki[b]; ki[b] = ti;
+        }
+      }
+      __syncthreads();
+    }
+  for (uint32_t j = threadIdx.x; j < topk; j += 256) {
+    oscore[(size_t)i * topk + j] = ks[j];
+    oid[(size_t)i * topk + j] = ki[j];
+  }
+}
+
+template <class T>
+int grow(svils_handle *h, T **p, uint64_t *cap, uint64_t need) {
+  if (*p && *cap >= need) return 0;
+  dfree(h, p);
+  *cap = 0;
+  if (int rc = dalloc(h, p, need, false)) return rc;
+  *cap = need;
+  return 0;
+}
+
+// the refusals shared by both entry points (include/svils.h)
+int check_handle(svils_handle *h, const char *name) {
+  if (!h) return fail(SVILS_ERR_ARG, "%s: null handle", name);
+  if (TILED(h)) return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a column-tiled handle (k > SVILS_MAX_K = %d)", name, SVILS_MAX_K);
+  if (h->d.ksh) return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a K-sharded handle", name);
+  if (h->geo.node_begin != 0 || h->geo.node_end != h->geo.n || h->blocks_set || h->comm)
+    return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a node-block handle", name);
+  if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "%s: set graph and state first", name);
+  if (h->step_open) return fail(SVILS_ERR_ARG, "%s: a mini-batch step is open (close it with phase D)", name);
+  return 0;
+}
+
+// what every top-k call needs besides its batches: the sorted rows (once), 1 / row sums and beta of the current state
+int prepare(svils_handle *h) {
+  const Geometry &g = h->geo;
+  const DeviceState &d = h->d;
+  svils_handle::PredictScratch &s = h->pred;
+  if (!s.scol) {
+    if (int rc = dalloc(h, &s.scol, 2 * d.nlinks, false)) return rc;
+    hipLaunchKernelGGL(k_sort_rows, dim3((g.n + 3) / 4), dim3(256), 0, h->stream, g.n, d.rowptr, d.col, s.scol);
+  }
+  if (!s.inv) {
+    if (int rc = dalloc(h, &s.inv, g.n, false)) return rc;
+    if (int rc = dalloc(h, &s.beta, g.K, false)) return rc;
+  }
+  hipLaunchKernelGGL(k_rowinv, dim3((g.n + 255) / 256), dim3(256), 0, h->stream, g.n, g.K, g.ld, d.gamma, s.inv);
+  hipLaunchKernelGGL(k_beta, dim3((g.K + 255) / 256), dim3(256), 0, h->stream, g.K, d.lambda, s.beta);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svils_link_prob(svils_handle *h, const uint32_t *pairs, uint64_t npairs, double *prob) {
+  if (int rc = check_handle(h, "svils_link_prob")) return rc;
+  if (npairs && (!pairs || !prob)) return fail(SVILS_ERR_ARG, "svils_link_prob: null argument");
+  const Geometry &g = h->geo;
+  for (uint64_t i = 0; i < npairs; ++i) {
+    const uint32_t p = pairs[2 * i], q = pairs[2 * i + 1];
+    if (p >= g.n || q >= g.n) return fail(SVILS_ERR_ARG, "svils_link_prob: pair %llu = (%u, %u): node id >= n = %u", (unsigned long long)i, p, q, g.n);
+    if (p == q) return fail(SVILS_ERR_ARG, "svils_link_prob: pair %llu = (%u, %u): p == q", (unsigned long long)i, p, q);
+  }
+  if (!npairs) return 0;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  svils_handle::PredictScratch &s = h->pred;
+  const uint64_t cap = std::min<uint64_t>(npairs, PAIR_BATCH);
+  if (!s.pairs || s.pair_cap < cap) {
+    uint64_t c1 = s.pair_cap, c2 = s.pair_cap;
+    if (int rc = grow(h, &s.pairs, &c1, 2 * cap)) return rc;
+    if (int rc = grow(h, &s.prob, &c2, cap)) return rc;
+    s.pair_cap = cap;
+  }
+  for (uint64_t b = 0; b < npairs; b += PAIR_BATCH) {
+    const uint64_t m = std::min<uint64_t>(PAIR_BATCH, npairs - b);
+    HIPCHK(hipMemcpyAsync(s.pairs, pairs + 2 * b, 2 * m * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_link_prob, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, h->stream, m, g.K, g.ld, h->d.gamma,
+                       h->d.lambda, s.pairs, s.prob);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(prob + b, s.prob, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+int svils_predict_links(svils_handle *h, const uint32_t *nodes, uint32_t nnodes, uint32_t topk, uint32_t *ids, double *scores) {
+  if (int rc = check_handle(h, "svils_predict_links")) return rc;
+  const Geometry &g = h->geo;
+  if (topk == 0 || topk > SVILS_PREDICT_MAX_TOPK)
+    return fail(SVILS_ERR_ARG, "svils_predict_links: topk = %u, need 1 .. %d", topk, SVILS_PREDICT_MAX_TOPK);
+  if (!nodes && nnodes != 0 && nnodes != g.n)
+    return fail(SVILS_ERR_ARG, "svils_predict_links: nodes = NULL means all %u nodes (nnodes = 0 or n, not %u)", g.n, nnodes);
+  const uint32_t nq = nodes ? nnodes : g.n;
+  if (nq && (!ids || !scores)) return fail(SVILS_ERR_ARG, "svils_predict_links: null argument");
+  if (nodes)
+    for (uint32_t i = 0; i < nq; ++i)
+      if (nodes[i] >= g.n) return fail(SVILS_ERR_ARG, "svils_predict_links: node %u (entry %u) >= n = %u", nodes[i], i, g.n);
+  if (!nq) return 0;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = prepare(h)) return rc;
+  int cus = 0;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
+  if (cus <= 0) cus = 256;
+  svils_handle::PredictScratch &s = h->pred;
+  const uint32_t k16 = (g.K + 15u) & ~15u;
+  const uint32_t nch_max = std::max<uint32_t>(1, MERGE_MAX / (4 * topk));
+  std::vector<uint32_t> qh;
+  for (uint32_t b = 0; b < nq; b += Q_BATCH) {
+    const uint32_t m = std::min(Q_BATCH, nq - b);
+    const uint32_t nqt = (m + PQ - 1) / PQ, rows = nqt * PQ;
+    // chunks: enough blocks for eight per CU, at most nch_max (the merge sorts 4 x nch x topk entries in LDS) and at
+    // least 64 candidates per chunk.  The result does not depend on the cut: it is the top k of one total order.
+    uint32_t nch = std::max<uint32_t>(1, (8u * (uint32_t)cus + nqt - 1) / nqt);
+    nch = std::min(nch, nch_max);
+    nch = std::min(nch, std::max<uint32_t>(1, g.n / PC));
+    uint32_t L = 4 * nch * topk, lp = 1;
+    while (lp < L) lp <<= 1;
+    if (int rc = grow(h, &s.qnodes, &s.q_cap, rows)) return rc;
+    if (int rc = grow(h, &s.aq, &s.aq_cap, (uint64_t)rows * k16)) return rc;
+    if (!s.ids || s.out_cap < (uint64_t)m * topk) {
+      uint64_t c1 = s.out_cap, c2 = s.out_cap;
+      if (int rc = grow(h, &s.ids, &c1, (uint64_t)Q_BATCH * topk)) return rc;
+      if (int rc = grow(h, &s.scores, &c2, (uint64_t)Q_BATCH * topk)) return rc;
+      s.out_cap = (uint64_t)Q_BATCH * topk;
+    }
+    const uint64_t hneed = (uint64_t)nqt * nch * topk * 256;
+    if (!s.hs || s.heap_cap < hneed) {
+      uint64_t c1 = s.heap_cap, c2 = s.heap_cap;
+      if (int rc = grow(h, &s.hs, &c1, hneed)) return rc;
+      if (int rc = grow(h, &s.hi, &c2, hneed)) return rc;
+      s.heap_cap = hneed;
+    }
+    qh.assign(rows, NONE);
+    for (uint32_t i = 0; i < m; ++i) qh[i] = nodes ? nodes[b + i] : b + i;
+    HIPCHK(hipMemcpyAsync(s.qnodes, qh.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    const uint64_t ae = (uint64_t)rows * k16;
+    hipLaunchKernelGGL(k_build_aq, dim3((uint32_t)((ae + 255) / 256)), dim3(256), 0, h->stream, rows, g.K, g.ld, k16, h->d.gamma,
+                       s.inv, s.beta, s.qnodes, s.aq);
+    hipLaunchKernelGGL(k_topk_tiles, dim3(nqt, nch), dim3(256), 0, h->stream, g.n, g.K, g.ld, k16, topk, nch, h->d.gamma, s.inv,
+                       s.aq, s.qnodes, h->d.rowptr, s.scol, s.hs, s.hi);
+    hipLaunchKernelGGL(k_topk_merge, dim3(m), dim3(256), 0, h->stream, topk, nch, lp, s.hs, s.hi, s.scores, s.ids);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ids + (size_t)b * topk, s.ids, (size_t)m * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(scores + (size_t)b * topk, s.scores, (size_t)m * topk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -59,6 +59,9 @@ class Env {
     int comm_rfd = -1;
     std::vector<int> comm_wfds;
     std::vector<int> device_list;   // -device-list d0,d1,..: the HIP ordinal of every rank (default: device, device+1, ..)
+    // link prediction from the final state (svils_link_prob / svils_predict_links): -predict-pairs <file>, -recommend <k>
+    std::string predict_pairs_fname;
+    int recommend = 0;              // top-k links per node written to recommendations.txt; 0 = none
   };
 
   explicit Env(const Args &a);
@@ -107,6 +110,8 @@ class Env {
   uint32_t minibatch;
   double tau0, kappa, nodetau0, nodekappa;
   int32_t sparse_after;
+  std::string predict_pairs_fname;   // -predict-pairs: pairs scored into link-prob.txt ("" = none)
+  uint32_t recommend;                // -recommend: top-k links per node into recommendations.txt (0 = none)
 
   static std::string prefix;
   static std::string file_str(const std::string &fname) { return prefix + fname; }

@@ -116,6 +116,7 @@ LinkSampling::LinkSampling(Env &env, Network &network, bool attach_device)
     Env::plog("load test from file:", true);     // sampler never saw these pairs
     load_test();
   }
+  if (!env_.predict_pairs_fname.empty()) load_predict_pairs();
 
   if (env_.nmi) {   // Network::load_ground_truth / write_gt_communities (src/network.cc:252-307,508-525)
     if (!read_cover_memberships(env_.ground_truth_fname, &ground_truth_)) {
@@ -432,6 +433,74 @@ void LinkSampling::load_test() {
     FILE *tef = open_or_die(Env::file_str("/test-edges.txt"), "test edges");
     fprintf(tef, "%s\n", edgelist_s(listed).c_str());
     fclose(tef);
+  }
+}
+
+// -predict-pairs: "id<TAB>id" lines of external ids, parsed like -load-test; an unknown id or a pair of one node ends the run
+void LinkSampling::load_predict_pairs() {
+  FILE *f = fopen(env_.predict_pairs_fname.c_str(), "r");
+  if (!f) {
+    fprintf(stderr, "error: cannot read -predict-pairs file %s\n", env_.predict_pairs_fname.c_str());
+    exit(2);
+  }
+  int a, b;
+  while (fscanf(f, "%d %d", &a, &b) == 2) {
+    uint32_t p, q;
+    if (!network_.id2seq((uint32_t)a, &p) || !network_.id2seq((uint32_t)b, &q)) {
+      fprintf(stderr, "error: -predict-pairs: id %d or id %d not found in original network\n", a, b);
+      exit(2);
+    }
+    if (p == q) {
+      fprintf(stderr, "error: -predict-pairs: pair %d %d is one node\n", a, b);
+      exit(2);
+    }
+    pp_ext_.push_back(a);
+    pp_ext_.push_back(b);
+    pp_seq_.push_back(p);
+    pp_seq_.push_back(q);
+  }
+  fclose(f);
+  Env::plog("link prediction: pairs to score:", (uint32_t)(pp_seq_.size() / 2));
+}
+
+// link-prob.txt (one line per -predict-pairs line, in input order: id_a, id_b, the network's y, link_prob) and
+// recommendations.txt (one line per node in groups.txt order: the node's id, then id and score of each of its -recommend
+// best candidates; an empty slot reads -1 -1.000000000e+00).  Under -minibatch the device holds the nodes relabelled
+// (dev_of_): pairs and queries go through the relabelling and results come back through seq_of_, so ties among
+// recommendations break by device id there.
+void LinkSampling::write_predictions() {
+  const std::vector<uint32_t> &s2i = network_.seq2id();
+  auto dev = [&](uint32_t seq) { return dev_of_.empty() ? seq : dev_of_[seq]; };
+  if (!pp_seq_.empty()) {
+    const size_t m = pp_seq_.size() / 2;
+    std::vector<uint32_t> pairs(2 * m);
+    for (size_t i = 0; i < 2 * m; ++i) pairs[i] = dev(pp_seq_[i]);
+    std::vector<double> prob(m);
+    if (svils_link_prob(h_, pairs.data(), m, prob.data())) die_svils("svils_link_prob");
+    FILE *f = open_or_die(Env::file_str("/link-prob.txt"), "link-prob");
+    for (size_t i = 0; i < m; ++i)
+      fprintf(f, "%d\t%d\t%d\t%.9e\n", pp_ext_[2 * i], pp_ext_[2 * i + 1], network_.y(pp_seq_[2 * i], pp_seq_[2 * i + 1]) ? 1 : 0, prob[i]);
+    fclose(f);
+  }
+  if (env_.recommend) {
+    const uint32_t k = env_.recommend;
+    std::vector<uint32_t> nodes;
+    if (!dev_of_.empty()) nodes = dev_of_;   // query row i = sequence id i
+    std::vector<uint32_t> ids((size_t)n_ * k);
+    std::vector<double> sc((size_t)n_ * k);
+    if (svils_predict_links(h_, nodes.empty() ? nullptr : nodes.data(), nodes.empty() ? 0 : n_, k, ids.data(), sc.data()))
+      die_svils("svils_predict_links");
+    FILE *f = open_or_die(Env::file_str("/recommendations.txt"), "recommendations");
+    for (uint32_t i = 0; i < n_; ++i) {
+      fprintf(f, "%d", (int)s2i[i]);
+      for (uint32_t j = 0; j < k; ++j) {
+        const uint32_t q = ids[(size_t)i * k + j];
+        if (q == 0xffffffffu) fprintf(f, "\t-1\t%.9e", sc[(size_t)i * k + j]);
+        else fprintf(f, "\t%d\t%.9e", (int)s2i[dev_of_.empty() ? q : seq_of_[q]], sc[(size_t)i * k + j]);
+      }
+      fprintf(f, "\n");
+    }
+    fclose(f);
   }
 }
 
@@ -1046,6 +1115,10 @@ void LinkSampling::do_on_stop_impl() {
   mark("communities.txt");
   save_model();
   mark("gamma.txt, lambda.txt (state fetched from the device first)");
+  if (!pp_seq_.empty() || env_.recommend) {
+    write_predictions();
+    mark("link-prob.txt / recommendations.txt");
+  }
   write_groups();
   mark("groups.txt");
 }

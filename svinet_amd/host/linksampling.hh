@@ -78,6 +78,8 @@ class LinkSampling {
   void init_validation();
   void load_validation();
   void load_test();                            // -load-test
+  void load_predict_pairs();                   // -predict-pairs: read and checked before any device work
+  void write_predictions();                    // link-prob.txt / recommendations.txt from the final state
   void init_gamma_external();                  // -init-communities
   void set_validation_sample(int s);
   void get_random_edge(bool link, Edge &e);
@@ -116,6 +118,8 @@ class LinkSampling {
   std::vector<uint32_t> val_accept_, val_sorted_;
   std::map<Edge, bool> test_map_;              // -load-test
   std::vector<uint32_t> test_sorted_;          // [T][3] p, q, y in map order
+  std::vector<int> pp_ext_;                    // -predict-pairs: [m][2] external ids as listed
+  std::vector<uint32_t> pp_seq_;               // [m][2] the same as sequence ids
   DVec gamma_;                                 // (empty while init_gamma2 is left to the device: defer_init_)
   std::vector<double> lambda_;
   uint64_t init_o0_ = 0;                       // outputs the generator had produced when init_gamma2 began

@@ -79,6 +79,11 @@ static void usage() {
           "\t-sweep-batch <b>\tsweeps per report chunk (default 0 = automatic: 1, 2, 4, 8, then 16 sweeps per report;\n\t\t\t\treports are written while the device sweeps on)\n\n"
           "\t-sparse-after <i>\tthe active-set branch of the phi pass is used once the iteration count exceeds i\n"
           "\t\t\t(default 1000, the reference's constant)\n\n"
+          "\t-predict-pairs <file>\tlink prediction: score the pairs of <file> (\"id<TAB>id\" lines of external ids) with\n"
+          "\t\t\tthe final state's link probability sum_z pi_pz pi_qz beta_z; writes link-prob.txt (id, id, y, probability)\n\n"
+          "\t-recommend <k>\tlink prediction: the k (1 .. 256) most probable links of every node that are not training links,\n"
+          "\t\t\tfrom the final state; writes recommendations.txt (one line per node, groups.txt order).  Both flags\n"
+          "\t\t\tbelong to single-GPU -link-sampling runs with -k <= 2048\n\n"
           "\t-minibatch <m>\tmini-batch mode of -link-sampling: one step = the links of m randomly chosen nodes,\n"
           "\t\t\tRobbins-Monro step sizes (-tau0 -kappa -nodetau0 -nodekappa; defaults 1024 0.9 1024 0.5);\n"
           "\t\t\tgive -rfreq <steps> after -link-sampling to evaluate the stop rule every <steps> steps\n\n");
@@ -148,6 +153,8 @@ int main(int argc, char **argv) {
     else if (is("-kappa")) { need(i); a.kappa = atof(argv[++i]); }
     else if (is("-nodetau0")) { need(i); a.nodetau0 = atof(argv[++i]); }
     else if (is("-nodekappa")) { need(i); a.nodekappa = atof(argv[++i]); }
+    else if (is("-predict-pairs")) { need(i); a.predict_pairs_fname = argv[++i]; }
+    else if (is("-recommend")) { need(i); a.recommend = atoi(argv[++i]); if (a.recommend == 0) a.recommend = -1; }
     else if (is("-init-communities")) { need(i); a.init_comm = true; a.init_comm_fname = argv[++i]; }   // src/main.cc:237-239
     else if (is("-stopthresh") || is("-inf") || is("-scale") || is("-itype") || is("-groups-file")) {
       need(i); ++i;   // value flags of other engines: consumed, no effect on this path
@@ -167,6 +174,27 @@ int main(int argc, char **argv) {
             "Use the reference build for the other engines.\n",
             unsupported ? "; unsupported option " : "", unsupported ? unsupported_flag.c_str() : "");
     return 2;
+  }
+  if (!a.predict_pairs_fname.empty() || a.recommend) {   // link prediction (svils_link_prob / svils_predict_links)
+    const char *flag = a.recommend ? "-recommend" : "-predict-pairs";
+    if (a.recommend && (a.recommend < 1 || a.recommend > 256)) {
+      fprintf(stderr, "error: -recommend wants a count of 1 .. 256 links per node\n");
+      return 2;
+    }
+    const char *why = a.batch ? "-batch" : a.gpus > 1 ? "-gpus N > 1" : a.kshard ? "-kshard" : a.sharded ? "-sharded"
+                    : a.k > 2048 ? "-k > 2048" : nullptr;
+    if (why) {
+      fprintf(stderr, "error: %s is not available with %s (single-GPU -link-sampling runs with -k <= 2048 only)\n", flag, why);
+      return 2;
+    }
+    if (!a.predict_pairs_fname.empty()) {
+      FILE *f = fopen(a.predict_pairs_fname.c_str(), "r");
+      if (!f) {
+        fprintf(stderr, "error: cannot read -predict-pairs file %s\n", a.predict_pairs_fname.c_str());
+        return 2;
+      }
+      fclose(f);
+    }
   }
   if (a.kshard && !a.link_sampling) {
     fprintf(stderr, "error: -kshard belongs to -link-sampling runs\n");
