@@ -39,7 +39,8 @@ extern "C" {
                                     getters that do not wait behind a stop the caller has seen ("After the stop");
                                  8: svils_init_gamma (init_gamma2 on the device); svils_set_option / svils_get_option / svils_option_table (every tunable in one documented table; nothing
                                     on a sweep path reads the environment); svils_gather_communities ends the no-wait window of "After the stop";
-                                    (additive, same version) svils_link_prob / svils_predict_links: link prediction from the state */
+                                    (additive, same version) svils_link_prob / svils_predict_links: link prediction from the state;
+                                    (additive, same version) svils_findk_*: -findk, the estimate of the number of communities */
 
 typedef enum {
   SVILS_OK = 0,
@@ -493,6 +494,45 @@ int svils_sweep_ksharded(svils_handle *h, uint32_t nsweeps);   /* collective, as
  * in this mode: the entries of the window's rows are one contiguous range) and of SVILS_KSH_ROWX.  With your own
  * collectives: svils_ksweep_phase in the order of a sweep; the first phase opens the step, SVILS_KPHASE_STOP closes it. */
 int svils_step_ksharded(svils_handle *h, uint32_t nsteps);      /* collective, asynchronous */
+
+/* ---- -findk: estimate the number of communities (an ADDITION of ABI 8; a handle of its own, nothing of svils_handle) ----
+ * The reference's FastInit::batch_infer (src/fastinit.cc:240-289, dispatched at src/main.cc:321-327): label propagation
+ * over a top-5 sparse gamma.  Every node holds 5 (label, value) slots, labels are node ids < n, slot 0's label is the
+ * node's current label.  One iteration is
+ *     svils_findk_count -> (host) padding draws for svils_findk_pad_requests -> svils_findk_apply -> svils_findk_report.
+ * The padding draws stay on the host: they continue the reference's single MT19937 stream in node order (:217-225).
+ * Without a HIP device every entry point answers SVILS_ERR_DEVICE ("no CPU path"); with one, a null handle SVILS_ERR_ARG. */
+typedef struct svils_findk svils_findk;
+/* alpha = 1 / k of -k (src/env.hh:344), link_thresh = -link-thresh; the state is [n][5] labels + values + pi on `device` */
+int svils_findk_create(int device, uint32_t n, double alpha, double link_thresh, svils_findk **out);
+int svils_findk_destroy(svils_findk *f);
+/* links [nlinks][2] (p < q): every link, held-out ones included -- the training likelihood (:448-465) and the groups
+ * (:291-414) run over all of them.  held_out[nlinks] (or null: none): 1 marks a link of the held-out set, left out of the
+ * count (:258-271) and only there.  heldout_pairs [nheldout][3] (p, q, y) in the order of the reference's std::map
+ * (heldout_likelihood, :511-543). */
+int svils_findk_set_graph(svils_findk *f, const uint32_t *links, uint64_t nlinks, const uint8_t *held_out,
+                          const uint32_t *heldout_pairs, uint64_t nheldout);
+/* labels / values [n][5] (init_gamma, :178-190); pi follows (estimate_all_pi, src/fastinit.hh:460-476) */
+int svils_findk_init_state(svils_findk *f, const uint32_t *labels, const double *values);
+/* the count of one iteration (:258-271, Jacobi: every count reads the labels of the previous iteration) and every node's
+ * top 5 of (count desc, label asc) -- the stable descending sort of set_gamma (:213-220).  *npad = nodes with 1 .. 4
+ * distinct labels: they need 5 - ndistinct padding labels each. */
+int svils_findk_count(svils_findk *f, uint32_t *npad);
+/* those nodes in ascending order: nodes[npad], ndistinct[npad], labels [npad][4] (their counted labels, then UINT32_MAX) */
+int svils_findk_pad_requests(svils_findk *f, uint32_t *nodes, uint32_t *ndistinct, uint32_t *labels);
+/* set_gamma (:200-236) + estimate_all_pi: pads [npad][4], the first 5 - ndistinct of each row used, in
+ * svils_findk_pad_requests order.  Counted slots get count + alpha, pads 2 alpha, nodes without a count keep their slots. */
+int svils_findk_apply(svils_findk *f, const uint32_t *pads);
+/* the likelihoods of the current state: *training_ll = mean edge_likelihood(p, q, 1) over all links (:448-465),
+ * heldout_sums[3] = sums of edge_likelihood(p, q, y) over the held-out pairs: all, y = 0, y = 1 (:511-531).  Both are
+ * fixed-order reductions (deterministic run to run, not the reference's sequential order).  With unlikely and masks
+ * (both or neither): compute_and_log_groups (:291-414) -- *unlikely = directed link entries below link_thresh,
+ * masks[n] = bit s set when slot s's label is a community of the node (the label 65535 is dropped, :341). */
+int svils_findk_report(svils_findk *f, double *training_ll, double *heldout_sums, uint32_t *unlikely, uint32_t *masks);
+/* labels / values / pi [n][5]; any may be null */
+int svils_findk_get_state(svils_findk *f, uint32_t *labels, double *values, double *pi);
+/* device milliseconds of the last count, apply, likelihoods and groups (hipEvent brackets; -1: not run yet) */
+int svils_findk_get_timing(svils_findk *f, double ms[4]);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * Every tunable of the library is a row of ONE table: key, the SVILS_* environment variable that sets its default, the

@@ -35,6 +35,8 @@ EXPORTS = (
     "svils_set_node_blocks", "svils_balance_node_blocks", "svils_prepare_graphs",
     "svils_set_option", "svils_get_option", "svils_option_table", "svils_init_gamma",
     "svils_link_prob", "svils_predict_links",
+    "svils_findk_create", "svils_findk_destroy", "svils_findk_set_graph", "svils_findk_init_state", "svils_findk_count",
+    "svils_findk_pad_requests", "svils_findk_apply", "svils_findk_report", "svils_findk_get_state", "svils_findk_get_timing",
 )
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
 
@@ -153,6 +155,16 @@ def load():
     L.svils_option_table.restype = C.c_char_p
     L.svils_link_prob.argtypes = [vp, vp, C.c_uint64, vp]
     L.svils_predict_links.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.svils_findk_create.argtypes = [C.c_int, C.c_uint32, C.c_double, C.c_double, C.POINTER(vp)]
+    L.svils_findk_destroy.argtypes = [vp]
+    L.svils_findk_set_graph.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]
+    L.svils_findk_init_state.argtypes = [vp, vp, vp]
+    L.svils_findk_count.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.svils_findk_pad_requests.argtypes = [vp, vp, vp, vp]
+    L.svils_findk_apply.argtypes = [vp, vp]
+    L.svils_findk_report.argtypes = [vp, C.POINTER(C.c_double), vp, C.POINTER(C.c_uint32), vp]
+    L.svils_findk_get_state.argtypes = [vp, vp, vp, vp]
+    L.svils_findk_get_timing.argtypes = [vp, vp]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):

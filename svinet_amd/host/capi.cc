@@ -8,6 +8,8 @@
 #include <memory>
 
 #include "env.hh"
+#include "findk.hh"
+#include "svils.h"
 #include "linksampling.hh"
 #include "mmsbbatch.hh"
 #include "network.hh"
@@ -197,5 +199,75 @@ uint64_t svih_fixed_format_mismatches(const double *v, uint64_t count) {
   }
   return bad;
 }
+
+// -findk through the host driver (findk.hh) in library mode: nothing is written to disk, the device work goes through the
+// svils_findk_* entry points.  svih_findk_step: 0 = an iteration with groups, 1 = the stop rule fired, 2 = the loop is over.
+struct svih_findk {
+  std::unique_ptr<Env> env;
+  std::unique_ptr<Network> net;
+  std::unique_ptr<FindK> fk;
+};
+
+static svih_findk *make_findk(const svih_options *o, const char *path, const int32_t *pairs, uint64_t nlines, int device) {
+  Env::Args a;
+  a.n = o->n;
+  a.k = o->k;
+  a.findk = true;
+  a.rand_seed = o->seed;
+  a.hol_ratio = o->heldout_ratio;
+  a.link_thresh = o->link_thresh;
+  a.accuracy = o->accuracy != 0;
+  a.device = device;
+  a.write_files = false;
+  svih_findk *s = new svih_findk();
+  s->env.reset(new Env(a));
+  s->net.reset(new Network(*s->env));
+  if (path) {
+    if (s->net->read(path) < 0) { delete s; return nullptr; }
+  } else {
+    s->net->read_pairs(pairs, nlines);
+  }
+  s->env->n = s->net->n() - s->net->singles();   // src/main.cc:291
+  try {
+    s->fk.reset(new FindK(*s->env, *s->net));
+  } catch (const FindKError &e) {   // svils_last_error() keeps the library's text
+    delete s;
+    return nullptr;
+  }
+  return s;
+}
+
+svih_findk *svih_findk_from_file(const char *path, const svih_options *o, int device) { return make_findk(o, path, nullptr, 0, device); }
+svih_findk *svih_findk_from_pairs(const int32_t *pairs, uint64_t nlines, const svih_options *o, int device) {
+  return make_findk(o, nullptr, pairs, nlines, device);
+}
+void svih_findk_free(svih_findk *s) { delete s; }
+int svih_findk_step(svih_findk *s) {
+  try {
+    return s->fk->step();
+  } catch (const FindKError &e) {
+    return e.rc;
+  }
+}
+uint32_t svih_findk_n(const svih_findk *s) { return s->fk->n(); }
+uint32_t svih_findk_iter(const svih_findk *s) { return s->fk->iter(); }
+uint32_t svih_findk_unlikely(const svih_findk *s) { return s->fk->unlikely(); }
+uint32_t svih_findk_npad(const svih_findk *s) { return s->fk->last_npad(); }
+double svih_findk_pad_seconds(const svih_findk *s) { return s->fk->pad_seconds(); }
+double svih_findk_training_ll(const svih_findk *s) { return s->fk->training_ll(); }
+uint64_t svih_findk_nheldout(const svih_findk *s) { return s->fk->heldout_pairs().size() / 3; }
+const uint32_t *svih_findk_heldout(const svih_findk *s) { return s->fk->heldout_pairs().data(); }
+const uint32_t *svih_findk_seq2id(const svih_findk *s) { return s->net->seq2id().data(); }
+void svih_findk_row(const svih_findk *s, double *row11) { memcpy(row11, s->fk->last_row(), 11 * sizeof(double)); }
+void svih_findk_state(const svih_findk *s, uint32_t *labels, double *values, uint32_t *masks) {
+  const FindK &f = *s->fk;
+  if (labels) memcpy(labels, f.labels().data(), f.labels().size() * sizeof(uint32_t));
+  if (values) memcpy(values, f.values().data(), f.values().size() * sizeof(double));
+  if (masks) {
+    if (f.masks().empty()) memset(masks, 0, (size_t)f.n() * sizeof(uint32_t));
+    else memcpy(masks, f.masks().data(), f.masks().size() * sizeof(uint32_t));
+  }
+}
+int svih_findk_timing(const svih_findk *s, double *ms4) { return svils_findk_get_timing(s->fk->handle(), ms4); }
 
 }  // extern "C"

@@ -65,7 +65,7 @@ Env::Env(const Args &a)
       use_init_communities(a.init_comm), init_communities_fname(a.init_comm_fname),
       nmi(a.nmi), ground_truth_fname(a.ground_truth_fname),
       datfname(a.datfname), label(a.label), gpus(a.gpus), rank(a.rank), kshard(a.kshard), sharded((a.sharded || a.gpus > 1) && !a.kshard), comm_rfd(a.comm_rfd), comm_wfds(a.comm_wfds),
-      batch_mode(a.batch), link_sampling(a.link_sampling), strid(a.strid),
+      batch_mode(a.batch), link_sampling(a.link_sampling), findk(a.findk), strid(a.strid),
       terminate(0), total_pairs(0), ones_prob(0), zeros_prob(1),
       device(a.device), sweep_batch(a.sweep_batch), write_files(a.write_files),
       minibatch(a.minibatch), tau0(a.tau0), kappa(a.kappa), nodetau0(a.nodetau0), nodekappa(a.nodekappa),
@@ -87,6 +87,7 @@ Env::Env(const Args &a)
   if (seed) sa << "-seed" << seed;
   if (batch_mode) { sa << "-batch"; reportfreq = 1; }
   else if (link_sampling) sa << "-linksampling";
+  else if (findk) sa << "-findk";
   if (a.nthreads > 0) sa << "-T" << a.nthreads;
   prefix = a.outdir_root.empty() ? sa.str() : a.outdir_root + "/" + sa.str();
 

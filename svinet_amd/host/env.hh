@@ -18,6 +18,7 @@ class Env {
     std::string datfname = "network.dat";
     std::string label = "mmsb";
     bool batch = false, link_sampling = false;
+    bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool load = false;
     std::string location;
     bool val_load = false;
@@ -97,7 +98,7 @@ class Env {
   bool kshard, sharded;
   int comm_rfd;
   std::vector<int> comm_wfds;
-  bool batch_mode, link_sampling;
+  bool batch_mode, link_sampling, findk;
   bool strid;
   volatile int terminate;
   // set by Network::set_env_variables

@@ -2,7 +2,8 @@
 //
 // Accepts the reference's flag set (src/main.cc:114-242, same spelling, same
 // positional/order-sensitive semantics: e.g. -link-sampling resets rfreq to 1,
-// so -rfreq must follow it).  Engines: -link-sampling (the MI355X path) and the
+// so -rfreq must follow it).  Engines: -link-sampling (the MI355X path), -findk (the
+// estimate of the number of communities, also on the device) and the
 // reference's small all-pairs CPU engine -batch (plumbing only); the
 // flags that select the reference's other engines are recognised and rejected
 // with a message instead of being silently ignored.
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "env.hh"
+#include "findk.hh"
 #include "linksampling.hh"
 #include "mmsbbatch.hh"
 #include "network.hh"
@@ -54,6 +56,8 @@ static void usage() {
           "\t-k <K>\t\tnumber of communities\n\n"
           "\t-link-sampling\tinference using link sampling (the MI355X engine of this build)\n\n"
           "\t-batch\t\trun batch variational inference over all pairs (host CPU, small graphs)\n\n"
+          "\t-findk\t\testimate the number of communities (label propagation over a top-5 sparse gamma, on the GPU);\n"
+          "\t\t\tpick -k for -link-sampling from the lines of its communities.txt.  Single GPU; -k only sets alpha = 1/k\n\n"
           "\t-load-validation <fname>\tuse the pairs in the file as the validation set for convergence\n\n"
           "\t-load <dir>\tresume from <dir>gamma.txt / <dir>lambda.txt\n\n"
           "\t-label\t\ttag output directory\n\n"
@@ -113,6 +117,7 @@ int main(int argc, char **argv) {
     else if (is("-file")) { need(i); a.datfname = argv[++i]; }
     else if (is("-batch")) { a.batch = true; a.link_sampling = false; a.rfreq = 1; }
     else if (is("-link-sampling")) { a.link_sampling = true; a.batch = false; a.rfreq = 1; }
+    else if (is("-findk")) { a.findk = true; }
     else if (is("-load")) { need(i); a.load = true; a.location = argv[++i]; }
     else if (is("-load-validation")) { need(i); a.val_load = true; a.val_file_location = argv[++i]; }
     else if (is("-load-test")) { need(i); a.test_load = true; a.test_file_location = argv[++i]; }
@@ -159,7 +164,7 @@ int main(int argc, char **argv) {
     else if (is("-stopthresh") || is("-inf") || is("-scale") || is("-itype") || is("-groups-file")) {
       need(i); ++i;   // value flags of other engines: consumed, no effect on this path
     }
-    else if (is("-gen") || is("-ppc") || is("-lcstats") || is("-gml") || is("-findk") || is("-stratified") ||
+    else if (is("-gen") || is("-ppc") || is("-lcstats") || is("-gml") || is("-stratified") ||
              is("-rnode") || is("-rpair") || is("-orig") || is("-infset") || is("-single") ||
              is("-preprocess") || is("-gp") || is("-adamic-adar") || is("-disjoint") ||
              is("-load-test-sets")) {
@@ -168,12 +173,20 @@ int main(int argc, char **argv) {
     }
     // unknown flags are ignored, as in the reference
   }
-  if (unsupported || !(a.batch || a.link_sampling)) {
+  if (unsupported || !(a.batch || a.link_sampling || a.findk)) {
     fprintf(stderr,
-            "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here%s%s.\n"
+            "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk)%s%s.\n"
             "Use the reference build for the other engines.\n",
             unsupported ? "; unsupported option " : "", unsupported ? unsupported_flag.c_str() : "");
     return 2;
+  }
+  if (a.findk) {   // one GPU, whole iterations: the flags of the other paths do not apply
+    const char *why = a.gpus > 1 ? "-gpus N > 1" : a.kshard ? "-kshard" : a.sharded ? "-sharded" : a.minibatch ? "-minibatch"
+                    : !a.predict_pairs_fname.empty() ? "-predict-pairs" : a.recommend ? "-recommend" : nullptr;
+    if (why) {
+      fprintf(stderr, "error: %s is not available with -findk (a single-GPU run)\n", why);
+      return 2;
+    }
   }
   if (!a.predict_pairs_fname.empty() || a.recommend) {   // link prediction (svils_link_prob / svils_predict_links)
     const char *flag = a.recommend ? "-recommend" : "-predict-pairs";
@@ -301,6 +314,16 @@ run:
   if (network.ones() == 0 || env.n < 2) {
     fprintf(stderr, "error: no links read from %s; quitting\n", a.datfname.c_str());
     return -1;
+  }
+  if (a.findk) {                             // src/main.cc:321-327, before the other engines (-batch / -link-sampling only name the directory)
+    try {
+      FindK fk(env, network);
+      fk.run();
+    } catch (const FindKError &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return -1;
+    }
+    exit(0);
   }
   if (a.batch) {                             // src/main.cc:354-358
     printf("+ running mmsb batch inference\n");

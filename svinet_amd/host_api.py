@@ -58,6 +58,21 @@ def load():
     L.svih_init_streams.restype = C.c_int
     L.svih_deg.argtypes = [vp, u32]
     L.svih_deg.restype = u32
+    L.svih_findk_from_file.argtypes = [C.c_char_p, P(Options), C.c_int]
+    L.svih_findk_from_file.restype = vp
+    L.svih_findk_from_pairs.argtypes = [vp, u64, P(Options), C.c_int]
+    L.svih_findk_from_pairs.restype = vp
+    for name, res in (("free", None), ("step", C.c_int), ("n", u32), ("iter", u32), ("unlikely", u32), ("npad", u32),
+                      ("pad_seconds", dbl), ("training_ll", dbl), ("nheldout", u64), ("heldout", P(u32)), ("seq2id", P(u32))):
+        f = getattr(L, "svih_findk_" + name)
+        f.argtypes = [vp]
+        f.restype = res
+    L.svih_findk_row.argtypes = [vp, vp]
+    L.svih_findk_row.restype = None
+    L.svih_findk_state.argtypes = [vp, vp, vp, vp]
+    L.svih_findk_state.restype = None
+    L.svih_findk_timing.argtypes = [vp, vp]
+    L.svih_findk_timing.restype = C.c_int
     _lib = L
     return L
 
@@ -237,6 +252,92 @@ class BatchEngine:
     def close(self):
         if getattr(self, "_h", None):
             load().svih_batch_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class FindK:
+    """-findk on the device (svils_findk_*), driven by the product's host side (host/findk.cc: init_gamma, the held-out
+    sample, the padding draws) with nothing written to disk.  step() runs one pass of the reference's batch_infer loop
+    (src/fastinit.cc:240-289): 0 = an iteration with its groups, 1 = the held-out stop rule fired (no groups), 2 = the loop
+    was already over.  -seed does not enter: FastInit draws from the default stream."""
+
+    STEP_ITERATION, STEP_STOPPED, STEP_DONE = 0, 1, 2
+
+    def __init__(self, path=None, n=0, k=0, pairs=None, heldout_ratio=0.01, link_thresh=0.5, accuracy=False, device=0):
+        L = load()
+        o = Options()
+        L.svih_options_default(C.byref(o), n, k)
+        o.heldout_ratio = heldout_ratio
+        o.link_thresh = link_thresh
+        o.accuracy = int(accuracy)
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+            self._h = L.svih_findk_from_pairs(pairs.ctypes.data, pairs.shape[0], C.byref(o), device)
+        else:
+            self._h = L.svih_findk_from_file(os.fsencode(path), C.byref(o), device)
+        if not self._h:
+            from . import _svils
+            raise RuntimeError("FindK: cannot read %r or no device: %s" % (path, _svils.load().svils_last_error().decode()))
+        self.n = L.svih_findk_n(self._h)
+        self.seq2id = _arr(L.svih_findk_seq2id(self._h), (self.n,), np.uint32)
+        self.heldout = _arr(L.svih_findk_heldout(self._h), (L.svih_findk_nheldout(self._h), 3), np.uint32)
+
+    def step(self):
+        rc = load().svih_findk_step(self._h)
+        if rc < 0:
+            from . import _svils
+            raise _svils.SvilsError(rc, _svils.load().svils_last_error().decode("utf-8", "replace"))
+        return rc
+
+    def run(self):
+        """every pass until the loop ends; returns the heldout.txt rows (11 columns each)"""
+        rows = []
+        while True:
+            r = self.step()
+            if r == self.STEP_DONE:
+                return np.array(rows).reshape(-1, 11)
+            rows.append(self.row)
+            if r == self.STEP_STOPPED:
+                return np.array(rows).reshape(-1, 11)
+
+    def state(self):
+        """(labels [n][5] uint32, values [n][5] float64, masks [n] uint32) after the last step"""
+        lab = np.zeros((self.n, 5), np.uint32)
+        val = np.zeros((self.n, 5), np.float64)
+        mk = np.zeros(self.n, np.uint32)
+        load().svih_findk_state(self._h, lab.ctypes.data, val.ctypes.data, mk.ctypes.data)
+        return lab, val, mk
+
+    @property
+    def row(self):
+        r = np.zeros(11, np.float64)
+        load().svih_findk_row(self._h, r.ctypes.data)
+        return r
+
+    @property
+    def iter(self):
+        return load().svih_findk_iter(self._h)
+
+    @property
+    def unlikely(self):
+        return load().svih_findk_unlikely(self._h)
+
+    @property
+    def training_ll(self):
+        return load().svih_findk_training_ll(self._h)
+
+    def timing(self):
+        """device ms of the last step's count, apply, likelihoods, groups; the host padding seconds; the padded nodes"""
+        ms = np.zeros(4, np.float64)
+        load().svih_findk_timing(self._h, ms.ctypes.data)
+        return {"count_ms": ms[0], "apply_ms": ms[1], "likelihood_ms": ms[2], "groups_ms": ms[3],
+                "pad_host_ms": 1e3 * load().svih_findk_pad_seconds(self._h), "npad": load().svih_findk_npad(self._h)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().svih_findk_free(self._h)
             self._h = None
 
     __del__ = close
