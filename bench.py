@@ -2,9 +2,15 @@
 """bench.py -- edge-updates/sec of the link-sampling sweep on MI355X.
 
   python bench.py --gpus 1 --steps 100 --warmup 5
+  python bench.py --gpus 1 --steps 100 --warmup 5 --full   # + every record beside the headline (see below)
   python bench.py --gpus N --steps K --warmup W            # bare: spawns its own N ranks (one process per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline alone: set-up, warm-up, the timed window (and its repetitions, whose median is
+`value`), --dump-outputs, the JSON line.  --full adds the records that take runs of their own: the phi event pass
+(`roofline`, `roofline_dense_only`), the HBM-bound and config-5 sizes, the svinet binary end to end, the CPU baselines;
+for N > 1 the exchange event pass, the same window on one GPU, the CPU baseline and the side records.
 
 A "step" is one sweep of LinkSampling::infer()'s loop (src/linksampling.cc:571-789)
 over all training links: phi pass, mean indicators, s3 pass, lambda update,
@@ -677,23 +683,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="astroph-k20",
                     help="|".join(WORKLOADS) + "|astroph-k<K>|synthetic:<n>:<k>:<mean_deg>|mmsb:<n>:<k>:<mean_deg>")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, take every record that needs runs of its own (roofline event passes, other "
+                         "sizes and layouts, the svinet binary, CPU baselines, N>1 side records); the --no-* options below "
+                         "leave some of them out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--event-period", type=int, default=9,
-                    help="N=1: the event pass after the timed region brackets the phi launch with hipEvents on every P-th "
+                    help="N=1 --full: the event pass after the timed region brackets the phi launch with hipEvents on every P-th "
                          "sweep of the same window (those sweeps launch eagerly, the others replay hipGraphs); lowered "
                          "automatically so that at least 10 launches are timed")
-    ap.add_argument("--no-hbm-bound", action="store_true", help="skip the HBM-bound sub-record (n=2e5, k=512; ~15 s)")
+    ap.add_argument("--no-hbm-bound", action="store_true", help="--full: skip the HBM-bound sub-record (n=2e5, k=512; ~15 s)")
     ap.add_argument("--no-config5", action="store_true",
-                    help="skip the config-5 sub-record (planted MMSB graph, n=1e6, k=512 on this one GPU; ~60 s, 13 GB of HBM)")
+                    help="--full: skip the config-5 sub-record (planted MMSB graph, n=1e6, k=512 on this one GPU; ~60 s, 13 GB of HBM)")
     ap.add_argument("--reps", type=int, default=50,
                     help="N=1: repetitions of the timed window from the re-seeded state; `value` is their median (0: the single first window)")
     ap.add_argument("--force-sharded", action="store_true",
-                    help="take the N>1 code path (process group, RCCL communicator, sharded driver, side records) with "
+                    help="take the N>1 code path (process group, RCCL communicator, sharded driver; side records with --full) with "
                          "whatever world size there is -- a one-GPU box can exercise it with a world of one")
-    ap.add_argument("--no-extra", action="store_true", help="N>1: skip the side records (config 4, HBM-bound size)")
-    ap.add_argument("--extra-list", default="", help="N>1: comma-separated names of the side records to run (default: all)")
+    ap.add_argument("--no-extra", action="store_true", help="N>1 --full: skip the side records (config 4, HBM-bound size)")
+    ap.add_argument("--extra-list", default="", help="N>1 --full: comma-separated names of the side records to run (default: all)")
     ap.add_argument("--test-one-gpu", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-cli", action="store_true", help="N=1: skip the cli_end_to_end record (three runs of the svinet binary to its stop rule, ~5 s)")
+    ap.add_argument("--no-cli", action="store_true", help="N=1 --full: skip the cli_end_to_end record (three runs of the svinet binary to its stop rule, ~5 s)")
     ap.add_argument("--cli-only", action="store_true", help="print the cli_end_to_end record alone")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write what their last step computed (gamma, lambda, converged flags, held-out "
@@ -867,6 +877,7 @@ def main():
             ctrl = eng.control()
         if args.dump_outputs:
             dumped = dump_outputs(eng, args.dump_outputs)     # the state after the last timed window, before the event pass
+    if rank == 0 and not multi and args.full:
         # event pass of its own over the same window: every `period`-th sweep launches eagerly between hipEvents
         _reseed(eng, setup)
         eng.sweep(args.warmup)
@@ -893,7 +904,7 @@ def main():
                            "unit": "GB/s", "frac": ach / HBM_PEAK_GBS}
         eng.enable_timing(0, 1)
 
-    if multi:
+    if multi and args.full:
         # phi and exchange times from an event pass of its own right after the timed region (all ranks: the
         # sweeps are collective), so that the event records do not sit in the measured sweeps
         nev = max(10, min(args.steps, 20))
@@ -909,7 +920,7 @@ def main():
     rccl = n1_same_box = cpu_rec = None
     if multi:
         rccl = _rccl_evidence(eng, dist, rank, world, local_rank, torch)
-        if rank == 0:
+        if rank == 0 and args.full:
             # the SAME window on ONE GPU of this box (rank 0's), plain engine: what the N = 1 run of this box gives,
             # for the consistency check of the N > 1 value -- the other ranks wait at the barrier below
             e1 = setup.engine(use_validation_stop=False, device=local_rank)
@@ -964,33 +975,36 @@ def main():
                                        "first_window_ms_per_step is the single first window" % (repeat["reps"], args.steps, args.warmup))
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        out["full"] = bool(args.full)
         if args.test_one_gpu:
             out["test_mode"] = "all ranks on GPU 0 over the tests' transport: a code-path check, not a measurement"
-        roof = {"bound": "hbm", "kernel": "k_phi_lpl (phi pass, A6)" if k <= 56 else "k_phi (phi pass, A6)"}
-        if not multi:
-            roof.update(_roofline_fields(same_window, k, n, args.workload))
-        else:   # this rank's node block: no PMC record describes it
-            roof.update(same_window)
-            roof["achieved_survey_model"], roof["frac_survey_model"] = roof.pop("achieved"), roof.pop("frac")
-            roof["pull_model"] = _pull_model(same_window, k, int(runner.bounds[rank + 1]) - int(runner.bounds[rank]))
-            roof["traffic"], roof["frac_basis"] = None, "pull_model"
-            roof["achieved"], roof["frac"] = roof["pull_model"]["achieved"], roof["pull_model"]["frac"]
-        roof["timing"] = ("hipEvents around the phi launch on the engine's own stream, in an event pass of its own after the "
-                          "timed region" + ("; sampled sweeps launch eagerly, the rest replay hipGraphs" if not multi else ""))
-        row_bytes = eng.device_buffer(_svils.BUF_GAMMA)[2]
-        resident = n * row_bytes < 200e6
-        roof["note"] = ("frac = HBM bytes per phi launch (%s) / launch time / 8 TB/s.  The state of this workload (%.1f MB per n-by-k "
-                        "array) is %s" % (
-                            "PMC counters 2*FETCH_SIZE + WRITE_SIZE" if roof["frac_basis"] == "hbm_counter" else "pull_model, no valid PMC record",
-                            n * row_bytes / 1e6,
-                            "resident in the 4 MB-per-XCD L2s / 256 MB Infinity Cache: the launch is bound by the dependent-miss chain, "
-                            "not by HBM (frac_survey_model is a cache-fed rate) -- the HBM-bound figures are hbm_bound and config5"
-                            if resident else "larger than the 256 MB Infinity Cache"))
-        out["roofline"] = roof
+        if same_window is not None:      # --full: the phi event pass
+            roof = {"bound": "hbm", "kernel": "k_phi_lpl (phi pass, A6)" if k <= 56 else "k_phi (phi pass, A6)"}
+            if not multi:
+                roof.update(_roofline_fields(same_window, k, n, args.workload))
+            else:   # this rank's node block: no PMC record describes it
+                roof.update(same_window)
+                roof["achieved_survey_model"], roof["frac_survey_model"] = roof.pop("achieved"), roof.pop("frac")
+                roof["pull_model"] = _pull_model(same_window, k, int(runner.bounds[rank + 1]) - int(runner.bounds[rank]))
+                roof["traffic"], roof["frac_basis"] = None, "pull_model"
+                roof["achieved"], roof["frac"] = roof["pull_model"]["achieved"], roof["pull_model"]["frac"]
+            roof["timing"] = ("hipEvents around the phi launch on the engine's own stream, in an event pass of its own after the "
+                              "timed region" + ("; sampled sweeps launch eagerly, the rest replay hipGraphs" if not multi else ""))
+            row_bytes = eng.device_buffer(_svils.BUF_GAMMA)[2]
+            resident = n * row_bytes < 200e6
+            roof["note"] = ("frac = HBM bytes per phi launch (%s) / launch time / 8 TB/s.  The state of this workload (%.1f MB per n-by-k "
+                            "array) is %s" % (
+                                "PMC counters 2*FETCH_SIZE + WRITE_SIZE" if roof["frac_basis"] == "hbm_counter" else "pull_model, no valid PMC record",
+                                n * row_bytes / 1e6,
+                                "resident in the 4 MB-per-XCD L2s / 256 MB Infinity Cache: the launch is bound by the dependent-miss chain, "
+                                "not by HBM (frac_survey_model is a cache-fed rate) -- the HBM-bound figures are hbm_bound and config5"
+                                if resident else "larger than the 256 MB Infinity Cache"))
+            out["roofline"] = roof
         if rccl is not None:
             out["rccl"] = rccl
-            out["n1_same_box"] = n1_same_box
-            out["speedup_vs_n1_same_box"] = out["value"] / n1_same_box["value"]
+            if n1_same_box is not None:
+                out["n1_same_box"] = n1_same_box
+                out["speedup_vs_n1_same_box"] = out["value"] / n1_same_box["value"]
             if cpu_rec is not None:
                 out["cpu_baseline"] = cpu_rec
                 out["speedup_vs_cpu_1core"] = out["value"] / cpu_rec["value"]
@@ -1007,6 +1021,7 @@ def main():
                                "note": "hipEvent time of the RCCL collectives on the engine stream, measured in the event pass after the "
                                        "timed region (eager launches; the timed region replays hipGraphs).  Two exchange points per sweep: "
                                        "{rows + sum[k]} and {s1,s2,s3}"}
+        if multi:
             out["load_balance"] = runner.balance
             mp = model_prediction(args.workload, "nodeblock", world)
             if mp is not None:
@@ -1014,28 +1029,29 @@ def main():
                 out["model_ms_per_step"] = mp.get("predicted_ms_per_step")
                 if mp.get("predicted_ms_per_step"):
                     out["measured_over_model"] = out["ms_per_step"] / mp["predicted_ms_per_step"]
-        if not multi and n * k * 8 < 256e6:
+        full1 = args.full and not multi     # N = 1 --full: the records beside the headline, each a run of its own
+        if full1 and n * k * 8 < 256e6:
             try:
                 out["roofline_dense_only"] = dense_only_window(setup, k, local_rank)
             except Exception as exc:
                 out["roofline_dense_only"] = {"error": repr(exc)[:200]}
-        if not multi and not args.no_hbm_bound and args.workload != HBM_BOUND_WORKLOAD:
+        if full1 and not args.no_hbm_bound and args.workload != HBM_BOUND_WORKLOAD:
             try:
                 out["hbm_bound"] = hbm_bound_record(local_rank)
             except Exception as exc:
                 out["hbm_bound"] = {"error": repr(exc)[:200]}
-        if not multi and not args.no_config5 and args.workload != CONFIG5_WORKLOAD:
+        if full1 and not args.no_config5 and args.workload != CONFIG5_WORKLOAD:
             # BASELINE config 5 at full size on this one GPU: the size the >= 50 % HBM-roofline claim is made on
             try:
                 out["config5"] = hbm_bound_record(local_rank, sweeps=5, workload=CONFIG5_WORKLOAD)
             except Exception as exc:
                 out["config5"] = {"error": repr(exc)[:200]}
-        if not multi and not args.no_cli and path and args.workload.startswith("astroph"):
+        if full1 and not args.no_cli and path and args.workload.startswith("astroph"):
             try:
                 out["cli_end_to_end"] = cli_end_to_end(path, n, k, out["ms_per_step"])
             except Exception as exc:
                 out["cli_end_to_end"] = {"error": repr(exc)[:200]}
-        if not args.no_cpu_baseline and not multi:
+        if full1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(path, pairs, n, k, args.warmup, args.steps)
             out["speedup_vs_cpu_1core"] = out["value"] / out["cpu_baseline"]["value"]
             try:
@@ -1083,8 +1099,8 @@ def main():
         threading.Thread(target=watchdog, daemon=True).start()
 
     # N > 1 side records: the same sharded driver on the workloads SURVEY 8e expects to scale -- BASELINE
-    # config 4 (ca-AstroPh K=200) and the HBM-bound size (n=2e5, k=512) -- one chain over the N ranks each.
-    if multi and not args.no_extra:
+    # config 4 (ca-AstroPh K=200) and the HBM-bound size (n=2e5, k=512) -- one chain over the N ranks each (--full).
+    if multi and args.full and not args.no_extra:
         extra = {}
         if rank == 0:
             out["sharded_extra"] = extra   # filled as the records complete: the watchdog prints what is there

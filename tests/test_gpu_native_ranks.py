@@ -496,7 +496,7 @@ def test_bench_bare_gpus_2_spawns_its_own_ranks(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--test-one-gpu",
-                        "--extra-list", "config4_astroph_k200"], env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+                        "--full", "--extra-list", "config4_astroph_k200"], env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     assert len([l for l in r.stdout.split("\n") if l.startswith("{")]) == 1      # ONE line, from rank 0
     out = _check_bench_line(r.stdout)
@@ -511,7 +511,7 @@ def test_bench_multi_gpu_code_path_two_ranks(tmp_path):
     env = _env(tmp_path)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29691", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2",
-                        "--test-one-gpu", "--extra-list", "config4_astroph_k200,minibatch_steps_astroph_k20,ksharded_config4_astroph_k200"],
+                        "--test-one-gpu", "--full", "--extra-list", "config4_astroph_k200,minibatch_steps_astroph_k20,ksharded_config4_astroph_k200"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     out = _check_bench_line(r.stdout)
@@ -531,7 +531,7 @@ def test_bench_side_record_that_hangs_does_not_cost_the_line(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--test-one-gpu",
-                        "--record-timeout", "20", "--no-cpu-baseline",
+                        "--full", "--record-timeout", "20", "--no-cpu-baseline",
                         "--extra-list", "config4_astroph_k200,minibatch_steps_astroph_k20,ksharded_config4_astroph_k200"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     lines = [l for l in r.stdout.split("\n") if l.startswith("{")]

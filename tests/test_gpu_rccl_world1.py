@@ -154,7 +154,7 @@ def test_bench_force_sharded_line(tmp_path):
     import sys
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("SVILS_RCCL_LIBRARY", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--steps", "64", "--warmup", "5", "--no-extra",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--full", "--steps", "64", "--warmup", "5", "--no-extra",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][-1])

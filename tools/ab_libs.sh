@@ -7,7 +7,7 @@ mkdir -p "$(dirname "$out")"; : > "$out"
 for rep in 1 2 3; do
 for lib in "$@"; do
   for wl in $WLS; do
-    line=$(SVILS_LIB=$PWD/svinet_amd/lib/$lib timeout 300 python bench.py --workload $wl --steps 100 --warmup 5 --reps 30 --no-hbm-bound --no-config5 --no-cpu-baseline --no-cli 2>/dev/null | tail -1 |
+    line=$(SVILS_LIB=$PWD/svinet_amd/lib/$lib timeout 300 python bench.py --full --workload $wl --steps 100 --warmup 5 --reps 30 --no-hbm-bound --no-config5 --no-cpu-baseline --no-cli 2>/dev/null | tail -1 |
       python -c "
 import json,sys
 d=json.loads(sys.stdin.read())

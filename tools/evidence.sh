@@ -4,8 +4,8 @@
 # Everything lands in gpurun_out/<tag>/; copy what is to be judged into profiles/<tag>_*.
 # steps:
 #   smoke        __graft_entry__.smoke()
-#   bench        the driver's command (--gpus 1 --steps 20 --warmup 5) and the default line
-#   bench-lite   the default line without the config5 / hbm_bound records (fast)
+#   bench        the driver's command (--gpus 1 --steps 20 --warmup 5) and the --full line
+#   bench-lite   the --full line without the config5 / hbm_bound records (fast)
 #   bench-extra  LFR K=28 and ca-AstroPh K=200 lines
 #   bench2       bare `python bench.py --gpus 2 --test-one-gpu` (self-spawned ranks on GPU 0, tests' transport, async)
 #   prof         rocprofv3 --kernel-trace --stats of the default command (ca-AstroPh K=20) and of LFR K=28
@@ -42,22 +42,22 @@ for step in "$@"; do
     smoke) python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tee $O/smoke.txt ;;
     bench)
       python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_astroph_k20_steps20.json 2> $O/bench.err; tail -c 300 $O/bench_astroph_k20_steps20.json; echo
-      python bench.py > $O/bench_astroph_k20.json 2>> $O/bench.err; tail -c 300 $O/bench_astroph_k20.json; echo ;;
-    bench-lite) python bench.py --no-hbm-bound --no-config5 > $O/bench_astroph_k20_lite.json 2>> $O/bench.err; tail -c 300 $O/bench_astroph_k20_lite.json; echo ;;
+      python bench.py --full > $O/bench_astroph_k20.json 2>> $O/bench.err; tail -c 300 $O/bench_astroph_k20.json; echo ;;
+    bench-lite) python bench.py --full --no-hbm-bound --no-config5 > $O/bench_astroph_k20_lite.json 2>> $O/bench.err; tail -c 300 $O/bench_astroph_k20_lite.json; echo ;;
     bench-extra)
-      python bench.py --workload lfr-k28 --no-hbm-bound --no-config5 --no-cpu-baseline > $O/bench_lfr_k28.json 2>> $O/bench.err
-      python bench.py --workload astroph-k200 --no-hbm-bound --no-config5 --no-cpu-baseline > $O/bench_astroph_k200.json 2>> $O/bench.err
+      python bench.py --full --workload lfr-k28 --no-hbm-bound --no-config5 --no-cpu-baseline > $O/bench_lfr_k28.json 2>> $O/bench.err
+      python bench.py --full --workload astroph-k200 --no-hbm-bound --no-config5 --no-cpu-baseline > $O/bench_astroph_k200.json 2>> $O/bench.err
       tail -c 200 $O/bench_lfr_k28.json; echo ;;
     bench2)
       python -c "import __graft_entry__ as g; g.build_test_transport()"
       SVILS_RCCL_LIBRARY=$R/tests/fakerccl/libfakerccl.so FAKERCCL_ASYNC=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 2 --test-one-gpu \
-        --extra-list config4_astroph_k200 > $O/bench_gpus2_one_gpu.json 2> $O/bench2.err; echo "rc=$?"; tail -c 400 $O/bench_gpus2_one_gpu.json; echo; tail -5 $O/bench2.err ;;
+        --full --extra-list config4_astroph_k200 > $O/bench_gpus2_one_gpu.json 2> $O/bench2.err; echo "rc=$?"; tail -c 400 $O/bench_gpus2_one_gpu.json; echo; tail -5 $O/bench2.err ;;
     prof)
-      prof_one astroph_k20 --no-cpu-baseline --no-hbm-bound --no-config5
-      prof_one lfr_k28 --workload lfr-k28 --no-cpu-baseline --no-hbm-bound --no-config5 ;;
+      prof_one astroph_k20 --full --no-cpu-baseline --no-hbm-bound --no-config5
+      prof_one lfr_k28 --full --workload lfr-k28 --no-cpu-baseline --no-hbm-bound --no-config5 ;;
     prof-large)   # rocprofv3 kernel stats of BASELINE config 4's shape and of config 5 at full size (one GPU)
-      prof_one astroph_k200 --workload astroph-k200 --no-cpu-baseline --no-hbm-bound --no-config5 --no-cli
-      prof_one mmsb_n1m_k512 --workload mmsb:1000000:512:24 --steps 10 --warmup 2 --reps 0 --no-cpu-baseline --no-hbm-bound --no-config5 --no-cli ;;
+      prof_one astroph_k200 --full --workload astroph-k200 --no-cpu-baseline --no-hbm-bound --no-config5 --no-cli
+      prof_one mmsb_n1m_k512 --full --workload mmsb:1000000:512:24 --steps 10 --warmup 2 --reps 0 --no-cpu-baseline --no-hbm-bound --no-config5 --no-cli ;;
     pmc|pmc-small)
       WLS="astroph-k20 synthetic:200000:512:24 mmsb:1000000:512:24"; [ $step = pmc-small ] && WLS="astroph-k20"
       ARGS=""
@@ -115,7 +115,7 @@ for step in "$@"; do
       rm -rf $O/st_* $O/pf_* $O/pw_* ;;
     forced)   # the N > 1 driver of bench.py on the REAL librccl with a world of one (eager window, then hipGraph replay with the collectives captured)
       for wl in astroph-k20 astroph-k200; do
-        timeout 600 python bench.py --force-sharded --workload $wl --no-cpu-baseline --no-extra > $O/bench_force_sharded_world1_$wl.json 2>> $O/bench_forced.err
+        timeout 600 python bench.py --force-sharded --full --workload $wl --no-cpu-baseline --no-extra > $O/bench_force_sharded_world1_$wl.json 2>> $O/bench_forced.err
         python - $O/bench_force_sharded_world1_$wl.json <<'PY'
 import json, sys
 d = [json.loads(l) for l in open(sys.argv[1]).read().splitlines() if l.startswith("{")][-1]   # (librccl prints a banner after the line)
@@ -132,7 +132,7 @@ PY
       python -c "import __graft_entry__ as g; g.build_test_transport()" >/dev/null 2>&1
       for N in 4 8; do
         SVILS_RCCL_LIBRARY=$R/tests/fakerccl/libfakerccl.so FAKERCCL_ASYNC=1 timeout 700 python bench.py --gpus $N --steps 10 --warmup 2 --test-one-gpu \
-          --extra-list ksharded_config4_astroph_k200 --no-cpu-baseline > $O/bench_gpus${N}_one_gpu_test_mode.json 2> $O/benchN_err$N.txt
+          --full --extra-list ksharded_config4_astroph_k200 --no-cpu-baseline > $O/bench_gpus${N}_one_gpu_test_mode.json 2> $O/benchN_err$N.txt
         echo "N=$N rc=$?"; tail -2 $O/benchN_err$N.txt; tail -c 600 $O/bench_gpus${N}_one_gpu_test_mode.json; echo
       done ;;
     bench8)   # bare `python bench.py --gpus 8 --test-one-gpu` with ALL SEVEN side records (tests' transport; a flow rehearsal,
@@ -140,7 +140,7 @@ PY
       python -c "import __graft_entry__ as g; g.build_test_transport()" >/dev/null 2>&1
       t0=$(date +%s)
       SVILS_RCCL_LIBRARY=$R/tests/fakerccl/libfakerccl.so FAKERCCL_ASYNC=1 timeout 2400 python bench.py --gpus 8 --steps 10 --warmup 2 --test-one-gpu \
-        --no-cpu-baseline > $O/bench_gpus8_all_records_one_gpu_test_mode.json 2> $O/bench8_err.txt
+        --full --no-cpu-baseline > $O/bench_gpus8_all_records_one_gpu_test_mode.json 2> $O/bench8_err.txt
       rc=$?; t1=$(date +%s)
       python - $O/bench_gpus8_all_records_one_gpu_test_mode.json $rc $((t1 - t0)) <<'PY' | tee $O/bench8_summary.txt
 import json, sys
