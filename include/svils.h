@@ -40,7 +40,8 @@ extern "C" {
                                  8: svils_init_gamma (init_gamma2 on the device); svils_set_option / svils_get_option / svils_option_table (every tunable in one documented table; nothing
                                     on a sweep path reads the environment); svils_gather_communities ends the no-wait window of "After the stop";
                                     (additive, same version) svils_link_prob / svils_predict_links: link prediction from the state;
-                                    (additive, same version) svils_findk_*: -findk, the estimate of the number of communities */
+                                    (additive, same version) svils_findk_*: -findk, the estimate of the number of communities;
+                                    (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model */
 
 typedef enum {
   SVILS_OK = 0,
@@ -533,6 +534,47 @@ int svils_findk_report(svils_findk *f, double *training_ll, double *heldout_sums
 int svils_findk_get_state(svils_findk *f, uint32_t *labels, double *values, double *pi);
 /* device milliseconds of the last count, apply, likelihoods and groups (hipEvent brackets; -1: not run yet) */
 int svils_findk_get_timing(svils_findk *f, double ms[4]);
+
+/* ---- -gml / -lcstats: link communities of a fitted model (an ADDITION of ABI 8; a handle of its own) -------------------
+ * The reference's MMSBGen::get_lc_stats and MMSBGen::gml (src/mmsbgen.cc:181-193, 911-961; dispatched at src/main.cc:307-318):
+ *   node pass  pi = gamma / s_i with s_i summed in k order (estimate_all, :700-729); group = the first strict maximum of
+ *              pi from 0 (most_likely_group, src/mmsbgen.hh:112-123); bridgeness = (1 - sqrt(v K / (K - 1))) deg(i) with
+ *              v = sum over k, in k order, of (pi - 1/K)^2 (bridgeness, :230-259)
+ *   link pass  per link p < q: x_k = (pi_p[k] pi_q[k]) beta_k, beta_k = l0 / (l0 + l1) (estimate_beta, src/mmsbgen.hh:213-222);
+ *              u / idx = the first strict maximum of x from 0, ratio = u / s, s the sum of x (inner_prod_max,
+ *              src/matrix.hh:460-476).  The link joins community idx unless ratio < 0.5 (lc_current_draw_helper, :425-470)
+ *              and is a GML edge unless ratio < 0.9 (gml, :936-954); a NaN ratio passes both.  s is summed in a fixed
+ *              tree; links within 2 K DBL_EPSILON ratio of a threshold are decided again with s in k order, so every
+ *              decision is the reference's
+ *   counts     deg_c[i][k] = coloured links of community k at node i (Community, src/community.hh); per community the
+ *              nodes with deg_c > 0, the sum of deg_c and the largest deg_c with its smallest node (deg_stats)
+ * Any k >= 2.  Without a HIP device every entry point answers SVILS_ERR_DEVICE ("no CPU path"); with one, a null handle
+ * SVILS_ERR_ARG. */
+typedef struct svils_lc svils_lc;
+/* device memory: pi [n][k] doubles (gamma is converted in place) and deg_c [n][k] uint32, plus O(n + links) */
+int svils_lc_create(int device, uint32_t n, uint32_t k, svils_lc **out);
+int svils_lc_destroy(svils_lc *h);
+/* links [nlinks][2] with p < q < n, every link of the network (no held-out split), no repeats; any order (the GML list comes
+ * out in (p, q) order, the per-link getters in this order) */
+int svils_lc_set_graph(svils_lc *h, const uint32_t *links, uint64_t nlinks);
+/* gamma [n][k], lambda [k][2]; svils_lc_run consumes the model: set it again before another run */
+int svils_lc_set_model(svils_lc *h, const double *gamma, const double *lambda);
+/* the three passes; synchronises */
+int svils_lc_run(svils_lc *h);
+/* after svils_lc_run (any pointer may be null): group / bridgeness / memberships (#k with deg_c > 0) / influence
+ * (deg_c[i][group]) [n] */
+int svils_lc_get_nodes(svils_lc *h, uint32_t *group, double *bridgeness, uint32_t *memberships, uint32_t *influence);
+int svils_lc_get_degrees(svils_lc *h, uint32_t *deg_c);               /* [n][k] */
+int svils_lc_get_pi(svils_lc *h, double *pi);                         /* [n][k] */
+/* [k] each: nodes with deg_c > 0, the sum of deg_c, the largest deg_c and its smallest node (0 and 0 when empty) */
+int svils_lc_get_communities(svils_lc *h, uint32_t *nodes, uint64_t *degsum, uint32_t *max, uint32_t *argmax);
+/* per link in svils_lc_set_graph order: colour (idx) and flags (1: joins community idx, 2: GML edge, 4: decided by the
+ * sequential recheck); counts[3] = links left out (ratio < 0.5), GML edges, rechecked links */
+int svils_lc_get_links(svils_lc *h, uint32_t *colour, uint8_t *flags, uint64_t counts[3]);
+/* the GML edges in (p, q) order: *count, and with edges non-null [count][3] (p, q, colour) */
+int svils_lc_get_gml(svils_lc *h, uint64_t *count, uint32_t *edges);
+/* device milliseconds of the last run's node pass, link pass (with the recheck) and counts (with the GML list); -1: not run */
+int svils_lc_get_timing(svils_lc *h, double ms[3]);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * Every tunable of the library is a row of ONE table: key, the SVILS_* environment variable that sets its default, the

@@ -37,6 +37,9 @@ EXPORTS = (
     "svils_link_prob", "svils_predict_links",
     "svils_findk_create", "svils_findk_destroy", "svils_findk_set_graph", "svils_findk_init_state", "svils_findk_count",
     "svils_findk_pad_requests", "svils_findk_apply", "svils_findk_report", "svils_findk_get_state", "svils_findk_get_timing",
+    "svils_lc_create", "svils_lc_destroy", "svils_lc_set_graph", "svils_lc_set_model", "svils_lc_run", "svils_lc_get_nodes",
+    "svils_lc_get_degrees", "svils_lc_get_pi", "svils_lc_get_communities", "svils_lc_get_links", "svils_lc_get_gml",
+    "svils_lc_get_timing",
 )
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
 
@@ -165,6 +168,18 @@ def load():
     L.svils_findk_report.argtypes = [vp, C.POINTER(C.c_double), vp, C.POINTER(C.c_uint32), vp]
     L.svils_findk_get_state.argtypes = [vp, vp, vp, vp]
     L.svils_findk_get_timing.argtypes = [vp, vp]
+    L.svils_lc_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.svils_lc_destroy.argtypes = [vp]
+    L.svils_lc_set_graph.argtypes = [vp, vp, C.c_uint64]
+    L.svils_lc_set_model.argtypes = [vp, vp, vp]
+    L.svils_lc_run.argtypes = [vp]
+    L.svils_lc_get_nodes.argtypes = [vp, vp, vp, vp, vp]
+    L.svils_lc_get_degrees.argtypes = [vp, vp]
+    L.svils_lc_get_pi.argtypes = [vp, vp]
+    L.svils_lc_get_communities.argtypes = [vp, vp, vp, vp, vp]
+    L.svils_lc_get_links.argtypes = [vp, vp, vp, vp]
+    L.svils_lc_get_gml.argtypes = [vp, C.POINTER(C.c_uint64), vp]
+    L.svils_lc_get_timing.argtypes = [vp, vp]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):

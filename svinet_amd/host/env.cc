@@ -65,7 +65,7 @@ Env::Env(const Args &a)
       use_init_communities(a.init_comm), init_communities_fname(a.init_comm_fname),
       nmi(a.nmi), ground_truth_fname(a.ground_truth_fname),
       datfname(a.datfname), label(a.label), gpus(a.gpus), rank(a.rank), kshard(a.kshard), sharded((a.sharded || a.gpus > 1) && !a.kshard), comm_rfd(a.comm_rfd), comm_wfds(a.comm_wfds),
-      batch_mode(a.batch), link_sampling(a.link_sampling), findk(a.findk), strid(a.strid),
+      batch_mode(a.batch), link_sampling(a.link_sampling), findk(a.findk), gml(a.gml), lcstats(a.lcstats), strid(a.strid),
       terminate(0), total_pairs(0), ones_prob(0), zeros_prob(1),
       device(a.device), sweep_batch(a.sweep_batch), write_files(a.write_files),
       minibatch(a.minibatch), tau0(a.tau0), kappa(a.kappa), nodetau0(a.nodetau0), nodekappa(a.nodekappa),
@@ -75,7 +75,8 @@ Env::Env(const Args &a)
     prefix.clear();
     return;
   }
-  // output directory name, src/env.hh:503-551
+  // output directory name, src/env.hh:503-568: "gml" for -gml; -lcstats names it like any run (no engine suffix unless
+  // one was given)
   std::ostringstream sa;
   sa << "n" << n << "-" << "k" << k;
   if (label != "") sa << "-" << label;
@@ -85,11 +86,12 @@ Env::Env(const Args &a)
     sa << "-" << q;
   }
   if (seed) sa << "-seed" << seed;
-  if (batch_mode) { sa << "-batch"; reportfreq = 1; }
+  if (batch_mode) { sa << "-batch"; if (!gml) reportfreq = 1; }   // the reference names no directory for -gml (the block is skipped)
   else if (link_sampling) sa << "-linksampling";
   else if (findk) sa << "-findk";
   if (a.nthreads > 0) sa << "-T" << a.nthreads;
-  prefix = a.outdir_root.empty() ? sa.str() : a.outdir_root + "/" + sa.str();
+  const std::string name = gml ? std::string("gml") : sa.str();
+  prefix = a.outdir_root.empty() ? name : a.outdir_root + "/" + name;
 
   fprintf(stdout, "+ Output directory: %s\n", prefix.c_str());
   fflush(stdout);

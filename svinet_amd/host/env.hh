@@ -19,6 +19,7 @@ class Env {
     std::string label = "mmsb";
     bool batch = false, link_sampling = false;
     bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
+    bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
     bool load = false;
     std::string location;
     bool val_load = false;
@@ -99,6 +100,7 @@ class Env {
   int comm_rfd;
   std::vector<int> comm_wfds;
   bool batch_mode, link_sampling, findk;
+  bool gml, lcstats;
   bool strid;
   volatile int terminate;
   // set by Network::set_env_variables

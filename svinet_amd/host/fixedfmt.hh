@@ -79,6 +79,7 @@ class RowOut {
   ~RowOut() { flush(); }
   template <int D> void fixed(double v, char sep) { room(); p_ = fmt_fixed<D>(p_, v, sep); }
   void integer(long v, char sep) { room(); p_ = fmt_int(p_, v, sep); }
+  void text(const char *s) { room(); while (*s) *p_++ = *s++; }   // a literal of < 400 bytes
   void flush() { o_.append(buf_, (size_t)(p_ - buf_)); p_ = buf_; }
  private:
   void room() { if (buf_ + sizeof buf_ - p_ < 400) flush(); }

@@ -3,12 +3,14 @@
 // Accepts the reference's flag set (src/main.cc:114-242, same spelling, same
 // positional/order-sensitive semantics: e.g. -link-sampling resets rfreq to 1,
 // so -rfreq must follow it).  Engines: -link-sampling (the MI355X path), -findk (the
-// estimate of the number of communities, also on the device) and the
+// estimate of the number of communities, also on the device), -gml / -lcstats (the
+// link communities of a fitted model's gamma.txt / lambda.txt, on the device) and the
 // reference's small all-pairs CPU engine -batch (plumbing only); the
 // flags that select the reference's other engines are recognised and rejected
 // with a message instead of being silently ignored.
 #include <csignal>
 #include <cerrno>
+#include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
 #include <cstdio>
@@ -20,6 +22,7 @@
 
 #include "env.hh"
 #include "findk.hh"
+#include "lcstats.hh"
 #include "linksampling.hh"
 #include "mmsbbatch.hh"
 #include "network.hh"
@@ -58,6 +61,11 @@ static void usage() {
           "\t-batch\t\trun batch variational inference over all pairs (host CPU, small graphs)\n\n"
           "\t-findk\t\testimate the number of communities (label propagation over a top-5 sparse gamma, on the GPU);\n"
           "\t\t\tpick -k for -link-sampling from the lines of its communities.txt.  Single GPU; -k only sets alpha = 1/k\n\n"
+          "\t-gml\t\tgenerate a GML format file that visualizes link communities: reads gamma.txt and lambda.txt of the\n"
+          "\t\t\tworking directory (the output directory of a fit) and writes gml/network.gml with the link-community\n"
+          "\t\t\tstatistics (community_stats.txt, node_bridgeness.txt, node_influence.txt, number_of_memberships.txt).\n"
+          "\t\t\tSingle GPU\n\n"
+          "\t-lcstats\tthe link-community statistics of -gml without network.gml, into the run's output directory\n\n"
           "\t-load-validation <fname>\tuse the pairs in the file as the validation set for convergence\n\n"
           "\t-load <dir>\tresume from <dir>gamma.txt / <dir>lambda.txt\n\n"
           "\t-label\t\ttag output directory\n\n"
@@ -118,6 +126,8 @@ int main(int argc, char **argv) {
     else if (is("-batch")) { a.batch = true; a.link_sampling = false; a.rfreq = 1; }
     else if (is("-link-sampling")) { a.link_sampling = true; a.batch = false; a.rfreq = 1; }
     else if (is("-findk")) { a.findk = true; }
+    else if (is("-gml")) { a.gml = true; }
+    else if (is("-lcstats")) { a.lcstats = true; }
     else if (is("-load")) { need(i); a.load = true; a.location = argv[++i]; }
     else if (is("-load-validation")) { need(i); a.val_load = true; a.val_file_location = argv[++i]; }
     else if (is("-load-test")) { need(i); a.test_load = true; a.test_file_location = argv[++i]; }
@@ -164,7 +174,7 @@ int main(int argc, char **argv) {
     else if (is("-stopthresh") || is("-inf") || is("-scale") || is("-itype") || is("-groups-file")) {
       need(i); ++i;   // value flags of other engines: consumed, no effect on this path
     }
-    else if (is("-gen") || is("-ppc") || is("-lcstats") || is("-gml") || is("-stratified") ||
+    else if (is("-gen") || is("-ppc") || is("-stratified") ||
              is("-rnode") || is("-rpair") || is("-orig") || is("-infset") || is("-single") ||
              is("-preprocess") || is("-gp") || is("-adamic-adar") || is("-disjoint") ||
              is("-load-test-sets")) {
@@ -173,12 +183,33 @@ int main(int argc, char **argv) {
     }
     // unknown flags are ignored, as in the reference
   }
-  if (unsupported || !(a.batch || a.link_sampling || a.findk)) {
+  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats)) {
     fprintf(stderr,
-            "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk)%s%s.\n"
+            "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk, -gml, -lcstats)%s%s.\n"
             "Use the reference build for the other engines.\n",
             unsupported ? "; unsupported option " : "", unsupported ? unsupported_flag.c_str() : "");
     return 2;
+  }
+  if (a.gml || a.lcstats) {   // one GPU, one pass over a saved model: the flags of the fitting paths do not apply
+    const char *flag = a.lcstats ? "-lcstats" : "-gml";   // the reference runs -lcstats when both are given (src/main.cc:307-318)
+    const char *why = a.gpus > 1 ? "-gpus N > 1" : a.kshard ? "-kshard" : a.sharded ? "-sharded" : a.minibatch ? "-minibatch"
+                    : !a.predict_pairs_fname.empty() ? "-predict-pairs" : a.recommend ? "-recommend" : nullptr;
+    if (why) {
+      fprintf(stderr, "error: %s is not available with %s (a single-GPU pass over gamma.txt / lambda.txt)\n", why, flag);
+      return 2;
+    }
+    for (const char *m : {"gamma.txt", "lambda.txt"}) {   // the reference asserts on a missing model (src/mmsbgen.cc:79-81)
+      FILE *f = fopen(m, "r");
+      if (!f) {
+        fprintf(stderr, "error: %s needs %s in the working directory (the output directory of a fit): %s\n", flag, m, strerror(errno));
+        return 2;
+      }
+      fclose(f);
+    }
+    if (a.k < 2) {
+      fprintf(stderr, "error: %s needs -k >= 2\n", flag);
+      return 2;
+    }
   }
   if (a.findk) {   // one GPU, whole iterations: the flags of the other paths do not apply
     const char *why = a.gpus > 1 ? "-gpus N > 1" : a.kshard ? "-kshard" : a.sharded ? "-sharded" : a.minibatch ? "-minibatch"
@@ -236,7 +267,7 @@ int main(int argc, char **argv) {
   // graph and runs the (seeded, deterministic) host-side initialisation itself; rank 0 owns the output
   // directory and the files, the others compute their node block (or column slice) only.  The communicator
   // id goes from rank 0 to rank r through a pipe made here.
-  if (a.link_sampling && a.gpus > 1) {
+  if (a.link_sampling && a.gpus > 1 && !a.gml && !a.lcstats) {
     // RCCL shares device buffers between the ranks' processes: the host driver of this GPU pool only supports dmabuf
     // IPC (without it: hipIpcGetMemHandle: invalid argument).  The runtime reads the variable when HIP is first
     // touched -- in the ranks, after the fork below; a value the user exported stays.
@@ -314,6 +345,36 @@ run:
   if (network.ones() == 0 || env.n < 2) {
     fprintf(stderr, "error: no links read from %s; quitting\n", a.datfname.c_str());
     return -1;
+  }
+  if (a.lcstats || a.gml) {                  // src/main.cc:307-318, before -findk and the other engines
+    if (a.lcstats) {
+      printf("+ computing lc stats\n");
+      unlink("ppc");                         // MMSBGen(env, network, true) makes ppc/ in the working directory
+      mkdir("ppc", S_IRWXU | S_IRWXG | S_IROTH | S_IXOTH);
+    } else {
+      printf("+ generating GML file\n");
+    }
+    fflush(stdout);
+    try {
+      LinkCommunities lc(env, network);
+      if (lc.load_model() < 0) return -1;
+      lc.run();
+      lc.write_stats();
+      if (!a.lcstats) lc.write_gml();
+      if (const char *tf = getenv("SVINET_TIMING_FILE")) {   // where the time went (tools/gml_bench.py)
+        if (FILE *f = fopen(tf, "w")) {
+          const double *ms = lc.timing_ms();
+          fprintf(f, "{\"node_ms\": %.4f, \"link_ms\": %.4f, \"count_ms\": %.4f, \"links\": %u, \"unlikely\": %llu, "
+                     "\"gml_edges\": %llu, \"rechecked\": %llu}\n", ms[0], ms[1], ms[2], network.ones(),
+                  (unsigned long long)lc.unlikely(), (unsigned long long)lc.gml_edges(), (unsigned long long)lc.rechecked());
+          fclose(f);
+        }
+      }
+    } catch (const LcError &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return -1;
+    }
+    exit(0);
   }
   if (a.findk) {                             // src/main.cc:321-327, before the other engines (-batch / -link-sampling only name the directory)
     try {

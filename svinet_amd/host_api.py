@@ -341,3 +341,71 @@ class FindK:
             self._h = None
 
     __del__ = close
+
+
+def LinkCommunities(links, gamma, lam, device=0, with_pi=False):
+    """-gml / -lcstats on the device (svils_lc_*) with nothing written to disk: the reference's MMSBGen::get_lc_stats and
+    gml (src/mmsbgen.cc:181-193, 911-961) for the model gamma [n][k], lam [k][2].  `links` is a [E][2] array of sequence
+    ids (p < q, every link of the network) or the path of an edge list, read with the product's reader (n = the rows of
+    gamma).  Returns a dict of numpy arrays: per node group, bridgeness, memberships, influence; deg_c [n][k]; per
+    community comm_nodes, comm_degsum, comm_max, comm_argmax; per link (in the given order) colour, join, gml, rechecked;
+    gml_edges [m][3] (p, q, colour) in (p, q) order; the counts unlikely / rechecked; timing_ms (node, link, count passes);
+    with_pi: pi [n][k]."""
+    from . import _svils
+    gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+    lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1, 2)
+    n, k = gamma.shape
+    out = {}
+    if isinstance(links, (str, bytes, os.PathLike)):
+        s = Setup(links, n, k, host_gamma=False)
+        try:
+            if s.n != n:
+                raise ValueError("the network has %d nodes with links; gamma has %d rows" % (s.n, n))
+            links, out["seq2id"] = s.edges, s.seq2id
+        finally:
+            s.close()
+    links = np.ascontiguousarray(links, dtype=np.uint32).reshape(-1, 2)
+    if lam.shape[0] != k:
+        raise ValueError("lam has %d rows; gamma has %d columns" % (lam.shape[0], k))
+    L = _svils.load()
+    E = links.shape[0]
+
+    def ok(rc):
+        if rc:
+            raise _svils.SvilsError(rc, L.svils_last_error().decode("utf-8", "replace"))
+
+    h = C.c_void_p()
+    ok(L.svils_lc_create(device, n, k, C.byref(h)))
+    try:
+        ok(L.svils_lc_set_graph(h, links.ctypes.data, E))
+        ok(L.svils_lc_set_model(h, gamma.ctypes.data, lam.ctypes.data))
+        ok(L.svils_lc_run(h))
+        for name in ("group", "memberships", "influence"):
+            out[name] = np.zeros(n, np.uint32)
+        out["bridgeness"] = np.zeros(n, np.float64)
+        ok(L.svils_lc_get_nodes(h, out["group"].ctypes.data, out["bridgeness"].ctypes.data, out["memberships"].ctypes.data,
+                                out["influence"].ctypes.data))
+        out["deg_c"] = np.zeros((n, k), np.uint32)
+        ok(L.svils_lc_get_degrees(h, out["deg_c"].ctypes.data))
+        if with_pi:
+            out["pi"] = np.zeros((n, k), np.float64)
+            ok(L.svils_lc_get_pi(h, out["pi"].ctypes.data))
+        out["comm_nodes"], out["comm_degsum"] = np.zeros(k, np.uint32), np.zeros(k, np.uint64)
+        out["comm_max"], out["comm_argmax"] = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        ok(L.svils_lc_get_communities(h, out["comm_nodes"].ctypes.data, out["comm_degsum"].ctypes.data, out["comm_max"].ctypes.data,
+                                      out["comm_argmax"].ctypes.data))
+        colour, flags, counts = np.zeros(E, np.uint32), np.zeros(E, np.uint8), np.zeros(3, np.uint64)
+        ok(L.svils_lc_get_links(h, colour.ctypes.data, flags.ctypes.data, counts.ctypes.data))
+        out["colour"] = colour
+        out["join"], out["gml"], out["rechecked"] = (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0
+        out["unlikely"], out["n_rechecked"] = int(counts[0]), int(counts[2])
+        out["gml_edges"] = np.zeros((int(counts[1]), 3), np.uint32)
+        m = C.c_uint64()
+        ok(L.svils_lc_get_gml(h, C.byref(m), out["gml_edges"].ctypes.data))
+        ms = np.zeros(3, np.float64)
+        ok(L.svils_lc_get_timing(h, ms.ctypes.data))
+        out["timing_ms"] = {"node": ms[0], "link": ms[1], "count": ms[2]}
+        out["links"] = links
+    finally:
+        L.svils_lc_destroy(h)
+    return out
