@@ -17,6 +17,18 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
+int open_device(int device, const char *bad_args) {
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0)
+    return fail(SVILS_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path",
+                e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+  if (bad_args) return fail(SVILS_ERR_ARG, "%s", bad_args);
+  if (device < 0 || device >= ndev) return fail(SVILS_ERR_ARG, "device %d out of range (%d devices)", device, ndev);
+  HIPCHK(hipSetDevice(device));
+  return 0;
+}
+
 int drain_timing(svils_handle *h) {
   for (int i = 0; i < SVILS_KERNEL_COUNT; ++i) {
     for (auto &ev : h->pending[i]) {
@@ -163,13 +175,7 @@ int svils_create(const svils_config *cfg, svils_handle **out) {
   if (cfg->reportfreq == 0) return fail(SVILS_ERR_ARG, "reportfreq must be >= 1");
   uint32_t nb = cfg->node_begin, ne = cfg->node_end ? cfg->node_end : cfg->n;
   if (nb > ne || ne > cfg->n) return fail(SVILS_ERR_ARG, "bad node block [%u,%u) for n=%u", nb, ne, cfg->n);
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return fail(SVILS_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path",
-                e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(SVILS_ERR_ARG, "device %d out of range (%d devices)", cfg->device, ndev);
-  HIPCHK(hipSetDevice(cfg->device));
+  if (int rc = open_device(cfg->device)) return rc;
   if (cfg->k > SVILS_MAX_K) return tiles_create(cfg, out);   // column tiles on this device (svils_handle::tiles)
 
   svils_handle *h = new (std::nothrow) svils_handle();

@@ -17,7 +17,7 @@
 //
 // The sort order (count desc, label asc) is what the reference's qsort with cmppairval gives over a std::map's ascending
 // labels under glibc's merge sort: a stable descending sort.
-#include "svils_handle.h"
+#include "svils_tool.h"
 
 // No fused multiply-adds in this unit: the reference computes every product and sum separately (x86, no contraction);
 // an FMA inside `u > max` compares the exact product and moves the winning label of a tie in compute_and_log_groups.
@@ -289,34 +289,15 @@ __global__ __launch_bounds__(256) void k_groups(uint64_t E, double thresh, const
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(unlikely, bad);
 }
 
-template <class T>
-int dalloc(T **p, size_t count) {
-  *p = nullptr;
-  if (!count) return 0;
-  HIPCHK(hipMalloc((void **)p, count * sizeof(T)));
-  return 0;
-}
-
-uint32_t blocks(uint64_t m, uint32_t per) { return (uint32_t)((m + per - 1) / per); }
-
-int no_device_or_null(const char *name) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(SVILS_ERR_DEVICE, "%s: no HIP device available; this library has no CPU path", name);
-  return fail(SVILS_ERR_ARG, "%s: null handle", name);
-}
-
 }  // namespace
 
-struct svils_findk {
-  int device = 0;
+// events ev[7]: count, compact + records, apply, end of apply, likelihoods, groups, end
+struct svils_findk : ToolHandle {
   uint32_t n = 0;
   double alpha = 0, thresh = 0.5;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[7] = {};                    // count, compact + records, apply, end of apply, likelihoods, groups, end
   bool timed[4] = {};                       // phases with a measurement: count, apply, likelihoods, groups
   uint64_t E = 0, H = 0;
-  // graph
+  // graph (GRAPH scope)
   uint32_t *links = nullptr;                // [E][2] p < q, every link
   uint32_t *held = nullptr;                 // [H][3] p, q, y: the held-out pairs in map order
   uint64_t *rowptr = nullptr;               // training CSR (links not held out)
@@ -325,13 +306,14 @@ struct svils_findk {
   uint32_t n_wave = 0, n_lds = 0, n_hub = 0;
   uint64_t *hub_off = nullptr;              // [n_hub + 1] offsets into hub_scratch (uint32 words)
   uint32_t *hub_scratch = nullptr;
-  // state
+  double *ll = nullptr, *part = nullptr;    // [max(E, H)] likelihoods, their partial sums
+  // state (HANDLE scope)
   uint32_t *labels = nullptr;               // [n][5]
   double *values = nullptr, *pi = nullptr;  // [n][5]
   uint32_t *top_lab = nullptr, *top_cnt = nullptr, *ndist = nullptr;
   uint32_t *rec = nullptr, *pads = nullptr, *counter = nullptr;   // counter[0]: records, counter[1]: unlikely
   uint32_t *masks = nullptr;
-  double *ll = nullptr, *part = nullptr, *sums = nullptr;          // sums[0..3]: training, held-out all / y = 0 / y = 1
+  double *sums = nullptr;                   // [4] training, held-out all / y = 0 / y = 1
   uint32_t npad = 0;
   bool have_graph = false, have_state = false, counted = false;
   std::vector<uint32_t> h_rec;
@@ -340,26 +322,8 @@ struct svils_findk {
 namespace {
 
 void free_graph(svils_findk *f) {
-  for (void *p : {(void *)f->links, (void *)f->held, (void *)f->rowptr, (void *)f->col, (void *)f->bin_wave, (void *)f->bin_lds,
-                  (void *)f->bin_hub, (void *)f->hub_off, (void *)f->hub_scratch, (void *)f->ll, (void *)f->part})
-    if (p) (void)hipFree(p);
-  f->links = f->held = f->col = f->bin_wave = f->bin_lds = f->bin_hub = f->hub_scratch = nullptr;
-  f->rowptr = f->hub_off = nullptr;
-  f->ll = f->part = nullptr;
+  f->release(ToolHandle::GRAPH);
   f->have_graph = false;
-}
-
-int check(svils_findk *f, const char *name) {
-  if (!f) return no_device_or_null(name);
-  HIPCHK(hipSetDevice(f->device));
-  return 0;
-}
-
-template <class T>
-int upload(T **dst, const std::vector<T> &v, hipStream_t st) {
-  if (int rc = dalloc(dst, v.size())) return rc;
-  if (!v.empty()) HIPCHK(hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  return 0;
 }
 
 }  // namespace
@@ -369,36 +333,26 @@ extern "C" {
 int svils_findk_create(int device, uint32_t n, double alpha, double link_thresh, svils_findk **out) {
   if (!out) return fail(SVILS_ERR_ARG, "svils_findk_create: null argument");
   *out = nullptr;
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return fail(SVILS_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path",
-                e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-  if (n < 2 || !(alpha > 0)) return fail(SVILS_ERR_ARG, "svils_findk_create: need n >= 2 and alpha > 0");
-  if (device < 0 || device >= ndev) return fail(SVILS_ERR_ARG, "device %d out of range (%d devices)", device, ndev);
-  HIPCHK(hipSetDevice(device));
+  if (int rc = open_device(device, n < 2 || !(alpha > 0) ? "svils_findk_create: need n >= 2 and alpha > 0" : nullptr)) return rc;
   svils_findk *f = new (std::nothrow) svils_findk();
   if (!f) return fail(SVILS_ERR_NOMEM, "out of host memory");
-  f->device = device;
   f->n = n;
   f->alpha = alpha;
   f->thresh = link_thresh;
-  int rc = 0;
-  if (hipStreamCreateWithFlags(&f->st, hipStreamNonBlocking) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "hipStreamCreate failed");
-  for (int i = 0; !rc && i < 7; ++i)
-    if (hipEventCreate(&f->ev[i]) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "hipEventCreate failed");
+  const auto scope = ToolHandle::HANDLE;
   const size_t ns = (size_t)n * S;
-  if (!rc) rc = dalloc(&f->labels, ns);
-  if (!rc) rc = dalloc(&f->values, ns);
-  if (!rc) rc = dalloc(&f->pi, ns);
-  if (!rc) rc = dalloc(&f->top_lab, ns);
-  if (!rc) rc = dalloc(&f->top_cnt, ns);
-  if (!rc) rc = dalloc(&f->ndist, (size_t)n);
-  if (!rc) rc = dalloc(&f->rec, (size_t)n * 6);
-  if (!rc) rc = dalloc(&f->pads, (size_t)n * 4);
-  if (!rc) rc = dalloc(&f->masks, (size_t)n);
-  if (!rc) rc = dalloc(&f->counter, 2);
-  if (!rc) rc = dalloc(&f->sums, 4);
+  int rc = f->open(device, 7);
+  if (!rc) rc = f->dalloc(scope, &f->labels, ns);
+  if (!rc) rc = f->dalloc(scope, &f->values, ns);
+  if (!rc) rc = f->dalloc(scope, &f->pi, ns);
+  if (!rc) rc = f->dalloc(scope, &f->top_lab, ns);
+  if (!rc) rc = f->dalloc(scope, &f->top_cnt, ns);
+  if (!rc) rc = f->dalloc(scope, &f->ndist, (size_t)n);
+  if (!rc) rc = f->dalloc(scope, &f->rec, (size_t)n * 6);
+  if (!rc) rc = f->dalloc(scope, &f->pads, (size_t)n * 4);
+  if (!rc) rc = f->dalloc(scope, &f->masks, (size_t)n);
+  if (!rc) rc = f->dalloc(scope, &f->counter, 2);
+  if (!rc) rc = f->dalloc(scope, &f->sums, 4);
   if (rc) {
     svils_findk_destroy(f);
     return rc;
@@ -408,17 +362,7 @@ int svils_findk_create(int device, uint32_t n, double alpha, double link_thresh,
 }
 
 int svils_findk_destroy(svils_findk *f) {
-  if (!f) return 0;
-  (void)hipSetDevice(f->device);
-  if (f->st) (void)hipStreamSynchronize(f->st);
-  free_graph(f);
-  for (void *p : {(void *)f->labels, (void *)f->values, (void *)f->pi, (void *)f->top_lab, (void *)f->top_cnt, (void *)f->ndist,
-                  (void *)f->rec, (void *)f->pads, (void *)f->masks, (void *)f->counter, (void *)f->sums})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : f->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (f->st) (void)hipStreamDestroy(f->st);
-  delete f;
+  delete f;   // ~ToolHandle: waits for the stream, frees both scopes
   return 0;
 }
 
@@ -467,19 +411,20 @@ int svils_findk_set_graph(svils_findk *f, const uint32_t *links, uint64_t nlinks
     }
   }
   std::vector<uint32_t> lk(links, links + 2 * nlinks), hp(heldout_pairs, heldout_pairs + 3 * nheldout);
+  const auto scope = ToolHandle::GRAPH;
   int rc = 0;
-  if (!rc) rc = upload(&f->links, lk, f->st);
-  if (!rc) rc = upload(&f->held, hp, f->st);
-  if (!rc) rc = upload(&f->rowptr, rp, f->st);
-  if (!rc) rc = upload(&f->col, col, f->st);
-  if (!rc) rc = upload(&f->bin_wave, bw, f->st);
-  if (!rc) rc = upload(&f->bin_lds, bl, f->st);
-  if (!rc) rc = upload(&f->bin_hub, bh, f->st);
-  if (!rc) rc = upload(&f->hub_off, hoff, f->st);
-  if (!rc) rc = dalloc(&f->hub_scratch, hoff.back());
+  if (!rc) rc = f->upload(scope, &f->links, lk);
+  if (!rc) rc = f->upload(scope, &f->held, hp);
+  if (!rc) rc = f->upload(scope, &f->rowptr, rp);
+  if (!rc) rc = f->upload(scope, &f->col, col);
+  if (!rc) rc = f->upload(scope, &f->bin_wave, bw);
+  if (!rc) rc = f->upload(scope, &f->bin_lds, bl);
+  if (!rc) rc = f->upload(scope, &f->bin_hub, bh);
+  if (!rc) rc = f->upload(scope, &f->hub_off, hoff);
+  if (!rc) rc = f->dalloc(scope, &f->hub_scratch, hoff.back());
   const uint64_t mx = std::max<uint64_t>(std::max<uint64_t>(nlinks, nheldout), 1);
-  if (!rc) rc = dalloc(&f->ll, mx);
-  if (!rc) rc = dalloc(&f->part, blocks(mx, SUM_CHUNK));
+  if (!rc) rc = f->dalloc(scope, &f->ll, mx);
+  if (!rc) rc = f->dalloc(scope, &f->part, blocks(mx, SUM_CHUNK));
   if (!rc && hipStreamSynchronize(f->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "svils_findk_set_graph: upload failed");
   if (rc) {
     free_graph(f);
@@ -651,10 +596,7 @@ int svils_findk_get_timing(svils_findk *f, double ms[4]) {
   if (!ms) return fail(SVILS_ERR_ARG, "svils_findk_get_timing: null argument");
   HIPCHK(hipStreamSynchronize(f->st));
   static const int from[4] = {0, 2, 4, 5}, to[4] = {1, 3, 5, 6};
-  for (int p = 0; p < 4; ++p) {
-    float t = 0;
-    ms[p] = f->timed[p] && hipEventElapsedTime(&t, f->ev[from[p]], f->ev[to[p]]) == hipSuccess ? (double)t : -1.0;
-  }
+  for (int p = 0; p < 4; ++p) ms[p] = f->elapsed_ms(from[p], to[p], f->timed[p]);
   return 0;
 }
 

@@ -241,6 +241,9 @@ inline int settle(svils_handle *h) {
 }
 
 // ---- svils_api.hip
+// the device probe of every *_create: no HIP device (SVILS_ERR_DEVICE), then the caller's own argument refusal `bad_args`
+// (SVILS_ERR_ARG; nullptr: none), then the range check of `device`; makes `device` current
+int open_device(int device, const char *bad_args = nullptr);
 int drain_timing(svils_handle *h);
 int fault_error(uint32_t code);
 void drop_graphs_of(svils_handle *h);

@@ -15,7 +15,7 @@
 //   k_gml_*       the GML edge list: an order-preserving compaction of the links (kept sorted by (p, q)) that pass 0.9
 //
 // Counts are integers, so the atomics of deg_c and of the community reductions are deterministic.
-#include "svils_handle.h"
+#include "svils_tool.h"
 
 // No fused multiply-adds in this unit: the reference computes every product and sum separately (x86, no contraction);
 // a contracted (pi_p pi_q) beta or (pi - 1/K)^2 + v changes the last bit of a ratio or a bridgeness.
@@ -254,43 +254,25 @@ __global__ __launch_bounds__(256) void k_gml_write(uint64_t E, const uint8_t *__
   out[3 * pos + 2] = colour[x];
 }
 
-template <class T>
-int dalloc(T **p, size_t count) {
-  *p = nullptr;
-  if (!count) return 0;
-  HIPCHK(hipMalloc((void **)p, count * sizeof(T)));
-  return 0;
-}
-
-uint32_t blocks(uint64_t m, uint32_t per) { return (uint32_t)((m + per - 1) / per); }
-
-int no_device_or_null(const char *name) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(SVILS_ERR_DEVICE, "%s: no HIP device available; this library has no CPU path", name);
-  return fail(SVILS_ERR_ARG, "%s: null handle", name);
-}
-
 }  // namespace
 
-struct svils_lc {
-  int device = 0;
+// events ev[4]: node pass, link pass (+ recheck), counts (+ GML list), end
+struct svils_lc : ToolHandle {
   uint32_t n = 0, k = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {};                 // node pass, link pass (+ recheck), counts (+ GML list), end
   bool timed = false;
   uint64_t E = 0;
-  // graph: links sorted by (p, q); order[x] = the caller's index of sorted link x
+  // graph (GRAPH scope): links sorted by (p, q); order[x] = the caller's index of sorted link x
   uint32_t *links = nullptr, *deg = nullptr;
   std::vector<uint32_t> order;
   bool identity = true;                  // the caller's links were sorted already
-  // model / results
-  double *pi = nullptr, *lam = nullptr, *beta = nullptr, *bridg = nullptr;
-  uint32_t *group = nullptr, *memb = nullptr, *infl = nullptr, *degc = nullptr;
-  uint32_t *colour = nullptr, *blist = nullptr, *counters = nullptr, *bcnt = nullptr, *gml = nullptr;
+  uint32_t *colour = nullptr, *blist = nullptr, *bcnt = nullptr, *gml = nullptr;   // per link / per block of 256 links
   uint8_t *flags = nullptr;
+  unsigned long long *boff = nullptr;
+  // model / results (HANDLE scope)
+  double *pi = nullptr, *lam = nullptr, *beta = nullptr, *bridg = nullptr;
+  uint32_t *group = nullptr, *memb = nullptr, *infl = nullptr, *degc = nullptr, *counters = nullptr;
   uint32_t *cnodes = nullptr;
-  unsigned long long *csum = nullptr, *ckey = nullptr, *boff = nullptr, *gtotal = nullptr;
+  unsigned long long *csum = nullptr, *ckey = nullptr, *gtotal = nullptr;
   bool have_graph = false, have_model = false, done = false;
   uint64_t n_gml = 0, n_band = 0, n_unlikely = 0;
 };
@@ -298,19 +280,8 @@ struct svils_lc {
 namespace {
 
 void free_graph(svils_lc *h) {
-  for (void *p : {(void *)h->links, (void *)h->deg, (void *)h->colour, (void *)h->flags, (void *)h->blist, (void *)h->bcnt,
-                  (void *)h->boff, (void *)h->gml})
-    if (p) (void)hipFree(p);
-  h->links = h->deg = h->colour = h->blist = h->bcnt = h->gml = nullptr;
-  h->flags = nullptr;
-  h->boff = nullptr;
+  h->release(ToolHandle::GRAPH);
   h->have_graph = h->done = false;
-}
-
-int check(svils_lc *h, const char *name) {
-  if (!h) return no_device_or_null(name);
-  HIPCHK(hipSetDevice(h->device));
-  return 0;
 }
 
 int check_done(svils_lc *h, const char *name) {
@@ -327,37 +298,27 @@ extern "C" {
 int svils_lc_create(int device, uint32_t n, uint32_t k, svils_lc **out) {
   if (!out) return fail(SVILS_ERR_ARG, "svils_lc_create: null argument");
   *out = nullptr;
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return fail(SVILS_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path",
-                e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-  if (n < 1 || k < 2) return fail(SVILS_ERR_ARG, "svils_lc_create: need n >= 1 and k >= 2");
-  if (device < 0 || device >= ndev) return fail(SVILS_ERR_ARG, "device %d out of range (%d devices)", device, ndev);
-  HIPCHK(hipSetDevice(device));
+  if (int rc = open_device(device, n < 1 || k < 2 ? "svils_lc_create: need n >= 1 and k >= 2" : nullptr)) return rc;
   svils_lc *h = new (std::nothrow) svils_lc();
   if (!h) return fail(SVILS_ERR_NOMEM, "out of host memory");
-  h->device = device;
   h->n = n;
   h->k = k;
-  int rc = 0;
-  if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "hipStreamCreate failed");
-  for (int i = 0; !rc && i < 4; ++i)
-    if (hipEventCreate(&h->ev[i]) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "hipEventCreate failed");
+  const auto scope = ToolHandle::HANDLE;
   const size_t nk = (size_t)n * k;
-  if (!rc) rc = dalloc(&h->pi, nk);
-  if (!rc) rc = dalloc(&h->degc, nk);
-  if (!rc) rc = dalloc(&h->lam, 2 * (size_t)k);
-  if (!rc) rc = dalloc(&h->beta, (size_t)k + 1);
-  if (!rc) rc = dalloc(&h->bridg, (size_t)n);
-  if (!rc) rc = dalloc(&h->group, (size_t)n);
-  if (!rc) rc = dalloc(&h->memb, (size_t)n);
-  if (!rc) rc = dalloc(&h->infl, (size_t)n);
-  if (!rc) rc = dalloc(&h->cnodes, (size_t)k);
-  if (!rc) rc = dalloc(&h->csum, (size_t)k);
-  if (!rc) rc = dalloc(&h->ckey, (size_t)k);
-  if (!rc) rc = dalloc(&h->counters, 2);
-  if (!rc) rc = dalloc(&h->gtotal, 1);
+  int rc = h->open(device, 4);
+  if (!rc) rc = h->dalloc(scope, &h->pi, nk);
+  if (!rc) rc = h->dalloc(scope, &h->degc, nk);
+  if (!rc) rc = h->dalloc(scope, &h->lam, 2 * (size_t)k);
+  if (!rc) rc = h->dalloc(scope, &h->beta, (size_t)k + 1);
+  if (!rc) rc = h->dalloc(scope, &h->bridg, (size_t)n);
+  if (!rc) rc = h->dalloc(scope, &h->group, (size_t)n);
+  if (!rc) rc = h->dalloc(scope, &h->memb, (size_t)n);
+  if (!rc) rc = h->dalloc(scope, &h->infl, (size_t)n);
+  if (!rc) rc = h->dalloc(scope, &h->cnodes, (size_t)k);
+  if (!rc) rc = h->dalloc(scope, &h->csum, (size_t)k);
+  if (!rc) rc = h->dalloc(scope, &h->ckey, (size_t)k);
+  if (!rc) rc = h->dalloc(scope, &h->counters, 2);
+  if (!rc) rc = h->dalloc(scope, &h->gtotal, 1);
   if (rc) {
     svils_lc_destroy(h);
     return rc;
@@ -367,17 +328,7 @@ int svils_lc_create(int device, uint32_t n, uint32_t k, svils_lc **out) {
 }
 
 int svils_lc_destroy(svils_lc *h) {
-  if (!h) return 0;
-  (void)hipSetDevice(h->device);
-  if (h->st) (void)hipStreamSynchronize(h->st);
-  free_graph(h);
-  for (void *p : {(void *)h->pi, (void *)h->degc, (void *)h->lam, (void *)h->beta, (void *)h->bridg, (void *)h->group, (void *)h->memb,
-                  (void *)h->infl, (void *)h->cnodes, (void *)h->csum, (void *)h->ckey, (void *)h->counters, (void *)h->gtotal})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->st) (void)hipStreamDestroy(h->st);
-  delete h;
+  delete h;   // ~ToolHandle: waits for the stream, frees both scopes
   return 0;
 }
 
@@ -414,15 +365,16 @@ int svils_lc_set_graph(svils_lc *h, const uint32_t *links, uint64_t nlinks) {
     src = sl.data();
   }
   const uint64_t nb = std::max<uint64_t>(blocks(nlinks, 256), 1);
+  const auto scope = ToolHandle::GRAPH;
   int rc = 0;
-  if (!rc) rc = dalloc(&h->links, 2 * nlinks);
-  if (!rc) rc = dalloc(&h->deg, (size_t)n);
-  if (!rc) rc = dalloc(&h->colour, nlinks);
-  if (!rc) rc = dalloc(&h->flags, nlinks);
-  if (!rc) rc = dalloc(&h->blist, nlinks);
-  if (!rc) rc = dalloc(&h->gml, 3 * nlinks);
-  if (!rc) rc = dalloc(&h->bcnt, nb);
-  if (!rc) rc = dalloc(&h->boff, nb);
+  if (!rc) rc = h->dalloc(scope, &h->links, 2 * nlinks);
+  if (!rc) rc = h->dalloc(scope, &h->deg, (size_t)n);
+  if (!rc) rc = h->dalloc(scope, &h->colour, nlinks);
+  if (!rc) rc = h->dalloc(scope, &h->flags, nlinks);
+  if (!rc) rc = h->dalloc(scope, &h->blist, nlinks);
+  if (!rc) rc = h->dalloc(scope, &h->gml, 3 * nlinks);
+  if (!rc) rc = h->dalloc(scope, &h->bcnt, nb);
+  if (!rc) rc = h->dalloc(scope, &h->boff, nb);
   if (!rc && nlinks && hipMemcpy(h->links, src, 2 * nlinks * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
     rc = fail(SVILS_ERR_DEVICE, "svils_lc_set_graph: upload failed");
   if (!rc && hipMemcpy(h->deg, deg.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
@@ -578,10 +530,7 @@ int svils_lc_get_timing(svils_lc *h, double ms[3]) {
   if (int rc = check(h, "svils_lc_get_timing")) return rc;
   if (!ms) return fail(SVILS_ERR_ARG, "svils_lc_get_timing: null argument");
   HIPCHK(hipStreamSynchronize(h->st));
-  for (int p = 0; p < 3; ++p) {
-    float t = 0;
-    ms[p] = h->timed && hipEventElapsedTime(&t, h->ev[p], h->ev[p + 1]) == hipSuccess ? (double)t : -1.0;
-  }
+  for (int p = 0; p < 3; ++p) ms[p] = h->elapsed_ms(p, p + 1, h->timed);
   return 0;
 }
 

@@ -17,6 +17,16 @@
 
 using namespace svinet;
 
+// fn()'s result, or the svils_error of the svils_* call that failed in it
+template <class Fn>
+static int svils_rc(Fn fn) {
+  try {
+    return fn();
+  } catch (const SvilsError &e) {
+    return e.rc;
+  }
+}
+
 extern "C" {
 
 typedef struct {
@@ -228,9 +238,7 @@ static svih_findk *make_findk(const svih_options *o, const char *path, const int
     s->net->read_pairs(pairs, nlines);
   }
   s->env->n = s->net->n() - s->net->singles();   // src/main.cc:291
-  try {
-    s->fk.reset(new FindK(*s->env, *s->net));
-  } catch (const FindKError &e) {   // svils_last_error() keeps the library's text
+  if (svils_rc([&] { s->fk.reset(new FindK(*s->env, *s->net)); return 0; })) {   // svils_last_error() keeps the library's text
     delete s;
     return nullptr;
   }
@@ -242,13 +250,7 @@ svih_findk *svih_findk_from_pairs(const int32_t *pairs, uint64_t nlines, const s
   return make_findk(o, nullptr, pairs, nlines, device);
 }
 void svih_findk_free(svih_findk *s) { delete s; }
-int svih_findk_step(svih_findk *s) {
-  try {
-    return s->fk->step();
-  } catch (const FindKError &e) {
-    return e.rc;
-  }
-}
+int svih_findk_step(svih_findk *s) { return svils_rc([&] { return s->fk->step(); }); }
 uint32_t svih_findk_n(const svih_findk *s) { return s->fk->n(); }
 uint32_t svih_findk_iter(const svih_findk *s) { return s->fk->iter(); }
 uint32_t svih_findk_unlikely(const svih_findk *s) { return s->fk->unlikely(); }

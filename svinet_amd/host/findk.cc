@@ -9,23 +9,9 @@
 #include <cstring>
 
 #include "svils.h"
+#include "util.hh"
 
 namespace svinet {
-
-namespace {
-FILE *open_or_die(const std::string &path, const char *what) {
-  FILE *f = fopen(path.c_str(), "w");
-  if (!f) {
-    printf("cannot open %s file:%s\n", what, strerror(errno));
-    exit(-1);
-  }
-  return f;
-}
-
-[[noreturn]] void die(const char *what, int rc) {
-  throw FindKError(rc, std::string(what) + " failed: " + svils_last_error());
-}
-}  // namespace
 
 // FastInit::FastInit, src/fastinit.cc:8-156
 FindK::FindK(Env &env, Network &network, bool attach_device)
@@ -145,7 +131,7 @@ void FindK::init_heldout() {
 
 void FindK::attach() {
   int rc = svils_findk_create(env_.device, n_, env_.alpha, env_.link_thresh, &h_);
-  if (rc) die("svils_findk_create", rc);
+  if (rc) throw_svils("svils_findk_create", rc);
   const std::vector<Edge> &ed = network_.edges();
   std::vector<uint32_t> links(2 * ed.size());
   std::vector<uint8_t> held(ed.size(), 0);
@@ -154,8 +140,8 @@ void FindK::attach() {
     links[2 * x + 1] = ed[x].second;
     held[x] = heldout_map_.count(ed[x]) ? 1 : 0;
   }
-  if ((rc = svils_findk_set_graph(h_, links.data(), ed.size(), held.data(), held_.data(), held_.size() / 3))) die("svils_findk_set_graph", rc);
-  if ((rc = svils_findk_init_state(h_, labels_.data(), values_.data()))) die("svils_findk_init_state", rc);
+  if ((rc = svils_findk_set_graph(h_, links.data(), ed.size(), held.data(), held_.data(), held_.size() / 3))) throw_svils("svils_findk_set_graph", rc);
+  if ((rc = svils_findk_init_state(h_, labels_.data(), values_.data()))) throw_svils("svils_findk_init_state", rc);
 }
 
 int FindK::run() {
@@ -174,10 +160,10 @@ int FindK::step() {
   // the count and the top 5 on the device, the padding draws here (:217-225), set_gamma + estimate_all_pi on the device
   uint32_t m = 0;
   int rc = svils_findk_count(h_, &m);
-  if (rc) die("svils_findk_count", rc);
+  if (rc) throw_svils("svils_findk_count", rc);
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<uint32_t> nodes(m), nd(m), lab(4 * (size_t)m), pads(4 * (size_t)m, 0);
-  if ((rc = svils_findk_pad_requests(h_, nodes.data(), nd.data(), lab.data()))) die("svils_findk_pad_requests", rc);
+  if ((rc = svils_findk_pad_requests(h_, nodes.data(), nd.data(), lab.data()))) throw_svils("svils_findk_pad_requests", rc);
   for (uint32_t x = 0; x < m; ++x) {
     const uint32_t *have = &lab[4 * (size_t)x];
     for (uint32_t j = nd[x]; j < S; ++j) {   // a draw already in the node's map is redrawn; earlier pads are not checked
@@ -188,11 +174,11 @@ int FindK::step() {
   }
   pad_s_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   npad_ = m;
-  if ((rc = svils_findk_apply(h_, pads.data()))) die("svils_findk_apply", rc);
+  if ((rc = svils_findk_apply(h_, pads.data()))) throw_svils("svils_findk_apply", rc);
   double sums[3] = {0, 0, 0};
   masks_.resize(n_);
-  if ((rc = svils_findk_report(h_, &training_ll_, sums, &unlikely_, masks_.data()))) die("svils_findk_report", rc);
-  if ((rc = svils_findk_get_state(h_, labels_.data(), values_.data(), nullptr))) die("svils_findk_get_state", rc);
+  if ((rc = svils_findk_report(h_, &training_ll_, sums, &unlikely_, masks_.data()))) throw_svils("svils_findk_report", rc);
+  if ((rc = svils_findk_get_state(h_, labels_.data(), values_.data(), nullptr))) throw_svils("svils_findk_get_state", rc);
   printf("avg. link training likelihood = %.5f\n", training_ll_);
   iter_++;
   printf("iteration = %d took %d secs\n", iter_, duration());

@@ -10,7 +10,6 @@
 #include <cstdio>
 #include <ctime>
 #include <map>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -18,21 +17,17 @@
 #include "network.hh"
 #include "nmi.hh"
 #include "rng.hh"
+#include "util.hh"
 
 struct svils_findk;
 
 namespace svinet {
 
-// a failed svils_findk_* call (rc: its svils_error)
-struct FindKError : std::runtime_error {
-  FindKError(int code, const std::string &msg) : std::runtime_error(msg), rc(code) {}
-  int rc;
-};
-
 class FindK {
  public:
   static constexpr uint32_t S = 5;   // FastInit::_k
-  // attach_device = false: the host-side state only (init_gamma and the held-out sample), no HIP device touched
+  // attach_device = false: the host-side state only (init_gamma and the held-out sample), no HIP device touched.
+  // A failed svils_findk_* call throws SvilsError (util.hh), here and in step().
   FindK(Env &env, Network &network, bool attach_device = true);
   ~FindK();
 

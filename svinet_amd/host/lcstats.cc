@@ -1,8 +1,6 @@
 // lcstats.cc -- -gml / -lcstats (src/mmsbgen.cc:74-150, 181-285, 418-499, 911-961).  See lcstats.hh.
 #include "lcstats.hh"
 
-#include <sched.h>
-
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -13,35 +11,16 @@
 
 #include "fixedfmt.hh"
 #include "svils.h"
+#include "util.hh"
 
 namespace svinet {
 
 namespace {
-unsigned worker_threads() {   // formatting / parsing threads: the affinity mask, at most 16
-  unsigned n = std::thread::hardware_concurrency();
-  cpu_set_t set;
-  if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::min<unsigned>(n ? n : 1u, (unsigned)CPU_COUNT(&set));
-  return std::max(1u, std::min(n, 16u));
-}
-
-[[noreturn]] void die(const char *what, int rc) {
-  throw LcError(rc, std::string(what) + " failed: " + svils_last_error());
-}
-
-FILE *open_or_die(const std::string &path, const char *what) {
-  FILE *f = fopen(path.c_str(), "w");
-  if (!f) {
-    printf("cannot open %s file:%s\n", what, strerror(errno));
-    exit(-1);
-  }
-  return f;
-}
-
 // rows [0, n) formatted by row(i, RowOut &) in blocks on worker threads, written in order
 template <class RowFn>
 void write_text(const std::string &path, const char *what, uint32_t n, RowFn row) {
   FILE *f = open_or_die(path, what);
-  const unsigned T = n < 4096 ? 1u : worker_threads();
+  const unsigned T = n < 4096 ? 1u : std::min(usable_cpus(), 16u);
   const uint32_t B = 4096;   // rows per block
   std::vector<std::string> buf(T);
   for (uint64_t w0 = 0; w0 < n; w0 += (uint64_t)T * B) {
@@ -94,7 +73,7 @@ int read_text_rows(const std::string &path, uint32_t skip, uint32_t cols, uint32
     fprintf(stderr, "error: %s has %zu rows, expected %u\n", path.c_str(), start.size(), rows);
     return -1;
   }
-  const unsigned T = rows < 4096 ? 1u : worker_threads();
+  const unsigned T = rows < 4096 ? 1u : std::min(usable_cpus(), 16u);
   std::vector<long> first_bad(T, -1);
   auto part = [&](unsigned t) {
     const uint64_t a = (uint64_t)rows * t / T, b = (uint64_t)rows * (t + 1) / T;
@@ -154,19 +133,19 @@ int LinkCommunities::load_model(const std::string &dir) {
 
 void LinkCommunities::run() {
   int rc = svils_lc_create(env_.device, n_, k_, &h_);
-  if (rc) die("svils_lc_create", rc);
+  if (rc) throw_svils("svils_lc_create", rc);
   const std::vector<Edge> &ed = network_.edges();
   std::vector<uint32_t> links(2 * ed.size());
   for (size_t x = 0; x < ed.size(); ++x) {
     links[2 * x] = ed[x].first;
     links[2 * x + 1] = ed[x].second;
   }
-  if ((rc = svils_lc_set_graph(h_, links.data(), ed.size()))) die("svils_lc_set_graph", rc);
-  if ((rc = svils_lc_set_model(h_, gamma_.data(), lambda_.data()))) die("svils_lc_set_model", rc);
+  if ((rc = svils_lc_set_graph(h_, links.data(), ed.size()))) throw_svils("svils_lc_set_graph", rc);
+  if ((rc = svils_lc_set_model(h_, gamma_.data(), lambda_.data()))) throw_svils("svils_lc_set_model", rc);
   std::vector<double>().swap(gamma_);
   printf("+ Computing link communities\n");
   fflush(stdout);
-  if ((rc = svils_lc_run(h_))) die("svils_lc_run", rc);
+  if ((rc = svils_lc_run(h_))) throw_svils("svils_lc_run", rc);
   group_.resize(n_);
   memb_.resize(n_);
   infl_.resize(n_);
@@ -176,13 +155,13 @@ void LinkCommunities::run() {
   csum_.resize(k_);
   cmax_.resize(k_);
   cargmax_.resize(k_);
-  if ((rc = svils_lc_get_nodes(h_, group_.data(), bridg_.data(), memb_.data(), infl_.data()))) die("svils_lc_get_nodes", rc);
-  if ((rc = svils_lc_get_degrees(h_, degc_.data()))) die("svils_lc_get_degrees", rc);
-  if ((rc = svils_lc_get_communities(h_, cnodes_.data(), csum_.data(), cmax_.data(), cargmax_.data()))) die("svils_lc_get_communities", rc);
-  if ((rc = svils_lc_get_links(h_, nullptr, nullptr, counts_))) die("svils_lc_get_links", rc);
+  if ((rc = svils_lc_get_nodes(h_, group_.data(), bridg_.data(), memb_.data(), infl_.data()))) throw_svils("svils_lc_get_nodes", rc);
+  if ((rc = svils_lc_get_degrees(h_, degc_.data()))) throw_svils("svils_lc_get_degrees", rc);
+  if ((rc = svils_lc_get_communities(h_, cnodes_.data(), csum_.data(), cmax_.data(), cargmax_.data()))) throw_svils("svils_lc_get_communities", rc);
+  if ((rc = svils_lc_get_links(h_, nullptr, nullptr, counts_))) throw_svils("svils_lc_get_links", rc);
   gml_.resize(3 * counts_[1]);
-  if ((rc = svils_lc_get_gml(h_, nullptr, gml_.data()))) die("svils_lc_get_gml", rc);
-  if ((rc = svils_lc_get_timing(h_, ms_))) die("svils_lc_get_timing", rc);
+  if ((rc = svils_lc_get_gml(h_, nullptr, gml_.data()))) throw_svils("svils_lc_get_gml", rc);
+  if ((rc = svils_lc_get_timing(h_, ms_))) throw_svils("svils_lc_get_timing", rc);
   svils_lc_destroy(h_);
   h_ = nullptr;
 }

@@ -7,22 +7,16 @@
 // include/svils.h, and the files are written here in the reference's formats.
 #pragma once
 #include <cstdint>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "env.hh"
 #include "network.hh"
+#include "util.hh"
 
 struct svils_lc;
 
 namespace svinet {
-
-// a failed svils_lc_* call (rc: its svils_error)
-struct LcError : std::runtime_error {
-  LcError(int code, const std::string &msg) : std::runtime_error(msg), rc(code) {}
-  int rc;
-};
 
 // Rows of a whitespace-separated text matrix, parsed by worker threads: every line must hold at least skip + cols numbers;
 // the first skip go to lead[row][skip] (if non-null), the next cols to out[row][cols].  Exactly `rows` lines.  Returns 0,
@@ -37,7 +31,7 @@ class LinkCommunities {
   // gamma.txt and lambda.txt of `dir` ("" = the working directory): n rows whose id column matches the reader's
   // numbering, k rows.  0, or -1 with a message on stderr.
   int load_model(const std::string &dir = "");
-  void run();                 // the three device passes (throws LcError)
+  void run();                 // the three device passes (throws SvilsError)
   // community_stats.txt, node_bridgeness.txt, node_influence.txt, number_of_memberships.txt into Env's directory
   void write_stats() const;
   void write_gml() const;     // network.gml (after write_stats: the reference's gml() calls get_lc_stats first)

@@ -6,7 +6,6 @@
 
 #include <algorithm>
 #include <fcntl.h>
-#include <sched.h>
 #include <sys/mman.h>
 #include <unistd.h>
 #include <cerrno>
@@ -17,6 +16,7 @@
 
 #include "fixedfmt.hh"
 #include "svils.h"
+#include "util.hh"
 
 namespace svinet {
 
@@ -24,41 +24,6 @@ namespace {
 void die_svils(const char *what) {
   fprintf(stderr, "error: %s: %s\n", what, svils_last_error());
   exit(-1);
-}
-FILE *open_or_die(const std::string &path, const char *what) {
-  FILE *f = fopen(path.c_str(), "w");
-  if (!f) {
-    printf("cannot open %s file:%s\n", what, strerror(errno));
-    exit(-1);
-  }
-  return f;
-}
-// CPUs this process may really use: the affinity mask and the cgroup CPU quota (v2 cpu.max, v1 cfs_quota_us), not the
-// machine's core count -- a container with a 16-CPU quota on a 256-core host gains nothing from 64 threads
-unsigned usable_cpus() {
-  unsigned n = std::thread::hardware_concurrency();
-  cpu_set_t set;
-  if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::min<unsigned>(n ? n : 1u, (unsigned)CPU_COUNT(&set));
-  double quota = 0.0;
-  if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-    char a[64];
-    long per = 0;
-    if (fscanf(f, "%63s %ld", a, &per) == 2 && strcmp(a, "max") != 0 && per > 0) quota = atof(a) / (double)per;
-    fclose(f);
-  } else if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {
-    long q = -1, per = 100000;
-    if (fscanf(g, "%ld", &q) != 1) q = -1;
-    fclose(g);
-    if (FILE *h2 = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(h2, "%ld", &per) != 1) per = 100000; fclose(h2); }
-    if (q > 0 && per > 0) quota = (double)q / (double)per;
-  }
-  if (quota >= 1.0) n = std::min<unsigned>(n, (unsigned)(quota + 0.5));
-  return std::max(1u, n);
-}
-double now_s() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 }  // namespace
 

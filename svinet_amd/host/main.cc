@@ -49,6 +49,44 @@ static void forward_handler(int sig) {
     if (k > 0) kill(k, sig);
 }
 
+// The single-GPU tool modes refuse the flags of the fitting paths.  Every flag a mode may refuse, in the order the checks
+// name them: a mode reports the first one set among its own.
+enum : unsigned { F_BATCH = 1, F_GPUS = 2, F_KSHARD = 4, F_SHARDED = 8, F_MINIBATCH = 16, F_PAIRS = 32, F_RECOMMEND = 64, F_K2048 = 128 };
+
+struct ToolMode {
+  unsigned refuses;   // F_* bits
+  const char *fmt;    // the refusal: %1$s the mode's flag, %2$s the refused flag
+};
+static const ToolMode kLinkCommunities = {   // -gml / -lcstats: one pass over a saved model
+    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND,
+    "error: %2$s is not available with %1$s (a single-GPU pass over gamma.txt / lambda.txt)\n"};
+static const ToolMode kFindK = {             // -findk: whole iterations
+    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND,
+    "error: %2$s is not available with %1$s (a single-GPU run)\n"};
+static const ToolMode kPrediction = {        // -predict-pairs / -recommend after a fit
+    F_BATCH | F_GPUS | F_KSHARD | F_SHARDED | F_K2048,
+    "error: %1$s is not available with %2$s (single-GPU -link-sampling runs with -k <= 2048 only)\n"};
+
+// true (the refusal printed) when a flag `mode` refuses is set
+static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) {
+  const struct { unsigned bit; bool set; const char *name; } flags[] = {
+      {F_BATCH, a.batch, "-batch"},
+      {F_GPUS, a.gpus > 1, "-gpus N > 1"},
+      {F_KSHARD, a.kshard, "-kshard"},
+      {F_SHARDED, a.sharded, "-sharded"},
+      {F_MINIBATCH, a.minibatch != 0, "-minibatch"},
+      {F_PAIRS, !a.predict_pairs_fname.empty(), "-predict-pairs"},
+      {F_RECOMMEND, a.recommend != 0, "-recommend"},
+      {F_K2048, a.k > 2048, "-k > 2048"},
+  };
+  for (const auto &f : flags)
+    if ((mode.refuses & f.bit) && f.set) {
+      fprintf(stderr, mode.fmt, flag, f.name);
+      return true;
+    }
+  return false;
+}
+
 static void usage() {
   fprintf(stdout,
           "\nSVINET (MI355X link-sampling build): stochastic variational inference of undirected networks\n"
@@ -190,14 +228,9 @@ int main(int argc, char **argv) {
             unsupported ? "; unsupported option " : "", unsupported ? unsupported_flag.c_str() : "");
     return 2;
   }
-  if (a.gml || a.lcstats) {   // one GPU, one pass over a saved model: the flags of the fitting paths do not apply
+  if (a.gml || a.lcstats) {
     const char *flag = a.lcstats ? "-lcstats" : "-gml";   // the reference runs -lcstats when both are given (src/main.cc:307-318)
-    const char *why = a.gpus > 1 ? "-gpus N > 1" : a.kshard ? "-kshard" : a.sharded ? "-sharded" : a.minibatch ? "-minibatch"
-                    : !a.predict_pairs_fname.empty() ? "-predict-pairs" : a.recommend ? "-recommend" : nullptr;
-    if (why) {
-      fprintf(stderr, "error: %s is not available with %s (a single-GPU pass over gamma.txt / lambda.txt)\n", why, flag);
-      return 2;
-    }
+    if (refused(a, kLinkCommunities, flag)) return 2;
     for (const char *m : {"gamma.txt", "lambda.txt"}) {   // the reference asserts on a missing model (src/mmsbgen.cc:79-81)
       FILE *f = fopen(m, "r");
       if (!f) {
@@ -211,26 +244,14 @@ int main(int argc, char **argv) {
       return 2;
     }
   }
-  if (a.findk) {   // one GPU, whole iterations: the flags of the other paths do not apply
-    const char *why = a.gpus > 1 ? "-gpus N > 1" : a.kshard ? "-kshard" : a.sharded ? "-sharded" : a.minibatch ? "-minibatch"
-                    : !a.predict_pairs_fname.empty() ? "-predict-pairs" : a.recommend ? "-recommend" : nullptr;
-    if (why) {
-      fprintf(stderr, "error: %s is not available with -findk (a single-GPU run)\n", why);
-      return 2;
-    }
-  }
+  if (a.findk && refused(a, kFindK, "-findk")) return 2;
   if (!a.predict_pairs_fname.empty() || a.recommend) {   // link prediction (svils_link_prob / svils_predict_links)
     const char *flag = a.recommend ? "-recommend" : "-predict-pairs";
     if (a.recommend && (a.recommend < 1 || a.recommend > 256)) {
       fprintf(stderr, "error: -recommend wants a count of 1 .. 256 links per node\n");
       return 2;
     }
-    const char *why = a.batch ? "-batch" : a.gpus > 1 ? "-gpus N > 1" : a.kshard ? "-kshard" : a.sharded ? "-sharded"
-                    : a.k > 2048 ? "-k > 2048" : nullptr;
-    if (why) {
-      fprintf(stderr, "error: %s is not available with %s (single-GPU -link-sampling runs with -k <= 2048 only)\n", flag, why);
-      return 2;
-    }
+    if (refused(a, kPrediction, flag)) return 2;
     if (!a.predict_pairs_fname.empty()) {
       FILE *f = fopen(a.predict_pairs_fname.c_str(), "r");
       if (!f) {
@@ -346,16 +367,16 @@ run:
     fprintf(stderr, "error: no links read from %s; quitting\n", a.datfname.c_str());
     return -1;
   }
-  if (a.lcstats || a.gml) {                  // src/main.cc:307-318, before -findk and the other engines
-    if (a.lcstats) {
-      printf("+ computing lc stats\n");
-      unlink("ppc");                         // MMSBGen(env, network, true) makes ppc/ in the working directory
-      mkdir("ppc", S_IRWXU | S_IRWXG | S_IROTH | S_IXOTH);
-    } else {
-      printf("+ generating GML file\n");
-    }
-    fflush(stdout);
-    try {
+  try {                                      // the device tools: a failed svils_* call ends the run here
+    if (a.lcstats || a.gml) {                // src/main.cc:307-318, before -findk and the other engines
+      if (a.lcstats) {
+        printf("+ computing lc stats\n");
+        unlink("ppc");                       // MMSBGen(env, network, true) makes ppc/ in the working directory
+        mkdir("ppc", S_IRWXU | S_IRWXG | S_IROTH | S_IXOTH);
+      } else {
+        printf("+ generating GML file\n");
+      }
+      fflush(stdout);
       LinkCommunities lc(env, network);
       if (lc.load_model() < 0) return -1;
       lc.run();
@@ -370,21 +391,15 @@ run:
           fclose(f);
         }
       }
-    } catch (const LcError &e) {
-      fprintf(stderr, "error: %s\n", e.what());
-      return -1;
+      exit(0);
     }
-    exit(0);
-  }
-  if (a.findk) {                             // src/main.cc:321-327, before the other engines (-batch / -link-sampling only name the directory)
-    try {
-      FindK fk(env, network);
-      fk.run();
-    } catch (const FindKError &e) {
-      fprintf(stderr, "error: %s\n", e.what());
-      return -1;
+    if (a.findk) {                           // src/main.cc:321-327, before the other engines (-batch / -link-sampling only name the directory)
+      FindK(env, network).run();
+      exit(0);
     }
-    exit(0);
+  } catch (const SvilsError &e) {
+    fprintf(stderr, "error: %s\n", e.what());
+    return -1;
   }
   if (a.batch) {                             // src/main.cc:354-358
     printf("+ running mmsb batch inference\n");

@@ -6,6 +6,8 @@
 #include <cstring>
 #include <sstream>
 
+#include "util.hh"
+
 namespace svinet {
 
 namespace {
@@ -13,15 +15,6 @@ namespace {
 const double kNegInit = -2147483647.0;     // _max_t/_max_h/_max_v/_prev_h, src/mmsbinfer.cc:33-38
 const uint32_t kOnlineIterations = 50;     // src/env.hh:415
 const double kMeanChangeThresh = 0.00001;  // src/env.hh:337
-
-FILE *open_or_die(const std::string &path, const char *what, const char *mode = "w") {
-  FILE *f = fopen(path.c_str(), mode);
-  if (!f) {
-    printf("cannot open %s file:%s\n", what, strerror(errno));
-    exit(-1);
-  }
-  return f;
-}
 
 // psi(x), x > 0: recurrence up to x >= 6, then the asymptotic series (double accurate)
 double digamma(double x) {

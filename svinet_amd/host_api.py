@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from . import _svils
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsvinet_host.so")
 ETA_TYPES = {"uniform": 0, "fromdata": 1, "sparse": 2, "dense": 3}
@@ -174,11 +176,10 @@ class Setup:
 
     def engine(self, **kw):
         """An svils Engine loaded with this setup (graph, validation set, state)."""
-        from ._svils import Engine
         args = dict(ones=self.ones, ones_prob=self.ones_prob, eta=self.eta,
                     link_thresh=self.link_thresh, lt_min_deg=self.lt_min_deg)
         args.update(kw)
-        eng = Engine(self.n, self.k, **args)
+        eng = _svils.Engine(self.n, self.k, **args)
         eng.set_graph(self.links)
         eng.set_validation(self.validation_sorted)
         if self.host_gamma:
@@ -278,7 +279,6 @@ class FindK:
         else:
             self._h = L.svih_findk_from_file(os.fsencode(path), C.byref(o), device)
         if not self._h:
-            from . import _svils
             raise RuntimeError("FindK: cannot read %r or no device: %s" % (path, _svils.load().svils_last_error().decode()))
         self.n = L.svih_findk_n(self._h)
         self.seq2id = _arr(L.svih_findk_seq2id(self._h), (self.n,), np.uint32)
@@ -287,8 +287,7 @@ class FindK:
     def step(self):
         rc = load().svih_findk_step(self._h)
         if rc < 0:
-            from . import _svils
-            raise _svils.SvilsError(rc, _svils.load().svils_last_error().decode("utf-8", "replace"))
+            _svils._chk(rc)
         return rc
 
     def run(self):
@@ -351,7 +350,6 @@ def LinkCommunities(links, gamma, lam, device=0, with_pi=False):
     community comm_nodes, comm_degsum, comm_max, comm_argmax; per link (in the given order) colour, join, gml, rechecked;
     gml_edges [m][3] (p, q, colour) in (p, q) order; the counts unlikely / rechecked; timing_ms (node, link, count passes);
     with_pi: pi [n][k]."""
-    from . import _svils
     gamma = np.ascontiguousarray(gamma, dtype=np.float64)
     lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1, 2)
     n, k = gamma.shape
@@ -369,11 +367,7 @@ def LinkCommunities(links, gamma, lam, device=0, with_pi=False):
         raise ValueError("lam has %d rows; gamma has %d columns" % (lam.shape[0], k))
     L = _svils.load()
     E = links.shape[0]
-
-    def ok(rc):
-        if rc:
-            raise _svils.SvilsError(rc, L.svils_last_error().decode("utf-8", "replace"))
-
+    ok = _svils._chk
     h = C.c_void_p()
     ok(L.svils_lc_create(device, n, k, C.byref(h)))
     try:
