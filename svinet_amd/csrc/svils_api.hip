@@ -80,13 +80,6 @@ int elogpi_rows(svils_handle *h, double **rows) {
   return 0;
 }
 
-void drop_graphs_of(svils_handle *h) {
-  for (auto &g_ : h->sgexec) if (g_) { (void)hipGraphExecDestroy(g_); g_ = nullptr; }
-  if (h->gexec1) { (void)hipGraphExecDestroy(h->gexec1); h->gexec1 = nullptr; }
-  if (h->gexecN) { (void)hipGraphExecDestroy(h->gexecN); h->gexecN = nullptr; }
-  for (auto &g_ : h->gexecP) if (g_) { (void)hipGraphExecDestroy(g_); g_ = nullptr; }
-}
-
 // chunk a row segment [off, off+len) of node p into items of <= ch neighbours
 void chunk_row(std::vector<Item> &items, uint32_t p, uint32_t off, uint32_t len, uint32_t ch,
                int32_t *next_slot, int32_t *first_slot, uint32_t *nsplit) {
@@ -332,10 +325,7 @@ int svils_destroy(svils_handle *h) {
   for (int i = 0; i < SVILS_KERNEL_COUNT; ++i)
     for (auto &ev : h->pending[i]) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
   for (auto &ev : h->freelist) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
-  if (h->gexec1) (void)hipGraphExecDestroy(h->gexec1);
-  if (h->gexecN) (void)hipGraphExecDestroy(h->gexecN);
-  for (auto &g_ : h->gexecP) if (g_) { (void)hipGraphExecDestroy(g_); g_ = nullptr; }
-  for (auto &g_ : h->sgexec) if (g_) { (void)hipGraphExecDestroy(g_); g_ = nullptr; }
+  drop_graphs(h);
   if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);   // nothing of a communicator may still be enqueued
   comm_destroy(h);
   if (h->stage) (void)hipFree(h->stage);
@@ -612,19 +602,18 @@ int svils_set_validation(svils_handle *h, const uint32_t *pairs_y, uint64_t nv) 
     return 0;
   }
   if (!h || (!pairs_y && nv)) return fail(SVILS_ERR_ARG, "svils_set_validation: null argument");
-  // captured kernel arguments hold the old validation pointers: drop every graph
+  // captured kernel arguments hold the old validation pointers and sizes: drop every graph
   (void)hipStreamSynchronize(h->stream);
-  if (h->gexec1) (void)hipGraphExecDestroy(h->gexec1);
-  if (h->gexecN) (void)hipGraphExecDestroy(h->gexecN);
-  for (auto &g_ : h->gexecP) if (g_) { (void)hipGraphExecDestroy(g_); g_ = nullptr; }
-  h->gexec1 = h->gexecN = nullptr;
-
+  drop_graphs(h);
   if (nv > 0xffffffffull) return fail(SVILS_ERR_UNSUPPORTED, "too many validation pairs");
   HIPCHK(hipSetDevice(h->cfg.device));
   for (uint64_t i = 0; i < nv; ++i)
     if (pairs_y[3 * i] >= h->geo.n || pairs_y[3 * i + 1] >= h->geo.n || pairs_y[3 * i + 2] > 1)
       return fail(SVILS_ERR_ARG, "validation pair %llu out of range", (unsigned long long)i);
   DeviceState &d = h->d;
+  dfree(h, &d.vpairs);   // (the stream is idle: synchronised above)
+  dfree(h, &d.uval);
+  dfree(h, &d.vdot);
   int rc = dalloc(h, &d.vpairs, 3 * (size_t)nv, false);
   if (!rc) rc = dalloc(h, &d.uval, nv);
   if (!rc && d.ksh) rc = dalloc(h, &d.vdot, std::max<uint64_t>(nv, 1));

@@ -68,7 +68,7 @@ int apply_s3_split(svils_handle *h) {
   const uint64_t L = d.nlinks;
   const uint64_t lb = L * (uint64_t)h->rank / (uint64_t)h->world, le = L * ((uint64_t)h->rank + 1) / (uint64_t)h->world;
   HIPCHK(hipStreamSynchronize(h->stream));
-  drop_graphs_of(h);
+  drop_graphs(h);
   auto cap = [](uint64_t x, uint32_t lim) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(x, lim)); };
   d.link_begin = lb;
   d.link_end = le;
@@ -327,36 +327,20 @@ int exchange_rows_and_expand(svils_handle *h) {
   return 0;
 }
 
-// one node-block sweep: two exchange points, whatever the annealing flag says (nothing here looks at the control block)
-int sharded_sweep_once(svils_handle *h) {
-  int rc;
-  if ((rc = run_phase(h, SVILS_PHASE_A, false, true))) return rc;
-  if ((rc = run_phase(h, SVILS_PHASE_B_LIGHT, false, true))) return rc;
-  if ((rc = exchange_rows_and_expand(h))) return rc;
-  if ((rc = run_phase(h, SVILS_PHASE_C, false, true))) return rc;
-  if ((rc = exchange_sum(h, h->d.kvec_c, 3 * (size_t)h->geo.K))) return rc;
-  return run_phase(h, SVILS_PHASE_D, false, true);
-}
-
-// `nsweeps` node-block sweeps, collectives included, captured into an executable graph.  RCCL's collectives are
-// stream-capturable; the communication stream of the pipelined exchange forks from and joins the handle's stream through
-// events, which capture follows.  Anything that fails ends the capture and the caller stays eager for good.
-hipGraphExec_t capture_sharded(svils_handle *h, uint32_t nsweeps) {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  const uint64_t issued = h->sweeps_issued;
-  const uint32_t saved = h->tmask;
-  h->tmask = 0;
-  if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed) != hipSuccess) { h->tmask = saved; (void)hipGetLastError(); return nullptr; }
-  int rc = 0;
-  for (uint32_t i = 0; i < nsweeps && !rc; ++i) rc = sharded_sweep_once(h);
-  const hipError_t e = hipStreamEndCapture(h->stream, &graph);
-  h->tmask = saved;
-  h->sweeps_issued = issued;   // nothing ran
-  if (rc || e != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); (void)hipGetLastError(); return nullptr; }
-  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) { exec = nullptr; (void)hipGetLastError(); }
-  (void)hipGraphDestroy(graph);
-  return exec;
+// node-block sweeps: two exchange points each, whatever the annealing flag says (nothing here looks at the control block).
+// Captured into hipGraphs as they stand (block_graphs): RCCL's collectives are stream-capturable, and the communication
+// stream of the pipelined exchange forks from and joins the handle's stream through events, which capture follows.
+int sharded_sweeps(svils_handle *h, uint32_t nsweeps) {
+  for (uint32_t i = 0; i < nsweeps; ++i) {
+    int rc;
+    if ((rc = run_phase(h, SVILS_PHASE_A, false, true))) return rc;
+    if ((rc = run_phase(h, SVILS_PHASE_B_LIGHT, false, true))) return rc;
+    if ((rc = exchange_rows_and_expand(h))) return rc;
+    if ((rc = run_phase(h, SVILS_PHASE_C, false, true))) return rc;
+    if ((rc = exchange_sum(h, h->d.kvec_c, 3 * (size_t)h->geo.K))) return rc;
+    if ((rc = run_phase(h, SVILS_PHASE_D, false, true))) return rc;
+  }
+  return 0;
 }
 }  // namespace svils_impl
 extern "C" {
@@ -384,32 +368,15 @@ int svils_sweep_sharded(svils_handle *h, uint32_t nsweeps) {
   // (an option of the handle, changed with svils_set_option: bench.py times an eager window first and a replayed one after
   // it, so that a first contact with real multi-GPU RCCL that blocks under capture still leaves the eager number behind)
   const bool graphs_wanted = h->opt.sharded_graphs != 0;
-  const bool warm = h->sgexec[0] != nullptr || h->sweeps_issued + nsweeps >= h->graph_after || nsweeps >= 64;
-  uint32_t left = nsweeps;
-  if (graphs_wanted && h->sgraphs_ok && h->tmask == 0 && nsweeps >= 4 && warm) {
+  const bool warm = h->block_graphs.g[0] != nullptr || h->sweeps_issued + nsweeps >= h->graph_after || nsweeps >= 64;
+  if (graphs_wanted && h->block_graphs.ok && h->tmask == 0 && nsweeps >= 4 && warm) {
     // the first sweep of a handle runs eagerly: lazily created objects (communication stream, second communicator,
     // events, the first stand-alone classification) must exist before a capture
-    if (h->sweeps_issued == 0) { if ((rc = sharded_sweep_once(h))) return rc; --left; }
+    if (h->sweeps_issued == 0) { if ((rc = sharded_sweeps(h, 1))) return rc; --nsweeps; }
     if ((rc = ensure_classes(h))) return rc;
-    for (int i = (int)svils_handle::kGraphMaxLog; i >= 0 && h->sgraphs_ok; --i) {
-      const uint32_t m = 1u << i;
-      if (left < m) continue;
-      if (!h->sgexec[i]) {
-        h->sgexec[i] = capture_sharded(h, m);
-        if (!h->sgexec[i]) {
-          if (i == 0) { h->sgraphs_ok = false; drop_graphs_of(h); }   // not even one sweep captures: eager from now on
-          continue;
-        }
-      }
-      for (; left >= m; left -= m) {
-        HIPCHK(hipGraphLaunch(h->sgexec[i], h->stream));
-        h->sweeps_issued += m;
-      }
-    }
+    return replay_sweeps(h, h->block_graphs, nsweeps);   // (a ladder that cannot capture one sweep stays eager from now on)
   }
-  for (; left > 0; --left)
-    if ((rc = sharded_sweep_once(h))) return rc;
-  return 0;
+  return sharded_sweeps(h, nsweeps);
 }
 
 }  // extern "C"

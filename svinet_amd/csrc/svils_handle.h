@@ -42,6 +42,28 @@ int fail(int code, const char *fmt, ...);   // sets svils_last_error(), returns 
 struct EvPair {
   hipEvent_t a, b;
 };
+
+// the sweeps a graph ladder captures, as they are enqueued eagerly
+int eager_sweeps(svils_handle *h, uint32_t nsweeps);     // whole-graph sweeps (svils_sweep.hip)
+int sharded_sweeps(svils_handle *h, uint32_t nsweeps);   // node-block sweeps, collectives included (svils_comm.hip)
+
+// hipGraphs of runs of one kind of sweep: g[i] replays 2^i sweeps, captured on first need (svils_sweep.hip: rung) and
+// launched as few at a time as possible -- 20 sweeps as 16 + 4, 100 as 64 + 32 + 4 (every graph launch is ~4.5 us of
+// idle device: profiles/r03zb_graph_granularity.txt).  The kernel arguments inside are by-value snapshots of the handle's
+// buffers and sizes: whatever changes one of them drops the graphs (drop_graphs).
+struct GraphLadder {
+  static constexpr int kMaxLog = 6;
+  int (*sweeps)(svils_handle *, uint32_t);   // what a capture records
+  hipStreamCaptureMode mode;
+  bool upload;                               // hipGraphUpload at capture (the first launch would pay for it)
+  hipGraphExec_t g[kMaxLog + 1] = {};
+  bool ok = true;                            // false after a capture failure that leaves these sweeps eager for good
+  bool v_flush = false;                      // a replayed sweep leaves its likelihood row / stop rule to the next launch
+  void drop() {
+    for (hipGraphExec_t &e : g)
+      if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+  }
+};
 }  // namespace svils_impl
 
 #define HIPCHK(expr)                                                                     \
@@ -60,7 +82,6 @@ struct EvPair {
 using namespace svils_impl;
 
 struct svils_handle {
-  static constexpr uint32_t kGraphMaxLog = 6;
   svils_config cfg;
   Geometry geo;
   DeviceState d;
@@ -93,7 +114,6 @@ struct svils_handle {
   bool stream_shared = false;     // a tile: its stream is tile 0's
   bool tiles_inited = false;      // the row sums / Elogpi of the tiles' state have been formed (needs graph and state)
   bool v_flush_needed = false;   // a three-launch sweep left its likelihood row / stop rule to the next launch
-  bool v_flush_capture = false;  // ... and so do the sweeps captured in the hipGraphs
   void *cls_zero = nullptr;      // ltot + shist + scan descriptors, one contiguous block
   size_t cls_zero_bytes = 0;
   // native multi-GPU driver (svils_comm_init)
@@ -114,19 +134,13 @@ struct svils_handle {
   bool blocks_set = false;
   bool blocks_explicit = false;     // bounds came from the caller (balanced): the s3 pass is split by link count, no mini-batch steps
   std::vector<uint32_t> h_upper;    // [n] offset of the first q > x inside row x (host copy, for the s3 split)
-  // hipGraphs of node-block sweeps (with their collectives captured): [i] = 2^i sweeps
-  hipGraphExec_t sgexec[kGraphMaxLog + 1] = {};
-  bool sgraphs_ok = true;
   std::vector<uint32_t> timed_sweeps;   // sweeps_done index of every sweep whose phi launch was bracketed
   uint64_t sweeps_issued = 0;           // sweeps enqueued so far (== DevCtrl.sweeps_done unless stopped)
-  // hipGraph replay of whole sweeps (host launch cost: 8 launches x ~7 us per sweep eager)
-  static constexpr uint32_t kGraphSweeps = 8;
-  hipGraphExec_t gexec1 = nullptr, gexecN = nullptr;   // 1 sweep / kGraphSweeps sweeps
-  // other powers of two up to kGraphMax sweeps, captured on first use: 20 sweeps replay as 16 + 4, 100 as 64 + 32 + 4
-  // (every graph launch is ~4.5 us of idle device: profiles/r03zb_graph_granularity.txt)
-  hipGraphExec_t gexecP[kGraphMaxLog + 1] = {};        // [i]: 2^i sweeps (i = 0 and 3 stay null: gexec1, gexecN)
-  bool graphs_ok = true;                               // false after a capture failure: stay eager
-  uint32_t graph_after = 128;                          // sweeps a handle runs eagerly before it captures graphs (svils_sweep)
+  // hipGraph replay (host launch cost: 8 launches x ~7 us per sweep eager) of whole sweeps (svils_sweep) and of node-block
+  // sweeps with their collectives captured (svils_sweep_sharded)
+  GraphLadder whole_graphs{eager_sweeps, hipStreamCaptureModeThreadLocal, true};
+  GraphLadder block_graphs{sharded_sweeps, hipStreamCaptureModeRelaxed, false};
+  uint32_t graph_after = 128;           // sweeps a handle runs eagerly before it captures graphs (svils_sweep, svils_sweep_sharded)
   double *elogpi_view = nullptr;   // DeviceState::skip_elogpi: where svils_get_aux(0) / SVILS_BUF_ELOGPI get their Elogpi rows computed
   std::vector<void *> allocs;
   // pipelined reports (svils_report_enqueue): staging slots, a copy stream, per-slot events
@@ -240,13 +254,19 @@ inline int settle(svils_handle *h) {
   return 0;
 }
 
+// whatever changes what a captured sweep reads -- buffers, sizes, the launches of a sweep -- drops every graph of the
+// handle (with nothing of them in flight)
+inline void drop_graphs(svils_handle *h) {
+  h->whole_graphs.drop();
+  h->block_graphs.drop();
+}
+
 // ---- svils_api.hip
 // the device probe of every *_create: no HIP device (SVILS_ERR_DEVICE), then the caller's own argument refusal `bad_args`
 // (SVILS_ERR_ARG; nullptr: none), then the range check of `device`; makes `device` current
 int open_device(int device, const char *bad_args = nullptr);
 int drain_timing(svils_handle *h);
 int fault_error(uint32_t code);
-void drop_graphs_of(svils_handle *h);
 int elogpi_rows(svils_handle *h, double **rows);
 int state_arrived(svils_handle *h, const double *lambda, const uint32_t *converged);   // the tail of svils_set_state   // the Elogpi rows of the state as it stands (computed now where a handle does not store them)
 void chunk_row(std::vector<Item> &items, uint32_t p, uint32_t off, uint32_t len, uint32_t ch,
@@ -259,8 +279,8 @@ int run_phase(svils_handle *h, svils_phase ph, const Geometry &g, const DeviceSt
               bool fused, bool shard = false);
 int run_phase(svils_handle *h, svils_phase ph, bool fused, bool shard = false);
 int ensure_classes(svils_handle *h);
-int eager_sweeps(svils_handle *h, uint32_t nsweeps);
 int flush_validation(svils_handle *h);
+int replay_sweeps(svils_handle *h, GraphLadder &lad, uint32_t nsweeps);
 // ---- svils_comm.hip
 int apply_s3_split(svils_handle *h);
 int apply_blocks(svils_handle *h, int rank, int world, const uint32_t *bounds, bool explicit_bounds);

@@ -17,7 +17,6 @@ struct Options {
   uint32_t graph_after = 128;   // sweeps a handle runs eagerly before svils_sweep captures hipGraphs (0: at once)
   int skip_elogpi = -1;         // 57 <= K <= 512: Elogpi not stored (DeviceState::skip_elogpi): -1 where the n-by-k state is >= 256 MB, 0 / 1 forced
   int shard_fold = 1;           // node-block sweeps, K <= 32: the kernels leave the K-vectors themselves (no k_colreduce)
-  int graph_pow2 = 1;           // replay as few graphs as possible (powers of two up to 64 sweeps); 0: 8-sweep graphs + singles
   // ---- read by svils_set_graph
   uint64_t lpl_max_entries = 1ull << 27;   // CSR entries up to which K <= 56 takes the lane-per-link kernels
   int wt = -1;                  // write-through row stores: -1 by the size of the state (1 - 8 MB), 0 / 1 forced

@@ -37,8 +37,6 @@ const Row kRows[] = {
      "sweeps a handle runs eagerly before svils_sweep / svils_sweep_sharded capture hipGraphs (0: at the first call of >= 4 sweeps)"},
     {"shard_fold", "SVILS_SHARD_FOLD", "1", ANY, I32, OFF(shard_fold), 0, 1,
      "node-block sweeps at K <= 32: the kernels leave sum / s1 / s2 / s3 themselves; 0 keeps the k_colreduce launches"},
-    {"graph_pow2", "SVILS_GRAPH_POW2", "1", ANY, I32, OFF(graph_pow2), 0, 1,
-     "replay runs of sweeps as powers of two up to 64 per graph; 0: 8-sweep graphs and singles"},
     {"lpl_max_entries", "SVILS_LPL_MAX_ENTRIES", "134217728", GRAPH, U64, OFF(lpl_max_entries), 0, 1ll << 27,
      "CSR entries (2 x links) below which K <= 56 takes the lane-per-link kernels (their class lists pack an entry index into 27 bits)"},
     {"wt", "SVILS_WT", "-1", GRAPH, I32, OFF(wt), -1, 1,
@@ -172,7 +170,7 @@ int svils_set_option(svils_handle *h, const char *key, const char *value) {
     // captured node-block sweeps took the other form: nothing of them may be in flight when they go
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    drop_graphs_of(h);
+    drop_graphs(h);
   }
   return 0;
 }

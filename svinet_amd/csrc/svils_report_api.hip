@@ -118,7 +118,7 @@ int svils_set_test(svils_handle *h, const uint32_t *pairs_y, uint64_t nt) {
   for (uint64_t i = 0; i < nt; ++i)
     if (pairs_y[3 * i] >= h->geo.n || pairs_y[3 * i + 1] >= h->geo.n || pairs_y[3 * i] == pairs_y[3 * i + 1])
       return fail(SVILS_ERR_ARG, "svils_set_test: pair %llu names node %u / %u (n = %u)", (unsigned long long)i, pairs_y[3 * i], pairs_y[3 * i + 1], h->geo.n);
-  drop_graphs_of(h);            // the captured sweeps do not know about the test launches (or still carry them)
+  drop_graphs(h);            // the captured sweeps do not know about the test launches (or still carry them)
   h->nt = 0;
   if (!nt) return 0;
   int rc;

@@ -52,7 +52,7 @@ int svils_set_stochastic(svils_handle *h, const svils_stochastic *cfg) {
     if ((rc = dalloc(h, &d.s12run, 2 * (size_t)h->geo.K))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     d.gacc = gacc;
-    drop_graphs_of(h);   // captured launches hold gacc == gamma
+    drop_graphs(h);   // captured launches hold gacc == gamma
   }
   h->stoch = true;
   h->scfg = *cfg;

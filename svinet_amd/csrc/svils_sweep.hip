@@ -152,33 +152,60 @@ int eager_sweeps(svils_handle *h, uint32_t nsweeps) {
   return 0;
 }
 
-void drop_graphs(svils_handle *h) {
-  if (h->gexec1) { (void)hipGraphExecDestroy(h->gexec1); h->gexec1 = nullptr; }
-  if (h->gexecN) { (void)hipGraphExecDestroy(h->gexecN); h->gexecN = nullptr; }
-  for (auto &g_ : h->gexecP) if (g_) { (void)hipGraphExecDestroy(g_); g_ = nullptr; }
-}
-
-// capture `nsweeps` sweeps of the library's own stream into an executable graph; every kernel
-// argument is a by-value snapshot of pointers/sizes that stay fixed after set_graph/set_state
-// (all loop state lives in device memory), so the graph can be replayed indefinitely
-hipGraphExec_t capture_sweeps(svils_handle *h, uint32_t nsweeps) {
+// Slot i of a ladder: 2^i sweeps of the handle's stream captured into an executable graph on first need, with event
+// recording off; nullptr if the capture fails.  Every kernel argument is a by-value snapshot of pointers / sizes that stay
+// fixed until drop_graphs (all loop state lives in device memory), so the graph can be replayed indefinitely.  Nothing
+// runs: the bookkeeping of the captured launches is put back, and what they leave owed is noted in the ladder.
+hipGraphExec_t rung(svils_handle *h, GraphLadder &lad, int i) {
+  if (lad.g[i]) return lad.g[i];
   hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
   const uint64_t issued = h->sweeps_issued;
+  const uint32_t tmask = h->tmask;
   const bool vf = h->v_flush_needed;
-  if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
-  const int rc = eager_sweeps(h, nsweeps);
+  h->tmask = 0;
+  if (hipStreamBeginCapture(h->stream, lad.mode) != hipSuccess) { h->tmask = tmask; (void)hipGetLastError(); return nullptr; }
+  const int rc = lad.sweeps(h, 1u << i);
   const hipError_t e = hipStreamEndCapture(h->stream, &graph);
+  h->tmask = tmask;
   h->sweeps_issued = issued;   // nothing ran
-  h->v_flush_capture = h->v_flush_needed;
+  lad.v_flush = h->v_flush_needed;
   h->v_flush_needed = vf;
   if (rc || e != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); (void)hipGetLastError(); return nullptr; }
-  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
+  if (hipGraphInstantiate(&lad.g[i], graph, nullptr, nullptr, 0) != hipSuccess) { lad.g[i] = nullptr; (void)hipGetLastError(); }
   (void)hipGraphDestroy(graph);
   // the first launch of an executable graph otherwise pays for its upload (measured in the drop-in binary's trace: 130 - 250 us
   // in front of the first chunk of every size): done here, where svils_prepare_graphs has the caller still in its set-up
-  if (exec && hipGraphUpload(exec, h->stream) != hipSuccess) (void)hipGetLastError();
-  return exec;
+  if (lad.g[i] && lad.upload && hipGraphUpload(lad.g[i], h->stream) != hipSuccess) (void)hipGetLastError();
+  return lad.g[i];
+}
+
+// `nsweeps` sweeps replayed from `lad` as few graphs as possible: powers of two from 2^kMaxLog down.  A size that does not
+// capture is skipped (smaller ones carry its sweeps); a ladder that cannot capture one sweep is off for good, and the
+// sweeps no graph carried are enqueued eagerly.
+int replay_sweeps(svils_handle *h, GraphLadder &lad, uint32_t nsweeps) {
+  for (int i = GraphLadder::kMaxLog; i >= 0 && lad.ok; --i) {
+    const uint32_t m = 1u << i;
+    if (nsweeps < m) continue;
+    if (!rung(h, lad, i)) {
+      if (i == 0) { lad.drop(); lad.ok = false; }
+      continue;
+    }
+    for (; nsweeps >= m; nsweeps -= m) {
+      HIPCHK(hipGraphLaunch(lad.g[i], h->stream));
+      h->sweeps_issued += m;
+    }
+  }
+  return lad.sweeps(h, nsweeps);
+}
+
+// the first replay of whole sweeps captures 1 and 8 of them: without both, the handle stays eager
+bool whole_graphs_ready(svils_handle *h) {
+  GraphLadder &lad = h->whole_graphs;
+  if (lad.ok && !lad.g[0] && !(rung(h, lad, 0) && rung(h, lad, 3))) {
+    lad.drop();
+    lad.ok = false;
+  }
+  return lad.ok;
 }
 
 // three-launch sweeps: the held-out likelihood and stop rule of the last sweep enqueued, as a launch of
@@ -210,42 +237,16 @@ int ensure_classes(svils_handle *h) {
 }  // namespace svils_impl
 namespace svils_impl {
 
-// replay `n` sweeps from the untimed graphs (captured on first use, with event recording off)
+// replay `n` sweeps from the untimed graphs
 int graph_sweeps(svils_handle *h, uint32_t n) {
   int rc = ensure_classes(h);
   if (rc) return rc;
-  if (!h->gexec1) {
-    const uint32_t saved = h->tmask;
-    h->tmask = 0;
-    h->gexec1 = capture_sweeps(h, 1);
-    h->gexecN = h->gexec1 ? capture_sweeps(h, svils_handle::kGraphSweeps) : nullptr;
-    h->tmask = saved;
-    if (!h->gexec1 || !h->gexecN) { drop_graphs(h); h->graphs_ok = false; return eager_sweeps(h, n); }
-  }
-  h->sweeps_issued += n;
-  if (n) h->v_flush_needed = h->v_flush_capture;   // what a captured sweep leaves behind
+  if (!whole_graphs_ready(h)) return eager_sweeps(h, n);
+  if (n) h->v_flush_needed = h->whole_graphs.v_flush;   // what a captured sweep leaves behind
   // ... and what run_phase's bookkeeping would have noted had the sweeps been launched eagerly: whole sweeps in derived
   // form leave the stored mean indicators behind gamma (same condition as d.derive_m there)
   if (n && !h->prm.stoch && !h->d.ksh && !h->d.lpl && h->derive_ok) h->mphi_stale = true;
-  // as few replays as possible: powers of two from 2^kGraphMaxLog down (option graph_pow2 = 0: 8-sweep graphs + singles)
-  if (h->opt.graph_pow2) {
-    for (int i = (int)svils_handle::kGraphMaxLog; i >= 1; --i) {
-      const uint32_t m = 1u << i;
-      if (n < m) continue;
-      hipGraphExec_t *ge = (m == svils_handle::kGraphSweeps) ? &h->gexecN : &h->gexecP[i];
-      if (!*ge) {
-        const uint32_t saved = h->tmask;
-        h->tmask = 0;
-        *ge = capture_sweeps(h, m);
-        h->tmask = saved;
-        if (!*ge) continue;               // (smaller graphs carry the sweeps)
-      }
-      for (; n >= m; n -= m) HIPCHK(hipGraphLaunch(*ge, h->stream));
-    }
-  }
-  for (; n >= svils_handle::kGraphSweeps; n -= svils_handle::kGraphSweeps) HIPCHK(hipGraphLaunch(h->gexecN, h->stream));
-  for (; n > 0; --n) HIPCHK(hipGraphLaunch(h->gexec1, h->stream));
-  return 0;
+  return replay_sweeps(h, h->whole_graphs, n);
 }
 
 }  // namespace svils_impl
@@ -270,10 +271,11 @@ int svils_sweep(svils_handle *h, uint32_t nsweeps) {
   // device time.  Graph replay only removes host launch cost, so it starts paying once a run is long: calls stay
   // eager until the handle has seen graph_after sweeps (128; SVILS_GRAPH_AFTER, read when the handle is created,
   // overrides; 0 = capture at the first call of >= 4 sweeps), unless a single call is itself long.  Results are identical either way (one code path per kernel).
-  const bool warm = h->gexec1 != nullptr || h->sweeps_issued + nsweeps >= h->graph_after || nsweeps >= 64;
-  // (short calls are not worth a capture -- but once the single-sweep graph exists, svils_prepare_graphs, they replay it:
-  // an eager three-launch sweep leaves ~20 us of gaps, a graph launch ~4.5)
-  if (!h->graphs_ok || !warm || (nsweeps < 4 && !(h->gexec1 && h->gexecN && h->tmask == 0))) rc = eager_sweeps(h, nsweeps);
+  const GraphLadder &lad = h->whole_graphs;
+  const bool warm = lad.g[0] != nullptr || h->sweeps_issued + nsweeps >= h->graph_after || nsweeps >= 64;
+  // (short calls are not worth a capture -- but once the graphs of 1 and 8 sweeps exist, svils_prepare_graphs, they replay
+  // them: an eager three-launch sweep leaves ~20 us of gaps, a graph launch ~4.5)
+  if (!lad.ok || !warm || (nsweeps < 4 && !(lad.g[0] && lad.g[3] && h->tmask == 0))) rc = eager_sweeps(h, nsweeps);
   else if (h->tmask == 0) rc = graph_sweeps(h, nsweeps);
   // Per-kernel hipEvent timing needs eager launches: events captured as graph nodes cannot be read
   // with hipEventElapsedTime on this runtime.  With a sampling period P > 1 only every P-th sweep is
@@ -302,22 +304,12 @@ int svils_prepare_graphs(svils_handle *h, uint32_t max_sweeps) {
   if (TILED(h)) return 0;   // column tiles launch eagerly (tens of launches of milliseconds each per sweep)
   if (!h) return fail(SVILS_ERR_ARG, "svils_prepare_graphs: null handle");
   if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "svils_prepare_graphs: set graph and state first");
-  if (h->stoch || h->d.ksh || !h->graphs_ok) return 0;
+  if (h->stoch || h->d.ksh || !h->whole_graphs.ok) return 0;
   HIPCHK(hipSetDevice(h->cfg.device));
   int rc = ensure_classes(h);
   if (rc) return rc;
-  const uint32_t saved = h->tmask;
-  h->tmask = 0;
-  if (!h->gexec1) h->gexec1 = capture_sweeps(h, 1);
-  if (h->gexec1 && !h->gexecN && max_sweeps >= svils_handle::kGraphSweeps) h->gexecN = capture_sweeps(h, svils_handle::kGraphSweeps);
-  if (!h->gexecN) h->gexecN = h->gexec1 ? capture_sweeps(h, svils_handle::kGraphSweeps) : nullptr;   // graph_sweeps expects both
-  for (int i = 2; i <= (int)svils_handle::kGraphMaxLog && h->gexec1; ++i) {
-    const uint32_t m = 1u << i;
-    if (m > max_sweeps || m == svils_handle::kGraphSweeps || h->gexecP[i]) continue;
-    h->gexecP[i] = capture_sweeps(h, m);
-  }
-  h->tmask = saved;
-  if (!h->gexec1 || !h->gexecN) { drop_graphs(h); h->graphs_ok = false; }
+  if (whole_graphs_ready(h))
+    for (int i = 2; i <= GraphLadder::kMaxLog && (1u << i) <= max_sweeps; ++i) rung(h, h->whole_graphs, i);
   return 0;
 }
 

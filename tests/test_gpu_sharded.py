@@ -280,3 +280,23 @@ def test_native_step_sharded_world1(graph_files, k):
     np.testing.assert_allclose(eng.rows(), plain.rows(), rtol=1e-9, atol=1e-12)
     with pytest.raises(_svils.SvilsError):
         plain.step_sharded(1)                            # no shard_block: not a node-block mini-batch handle
+
+
+def test_node_block_graphs_follow_a_new_validation_set(graph_files):
+    """svils_set_validation drops the captured node-block sweeps too: a whole-graph handle driven by svils_sweep_sharded
+    (a world of one, no communicator) that replayed them before the held-out set changed computes the rows after it on
+    the new set -- bit for bit the rows of its twin that never captures (option sharded_graphs = 0)."""
+    from svinet_amd.host_api import Setup
+    setup = Setup(graph_files["lfr"], 1000, 28)
+    other = np.ascontiguousarray(setup.validation_sorted[::2])
+    rows = []
+    for graphs in (1, 0):
+        eng = setup.engine(use_validation_stop=False)
+        eng.set_option("sharded_graphs", graphs)
+        eng.sweep_sharded(9)          # (conftest: SVILS_GRAPH_AFTER=0) one eager sweep, then a graph of 8
+        eng.set_validation(other)
+        eng.sweep_sharded(8)
+        eng.synchronize()
+        rows.append(eng.rows())
+    assert rows[0].shape == (17, 10)
+    assert np.array_equal(rows[0], rows[1])

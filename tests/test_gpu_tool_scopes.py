@@ -1,7 +1,7 @@
 """-m gpu: the device memory of the standalone tool handles (svils_findk_*, svils_lc_*; csrc/svils_tool.h).  After a warm-up
 cycle, three cycles of create -> set_graph (a refused one on the way, then a graph of another size) -> state / model -> run ->
 destroy leave the device's free memory where the warm-up left it: both allocation scopes, the handle's and the graph's,
-come back."""
+come back.  So does a sweep handle's held-out set when svils_set_validation replaces it."""
 import ctypes as C
 
 import numpy as np
@@ -114,3 +114,24 @@ def test_tool_handles_give_back_device_memory(tool):
         cycle(i)
         free = _free_bytes()
         assert free >= warm - SLACK, (tool, i, warm - free)
+
+
+def test_set_validation_gives_back_the_set_it_replaces(graph_files):
+    """svils_set_validation three times with sets of the same size: the device's free memory stays where the first call left it"""
+    from svinet_amd.host_api import Setup
+    setup = Setup(graph_files["lfr"], 1000, 28)
+    eng = setup.engine(use_validation_stop=False)
+    rng = np.random.default_rng(7)
+    nv = 2000000   # 40 MB of pairs and values per set
+    p = rng.integers(0, 999, nv)
+    pairs = np.stack([p, rng.integers(p + 1, 1000), rng.integers(0, 2, nv)], axis=1).astype(np.uint32)
+    eng.set_validation(pairs)
+    warm = _free_bytes()
+    for i in range(2):
+        eng.set_validation(pairs)
+        free = _free_bytes()
+        assert free >= warm - SLACK, (i, warm - free)
+    eng.set_validation(setup.validation_sorted)   # ... and the handle sweeps on the set it holds
+    eng.sweep(2)
+    eng.synchronize()
+    assert eng.rows().shape == (2, 10) and np.all(np.isfinite(eng.rows()))
