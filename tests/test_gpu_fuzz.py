@@ -1,5 +1,5 @@
 """-m gpu: randomized small graphs / community counts against the oracle (both
-kernel layouts: lane-per-link for K <= 32, row-per-wavefront above), including
+kernel layouts: lane-per-link for K <= 56, row-per-wavefront above), including
 declared-but-absent nodes, duplicate and reversed input lines, hubs, tiny K, the
 converged shortcuts (forced by seeding converged flags) and the active-set path."""
 import numpy as np
@@ -174,7 +174,9 @@ def test_empty_and_tiny_graphs():
         assert np.allclose(g, ref.gamma, rtol=1e-10) and np.allclose(lam, ref.lam, rtol=1e-10)
 
 
-@pytest.mark.parametrize("k,no_elogpi", [(20, False), (64, False), (200, False), (64, True), (200, True), (500, True)])
+@pytest.mark.parametrize("k,no_elogpi", [(20, False), (64, False), (200, False), (64, True), (200, True), (500, True),
+                                         # the lane-per-link layout above K = 32: k_phi_lpl<18 / 20 / 28> (K = 49: seven padding columns)
+                                         (33, False), (40, False), (49, False), (56, False)])
 def test_softmax_rows_that_underflow(k, no_elogpi, monkeypatch):
     """Links whose endpoints have (almost) disjoint supports: every exp(x_k) underflows without a
     shift (x_k < -745 for all k).  The row-per-wavefront kernel computes its softmax without the max
