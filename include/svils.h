@@ -303,7 +303,7 @@ int svils_get_aux(svils_handle *h, int which, void *out);
  * auc() / biased_auc() / uniform_auc() (src/linksampling.cc:855-877, 1185-1226) sit behind create_test_precision_sets, which
  * its main.cc never sets, and behind load_test_sets(), which nothing calls.  For y = 1 the held-out likelihood already uses it:
  * edge_likelihood (:259-294) is log(max(link_prob, 1e-30)).
- * Both calls enqueue on the handle's stream behind the sweeps already enqueued and synchronise before returning; they read
+ * The calls enqueue on the handle's stream behind the sweeps already enqueued and synchronise before returning; they read
  * gamma, lambda and the training CSR and write nothing a sweep reads (a handle whose stop rule has fired and a mini-batch
  * handle between steps work the same way).  Device scratch is allocated on first use and freed by svils_destroy: at most
  * ~0.5 GB (queries go through in internal batches of 8192: 384 MB of partial top-k heaps, 64 MB of query rows, 24 MB of
@@ -322,6 +322,23 @@ int svils_link_prob(svils_handle *h, const uint32_t *pairs, uint64_t npairs, dou
  * (sum_z (gamma_pz / sum gamma_p) beta_z gamma_qz) / sum gamma_q on the matrix cores (fp64), within a few ulps of
  * svils_link_prob's. */
 int svils_predict_links(svils_handle *h, const uint32_t *nodes, uint32_t nnodes, uint32_t topk, uint32_t *ids, double *scores);
+/* For every directed pair (p, q), pairs[npairs][2]: where q stands among the candidates of p.  Candidates of p are exactly
+ * those of svils_predict_links: every node except p and p's training neighbours.  With s = the score svils_predict_links
+ * computes for (p, q):
+ *   above[i] = #{candidates c != q : score(p,c) >  s}
+ *   tied[i]  = #{candidates c != q : score(p,c) == s}
+ *   ncand[i] = #{candidates c != q}
+ *   score[i] = s
+ * q need not itself be a candidate (a training neighbour of p is ranked against the same set).  Any output pointer may be
+ * NULL.  s and the scores it is compared with come from one device function on the matrix cores: score[i] is bitwise the
+ * score svils_predict_links lists for q, q ties exactly with itself, and the counts agree exactly with those lists (q at
+ * place j of p's list has above <= j <= above + tied).  A pair's result does not depend on which other pairs are in the call;
+ * the counts of the candidate chunks are combined with integer atomics.  One query row per pair, in internal batches of 8192:
+ * the call shares the query rows and the sorted CSR copy with svils_predict_links, keeps no heaps, and grows the scratch by
+ * 24 bytes per row of a batch (q, s and the three counters: under 200 KB).
+ * SVILS_ERR_ARG / SVILS_ERR_UNSUPPORTED: as for svils_link_prob. */
+int svils_rank_links(svils_handle *h, const uint32_t *pairs, uint64_t npairs, uint32_t *above, uint32_t *tied, uint32_t *ncand,
+                     double *score);
 
 /* Evaluate the kernels' own special functions on a plain array (unit tests):
  * which = 0 digamma(x) [stands for gsl_sf_psi], 1 exp(x) for x <= 0, 2 1/x, 3 ln(x) for x >= 1. */

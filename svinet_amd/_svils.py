@@ -34,7 +34,7 @@ EXPORTS = (
     "svils_report_tag_count", "svils_report_fetch_tags", "svils_get_community_tags",
     "svils_set_node_blocks", "svils_balance_node_blocks", "svils_prepare_graphs",
     "svils_set_option", "svils_get_option", "svils_option_table", "svils_init_gamma",
-    "svils_link_prob", "svils_predict_links",
+    "svils_link_prob", "svils_predict_links", "svils_rank_links",
     "svils_findk_create", "svils_findk_destroy", "svils_findk_set_graph", "svils_findk_init_state", "svils_findk_count",
     "svils_findk_pad_requests", "svils_findk_apply", "svils_findk_report", "svils_findk_get_state", "svils_findk_get_timing",
     "svils_lc_create", "svils_lc_destroy", "svils_lc_set_graph", "svils_lc_set_model", "svils_lc_run", "svils_lc_get_nodes",
@@ -158,6 +158,7 @@ def load():
     L.svils_option_table.restype = C.c_char_p
     L.svils_link_prob.argtypes = [vp, vp, C.c_uint64, vp]
     L.svils_predict_links.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.svils_rank_links.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
     L.svils_findk_create.argtypes = [C.c_int, C.c_uint32, C.c_double, C.c_double, C.POINTER(vp)]
     L.svils_findk_destroy.argtypes = [vp]
     L.svils_findk_set_graph.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]
@@ -434,6 +435,18 @@ class Engine:
         _chk(load().svils_predict_links(self._h, ptr, nq if nodes is not None else 0, int(topk), ids.ctypes.data,
                                         scores.ctypes.data))
         return ids, scores
+
+    def rank_links(self, pairs):
+        """where q stands among the candidates of p, for directed pairs [m][2] (p != q) -> (above uint32[m], tied uint32[m],
+        ncand uint32[m], score float64[m]): candidates other than q that score above / the same as (p, q), how many there
+        are, and the score itself, bitwise that of predict_links (svils_rank_links)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        m = pairs.shape[0]
+        above, tied, ncand = (np.zeros(m, dtype=np.uint32) for _ in range(3))
+        score = np.zeros(m, dtype=np.float64)
+        _chk(load().svils_rank_links(self._h, pairs.ctypes.data, m, above.ctypes.data, tied.ctypes.data, ncand.ctypes.data,
+                                     score.ctypes.data))
+        return above, tied, ncand, score
 
     def debug_eval(self, which, x):
         x = np.ascontiguousarray(x, dtype=np.float64)

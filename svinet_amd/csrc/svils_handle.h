@@ -154,7 +154,7 @@ struct svils_handle {
   uint32_t *t_pairs = nullptr;
   double *t_uval = nullptr, *t_rows = nullptr;
   uint32_t nt = 0, t_cap = 0;
-  // link prediction (svils_link_prob / svils_predict_links, svils_predict.hip): device scratch allocated on first use and
+  // link prediction (svils_link_prob / svils_predict_links / svils_rank_links, svils_predict.hip): device scratch allocated on first use and
   // grown on demand, all of it dalloc()ed (freed by svils_destroy); nothing a sweep reads lives here
   struct PredictScratch {
     uint32_t *scol = nullptr;        // [2L] the CSR rows with every row sorted ascending (built once: the graph never changes)
@@ -171,6 +171,10 @@ struct svils_handle {
     double *hs = nullptr;            // per-thread partial top-k heaps of the candidate chunks (scores, ids)
     uint32_t *hi = nullptr;
     uint64_t heap_cap = 0;
+    uint32_t *rq = nullptr;          // svils_rank_links: [rank_cap] the q of every query row, UINT32_MAX past the batch
+    double *rthr = nullptr;          // [rank_cap] the score of (p, q): the row's threshold
+    uint32_t *rcnt = nullptr;        // [rank_cap][3] candidates above it, tied with it, seen
+    uint64_t rank_cap = 0;
   } pred;
   ReportSlot rslot[SVILS_REPORT_SLOTS];
   ReportLayout rlay{};

@@ -1,5 +1,5 @@
 // svils_predict.hip -- link prediction from a fitted state: svils_link_prob (scores of given pairs) and svils_predict_links
-// (the top-k candidate links of query nodes).  The quantity is the reference's LinkSampling::link_prob
+// (the top-k candidate links of query nodes), svils_rank_links (where a given node stands among them).  The quantity is the reference's LinkSampling::link_prob
 // (src/linksampling.hh:240-256): sum_z pi_pz pi_qz beta_z with pi_p = gamma_p / sum gamma_p (estimate_pi, :205-214) and
 // beta_z = lambda_z0 / (lambda_z0 + lambda_z1) (estimate_bernoulli_rate, :217-225).
 //
@@ -11,6 +11,10 @@
 //   k_topk_tiles    grid (query tile of 64, candidate chunk): 64 x 64 score tiles from v_mfma_f64_16x16x4_f64, then every
 //                   query's four selector threads keep a top-k heap each over their quarter of the chunk's candidates
 //   k_topk_merge    one block per query: the 4 x chunks heaps sorted together (bitonic, in LDS), the first k kept
+//   k_rank_thresh   svils_rank_links, one query row per directed pair (p, q): the score of (p, q) itself, from the tile code of
+//                   the top-k kernel with the q's of a query tile gathered as its 64 candidates (the diagonal is kept)
+//   k_rank_tiles    the grid and tiles of k_topk_tiles; in place of a heap every selector thread counts the candidates of its
+//                   quarter that score above / equal to the row's threshold, and how many it saw (integer atomics per row)
 //
 // Read-only: everything here reads gamma, lambda and the CSR, and writes the scratch of svils_handle::pred only.
 #include "svils_handle.h"
@@ -240,6 +244,120 @@ __global__ __launch_bounds__(256) void k_topk_merge(uint32_t topk, uint32_t nch,
   }
 }
 
+// The 64 x 64 score tile of k_topk_tiles for any four candidate columns per lane: cand[j] is the node behind column
+// 16 j + (l & 15), NONE for a column past the end (its scores are zero).  The same loads, the same MFMA sequence over
+// k16 and the same final * 1 / sum gamma: element (row, candidate) has the bits k_topk_tiles gives it, wherever it sits.
+__device__ __forceinline__ void score_tile(double (*S)[PC + 1], const double *__restrict__ arow, const uint32_t *cand, uint32_t K,
+                                           uint32_t ld, uint32_t k16, const double *__restrict__ gamma,
+                                           const double *__restrict__ inv, uint32_t w, uint32_t g, uint32_t r16) {
+  d4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
+  for (uint32_t kc = 0; kc < k16; kc += 16) {
+    const uint32_t col = kc + 4 * g;
+    const double2 a01 = *(const double2 *)(arow + col), a23 = *(const double2 *)(arow + col + 2);
+    const double a[4] = {a01.x, a01.y, a23.x, a23.y};
+    double b[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (cand[j] != NONE) load4(gamma + (size_t)cand[j] * ld, col, K, b[j]);
+      else b[j][0] = b[j][1] = b[j][2] = b[j][3] = 0.0;
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[j][s], acc[j], 0, 0, 0);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const double iq = cand[j] != NONE ? inv[cand[j]] : 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) S[16 * w + g + 4 * r][16 * j + r16] = acc[j][r] * iq;
+  }
+}
+
+// Block qt: thr[i] = the score of (qnodes[i], qcand[i]) for the 64 rows i of query tile qt -- the diagonal of the tile whose
+// candidate columns are the rows' own q's.
+__global__ __launch_bounds__(256) void k_rank_thresh(uint32_t K, uint32_t ld, uint32_t k16, const double *__restrict__ gamma,
+                                                     const double *__restrict__ inv, const double *__restrict__ aq,
+                                                     const uint32_t *__restrict__ qcand, double *__restrict__ thr) {
+  __shared__ double S[PQ][PC + 1];
+  const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63, g = l >> 4, r16 = l & 15, qt = blockIdx.x;
+  uint32_t cand[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cand[j] = qcand[qt * PQ + 16 * j + r16];
+  score_tile(S, aq + (size_t)(qt * PQ + 16 * w + r16) * k16, cand, K, ld, k16, gamma, inv, w, g, r16);
+  __syncthreads();
+  if (t < PQ) thr[qt * PQ + t] = S[t][t];
+}
+
+// Block (qt, c) as in k_topk_tiles.  Thread t serves row t >> 2 over the candidates t & 3, t & 3 + 4, ... of every tile in
+// ascending order; `np` walks the row's sorted training neighbours along with them (nv = the neighbour it stands on, NONE
+// past the end), so p's neighbours, p and q are passed over without a search.  cnt[row][3] += above, tied, seen: the four
+// threads of a row are summed by shuffles, the chunks by integer atomics (exact in any order).
+__global__ __launch_bounds__(256) void k_rank_tiles(uint32_t n, uint32_t K, uint32_t ld, uint32_t k16, uint32_t nch,
+                                                    const double *__restrict__ gamma, const double *__restrict__ inv,
+                                                    const double *__restrict__ aq, const uint32_t *__restrict__ qnodes,
+                                                    const uint32_t *__restrict__ qcand, const double *__restrict__ thr,
+                                                    const uint64_t *__restrict__ rowptr, const uint32_t *__restrict__ scol,
+                                                    uint32_t *__restrict__ cnt) {
+  __shared__ double S[PQ][PC + 1];
+  const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63, g = l >> 4, r16 = l & 15;
+  const uint32_t qt = blockIdx.x, c = blockIdx.y;
+  uint32_t cb, ce;
+  chunk_range(n, c, nch, &cb, &ce);
+  const uint32_t qi = t >> 2, sub = t & 3, row = qt * PQ + qi;
+  const uint32_t p = qnodes[row];
+  uint32_t q = NONE, nv = NONE;
+  uint64_t np = 0, ne = 0;
+  double s = 0.0;
+  if (p != NONE) {
+    q = qcand[row];
+    s = thr[row];
+    uint64_t b = rowptr[p];
+    ne = rowptr[p + 1];
+    for (uint64_t e = ne; b < e;) {   // the first neighbour >= cb
+      const uint64_t m = (b + e) >> 1;
+      if (scol[m] < cb) b = m + 1; else e = m;
+    }
+    np = b;
+    if (np < ne) nv = scol[np];
+  }
+  uint32_t above = 0, tied = 0, seen = 0;
+  const double *arow = aq + (size_t)(qt * PQ + 16 * w + r16) * k16;
+  for (uint32_t c0 = cb; c0 < ce; c0 += PC) {
+    uint32_t cand[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cand[j] = c0 + 16 * j + r16 < ce ? c0 + 16 * j + r16 : NONE;
+    score_tile(S, arow, cand, K, ld, k16, gamma, inv, w, g, r16);
+    __syncthreads();
+    if (p != NONE) {
+      for (uint32_t i = 0; i < PC / 4; ++i) {
+        const uint32_t cc = sub + 4 * i, x = c0 + cc;
+        if (x >= ce) break;
+        while (nv < x) nv = ++np < ne ? scol[np] : NONE;
+        if (x == p || x == q || x == nv) continue;
+        const double sc = S[qi][cc];
+        above += sc > s ? 1u : 0u;
+        tied += sc == s ? 1u : 0u;
+        ++seen;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int m = 1; m <= 2; m <<= 1) {
+    above += __shfl_xor(above, m);
+    tied += __shfl_xor(tied, m);
+    seen += __shfl_xor(seen, m);
+  }
+  if (p != NONE && sub == 0) {
+    atomicAdd(cnt + 3 * (size_t)row, above);
+    atomicAdd(cnt + 3 * (size_t)row + 1, tied);
+    atomicAdd(cnt + 3 * (size_t)row + 2, seen);
+  }
+}
+
 template <class T>
 int grow(svils_handle *h, T **p, uint64_t *cap, uint64_t need) {
   if (*p && *cap >= need) return 0;
@@ -250,7 +368,7 @@ int grow(svils_handle *h, T **p, uint64_t *cap, uint64_t need) {
   return 0;
 }
 
-// the refusals shared by both entry points (include/svils.h)
+// the refusals shared by the entry points (include/svils.h)
 int check_handle(svils_handle *h, const char *name) {
   if (!h) return fail(SVILS_ERR_ARG, "%s: null handle", name);
   if (TILED(h)) return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a column-tiled handle (k > SVILS_MAX_K = %d)", name, SVILS_MAX_K);
@@ -262,7 +380,7 @@ int check_handle(svils_handle *h, const char *name) {
   return 0;
 }
 
-// what every top-k call needs besides its batches: the sorted rows (once), 1 / row sums and beta of the current state
+// what every top-k or rank call needs besides its batches: the sorted rows (once), 1 / row sums and beta of the current state
 int prepare(svils_handle *h) {
   const Geometry &g = h->geo;
   const DeviceState &d = h->d;
@@ -376,6 +494,69 @@ int svils_predict_links(svils_handle *h, const uint32_t *nodes, uint32_t nnodes,
     HIPCHK(hipMemcpyAsync(ids + (size_t)b * topk, s.ids, (size_t)m * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(scores + (size_t)b * topk, s.scores, (size_t)m * topk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+int svils_rank_links(svils_handle *h, const uint32_t *pairs, uint64_t npairs, uint32_t *above, uint32_t *tied, uint32_t *ncand,
+                     double *score) {
+  if (int rc = check_handle(h, "svils_rank_links")) return rc;
+  if (npairs && !pairs) return fail(SVILS_ERR_ARG, "svils_rank_links: null argument");
+  const Geometry &g = h->geo;
+  for (uint64_t i = 0; i < npairs; ++i) {
+    const uint32_t p = pairs[2 * i], q = pairs[2 * i + 1];
+    if (p >= g.n || q >= g.n) return fail(SVILS_ERR_ARG, "svils_rank_links: pair %llu = (%u, %u): node id >= n = %u", (unsigned long long)i, p, q, g.n);
+    if (p == q) return fail(SVILS_ERR_ARG, "svils_rank_links: pair %llu = (%u, %u): p == q", (unsigned long long)i, p, q);
+  }
+  if (!npairs) return 0;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = prepare(h)) return rc;
+  int cus = 0;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
+  if (cus <= 0) cus = 256;
+  svils_handle::PredictScratch &s = h->pred;
+  const uint32_t k16 = (g.K + 15u) & ~15u;
+  std::vector<uint32_t> ph, qh, ch;
+  std::vector<double> th;
+  for (uint64_t b = 0; b < npairs; b += Q_BATCH) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(Q_BATCH, npairs - b);
+    const uint32_t nqt = (m + PQ - 1) / PQ, rows = nqt * PQ;
+    // chunks as in svils_predict_links, without the merge's bound: the counts are sums over the chunks, whatever the cut
+    uint32_t nch = std::max<uint32_t>(1, (8u * (uint32_t)cus + nqt - 1) / nqt);
+    nch = std::min(nch, std::max<uint32_t>(1, g.n / PC));
+    if (int rc = grow(h, &s.qnodes, &s.q_cap, rows)) return rc;
+    if (int rc = grow(h, &s.aq, &s.aq_cap, (uint64_t)rows * k16)) return rc;
+    if (!s.rq || s.rank_cap < rows) {
+      uint64_t c1 = s.rank_cap, c2 = s.rank_cap, c3 = s.rank_cap;
+      if (int rc = grow(h, &s.rq, &c1, rows)) return rc;
+      if (int rc = grow(h, &s.rthr, &c2, rows)) return rc;
+      if (int rc = grow(h, &s.rcnt, &c3, 3 * (uint64_t)rows)) return rc;
+      s.rank_cap = rows;
+    }
+    ph.assign(rows, NONE);
+    qh.assign(rows, NONE);
+    for (uint32_t i = 0; i < m; ++i) { ph[i] = pairs[2 * (b + i)]; qh[i] = pairs[2 * (b + i) + 1]; }
+    HIPCHK(hipMemcpyAsync(s.qnodes, ph.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(s.rq, qh.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(s.rcnt, 0, 3 * (size_t)rows * sizeof(uint32_t), h->stream));
+    const uint64_t ae = (uint64_t)rows * k16;
+    hipLaunchKernelGGL(k_build_aq, dim3((uint32_t)((ae + 255) / 256)), dim3(256), 0, h->stream, rows, g.K, g.ld, k16, h->d.gamma,
+                       s.inv, s.beta, s.qnodes, s.aq);
+    hipLaunchKernelGGL(k_rank_thresh, dim3(nqt), dim3(256), 0, h->stream, g.K, g.ld, k16, h->d.gamma, s.inv, s.aq, s.rq, s.rthr);
+    hipLaunchKernelGGL(k_rank_tiles, dim3(nqt, nch), dim3(256), 0, h->stream, g.n, g.K, g.ld, k16, nch, h->d.gamma, s.inv, s.aq,
+                       s.qnodes, s.rq, s.rthr, h->d.rowptr, s.scol, s.rcnt);
+    HIPCHK(hipGetLastError());
+    ch.resize(3 * (size_t)m);
+    th.resize(m);
+    HIPCHK(hipMemcpyAsync(ch.data(), s.rcnt, 3 * (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(th.data(), s.rthr, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (uint32_t i = 0; i < m; ++i) {
+      if (above) above[b + i] = ch[3 * (size_t)i];
+      if (tied) tied[b + i] = ch[3 * (size_t)i + 1];
+      if (ncand) ncand[b + i] = ch[3 * (size_t)i + 2];
+      if (score) score[b + i] = th[i];
+    }
   }
   return 0;
 }

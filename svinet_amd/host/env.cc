@@ -69,7 +69,8 @@ Env::Env(const Args &a)
       terminate(0), total_pairs(0), ones_prob(0), zeros_prob(1),
       device(a.device), sweep_batch(a.sweep_batch), write_files(a.write_files),
       minibatch(a.minibatch), tau0(a.tau0), kappa(a.kappa), nodetau0(a.nodetau0), nodekappa(a.nodekappa),
-      sparse_after(a.sparse_after), predict_pairs_fname(a.predict_pairs_fname), recommend((uint32_t)a.recommend) {
+      sparse_after(a.sparse_after), predict_pairs_fname(a.predict_pairs_fname), recommend((uint32_t)a.recommend),
+      rank_pairs_fname(a.rank_pairs_fname), rank_heldout(a.rank_heldout) {
   if (!write_files) {
     if (plogf_) { fclose(plogf_); plogf_ = nullptr; }
     prefix.clear();

@@ -64,6 +64,9 @@ class Env {
     // link prediction from the final state (svils_link_prob / svils_predict_links): -predict-pairs <file>, -recommend <k>
     std::string predict_pairs_fname;
     int recommend = 0;              // top-k links per node written to recommendations.txt; 0 = none
+    // where given links stand among their nodes' candidates (svils_rank_links): -rank-pairs <file>, -rank-heldout
+    std::string rank_pairs_fname;
+    bool rank_heldout = false;
   };
 
   explicit Env(const Args &a);
@@ -115,6 +118,8 @@ class Env {
   int32_t sparse_after;
   std::string predict_pairs_fname;   // -predict-pairs: pairs scored into link-prob.txt ("" = none)
   uint32_t recommend;                // -recommend: top-k links per node into recommendations.txt (0 = none)
+  std::string rank_pairs_fname;      // -rank-pairs: pairs ranked into link-ranks.txt ("" = none)
+  bool rank_heldout;                 // -rank-heldout: the held-out links ranked into heldout-ranks.txt
 
   static std::string prefix;
   static std::string file_str(const std::string &fname) { return prefix + fname; }

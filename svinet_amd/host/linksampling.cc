@@ -81,7 +81,7 @@ LinkSampling::LinkSampling(Env &env, Network &network, bool attach_device)
     Env::plog("load test from file:", true);     // sampler never saw these pairs
     load_test();
   }
-  if (!env_.predict_pairs_fname.empty()) load_predict_pairs();
+  load_predict_pairs();
 
   if (env_.nmi) {   // Network::load_ground_truth / write_gt_communities (src/network.cc:252-307,508-525)
     if (!read_cover_memberships(env_.ground_truth_fname, &ground_truth_)) {
@@ -378,7 +378,7 @@ void LinkSampling::load_test() {
   }
   int a, b;
   uint32_t cnt = 0;
-  std::vector<uint32_t> listed;
+  std::vector<uint32_t> &listed = test_listed_;
   while (fscanf(f, "%d %d", &a, &b) == 2) {
     uint32_t p, q;
     if (!network_.id2seq((uint32_t)a, &p) || !network_.id2seq((uint32_t)b, &q)) {
@@ -401,31 +401,42 @@ void LinkSampling::load_test() {
   }
 }
 
-// -predict-pairs: "id<TAB>id" lines of external ids, parsed like -load-test; an unknown id or a pair of one node ends the run
-void LinkSampling::load_predict_pairs() {
-  FILE *f = fopen(env_.predict_pairs_fname.c_str(), "r");
+// -predict-pairs / -rank-pairs: "id<TAB>id" lines of external ids, parsed like -load-test; an unknown id or a pair of one node
+// ends the run
+void LinkSampling::load_pairs_file(const char *flag, const std::string &fname, std::vector<int> *ext, std::vector<uint32_t> *seq) const {
+  FILE *f = fopen(fname.c_str(), "r");
   if (!f) {
-    fprintf(stderr, "error: cannot read -predict-pairs file %s\n", env_.predict_pairs_fname.c_str());
+    fprintf(stderr, "error: cannot read %s file %s\n", flag, fname.c_str());
     exit(2);
   }
   int a, b;
   while (fscanf(f, "%d %d", &a, &b) == 2) {
     uint32_t p, q;
     if (!network_.id2seq((uint32_t)a, &p) || !network_.id2seq((uint32_t)b, &q)) {
-      fprintf(stderr, "error: -predict-pairs: id %d or id %d not found in original network\n", a, b);
+      fprintf(stderr, "error: %s: id %d or id %d not found in original network\n", flag, a, b);
       exit(2);
     }
     if (p == q) {
-      fprintf(stderr, "error: -predict-pairs: pair %d %d is one node\n", a, b);
+      fprintf(stderr, "error: %s: pair %d %d is one node\n", flag, a, b);
       exit(2);
     }
-    pp_ext_.push_back(a);
-    pp_ext_.push_back(b);
-    pp_seq_.push_back(p);
-    pp_seq_.push_back(q);
+    ext->push_back(a);
+    ext->push_back(b);
+    seq->push_back(p);
+    seq->push_back(q);
   }
   fclose(f);
-  Env::plog("link prediction: pairs to score:", (uint32_t)(pp_seq_.size() / 2));
+}
+
+void LinkSampling::load_predict_pairs() {
+  if (!env_.predict_pairs_fname.empty()) {
+    load_pairs_file("-predict-pairs", env_.predict_pairs_fname, &pp_ext_, &pp_seq_);
+    Env::plog("link prediction: pairs to score:", (uint32_t)(pp_seq_.size() / 2));
+  }
+  if (!env_.rank_pairs_fname.empty()) {
+    load_pairs_file("-rank-pairs", env_.rank_pairs_fname, &rp_ext_, &rp_seq_);
+    Env::plog("link prediction: pairs to rank:", (uint32_t)(rp_seq_.size() / 2));
+  }
 }
 
 // link-prob.txt (one line per -predict-pairs line, in input order: id_a, id_b, the network's y, link_prob) and
@@ -467,6 +478,80 @@ void LinkSampling::write_predictions() {
     }
     fclose(f);
   }
+}
+
+bool LinkSampling::held_out(uint32_t p, uint32_t q) const {
+  const Edge e = p < q ? Edge(p, q) : Edge(q, p);
+  return validation_map_.count(e) || test_map_.count(e);
+}
+
+// link-ranks.txt (one line per -rank-pairs line, in input order) and heldout-ranks.txt (-rank-heldout: the y = 1 pairs of
+// validation-edges.txt in its order, then those of test-edges.txt): id_p, id_q, the network's y, the score of (p, q), the
+// mid-rank of q among p's candidates (above + 1 + tied / 2 of svils_rank_links, "%.3f") and their count, the same for p among
+// q's.  link-ranks-summary.txt: a header and one line of values over the directed pairs (p -> q, then q -> p, in file order)
+// of the lines with y = 1 whose pair is held out, i.e. no training link -- of heldout-ranks.txt when that is written, of
+// link-ranks.txt otherwise; a direction without a candidate is left out.  The means are sequential double sums in that
+// order.  Under -minibatch the pairs go through the relabelling like those of -predict-pairs.
+void LinkSampling::write_ranks() {
+  const std::vector<uint32_t> &s2i = network_.seq2id();
+  auto dev = [&](uint32_t seq) { return dev_of_.empty() ? seq : dev_of_[seq]; };
+  struct Sum { uint64_t cnt = 0, h1 = 0, h10 = 0, h100 = 0; double auc = .0, mrr = .0, chance = .0; } sum;
+  auto write = [&](const char *fname, const std::vector<uint32_t> &seq, const std::vector<int> *ext) {
+    const size_t m = seq.size() / 2;
+    std::vector<uint32_t> pairs(4 * m), above(2 * m), tied(2 * m), ncand(2 * m);
+    std::vector<double> sc(2 * m);
+    for (size_t i = 0; i < m; ++i) {
+      pairs[4 * i] = pairs[4 * i + 3] = dev(seq[2 * i]);
+      pairs[4 * i + 1] = pairs[4 * i + 2] = dev(seq[2 * i + 1]);
+    }
+    if (svils_rank_links(h_, pairs.data(), 2 * m, above.data(), tied.data(), ncand.data(), sc.data())) die_svils("svils_rank_links");
+    sum = Sum();
+    std::string o;
+    {
+      RowOut out(o);
+      char num[64];
+      for (size_t i = 0; i < m; ++i) {
+        const uint32_t p = seq[2 * i], q = seq[2 * i + 1];
+        const bool y = network_.y(p, q);
+        out.integer(ext ? (*ext)[2 * i] : (long)s2i[p], '\t');
+        out.integer(ext ? (*ext)[2 * i + 1] : (long)s2i[q], '\t');
+        out.integer(y ? 1 : 0, '\t');
+        snprintf(num, sizeof num, "%.9e\t", sc[2 * i]);
+        out.text(num);
+        for (size_t d = 2 * i; d < 2 * i + 2; ++d) {
+          const double ahead_mid = (double)above[d] + 0.5 * (double)tied[d];   // candidates ahead of the link, ties halved
+          out.fixed<3>(ahead_mid + 1.0, '\t');
+          out.integer((long)ncand[d], d == 2 * i ? '\t' : '\n');
+          if (!y || !held_out(p, q) || ncand[d] == 0) continue;
+          const uint64_t ahead = (uint64_t)above[d] + tied[d];
+          ++sum.cnt;
+          sum.auc += 1.0 - ahead_mid / (double)ncand[d];
+          sum.mrr += 1.0 / (ahead_mid + 1.0);
+          sum.h1 += ahead < 1;
+          sum.h10 += ahead < 10;
+          sum.h100 += ahead < 100;
+          sum.chance += 10.0 / (double)ncand[d];
+        }
+      }
+    }
+    FILE *f = open_or_die(Env::file_str(fname), fname + 1);
+    fwrite(o.data(), 1, o.size(), f);
+    fclose(f);
+  };
+  if (!env_.rank_pairs_fname.empty()) write("/link-ranks.txt", rp_seq_, &rp_ext_);
+  if (env_.rank_heldout) {
+    std::vector<uint32_t> seq;
+    for (const std::vector<uint32_t> *t : {&val_accept_, &test_listed_})
+      for (size_t i = 0; i + 2 < t->size(); i += 3)
+        if ((*t)[i + 2]) { seq.push_back((*t)[i]); seq.push_back((*t)[i + 1]); }
+    write("/heldout-ranks.txt", seq, nullptr);
+  }
+  FILE *f = open_or_die(Env::file_str("/link-ranks-summary.txt"), "link-ranks-summary");
+  const double c = sum.cnt ? (double)sum.cnt : 1.0;
+  fprintf(f, "pairs\tauc\tmrr\thits1\thits10\thits100\tchance10\n%llu\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\n",
+          (unsigned long long)sum.cnt, sum.auc / c, sum.mrr / c, (double)sum.h1 / c, (double)sum.h10 / c, (double)sum.h100 / c,
+          sum.chance / c);
+  fclose(f);
 }
 
 std::string LinkSampling::edgelist_s(const std::vector<uint32_t> &t) const {  // :190-206
@@ -1083,6 +1168,10 @@ void LinkSampling::do_on_stop_impl() {
   if (!pp_seq_.empty() || env_.recommend) {
     write_predictions();
     mark("link-prob.txt / recommendations.txt");
+  }
+  if (!env_.rank_pairs_fname.empty() || env_.rank_heldout) {
+    write_ranks();
+    mark("link-ranks.txt / heldout-ranks.txt");
   }
   write_groups();
   mark("groups.txt");

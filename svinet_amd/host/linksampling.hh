@@ -78,8 +78,11 @@ class LinkSampling {
   void init_validation();
   void load_validation();
   void load_test();                            // -load-test
-  void load_predict_pairs();                   // -predict-pairs: read and checked before any device work
+  void load_predict_pairs();                   // -predict-pairs / -rank-pairs: read and checked before any device work
+  void load_pairs_file(const char *flag, const std::string &fname, std::vector<int> *ext, std::vector<uint32_t> *seq) const;
   void write_predictions();                    // link-prob.txt / recommendations.txt from the final state
+  void write_ranks();                          // link-ranks.txt / heldout-ranks.txt / link-ranks-summary.txt from the final state
+  bool held_out(uint32_t p, uint32_t q) const; // the pair is in the validation or the test set (a link there is no training link)
   void init_gamma_external();                  // -init-communities
   void set_validation_sample(int s);
   void get_random_edge(bool link, Edge &e);
@@ -120,6 +123,9 @@ class LinkSampling {
   std::vector<uint32_t> test_sorted_;          // [T][3] p, q, y in map order
   std::vector<int> pp_ext_;                    // -predict-pairs: [m][2] external ids as listed
   std::vector<uint32_t> pp_seq_;               // [m][2] the same as sequence ids
+  std::vector<int> rp_ext_;                    // -rank-pairs: likewise
+  std::vector<uint32_t> rp_seq_;
+  std::vector<uint32_t> test_listed_;          // -load-test: [T][3] p, q, y of every line, as test-edges.txt lists them
   DVec gamma_;                                 // (empty while init_gamma2 is left to the device: defer_init_)
   std::vector<double> lambda_;
   uint64_t init_o0_ = 0;                       // outputs the generator had produced when init_gamma2 began

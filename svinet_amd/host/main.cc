@@ -51,19 +51,20 @@ static void forward_handler(int sig) {
 
 // The single-GPU tool modes refuse the flags of the fitting paths.  Every flag a mode may refuse, in the order the checks
 // name them: a mode reports the first one set among its own.
-enum : unsigned { F_BATCH = 1, F_GPUS = 2, F_KSHARD = 4, F_SHARDED = 8, F_MINIBATCH = 16, F_PAIRS = 32, F_RECOMMEND = 64, F_K2048 = 128 };
+enum : unsigned { F_BATCH = 1, F_GPUS = 2, F_KSHARD = 4, F_SHARDED = 8, F_MINIBATCH = 16, F_PAIRS = 32, F_RECOMMEND = 64, F_K2048 = 128,
+                  F_RANKPAIRS = 256, F_RANKHELDOUT = 512 };
 
 struct ToolMode {
   unsigned refuses;   // F_* bits
   const char *fmt;    // the refusal: %1$s the mode's flag, %2$s the refused flag
 };
 static const ToolMode kLinkCommunities = {   // -gml / -lcstats: one pass over a saved model
-    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND,
+    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT,
     "error: %2$s is not available with %1$s (a single-GPU pass over gamma.txt / lambda.txt)\n"};
 static const ToolMode kFindK = {             // -findk: whole iterations
-    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND,
+    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT,
     "error: %2$s is not available with %1$s (a single-GPU run)\n"};
-static const ToolMode kPrediction = {        // -predict-pairs / -recommend after a fit
+static const ToolMode kPrediction = {        // -predict-pairs / -recommend / -rank-pairs / -rank-heldout after a fit
     F_BATCH | F_GPUS | F_KSHARD | F_SHARDED | F_K2048,
     "error: %1$s is not available with %2$s (single-GPU -link-sampling runs with -k <= 2048 only)\n"};
 
@@ -77,6 +78,8 @@ static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) 
       {F_MINIBATCH, a.minibatch != 0, "-minibatch"},
       {F_PAIRS, !a.predict_pairs_fname.empty(), "-predict-pairs"},
       {F_RECOMMEND, a.recommend != 0, "-recommend"},
+      {F_RANKPAIRS, !a.rank_pairs_fname.empty(), "-rank-pairs"},
+      {F_RANKHELDOUT, a.rank_heldout, "-rank-heldout"},
       {F_K2048, a.k > 2048, "-k > 2048"},
   };
   for (const auto &f : flags)
@@ -134,6 +137,11 @@ static void usage() {
           "\t-recommend <k>\tlink prediction: the k (1 .. 256) most probable links of every node that are not training links,\n"
           "\t\t\tfrom the final state; writes recommendations.txt (one line per node, groups.txt order).  Both flags\n"
           "\t\t\tbelong to single-GPU -link-sampling runs with -k <= 2048\n\n"
+          "\t-rank-pairs <file>\tlink prediction: where each pair of <file> (\"id<TAB>id\" lines of external ids) stands among the\n"
+          "\t\t\tcandidates -recommend chooses from, in both directions; writes link-ranks.txt (id_p, id_q, y, score, mid-rank of q\n"
+          "\t\t\tamong p's candidates and their count, the same for p among q's) and link-ranks-summary.txt (per-link AUC, MRR, hits@k)\n\n"
+          "\t-rank-heldout\tthe same for the held-out links of the run (the y = 1 pairs of validation-edges.txt and, with -load-test,\n"
+          "\t\t\tof test-edges.txt); writes heldout-ranks.txt and link-ranks-summary.txt.  Where -recommend is available\n\n"
           "\t-minibatch <m>\tmini-batch mode of -link-sampling: one step = the links of m randomly chosen nodes,\n"
           "\t\t\tRobbins-Monro step sizes (-tau0 -kappa -nodetau0 -nodekappa; defaults 1024 0.9 1024 0.5);\n"
           "\t\t\tgive -rfreq <steps> after -link-sampling to evaluate the stop rule every <steps> steps\n\n");
@@ -207,6 +215,8 @@ int main(int argc, char **argv) {
     else if (is("-nodetau0")) { need(i); a.nodetau0 = atof(argv[++i]); }
     else if (is("-nodekappa")) { need(i); a.nodekappa = atof(argv[++i]); }
     else if (is("-predict-pairs")) { need(i); a.predict_pairs_fname = argv[++i]; }
+    else if (is("-rank-pairs")) { need(i); a.rank_pairs_fname = argv[++i]; }
+    else if (is("-rank-heldout")) { a.rank_heldout = true; }
     else if (is("-recommend")) { need(i); a.recommend = atoi(argv[++i]); if (a.recommend == 0) a.recommend = -1; }
     else if (is("-init-communities")) { need(i); a.init_comm = true; a.init_comm_fname = argv[++i]; }   // src/main.cc:237-239
     else if (is("-stopthresh") || is("-inf") || is("-scale") || is("-itype") || is("-groups-file")) {
@@ -256,6 +266,17 @@ int main(int argc, char **argv) {
       FILE *f = fopen(a.predict_pairs_fname.c_str(), "r");
       if (!f) {
         fprintf(stderr, "error: cannot read -predict-pairs file %s\n", a.predict_pairs_fname.c_str());
+        return 2;
+      }
+      fclose(f);
+    }
+  }
+  if (!a.rank_pairs_fname.empty() || a.rank_heldout) {   // ranks of given links (svils_rank_links)
+    if (refused(a, kPrediction, a.rank_heldout ? "-rank-heldout" : "-rank-pairs")) return 2;
+    if (!a.rank_pairs_fname.empty()) {
+      FILE *f = fopen(a.rank_pairs_fname.c_str(), "r");
+      if (!f) {
+        fprintf(stderr, "error: cannot read -rank-pairs file %s\n", a.rank_pairs_fname.c_str());
         return 2;
       }
       fclose(f);

@@ -1,0 +1,108 @@
+"""svils_rank_links: its time against svils_predict_links(topk = 10) on the same handle, and what it measures on fitted models.
+
+  python tools/rank_bench.py [--reps R] [--out file.jsonl] [--workloads time,lfr,astroph]
+
+  time     n = 1e6, K = 512 seeded random state (that of tools/predict_bench.py's workload 3): 8192 directed pairs (p, q), one
+           per query node, through rank_links, and the same 8192 nodes through predict_links(topk = 10); same handle, same
+           process.  Each call is synchronous; the time is the wall time of a warm call, best and median of --reps.
+  lfr      LFR n = 1000, K = 28 fitted to the stop rule: the held-out links of the validation set, both directions, ranked;
+           per-link AUC, MRR and hits@k as link-ranks-summary.txt defines them
+  astroph  the same for ca-AstroPh, K = 20 (at most 6400 sweeps; "stopped" says whether the stop rule fired)"""
+import argparse
+import gzip
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+GRAPHS = {"lfr": ("LFR-network-n1000-k28.txt.gz", 1000, 28), "astroph": ("ca-AstroPh.csv.gz", 17903, 20)}
+
+
+def _time(fn, reps):
+    fn()   # warm: scratch, sorted rows
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return min(ts) * 1e3, float(np.median(ts)) * 1e3
+
+
+def run_time(reps):
+    from svinet_amd import _svils
+    n, k, nq = 1000000, 512, 8192
+    rng = np.random.default_rng(12345)
+    a, b = rng.integers(0, n, size=(2, 2 * n))
+    e = np.stack([np.minimum(a, b), np.maximum(a, b)], 1)
+    e = np.unique(e[e[:, 0] != e[:, 1]], axis=0)
+    links = np.ascontiguousarray(e, dtype=np.uint32)
+    eng = _svils.Engine(n, k, ones=len(links), ones_prob=len(links) / (n * (n - 1) / 2), use_validation_stop=False)
+    eng.set_graph(links)
+    eng.set_state(rng.random((n, k)) + 0.01, rng.random((k, 2)) + 0.1)
+    nodes = rng.choice(n, size=nq, replace=False).astype(np.uint32)
+    pairs = np.stack([nodes, (nodes + 1 + rng.integers(0, n - 1, size=nq)) % n], 1).astype(np.uint32)
+    rbest, rmed = _time(lambda: eng.rank_links(pairs), reps)
+    pbest, pmed = _time(lambda: eng.predict_links(10, nodes), reps)
+    flop = 2.0 * nq * n * k
+    eng.close()
+    return {"workload": "time", "name": "n=1e6 K=512 random state, 8192 query rows", "n": n, "K": k, "rows": nq, "flop": flop,
+            "rank_links_best_ms": rbest, "rank_links_median_ms": rmed, "predict_links_top10_best_ms": pbest,
+            "predict_links_top10_median_ms": pmed, "rank_tflops": flop / rbest / 1e9, "predict_tflops": flop / pbest / 1e9,
+            "rank_over_predict": rbest / pbest}
+
+
+def run_quality(which):
+    from svinet_amd.host_api import Setup
+    fname, n, k = GRAPHS[which]
+    tmp = tempfile.NamedTemporaryFile(delete=False, suffix=".txt")
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "graphs", fname), "rb") as f:
+        tmp.write(f.read())
+    tmp.close()
+    try:
+        s = Setup(tmp.name, n, k)
+    finally:
+        os.unlink(tmp.name)
+    eng = s.engine(use_validation_stop=True)
+    for _ in range(100):
+        eng.sweep(64)
+        if eng.control().stopped:
+            break
+    c = eng.control()
+    v1 = s.validation_accept[s.validation_accept[:, 2] == 1][:, :2]
+    pairs = np.ascontiguousarray(np.stack([v1, v1[:, ::-1]], 1).reshape(-1, 2), dtype=np.uint32)
+    t0 = time.perf_counter()
+    above, tied, ncand, _ = eng.rank_links(pairs)
+    ms = (time.perf_counter() - t0) * 1e3
+    mid = above + 0.5 * tied
+    ahead = above.astype(np.int64) + tied
+    rec = {"workload": which, "n": s.n, "K": k, "stopped": bool(c.stopped), "iterations": int(c.iter), "directed_pairs": len(pairs),
+           "auc": float(np.mean(1.0 - mid / ncand)), "mrr": float(np.mean(1.0 / (mid + 1.0))),
+           "hits1": float(np.mean(ahead < 1)), "hits10": float(np.mean(ahead < 10)), "hits100": float(np.mean(ahead < 100)),
+           "chance10": float(np.mean(10.0 / ncand)), "tied_pairs": int(np.sum(tied > 0)), "rank_links_first_call_ms": ms}
+    eng.close()
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--workloads", default="time,lfr,astroph")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    for w in a.workloads.split(","):
+        rec = run_time(a.reps) if w == "time" else run_quality(w)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
