@@ -41,7 +41,9 @@ extern "C" {
                                     on a sweep path reads the environment); svils_gather_communities ends the no-wait window of "After the stop";
                                     (additive, same version) svils_link_prob / svils_predict_links: link prediction from the state;
                                     (additive, same version) svils_findk_*: -findk, the estimate of the number of communities;
-                                    (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model */
+                                    (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
+                                    (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
+                                    resource-allocation scores of pairs, the model-free baselines of svils_rank_links */
 
 typedef enum {
   SVILS_OK = 0,
@@ -339,6 +341,36 @@ int svils_predict_links(svils_handle *h, const uint32_t *nodes, uint32_t nnodes,
  * SVILS_ERR_ARG / SVILS_ERR_UNSUPPORTED: as for svils_link_prob. */
 int svils_rank_links(svils_handle *h, const uint32_t *pairs, uint64_t npairs, uint32_t *above, uint32_t *tied, uint32_t *ncand,
                      double *score);
+
+/* ---- neighbourhood scores: the model-free baselines of link ranks (an ADDITION of ABI 8; nothing on the sweep path changes) ----
+ * score(p, q) = sum over the common TRAINING neighbours z of p and q, in ascending z, of w[deg z], deg = training degree:
+ *   SVILS_NBR_CN  w = 1                  the number of common neighbours
+ *   SVILS_NBR_AA  w = 1 / log(deg z)     Adamic-Adar: the reference's -adamic-adar (FastAMM::compute_adamic_adar_score,
+ *                                        src/fastamm.cc:1486-1575), wired there to engines this build does not carry
+ *   SVILS_NBR_RA  w = 1 / deg z          resource allocation
+ * w is a table over the degrees 0 .. the largest training degree, w[0] = w[1] = 0 (a common neighbour of p != q has degree
+ * >= 2), computed ON THE HOST as 1.0 / std::log((double)d) and 1.0 / (double)d, once per handle and measure, and uploaded:
+ * a score is bitwise the sequential sum, in ascending z, of those doubles, so that equal scores are ties a caller can
+ * restate.  CN scores and every count are exact integers.
+ * The contract is that of svils_link_prob / svils_rank_links: the calls enqueue on the handle's stream behind what is there
+ * and synchronise; they read the training CSR only and need a graph but NO state; any output pointer may be NULL; results
+ * are bitwise deterministic and a pair's result does not depend on the other pairs of the call, on their order or on the
+ * workgroup that served it.  Device scratch, allocated on first use and freed by svils_destroy: the sorted CSR copy shared
+ * with svils_predict_links (4 bytes per CSR entry), 8 bytes per degree up to the largest for every measure used, 36 bytes
+ * per pair of an internal batch of 65536 (2.4 MB), and for svils_nbr_rank one bitmap of n bits per workgroup, four
+ * workgroups per CU: n / 8 x 1024 bytes on 256 CUs (128 MB at n = 10^6).
+ * SVILS_ERR_ARG: a null handle, no graph, a node id >= n, a pair with p == q, an unknown measure.
+ * SVILS_ERR_UNSUPPORTED: column-tiled handles (k > SVILS_MAX_K), K-sharded handles (k_total != 0), node-block handles. */
+typedef enum { SVILS_NBR_CN = 0, SVILS_NBR_AA = 1, SVILS_NBR_RA = 2 } svils_nbr_measure;
+/* pairs[npairs][2] (p != q, both < n) -> score[npairs], common[npairs] = the number of common training neighbours */
+int svils_nbr_score(svils_handle *h, int measure, const uint32_t *pairs, uint64_t npairs, double *score, uint32_t *common);
+/* svils_rank_links with this score in place of link_prob: for every directed pair (p, q), over the candidates c != q of p
+ * (every node except p and p's training neighbours; q may itself be a training neighbour)
+ *   above[i] = #{c : score(p,c) > s}, tied[i] = #{c : score(p,c) == s}, ncand[i] = #{c}, score[i] = s = score(p, q),
+ * s bitwise that of svils_nbr_score.  Only the candidates two steps from p can score above zero: they are visited and
+ * scored by the device function that computes s; the others score exactly 0 and are counted (they tie when s == 0). */
+int svils_nbr_rank(svils_handle *h, int measure, const uint32_t *pairs, uint64_t npairs, uint32_t *above, uint32_t *tied,
+                   uint32_t *ncand, double *score);
 
 /* Evaluate the kernels' own special functions on a plain array (unit tests):
  * which = 0 digamma(x) [stands for gsl_sf_psi], 1 exp(x) for x <= 0, 2 1/x, 3 ln(x) for x >= 1. */

@@ -34,7 +34,7 @@ EXPORTS = (
     "svils_report_tag_count", "svils_report_fetch_tags", "svils_get_community_tags",
     "svils_set_node_blocks", "svils_balance_node_blocks", "svils_prepare_graphs",
     "svils_set_option", "svils_get_option", "svils_option_table", "svils_init_gamma",
-    "svils_link_prob", "svils_predict_links", "svils_rank_links",
+    "svils_link_prob", "svils_predict_links", "svils_rank_links", "svils_nbr_score", "svils_nbr_rank",
     "svils_findk_create", "svils_findk_destroy", "svils_findk_set_graph", "svils_findk_init_state", "svils_findk_count",
     "svils_findk_pad_requests", "svils_findk_apply", "svils_findk_report", "svils_findk_get_state", "svils_findk_get_timing",
     "svils_lc_create", "svils_lc_destroy", "svils_lc_set_graph", "svils_lc_set_model", "svils_lc_run", "svils_lc_get_nodes",
@@ -42,6 +42,7 @@ EXPORTS = (
     "svils_lc_get_timing",
 )
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
+NBR_CN, NBR_AA, NBR_RA = range(3)   # svils_nbr_measure
 
 
 class SvilsError(RuntimeError):
@@ -159,6 +160,8 @@ def load():
     L.svils_link_prob.argtypes = [vp, vp, C.c_uint64, vp]
     L.svils_predict_links.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.svils_rank_links.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
+    L.svils_nbr_score.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, vp]
+    L.svils_nbr_rank.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, vp, vp, vp]
     L.svils_findk_create.argtypes = [C.c_int, C.c_uint32, C.c_double, C.c_double, C.POINTER(vp)]
     L.svils_findk_destroy.argtypes = [vp]
     L.svils_findk_set_graph.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]
@@ -446,6 +449,27 @@ class Engine:
         score = np.zeros(m, dtype=np.float64)
         _chk(load().svils_rank_links(self._h, pairs.ctypes.data, m, above.ctypes.data, tied.ctypes.data, ncand.ctypes.data,
                                      score.ctypes.data))
+        return above, tied, ncand, score
+
+    def nbr_score(self, measure, pairs):
+        """the neighbourhood score (NBR_CN / NBR_AA / NBR_RA) of node pairs [m][2] (p != q) from the training graph alone
+        -> (score float64[m], common uint32[m]) (svils_nbr_score)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        m = pairs.shape[0]
+        score = np.zeros(m, dtype=np.float64)
+        common = np.zeros(m, dtype=np.uint32)
+        _chk(load().svils_nbr_score(self._h, int(measure), pairs.ctypes.data, m, score.ctypes.data, common.ctypes.data))
+        return score, common
+
+    def nbr_rank(self, measure, pairs):
+        """rank_links by a neighbourhood score instead of the model's: directed pairs [m][2] -> (above uint32[m],
+        tied uint32[m], ncand uint32[m], score float64[m]), score bitwise that of nbr_score (svils_nbr_rank)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        m = pairs.shape[0]
+        above, tied, ncand = (np.zeros(m, dtype=np.uint32) for _ in range(3))
+        score = np.zeros(m, dtype=np.float64)
+        _chk(load().svils_nbr_rank(self._h, int(measure), pairs.ctypes.data, m, above.ctypes.data, tied.ctypes.data,
+                                   ncand.ctypes.data, score.ctypes.data))
         return above, tied, ncand, score
 
     def debug_eval(self, which, x):

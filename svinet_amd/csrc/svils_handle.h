@@ -176,6 +176,17 @@ struct svils_handle {
     uint32_t *rcnt = nullptr;        // [rank_cap][3] candidates above it, tied with it, seen
     uint64_t rank_cap = 0;
   } pred;
+  // neighbourhood scores (svils_nbr_score / svils_nbr_rank, svils_nbr.hip): scratch of their own, dalloc()ed on first use;
+  // the sorted rows are pred.scol
+  struct NbrScratch {
+    double *w[3] = {nullptr, nullptr, nullptr};   // [maxdeg + 1] the weight of a common neighbour by its degree, per measure (host-built)
+    uint32_t *pairs = nullptr;       // [cap][2]
+    double *score = nullptr;         // [cap]
+    uint32_t *cnt = nullptr;         // [cap][3] svils_nbr_score: common; svils_nbr_rank: above, tied, ncand
+    uint64_t cap = 0;
+    uint32_t *bitmap = nullptr;      // [blocks][ceil(n / 32)] the claimed two-hop nodes of the pair a block is serving; all zero between launches
+    uint32_t blocks = 0;
+  } nbr;
   ReportSlot rslot[SVILS_REPORT_SLOTS];
   ReportLayout rlay{};
   hipStream_t copy_stream = nullptr;
@@ -290,6 +301,8 @@ int apply_s3_split(svils_handle *h);
 int apply_blocks(svils_handle *h, int rank, int world, const uint32_t *bounds, bool explicit_bounds);
 int ensure_blocks(svils_handle *h);
 void comm_destroy(svils_handle *h);
+// ---- svils_predict.hip
+int sorted_rows(svils_handle *h);   // PredictScratch::scol exists (enqueued on the handle's stream the first time)
 // ---- svils_stoch.hip
 int open_step(svils_handle *h);
 int step_phase_impl(svils_handle *h, svils_phase phase, bool fused);

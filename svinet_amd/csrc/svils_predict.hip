@@ -380,15 +380,26 @@ int check_handle(svils_handle *h, const char *name) {
   return 0;
 }
 
+}  // namespace
+
+// the sorted copy of the CSR (svils_handle::PredictScratch::scol), built on the handle's stream the first time it is asked for
+int svils_impl::sorted_rows(svils_handle *h) {
+  svils_handle::PredictScratch &s = h->pred;
+  if (s.scol) return 0;
+  if (int rc = dalloc(h, &s.scol, 2 * h->d.nlinks, false)) return rc;
+  hipLaunchKernelGGL(k_sort_rows, dim3((h->geo.n + 3) / 4), dim3(256), 0, h->stream, h->geo.n, h->d.rowptr, h->d.col, s.scol);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+namespace {
+
 // what every top-k or rank call needs besides its batches: the sorted rows (once), 1 / row sums and beta of the current state
 int prepare(svils_handle *h) {
   const Geometry &g = h->geo;
   const DeviceState &d = h->d;
   svils_handle::PredictScratch &s = h->pred;
-  if (!s.scol) {
-    if (int rc = dalloc(h, &s.scol, 2 * d.nlinks, false)) return rc;
-    hipLaunchKernelGGL(k_sort_rows, dim3((g.n + 3) / 4), dim3(256), 0, h->stream, g.n, d.rowptr, d.col, s.scol);
-  }
+  if (int rc = sorted_rows(h)) return rc;
   if (!s.inv) {
     if (int rc = dalloc(h, &s.inv, g.n, false)) return rc;
     if (int rc = dalloc(h, &s.beta, g.K, false)) return rc;

@@ -70,7 +70,7 @@ Env::Env(const Args &a)
       device(a.device), sweep_batch(a.sweep_batch), write_files(a.write_files),
       minibatch(a.minibatch), tau0(a.tau0), kappa(a.kappa), nodetau0(a.nodetau0), nodekappa(a.nodekappa),
       sparse_after(a.sparse_after), predict_pairs_fname(a.predict_pairs_fname), recommend((uint32_t)a.recommend),
-      rank_pairs_fname(a.rank_pairs_fname), rank_heldout(a.rank_heldout) {
+      rank_pairs_fname(a.rank_pairs_fname), rank_heldout(a.rank_heldout), adamic_adar(a.adamic_adar) {
   if (!write_files) {
     if (plogf_) { fclose(plogf_); plogf_ = nullptr; }
     prefix.clear();

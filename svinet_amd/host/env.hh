@@ -67,6 +67,9 @@ class Env {
     // where given links stand among their nodes' candidates (svils_rank_links): -rank-pairs <file>, -rank-heldout
     std::string rank_pairs_fname;
     bool rank_heldout = false;
+    // -adamic-adar: the same pair lists scored and ranked by common neighbours, Adamic-Adar and resource allocation
+    // (svils_nbr_score / svils_nbr_rank), the baselines beside the model's ranks
+    bool adamic_adar = false;
   };
 
   explicit Env(const Args &a);
@@ -120,6 +123,7 @@ class Env {
   uint32_t recommend;                // -recommend: top-k links per node into recommendations.txt (0 = none)
   std::string rank_pairs_fname;      // -rank-pairs: pairs ranked into link-ranks.txt ("" = none)
   bool rank_heldout;                 // -rank-heldout: the held-out links ranked into heldout-ranks.txt
+  bool adamic_adar;                  // -adamic-adar: link-nbr.txt / *-ranks-aa.txt / link-ranks-baselines.txt beside them
 
   static std::string prefix;
   static std::string file_str(const std::string &fname) { return prefix + fname; }

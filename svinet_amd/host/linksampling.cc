@@ -480,6 +480,20 @@ void LinkSampling::write_predictions() {
   }
 }
 
+// link-nbr.txt (-adamic-adar with -predict-pairs; one line per input line like link-prob.txt): id_a, id_b, the network's y,
+// the number of common training neighbours and the Adamic-Adar score (svils_nbr_score).  No relabelling: -minibatch is refused.
+void LinkSampling::write_nbr_scores() {
+  const size_t m = pp_seq_.size() / 2;
+  std::vector<double> aa(m);
+  std::vector<uint32_t> common(m);
+  if (svils_nbr_score(h_, SVILS_NBR_AA, pp_seq_.data(), m, aa.data(), common.data())) die_svils("svils_nbr_score");
+  FILE *f = open_or_die(Env::file_str("/link-nbr.txt"), "link-nbr");
+  for (size_t i = 0; i < m; ++i)
+    fprintf(f, "%d\t%d\t%d\t%u\t%.9e\n", pp_ext_[2 * i], pp_ext_[2 * i + 1], network_.y(pp_seq_[2 * i], pp_seq_[2 * i + 1]) ? 1 : 0,
+            common[i], aa[i]);
+  fclose(f);
+}
+
 bool LinkSampling::held_out(uint32_t p, uint32_t q) const {
   const Edge e = p < q ? Edge(p, q) : Edge(q, p);
   return validation_map_.count(e) || test_map_.count(e);
@@ -492,11 +506,37 @@ bool LinkSampling::held_out(uint32_t p, uint32_t q) const {
 // of the lines with y = 1 whose pair is held out, i.e. no training link -- of heldout-ranks.txt when that is written, of
 // link-ranks.txt otherwise; a direction without a candidate is left out.  The means are sequential double sums in that
 // order.  Under -minibatch the pairs go through the relabelling like those of -predict-pairs.
-void LinkSampling::write_ranks() {
+// With -adamic-adar the same lists are ranked by the neighbourhood scores of the training graph (svils_nbr_rank):
+// link-ranks-aa.txt / heldout-ranks-aa.txt have the columns of their namesakes with the Adamic-Adar score and the ranks by
+// it, and link-ranks-baselines.txt holds the summary's line once per measure -- model (the values of link-ranks-summary.txt),
+// cn, aa, ra -- over the same selection of pairs, accumulated by the same code.
+void LinkSampling::write_ranks(const std::function<void(const char *)> &mark) {
   const std::vector<uint32_t> &s2i = network_.seq2id();
   auto dev = [&](uint32_t seq) { return dev_of_.empty() ? seq : dev_of_[seq]; };
-  struct Sum { uint64_t cnt = 0, h1 = 0, h10 = 0, h100 = 0; double auc = .0, mrr = .0, chance = .0; } sum;
-  auto write = [&](const char *fname, const std::vector<uint32_t> &seq, const std::vector<int> *ext) {
+  // the summary of one ranking: sequential sums over the directed pairs in file order
+  struct Sum {
+    uint64_t cnt = 0, h1 = 0, h10 = 0, h100 = 0;
+    double auc = .0, mrr = .0, chance = .0;
+    void add(uint32_t above, uint32_t tied, uint32_t ncand) {
+      const double ahead_mid = (double)above + 0.5 * (double)tied;   // candidates ahead of the link, ties halved
+      const uint64_t ahead = (uint64_t)above + tied;
+      ++cnt;
+      auc += 1.0 - ahead_mid / (double)ncand;
+      mrr += 1.0 / (ahead_mid + 1.0);
+      h1 += ahead < 1;
+      h10 += ahead < 10;
+      h100 += ahead < 100;
+      chance += 10.0 / (double)ncand;
+    }
+    void print(FILE *f) const {
+      const double c = cnt ? (double)cnt : 1.0;
+      fprintf(f, "%llu\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\n", (unsigned long long)cnt, auc / c, mrr / c, (double)h1 / c,
+              (double)h10 / c, (double)h100 / c, chance / c);
+    }
+  };
+  enum { MODEL = -1 };   // or a svils_nbr_measure
+  // ranks `seq` by `measure`, returns the summary; fname: the per-pair file (nullptr: the summary only)
+  auto rank = [&](int measure, const char *fname, const std::vector<uint32_t> &seq, const std::vector<int> *ext) {
     const size_t m = seq.size() / 2;
     std::vector<uint32_t> pairs(4 * m), above(2 * m), tied(2 * m), ncand(2 * m);
     std::vector<double> sc(2 * m);
@@ -504,8 +544,12 @@ void LinkSampling::write_ranks() {
       pairs[4 * i] = pairs[4 * i + 3] = dev(seq[2 * i]);
       pairs[4 * i + 1] = pairs[4 * i + 2] = dev(seq[2 * i + 1]);
     }
-    if (svils_rank_links(h_, pairs.data(), 2 * m, above.data(), tied.data(), ncand.data(), sc.data())) die_svils("svils_rank_links");
-    sum = Sum();
+    if (measure == MODEL) {
+      if (svils_rank_links(h_, pairs.data(), 2 * m, above.data(), tied.data(), ncand.data(), sc.data())) die_svils("svils_rank_links");
+    } else if (svils_nbr_rank(h_, measure, pairs.data(), 2 * m, above.data(), tied.data(), ncand.data(), sc.data())) {
+      die_svils("svils_nbr_rank");
+    }
+    Sum sum;
     std::string o;
     {
       RowOut out(o);
@@ -519,39 +563,49 @@ void LinkSampling::write_ranks() {
         snprintf(num, sizeof num, "%.9e\t", sc[2 * i]);
         out.text(num);
         for (size_t d = 2 * i; d < 2 * i + 2; ++d) {
-          const double ahead_mid = (double)above[d] + 0.5 * (double)tied[d];   // candidates ahead of the link, ties halved
-          out.fixed<3>(ahead_mid + 1.0, '\t');
+          out.fixed<3>((double)above[d] + 0.5 * (double)tied[d] + 1.0, '\t');
           out.integer((long)ncand[d], d == 2 * i ? '\t' : '\n');
-          if (!y || !held_out(p, q) || ncand[d] == 0) continue;
-          const uint64_t ahead = (uint64_t)above[d] + tied[d];
-          ++sum.cnt;
-          sum.auc += 1.0 - ahead_mid / (double)ncand[d];
-          sum.mrr += 1.0 / (ahead_mid + 1.0);
-          sum.h1 += ahead < 1;
-          sum.h10 += ahead < 10;
-          sum.h100 += ahead < 100;
-          sum.chance += 10.0 / (double)ncand[d];
+          if (y && held_out(p, q) && ncand[d] != 0) sum.add(above[d], tied[d], ncand[d]);
         }
       }
     }
-    FILE *f = open_or_die(Env::file_str(fname), fname + 1);
-    fwrite(o.data(), 1, o.size(), f);
-    fclose(f);
+    if (fname) {
+      FILE *f = open_or_die(Env::file_str(fname), fname + 1);
+      fwrite(o.data(), 1, o.size(), f);
+      fclose(f);
+    }
+    return sum;
   };
-  if (!env_.rank_pairs_fname.empty()) write("/link-ranks.txt", rp_seq_, &rp_ext_);
-  if (env_.rank_heldout) {
-    std::vector<uint32_t> seq;
+  // the list the summary is about: the held-out links when they are ranked, the -rank-pairs file otherwise
+  std::vector<uint32_t> ho;
+  if (env_.rank_heldout)
     for (const std::vector<uint32_t> *t : {&val_accept_, &test_listed_})
       for (size_t i = 0; i + 2 < t->size(); i += 3)
-        if ((*t)[i + 2]) { seq.push_back((*t)[i]); seq.push_back((*t)[i + 1]); }
-    write("/heldout-ranks.txt", seq, nullptr);
-  }
+        if ((*t)[i + 2]) { ho.push_back((*t)[i]); ho.push_back((*t)[i + 1]); }
+  const std::vector<uint32_t> &last = env_.rank_heldout ? ho : rp_seq_;
+  const std::vector<int> *last_ext = env_.rank_heldout ? nullptr : &rp_ext_;
+  Sum model;
+  if (!env_.rank_pairs_fname.empty()) model = rank(MODEL, "/link-ranks.txt", rp_seq_, &rp_ext_);
+  if (env_.rank_heldout) model = rank(MODEL, "/heldout-ranks.txt", ho, nullptr);
   FILE *f = open_or_die(Env::file_str("/link-ranks-summary.txt"), "link-ranks-summary");
-  const double c = sum.cnt ? (double)sum.cnt : 1.0;
-  fprintf(f, "pairs\tauc\tmrr\thits1\thits10\thits100\tchance10\n%llu\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\n",
-          (unsigned long long)sum.cnt, sum.auc / c, sum.mrr / c, (double)sum.h1 / c, (double)sum.h10 / c, (double)sum.h100 / c,
-          sum.chance / c);
+  fprintf(f, "pairs\tauc\tmrr\thits1\thits10\thits100\tchance10\n");
+  model.print(f);
   fclose(f);
+  mark("link-ranks.txt / heldout-ranks.txt");
+  if (!env_.adamic_adar) return;
+  Sum aa;
+  if (!env_.rank_pairs_fname.empty()) aa = rank(SVILS_NBR_AA, "/link-ranks-aa.txt", rp_seq_, &rp_ext_);
+  if (env_.rank_heldout) aa = rank(SVILS_NBR_AA, "/heldout-ranks-aa.txt", ho, nullptr);
+  const Sum cn = rank(SVILS_NBR_CN, nullptr, last, last_ext), ra = rank(SVILS_NBR_RA, nullptr, last, last_ext);
+  f = open_or_die(Env::file_str("/link-ranks-baselines.txt"), "link-ranks-baselines");
+  fprintf(f, "measure\tpairs\tauc\tmrr\thits1\thits10\thits100\tchance10\n");
+  const struct { const char *name; const Sum *sum; } rows[] = {{"model", &model}, {"cn", &cn}, {"aa", &aa}, {"ra", &ra}};
+  for (const auto &row : rows) {
+    fprintf(f, "%s\t", row.name);
+    row.sum->print(f);
+  }
+  fclose(f);
+  mark("link-ranks-aa.txt / heldout-ranks-aa.txt / link-ranks-baselines.txt");
 }
 
 std::string LinkSampling::edgelist_s(const std::vector<uint32_t> &t) const {  // :190-206
@@ -1169,9 +1223,12 @@ void LinkSampling::do_on_stop_impl() {
     write_predictions();
     mark("link-prob.txt / recommendations.txt");
   }
+  if (!pp_seq_.empty() && env_.adamic_adar) {
+    write_nbr_scores();
+    mark("link-nbr.txt");
+  }
   if (!env_.rank_pairs_fname.empty() || env_.rank_heldout) {
-    write_ranks();
-    mark("link-ranks.txt / heldout-ranks.txt");
+    write_ranks(mark);
   }
   write_groups();
   mark("groups.txt");

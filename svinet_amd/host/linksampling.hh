@@ -9,6 +9,7 @@
 // of include/svils.h and writes the reference's output files.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <cstdio>
 #include <ctime>
 #include <map>
@@ -81,7 +82,10 @@ class LinkSampling {
   void load_predict_pairs();                   // -predict-pairs / -rank-pairs: read and checked before any device work
   void load_pairs_file(const char *flag, const std::string &fname, std::vector<int> *ext, std::vector<uint32_t> *seq) const;
   void write_predictions();                    // link-prob.txt / recommendations.txt from the final state
-  void write_ranks();                          // link-ranks.txt / heldout-ranks.txt / link-ranks-summary.txt from the final state
+  // link-ranks.txt / heldout-ranks.txt / link-ranks-summary.txt from the final state, then the -adamic-adar files; `mark` is
+  // called with the names of the files just written (the trace of do_on_stop_impl)
+  void write_ranks(const std::function<void(const char *)> &mark);
+  void write_nbr_scores();                     // -adamic-adar with -predict-pairs: link-nbr.txt from the training graph
   bool held_out(uint32_t p, uint32_t q) const; // the pair is in the validation or the test set (a link there is no training link)
   void init_gamma_external();                  // -init-communities
   void set_validation_sample(int s);

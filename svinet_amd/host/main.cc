@@ -7,7 +7,9 @@
 // link communities of a fitted model's gamma.txt / lambda.txt, on the device) and the
 // reference's small all-pairs CPU engine -batch (plumbing only); the
 // flags that select the reference's other engines are recognised and rejected
-// with a message instead of being silently ignored.
+// with a message instead of being silently ignored.  -adamic-adar (src/main.cc:173), which
+// the reference wires to two of those engines, is here an option of the link-prediction
+// flags of -link-sampling runs.
 #include <csignal>
 #include <cerrno>
 #include <sys/stat.h>
@@ -52,21 +54,24 @@ static void forward_handler(int sig) {
 // The single-GPU tool modes refuse the flags of the fitting paths.  Every flag a mode may refuse, in the order the checks
 // name them: a mode reports the first one set among its own.
 enum : unsigned { F_BATCH = 1, F_GPUS = 2, F_KSHARD = 4, F_SHARDED = 8, F_MINIBATCH = 16, F_PAIRS = 32, F_RECOMMEND = 64, F_K2048 = 128,
-                  F_RANKPAIRS = 256, F_RANKHELDOUT = 512 };
+                  F_RANKPAIRS = 256, F_RANKHELDOUT = 512, F_ADAMIC = 1024 };
 
 struct ToolMode {
   unsigned refuses;   // F_* bits
   const char *fmt;    // the refusal: %1$s the mode's flag, %2$s the refused flag
 };
 static const ToolMode kLinkCommunities = {   // -gml / -lcstats: one pass over a saved model
-    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT,
+    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %2$s is not available with %1$s (a single-GPU pass over gamma.txt / lambda.txt)\n"};
 static const ToolMode kFindK = {             // -findk: whole iterations
-    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT,
+    F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %2$s is not available with %1$s (a single-GPU run)\n"};
 static const ToolMode kPrediction = {        // -predict-pairs / -recommend / -rank-pairs / -rank-heldout after a fit
     F_BATCH | F_GPUS | F_KSHARD | F_SHARDED | F_K2048,
     "error: %1$s is not available with %2$s (single-GPU -link-sampling runs with -k <= 2048 only)\n"};
+static const ToolMode kBaselines = {         // -adamic-adar beside them: sums in ascending device id, which -minibatch relabels
+    F_MINIBATCH,
+    "error: %1$s is not available with %2$s (the relabelled device ids would change the order in which a score is summed)\n"};
 
 // true (the refusal printed) when a flag `mode` refuses is set
 static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) {
@@ -80,6 +85,7 @@ static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) 
       {F_RECOMMEND, a.recommend != 0, "-recommend"},
       {F_RANKPAIRS, !a.rank_pairs_fname.empty(), "-rank-pairs"},
       {F_RANKHELDOUT, a.rank_heldout, "-rank-heldout"},
+      {F_ADAMIC, a.adamic_adar, "-adamic-adar"},
       {F_K2048, a.k > 2048, "-k > 2048"},
   };
   for (const auto &f : flags)
@@ -142,6 +148,10 @@ static void usage() {
           "\t\t\tamong p's candidates and their count, the same for p among q's) and link-ranks-summary.txt (per-link AUC, MRR, hits@k)\n\n"
           "\t-rank-heldout\tthe same for the held-out links of the run (the y = 1 pairs of validation-edges.txt and, with -load-test,\n"
           "\t\t\tof test-edges.txt); writes heldout-ranks.txt and link-ranks-summary.txt.  Where -recommend is available\n\n"
+          "\t-adamic-adar\twith -predict-pairs, -rank-pairs or -rank-heldout: the same pairs scored and ranked from the training\n"
+          "\t\t\tgraph alone, by common neighbours, Adamic-Adar (sum of 1 / log degree over them) and resource allocation; writes\n"
+          "\t\t\tlink-nbr.txt (id, id, y, common neighbours, Adamic-Adar), link-ranks-aa.txt / heldout-ranks-aa.txt (the ranks by\n"
+          "\t\t\tAdamic-Adar) and link-ranks-baselines.txt (the summary line of the model, cn, aa and ra).  Not with -minibatch\n\n"
           "\t-minibatch <m>\tmini-batch mode of -link-sampling: one step = the links of m randomly chosen nodes,\n"
           "\t\t\tRobbins-Monro step sizes (-tau0 -kappa -nodetau0 -nodekappa; defaults 1024 0.9 1024 0.5);\n"
           "\t\t\tgive -rfreq <steps> after -link-sampling to evaluate the stop rule every <steps> steps\n\n");
@@ -217,6 +227,7 @@ int main(int argc, char **argv) {
     else if (is("-predict-pairs")) { need(i); a.predict_pairs_fname = argv[++i]; }
     else if (is("-rank-pairs")) { need(i); a.rank_pairs_fname = argv[++i]; }
     else if (is("-rank-heldout")) { a.rank_heldout = true; }
+    else if (is("-adamic-adar")) { a.adamic_adar = true; }
     else if (is("-recommend")) { need(i); a.recommend = atoi(argv[++i]); if (a.recommend == 0) a.recommend = -1; }
     else if (is("-init-communities")) { need(i); a.init_comm = true; a.init_comm_fname = argv[++i]; }   // src/main.cc:237-239
     else if (is("-stopthresh") || is("-inf") || is("-scale") || is("-itype") || is("-groups-file")) {
@@ -224,7 +235,7 @@ int main(int argc, char **argv) {
     }
     else if (is("-gen") || is("-ppc") || is("-stratified") ||
              is("-rnode") || is("-rpair") || is("-orig") || is("-infset") || is("-single") ||
-             is("-preprocess") || is("-gp") || is("-adamic-adar") || is("-disjoint") ||
+             is("-preprocess") || is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
       unsupported = true;
       unsupported_flag = f;
@@ -255,6 +266,13 @@ int main(int argc, char **argv) {
     }
   }
   if (a.findk && refused(a, kFindK, "-findk")) return 2;
+  if (a.adamic_adar) {                                   // baselines of link ranks (svils_nbr_score / svils_nbr_rank)
+    if (refused(a, kPrediction, "-adamic-adar") || refused(a, kBaselines, "-adamic-adar")) return 2;
+    if (!a.link_sampling || (a.predict_pairs_fname.empty() && a.rank_pairs_fname.empty() && !a.rank_heldout)) {
+      fprintf(stderr, "error: -adamic-adar belongs to -link-sampling runs with -predict-pairs, -rank-pairs or -rank-heldout\n");
+      return 2;
+    }
+  }
   if (!a.predict_pairs_fname.empty() || a.recommend) {   // link prediction (svils_link_prob / svils_predict_links)
     const char *flag = a.recommend ? "-recommend" : "-predict-pairs";
     if (a.recommend && (a.recommend < 1 || a.recommend > 256)) {
