@@ -426,10 +426,8 @@ int svils_set_graph(svils_handle *h, const uint32_t *links, uint64_t nlinks) {
     // K-sharded handles: their finalise pass (k_fin1_ksh) is a small-register kernel of its own, sized here rather than by
     // k_finalize's occupancy: eight blocks per CU.  (It stays the weakest kernel of a rank-sweep -- 650 us at n = 1e6 on a
     // 64-column slice, 60 % of its wave cycles parked on memory, profiles/r07p_kshard_sq.txt; the grid is not why.)
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
     const uint32_t npb = g.V == 1 ? 16u : 4u;   // nodes per block: four per wavefront on slices of <= 64 columns
-    d.nb_b = cap(((uint64_t)(g.node_end - g.node_begin) + npb - 1) / npb, 8u * (uint32_t)(cus > 0 ? cus : 256));
+    d.nb_b = cap(((uint64_t)(g.node_end - g.node_begin) + npb - 1) / npb, 8u * cu_count(h->cfg.device));
   }
   d.nb_c = cap((d.nitems_s3 + 3) / 4, 2 * rpw_resident_blocks(g, 1, h->cfg.device));
   // lane-per-link layout for small K: wave-items of 64 consecutive entries of a class list
@@ -478,11 +476,7 @@ int svils_set_graph(svils_handle *h, const uint32_t *links, uint64_t nlinks) {
     d.nb_a = cap((phi_items + nw - 1) / nw, std::min<uint32_t>(SVILS_FOLD_ROWS, lpl_phi_resident_blocks(g.K, h->cfg.device)));
     // finalise pass: 12-wave blocks of 64 / lpl_finalize_group(K) nodes per wavefront, as many as the device holds at
     // once (one per CU at its register budget); larger graphs loop inside the blocks
-    {
-      int cus = 0;
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-      d.fin_waves = lpl_finalize_waves(g.K, g.node_end - g.node_begin, cus > 0 ? (uint32_t)cus : 256u);
-    }
+    d.fin_waves = lpl_finalize_waves(g.K, g.node_end - g.node_begin, cu_count(h->cfg.device));
     const uint32_t fnodes = d.fin_waves * (64u / (uint32_t)lpl_finalize_group(g.K));
     d.nb_b = cap(((uint64_t)(g.node_end - g.node_begin) + fnodes - 1) / fnodes,
                  std::min<uint32_t>(SVILS_FOLD_ROWS, lpl_finalize_resident_blocks(g.K, h->cfg.device)));

@@ -43,6 +43,13 @@ struct EvPair {
   hipEvent_t a, b;
 };
 
+// a dalloc()ed device buffer that is re-sized by later calls, with the element count it was allocated for (reserve, below)
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  uint64_t cap = 0;
+};
+
 // the sweeps a graph ladder captures, as they are enqueued eagerly
 int eager_sweeps(svils_handle *h, uint32_t nsweeps);     // whole-graph sweeps (svils_sweep.hip)
 int sharded_sweeps(svils_handle *h, uint32_t nsweeps);   // node-block sweeps, collectives included (svils_comm.hip)
@@ -154,36 +161,32 @@ struct svils_handle {
   uint32_t *t_pairs = nullptr;
   double *t_uval = nullptr, *t_rows = nullptr;
   uint32_t nt = 0, t_cap = 0;
-  // link prediction (svils_link_prob / svils_predict_links / svils_rank_links, svils_predict.hip): device scratch allocated on first use and
-  // grown on demand, all of it dalloc()ed (freed by svils_destroy); nothing a sweep reads lives here
+  // link prediction (svils_link_prob / svils_predict_links / svils_rank_links, svils_predict.hip): device scratch allocated on
+  // first use, all of it dalloc()ed (freed by svils_destroy); nothing a sweep reads lives here.  scol, inv and beta are
+  // allocated once; a DevBuf is reserve()d to what the batch at hand needs
   struct PredictScratch {
     uint32_t *scol = nullptr;        // [2L] the CSR rows with every row sorted ascending (built once: the graph never changes)
     double *inv = nullptr;           // [n] 1 / sum_k gamma_pk of the state of the current call
     double *beta = nullptr;          // [K] lambda_k0 / (lambda_k0 + lambda_k1)
-    uint32_t *pairs = nullptr;       // [pair_cap][2]
-    double *prob = nullptr;          // [pair_cap]
-    uint64_t pair_cap = 0;
-    uint32_t *qnodes = nullptr;      // [q_cap] query nodes of a batch, UINT32_MAX past its end
-    double *aq = nullptr;            // [q_cap][k16] query rows gamma_p / sum gamma_p * beta, zero past column K
-    uint32_t *ids = nullptr;         // [q_cap][topk] results of a batch
-    double *scores = nullptr;
-    uint64_t q_cap = 0, aq_cap = 0, out_cap = 0;
-    double *hs = nullptr;            // per-thread partial top-k heaps of the candidate chunks (scores, ids)
-    uint32_t *hi = nullptr;
-    uint64_t heap_cap = 0;
-    uint32_t *rq = nullptr;          // svils_rank_links: [rank_cap] the q of every query row, UINT32_MAX past the batch
-    double *rthr = nullptr;          // [rank_cap] the score of (p, q): the row's threshold
-    uint32_t *rcnt = nullptr;        // [rank_cap][3] candidates above it, tied with it, seen
-    uint64_t rank_cap = 0;
+    DevBuf<uint32_t> pairs;          // svils_link_prob: [batch][2]
+    DevBuf<double> prob;             // [batch]
+    DevBuf<uint32_t> qnodes;         // [rows] query nodes of a batch, UINT32_MAX past its end (rows: the batch rounded up to 64)
+    DevBuf<double> aq;               // [rows][k16] query rows gamma_p / sum gamma_p * beta, zero past column K
+    DevBuf<uint32_t> ids;            // svils_predict_links: [8192][topk] results of a batch
+    DevBuf<double> scores;
+    DevBuf<double> hs;               // per-thread partial top-k heaps of the candidate chunks (scores, ids)
+    DevBuf<uint32_t> hi;
+    DevBuf<uint32_t> rq;             // svils_rank_links: [rows] the q of every query row, UINT32_MAX past the batch
+    DevBuf<double> rthr;             // [rows] the score of (p, q): the row's threshold
+    DevBuf<uint32_t> rcnt;           // [rows][3] candidates above it, tied with it, seen
   } pred;
   // neighbourhood scores (svils_nbr_score / svils_nbr_rank, svils_nbr.hip): scratch of their own, dalloc()ed on first use;
   // the sorted rows are pred.scol
   struct NbrScratch {
     double *w[3] = {nullptr, nullptr, nullptr};   // [maxdeg + 1] the weight of a common neighbour by its degree, per measure (host-built)
-    uint32_t *pairs = nullptr;       // [cap][2]
-    double *score = nullptr;         // [cap]
-    uint32_t *cnt = nullptr;         // [cap][3] svils_nbr_score: common; svils_nbr_rank: above, tied, ncand
-    uint64_t cap = 0;
+    DevBuf<uint32_t> pairs;          // [batch][2]
+    DevBuf<double> score;            // [batch]
+    DevBuf<uint32_t> cnt;            // [batch][3] svils_nbr_score: common; svils_nbr_rank: above, tied, ncand
     uint32_t *bitmap = nullptr;      // [blocks][ceil(n / 32)] the claimed two-hop nodes of the pair a block is serving; all zero between launches
     uint32_t blocks = 0;
   } nbr;
@@ -236,6 +239,24 @@ void dfree(svils_handle *h, T **p) {
   if (it != h->allocs.end()) h->allocs.erase(it);
   (void)hipFree((void *)*p);
   *p = nullptr;
+}
+
+// room for `need` elements: kept while it suffices, otherwise given back and allocated anew (the contents are not kept)
+template <class T>
+int reserve(svils_handle *h, DevBuf<T> &b, uint64_t need) {
+  if (b.cap >= need) return 0;
+  dfree(h, &b.p);
+  b.cap = 0;
+  if (int rc = dalloc(h, &b.p, need, false)) return rc;
+  b.cap = need;
+  return 0;
+}
+
+// compute units of a device; 256 (an MI355X) where the runtime does not say
+inline uint32_t cu_count(int device) {
+  int cus = 0;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  return cus > 0 ? (uint32_t)cus : 256u;
 }
 
 struct Timed {
@@ -301,7 +322,7 @@ int apply_s3_split(svils_handle *h);
 int apply_blocks(svils_handle *h, int rank, int world, const uint32_t *bounds, bool explicit_bounds);
 int ensure_blocks(svils_handle *h);
 void comm_destroy(svils_handle *h);
-// ---- svils_predict.hip
+// ---- svils_predict.hip (what it shares with svils_nbr.hip besides this: svils_pairs.h)
 int sorted_rows(svils_handle *h);   // PredictScratch::scol exists (enqueued on the handle's stream the first time)
 // ---- svils_stoch.hip
 int open_step(svils_handle *h);

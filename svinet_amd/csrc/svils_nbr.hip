@@ -15,25 +15,15 @@
 //                 them with nbr_pair against s = nbr_pair(p, q) into integer counters.  Every other candidate scores
 //                 exactly zero: they are counted, not visited.  The walk is repeated to clear the claimed bits.
 //
-// Read-only: rowptr, the sorted rows of svils_handle::pred and the scratch of svils_handle::nbr; needs no state.
-#include "svils_handle.h"
+// Read-only: rowptr, the sorted rows of svils_handle::pred and the scratch of svils_handle::nbr; needs no state.  The
+// refusals, NONE, in_row and the way ranks go back to the caller are svils_pairs.h, shared with svils_predict.hip.
+#include "svils_pairs.h"
 
 namespace {
 
 constexpr uint32_t LIST_CAP = 2048;           // candidates a block lists before its wavefronts score them
 constexpr uint64_t NBR_BATCH = 1u << 16;      // pairs per internal batch (bounds the scratch, see include/svils.h)
 constexpr uint32_t BLOCKS_PER_CU = 4;
-constexpr uint32_t NONE = 0xffffffffu;
-
-__device__ inline bool in_row(const uint32_t *__restrict__ s, uint64_t b, uint64_t e, uint32_t q) {
-  while (b < e) {
-    const uint64_t m = (b + e) >> 1;
-    const uint32_t v = s[m];
-    if (v == q) return true;
-    if (v < q) b = m + 1; else e = m;
-  }
-  return false;
-}
 
 // The score of (p, q) and the number of their common neighbours, the same value in every lane.  Called by a whole wavefront
 // with p and q uniform.  The sum is sequential in ascending z whatever the row lengths: chunks ascend along the shorter
@@ -176,30 +166,12 @@ __global__ __launch_bounds__(256) void k_nbr_rank(uint32_t np, uint32_t n, uint3
   }
 }
 
-template <class T>
-int grow(svils_handle *h, T **p, uint64_t need) {
-  dfree(h, p);
-  return dalloc(h, p, need, false);
-}
-
 // the refusals of both entry points (include/svils.h): those of svils_link_prob, without the state
 int check(svils_handle *h, const char *name, int measure, const uint32_t *pairs, uint64_t npairs) {
-  if (!h) return fail(SVILS_ERR_ARG, "%s: null handle", name);
-  if (TILED(h)) return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a column-tiled handle (k > SVILS_MAX_K = %d)", name, SVILS_MAX_K);
-  if (h->d.ksh) return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a K-sharded handle", name);
-  if (h->geo.node_begin != 0 || h->geo.node_end != h->geo.n || h->blocks_set || h->comm)
-    return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a node-block handle", name);
-  if (!h->have_graph) return fail(SVILS_ERR_ARG, "%s: set the graph first", name);
+  if (int rc = check_pair_handle(h, name, false)) return rc;
   if (measure != SVILS_NBR_CN && measure != SVILS_NBR_AA && measure != SVILS_NBR_RA)
     return fail(SVILS_ERR_ARG, "%s: unknown measure %d", name, measure);
-  if (npairs && !pairs) return fail(SVILS_ERR_ARG, "%s: null argument", name);
-  const uint32_t n = h->geo.n;
-  for (uint64_t i = 0; i < npairs; ++i) {
-    const uint32_t p = pairs[2 * i], q = pairs[2 * i + 1];
-    if (p >= n || q >= n) return fail(SVILS_ERR_ARG, "%s: pair %llu = (%u, %u): node id >= n = %u", name, (unsigned long long)i, p, q, n);
-    if (p == q) return fail(SVILS_ERR_ARG, "%s: pair %llu = (%u, %u): p == q", name, (unsigned long long)i, p, q);
-  }
-  return 0;
+  return check_pairs(h, name, pairs, npairs);
 }
 
 // w[d] for d = 0 .. the largest training degree, once per handle and measure.  Host arithmetic: 1.0 / std::log((double)d)
@@ -223,14 +195,9 @@ int prepare(svils_handle *h, int measure, uint64_t m) {
   if (int rc = sorted_rows(h)) return rc;
   if (int rc = build_weights(h, measure)) return rc;
   svils_handle::NbrScratch &s = h->nbr;
-  if (s.cap < m) {
-    s.cap = 0;
-    if (int rc = grow(h, &s.pairs, 2 * m)) return rc;
-    if (int rc = grow(h, &s.score, m)) return rc;
-    if (int rc = grow(h, &s.cnt, 3 * m)) return rc;
-    s.cap = m;
-  }
-  return 0;
+  if (int rc = reserve(h, s.pairs, 2 * m)) return rc;
+  if (int rc = reserve(h, s.score, m)) return rc;
+  return reserve(h, s.cnt, 3 * m);
 }
 
 }  // namespace
@@ -245,12 +212,12 @@ int svils_nbr_score(svils_handle *h, int measure, const uint32_t *pairs, uint64_
   svils_handle::NbrScratch &s = h->nbr;
   for (uint64_t b = 0; b < npairs; b += NBR_BATCH) {
     const uint32_t m = (uint32_t)std::min(NBR_BATCH, npairs - b);
-    HIPCHK(hipMemcpyAsync(s.pairs, pairs + 2 * b, 2 * (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_nbr_pairs, dim3((m + 3) / 4), dim3(256), 0, h->stream, m, h->d.rowptr, h->pred.scol, s.w[measure], s.pairs,
-                       s.score, s.cnt);
+    HIPCHK(hipMemcpyAsync(s.pairs.p, pairs + 2 * b, 2 * (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_nbr_pairs, dim3((m + 3) / 4), dim3(256), 0, h->stream, m, h->d.rowptr, h->pred.scol, s.w[measure],
+                       s.pairs.p, s.score.p, s.cnt.p);
     HIPCHK(hipGetLastError());
-    if (score) HIPCHK(hipMemcpyAsync(score + b, s.score, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (common) HIPCHK(hipMemcpyAsync(common + b, s.cnt, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (score) HIPCHK(hipMemcpyAsync(score + b, s.score.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (common) HIPCHK(hipMemcpyAsync(common + b, s.cnt.p, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   return 0;
@@ -265,28 +232,16 @@ int svils_nbr_rank(svils_handle *h, int measure, const uint32_t *pairs, uint64_t
   svils_handle::NbrScratch &s = h->nbr;
   const uint32_t n = h->geo.n, words = (n + 31) / 32;
   if (!s.bitmap) {
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-    if (cus <= 0) cus = 256;
-    s.blocks = BLOCKS_PER_CU * (uint32_t)cus;
+    s.blocks = BLOCKS_PER_CU * cu_count(h->cfg.device);
     if (int rc = dalloc(h, &s.bitmap, (size_t)s.blocks * words, true)) return rc;   // zeroed once; every launch leaves it so
   }
-  std::vector<uint32_t> ch;
   for (uint64_t b = 0; b < npairs; b += NBR_BATCH) {
     const uint32_t m = (uint32_t)std::min(NBR_BATCH, npairs - b);
-    HIPCHK(hipMemcpyAsync(s.pairs, pairs + 2 * b, 2 * (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(s.pairs.p, pairs + 2 * b, 2 * (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_nbr_rank, dim3(std::min(m, s.blocks)), dim3(256), 0, h->stream, m, n, words, h->d.rowptr, h->pred.scol,
-                       s.w[measure], s.pairs, s.bitmap, s.score, s.cnt);
+                       s.w[measure], s.pairs.p, s.bitmap, s.score.p, s.cnt.p);
     HIPCHK(hipGetLastError());
-    ch.resize(3 * (size_t)m);
-    HIPCHK(hipMemcpyAsync(ch.data(), s.cnt, 3 * (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (score) HIPCHK(hipMemcpyAsync(score + b, s.score, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (uint32_t i = 0; i < m; ++i) {
-      if (above) above[b + i] = ch[3 * (size_t)i];
-      if (tied) tied[b + i] = ch[3 * (size_t)i + 1];
-      if (ncand) ncand[b + i] = ch[3 * (size_t)i + 2];
-    }
+    if (int rc = fetch_ranks(h, s.cnt.p, s.score.p, m, b, above, tied, ncand, score)) return rc;
   }
   return 0;
 }

@@ -8,16 +8,20 @@
 //   k_beta          beta_z
 //   k_build_aq      the query rows of a batch: gamma_p / sum gamma_p * beta, zero-padded to a multiple of 16 columns
 //   k_sort_rows     once per handle: every CSR row sorted ascending (the upper part of a row is in adjacency order)
-//   k_topk_tiles    grid (query tile of 64, candidate chunk): 64 x 64 score tiles from v_mfma_f64_16x16x4_f64, then every
-//                   query's four selector threads keep a top-k heap each over their quarter of the chunk's candidates
+//   score_tile      (device function) the one 64 x 64 score tile of the three tile kernels, from v_mfma_f64_16x16x4_f64
+//   k_topk_tiles    grid (query tile of 64, candidate chunk): score tiles of the chunk's candidates, then every query's four
+//                   selector threads keep a top-k heap each over their quarter of the chunk's candidates
 //   k_topk_merge    one block per query: the 4 x chunks heaps sorted together (bitonic, in LDS), the first k kept
-//   k_rank_thresh   svils_rank_links, one query row per directed pair (p, q): the score of (p, q) itself, from the tile code of
-//                   the top-k kernel with the q's of a query tile gathered as its 64 candidates (the diagonal is kept)
+//   k_rank_thresh   svils_rank_links, one query row per directed pair (p, q): the score of (p, q) itself, from the tile
+//                   whose 64 candidates are the q's of a query tile (the diagonal is kept)
 //   k_rank_tiles    the grid and tiles of k_topk_tiles; in place of a heap every selector thread counts the candidates of its
 //                   quarter that score above / equal to the row's threshold, and how many it saw (integer atomics per row)
 //
+// Host side: begin_tile_batch is the start of every batch of the two tile queries (chunks, query rows); the refusals, NONE,
+// in_row and the way ranks go back to the caller are svils_pairs.h, shared with svils_nbr.hip.
+//
 // Read-only: everything here reads gamma, lambda and the CSR, and writes the scratch of svils_handle::pred only.
-#include "svils_handle.h"
+#include "svils_pairs.h"
 
 namespace {
 
@@ -26,7 +30,6 @@ constexpr uint32_t PC = 64;               // candidates per tile (four 16-column
 constexpr uint32_t Q_BATCH = 8192;        // query nodes per internal batch (bounds the scratch, see include/svils.h)
 constexpr uint32_t MERGE_MAX = 4096;      // entries one merge block sorts: 4 selectors x chunks x topk
 constexpr uint64_t PAIR_BATCH = 1u << 20; // pairs per internal batch of svils_link_prob
-constexpr uint32_t NONE = 0xffffffffu;
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -90,16 +93,6 @@ __global__ __launch_bounds__(256) void k_sort_rows(uint32_t n, const uint64_t *_
   }
 }
 
-__device__ inline bool in_row(const uint32_t *__restrict__ s, uint64_t b, uint64_t e, uint32_t q) {
-  while (b < e) {
-    const uint64_t m = (b + e) >> 1;
-    const uint32_t v = s[m];
-    if (v == q) return true;
-    if (v < q) b = m + 1; else e = m;
-  }
-  return false;
-}
-
 // (as, ai) ranks below (bs, bi): lower score, or the same score and the higher id
 __device__ inline bool worse(double as, uint32_t ai, double bs, uint32_t bi) { return as < bs || (as == bs && ai > bi); }
 
@@ -114,15 +107,48 @@ __device__ inline void load4(const double *__restrict__ row, uint32_t col, uint3
   }
 }
 
-// Block (qt, c): query rows [64 qt, 64 qt + 64) of the batch against the candidates of chunk c of nch.  Per tile of 64
-// candidates wavefront w computes the 16 x 64 scores of query rows 16 w .. 16 w + 15 as four 16 x 16 MFMA blocks, K in steps
+// The 64 x 64 score tile of the three tile kernels: 64 query rows (arow: this lane's row 16 w + (l & 15) of aq) against four
+// candidate columns per lane -- cand[j] is the node behind column 16 j + (l & 15), NONE for a column past the end (its scores
+// are zero).  Wavefront w computes the 16 x 64 scores of query rows 16 w .. 16 w + 15 as four 16 x 16 MFMA blocks, K in steps
 // of 4.  Operand map of v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k-slot l >> 4] and B[k-slot l >> 4][col l & 15];
 // the k column behind k-slot g in step s of a 16-column chunk is kc + 4 g + s (both operands use the same map, so every
 // lane reads four consecutive doubles of its row per chunk).  C/D: register r of lane l is row (l >> 4) + 4 r, col l & 15.
-// Selection: thread t serves query row t >> 2 over the candidates t & 3, t & 3 + 4, ... of every tile (ascending ids) with a
-// k-entry heap of its own in global scratch (slot i at stride 256: the block's heaps interleave), worst entry on top; a
-// candidate is looked at further only if it beats that entry.  (Heaps in LDS for k <= 10 measured no faster:
-// profiles/r09a_predict.md.)
+// An element depends on its row of aq, its candidate and the k order only: (row, candidate) has the same bits wherever it
+// sits in a tile and whichever kernel asks -- what svils_rank_links' "bitwise the score of svils_predict_links" rests on.
+__device__ __forceinline__ void score_tile(double (*S)[PC + 1], const double *__restrict__ arow, const uint32_t *cand, uint32_t K,
+                                           uint32_t ld, uint32_t k16, const double *__restrict__ gamma,
+                                           const double *__restrict__ inv, uint32_t w, uint32_t g, uint32_t r16) {
+  d4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
+  for (uint32_t kc = 0; kc < k16; kc += 16) {
+    const uint32_t col = kc + 4 * g;
+    const double2 a01 = *(const double2 *)(arow + col), a23 = *(const double2 *)(arow + col + 2);
+    const double a[4] = {a01.x, a01.y, a23.x, a23.y};
+    double b[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (cand[j] != NONE) load4(gamma + (size_t)cand[j] * ld, col, K, b[j]);
+      else b[j][0] = b[j][1] = b[j][2] = b[j][3] = 0.0;
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[j][s], acc[j], 0, 0, 0);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const double iq = cand[j] != NONE ? inv[cand[j]] : 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) S[16 * w + g + 4 * r][16 * j + r16] = acc[j][r] * iq;
+  }
+}
+
+// Block (qt, c): query rows [64 qt, 64 qt + 64) of the batch against the candidates of chunk c of nch, a score_tile of 64
+// candidates at a time.  Selection: thread t serves query row t >> 2 over the candidates t & 3, t & 3 + 4, ... of every tile
+// (ascending ids) with a k-entry heap of its own in global scratch (slot i at stride 256: the block's heaps interleave),
+// worst entry on top; a candidate is looked at further only if it beats that entry.  (Heaps in LDS for k <= 10 measured no
+// faster: profiles/r09a_predict.md.)
 __global__ __launch_bounds__(256) void k_topk_tiles(uint32_t n, uint32_t K, uint32_t ld, uint32_t k16, uint32_t topk, uint32_t nch,
                                                     const double *__restrict__ gamma, const double *__restrict__ inv,
                                                     const double *__restrict__ aq, const uint32_t *__restrict__ qnodes,
@@ -144,32 +170,10 @@ __global__ __launch_bounds__(256) void k_topk_tiles(uint32_t n, uint32_t K, uint
   double worst = -1.0;
   const double *arow = aq + (size_t)(qt * PQ + 16 * w + r16) * k16;
   for (uint32_t c0 = cb; c0 < ce; c0 += PC) {
-    d4 acc[4];
+    uint32_t cand[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
-    for (uint32_t kc = 0; kc < k16; kc += 16) {
-      const uint32_t col = kc + 4 * g;
-      const double2 a01 = *(const double2 *)(arow + col), a23 = *(const double2 *)(arow + col + 2);
-      const double a[4] = {a01.x, a01.y, a23.x, a23.y};
-      double b[4][4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t cand = c0 + 16 * j + r16;
-        if (cand < ce) load4(gamma + (size_t)cand * ld, col, K, b[j]);
-        else b[j][0] = b[j][1] = b[j][2] = b[j][3] = 0.0;
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[j][s], acc[j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t cand = c0 + 16 * j + r16;
-      const double iq = cand < ce ? inv[cand] : 0.0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) S[16 * w + g + 4 * r][16 * j + r16] = acc[j][r] * iq;
-    }
+    for (int j = 0; j < 4; ++j) cand[j] = c0 + 16 * j + r16 < ce ? c0 + 16 * j + r16 : NONE;
+    score_tile(S, arow, cand, K, ld, k16, gamma, inv, w, g, r16);
     __syncthreads();
     if (p != NONE) {
       for (uint32_t i = 0; i < PC / 4; ++i) {
@@ -241,38 +245,6 @@ __global__ __launch_bounds__(256) void k_topk_merge(uint32_t topk, uint32_t nch,
   for (uint32_t j = threadIdx.x; j < topk; j += 256) {
     oscore[(size_t)i * topk + j] = ks[j];
     oid[(size_t)i * topk + j] = ki[j];
-  }
-}
-
-// The 64 x 64 score tile of k_topk_tiles for any four candidate columns per lane: cand[j] is the node behind column
-// 16 j + (l & 15), NONE for a column past the end (its scores are zero).  The same loads, the same MFMA sequence over
-// k16 and the same final * 1 / sum gamma: element (row, candidate) has the bits k_topk_tiles gives it, wherever it sits.
-__device__ __forceinline__ void score_tile(double (*S)[PC + 1], const double *__restrict__ arow, const uint32_t *cand, uint32_t K,
-                                           uint32_t ld, uint32_t k16, const double *__restrict__ gamma,
-                                           const double *__restrict__ inv, uint32_t w, uint32_t g, uint32_t r16) {
-  d4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
-  for (uint32_t kc = 0; kc < k16; kc += 16) {
-    const uint32_t col = kc + 4 * g;
-    const double2 a01 = *(const double2 *)(arow + col), a23 = *(const double2 *)(arow + col + 2);
-    const double a[4] = {a01.x, a01.y, a23.x, a23.y};
-    double b[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (cand[j] != NONE) load4(gamma + (size_t)cand[j] * ld, col, K, b[j]);
-      else b[j][0] = b[j][1] = b[j][2] = b[j][3] = 0.0;
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[j][s], acc[j], 0, 0, 0);
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const double iq = cand[j] != NONE ? inv[cand[j]] : 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) S[16 * w + g + 4 * r][16 * j + r16] = acc[j][r] * iq;
   }
 }
 
@@ -358,28 +330,6 @@ __global__ __launch_bounds__(256) void k_rank_tiles(uint32_t n, uint32_t K, uint
   }
 }
 
-template <class T>
-int grow(svils_handle *h, T **p, uint64_t *cap, uint64_t need) {
-  if (*p && *cap >= need) return 0;
-  dfree(h, p);
-  *cap = 0;
-  if (int rc = dalloc(h, p, need, false)) return rc;
-  *cap = need;
-  return 0;
-}
-
-// the refusals shared by the entry points (include/svils.h)
-int check_handle(svils_handle *h, const char *name) {
-  if (!h) return fail(SVILS_ERR_ARG, "%s: null handle", name);
-  if (TILED(h)) return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a column-tiled handle (k > SVILS_MAX_K = %d)", name, SVILS_MAX_K);
-  if (h->d.ksh) return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a K-sharded handle", name);
-  if (h->geo.node_begin != 0 || h->geo.node_end != h->geo.n || h->blocks_set || h->comm)
-    return fail(SVILS_ERR_UNSUPPORTED, "%s: not available on a node-block handle", name);
-  if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "%s: set graph and state first", name);
-  if (h->step_open) return fail(SVILS_ERR_ARG, "%s: a mini-batch step is open (close it with phase D)", name);
-  return 0;
-}
-
 }  // namespace
 
 // the sorted copy of the CSR (svils_handle::PredictScratch::scol), built on the handle's stream the first time it is asked for
@@ -410,43 +360,62 @@ int prepare(svils_handle *h) {
   return 0;
 }
 
+// The start of a batch for the tile kernels.  qh holds the batch's m query nodes and is padded here with NONE to rows = a
+// multiple of PQ; the device gets them (pred.qnodes) and their rows of aq (k_build_aq).  nch = the candidate chunks of the
+// grid: enough blocks for eight per CU, at most nch_max (the caller's own bound, if it has one) and at least 64 candidates
+// per chunk.  No result depends on the cut: a top k is that of one total order, counts are sums over the chunks.
+struct TileBatch {
+  uint32_t nqt, rows, nch, k16;
+};
+int begin_tile_batch(svils_handle *h, std::vector<uint32_t> &qh, uint32_t nch_max, TileBatch *tb) {
+  const Geometry &g = h->geo;
+  svils_handle::PredictScratch &s = h->pred;
+  tb->nqt = ((uint32_t)qh.size() + PQ - 1) / PQ;
+  tb->rows = tb->nqt * PQ;
+  tb->k16 = (g.K + 15u) & ~15u;
+  tb->nch = std::max<uint32_t>(1, (8u * cu_count(h->cfg.device) + tb->nqt - 1) / tb->nqt);
+  tb->nch = std::min(tb->nch, nch_max);
+  tb->nch = std::min(tb->nch, std::max<uint32_t>(1, g.n / PC));
+  const uint64_t ae = (uint64_t)tb->rows * tb->k16;
+  if (int rc = reserve(h, s.qnodes, tb->rows)) return rc;
+  if (int rc = reserve(h, s.aq, ae)) return rc;
+  qh.resize(tb->rows, NONE);
+  HIPCHK(hipMemcpyAsync(s.qnodes.p, qh.data(), tb->rows * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_build_aq, dim3((uint32_t)((ae + 255) / 256)), dim3(256), 0, h->stream, tb->rows, g.K, g.ld, tb->k16,
+                     h->d.gamma, s.inv, s.beta, s.qnodes.p, s.aq.p);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int svils_link_prob(svils_handle *h, const uint32_t *pairs, uint64_t npairs, double *prob) {
-  if (int rc = check_handle(h, "svils_link_prob")) return rc;
+  if (int rc = check_pair_handle(h, "svils_link_prob", true)) return rc;
   if (npairs && (!pairs || !prob)) return fail(SVILS_ERR_ARG, "svils_link_prob: null argument");
-  const Geometry &g = h->geo;
-  for (uint64_t i = 0; i < npairs; ++i) {
-    const uint32_t p = pairs[2 * i], q = pairs[2 * i + 1];
-    if (p >= g.n || q >= g.n) return fail(SVILS_ERR_ARG, "svils_link_prob: pair %llu = (%u, %u): node id >= n = %u", (unsigned long long)i, p, q, g.n);
-    if (p == q) return fail(SVILS_ERR_ARG, "svils_link_prob: pair %llu = (%u, %u): p == q", (unsigned long long)i, p, q);
-  }
+  if (int rc = check_pairs(h, "svils_link_prob", pairs, npairs)) return rc;
   if (!npairs) return 0;
   HIPCHK(hipSetDevice(h->cfg.device));
+  const Geometry &g = h->geo;
   svils_handle::PredictScratch &s = h->pred;
   const uint64_t cap = std::min<uint64_t>(npairs, PAIR_BATCH);
-  if (!s.pairs || s.pair_cap < cap) {
-    uint64_t c1 = s.pair_cap, c2 = s.pair_cap;
-    if (int rc = grow(h, &s.pairs, &c1, 2 * cap)) return rc;
-    if (int rc = grow(h, &s.prob, &c2, cap)) return rc;
-    s.pair_cap = cap;
-  }
+  if (int rc = reserve(h, s.pairs, 2 * cap)) return rc;
+  if (int rc = reserve(h, s.prob, cap)) return rc;
   for (uint64_t b = 0; b < npairs; b += PAIR_BATCH) {
     const uint64_t m = std::min<uint64_t>(PAIR_BATCH, npairs - b);
-    HIPCHK(hipMemcpyAsync(s.pairs, pairs + 2 * b, 2 * m * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(s.pairs.p, pairs + 2 * b, 2 * m * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_link_prob, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, h->stream, m, g.K, g.ld, h->d.gamma,
-                       h->d.lambda, s.pairs, s.prob);
+                       h->d.lambda, s.pairs.p, s.prob.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(prob + b, s.prob, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(prob + b, s.prob.p, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   return 0;
 }
 
 int svils_predict_links(svils_handle *h, const uint32_t *nodes, uint32_t nnodes, uint32_t topk, uint32_t *ids, double *scores) {
-  if (int rc = check_handle(h, "svils_predict_links")) return rc;
+  if (int rc = check_pair_handle(h, "svils_predict_links", true)) return rc;
   const Geometry &g = h->geo;
   if (topk == 0 || topk > SVILS_PREDICT_MAX_TOPK)
     return fail(SVILS_ERR_ARG, "svils_predict_links: topk = %u, need 1 .. %d", topk, SVILS_PREDICT_MAX_TOPK);
@@ -460,50 +429,27 @@ int svils_predict_links(svils_handle *h, const uint32_t *nodes, uint32_t nnodes,
   if (!nq) return 0;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = prepare(h)) return rc;
-  int cus = 0;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-  if (cus <= 0) cus = 256;
   svils_handle::PredictScratch &s = h->pred;
-  const uint32_t k16 = (g.K + 15u) & ~15u;
-  const uint32_t nch_max = std::max<uint32_t>(1, MERGE_MAX / (4 * topk));
   std::vector<uint32_t> qh;
   for (uint32_t b = 0; b < nq; b += Q_BATCH) {
     const uint32_t m = std::min(Q_BATCH, nq - b);
-    const uint32_t nqt = (m + PQ - 1) / PQ, rows = nqt * PQ;
-    // chunks: enough blocks for eight per CU, at most nch_max (the merge sorts 4 x nch x topk entries in LDS) and at
-    // least 64 candidates per chunk.  The result does not depend on the cut: it is the top k of one total order.
-    uint32_t nch = std::max<uint32_t>(1, (8u * (uint32_t)cus + nqt - 1) / nqt);
-    nch = std::min(nch, nch_max);
-    nch = std::min(nch, std::max<uint32_t>(1, g.n / PC));
-    uint32_t L = 4 * nch * topk, lp = 1;
-    while (lp < L) lp <<= 1;
-    if (int rc = grow(h, &s.qnodes, &s.q_cap, rows)) return rc;
-    if (int rc = grow(h, &s.aq, &s.aq_cap, (uint64_t)rows * k16)) return rc;
-    if (!s.ids || s.out_cap < (uint64_t)m * topk) {
-      uint64_t c1 = s.out_cap, c2 = s.out_cap;
-      if (int rc = grow(h, &s.ids, &c1, (uint64_t)Q_BATCH * topk)) return rc;
-      if (int rc = grow(h, &s.scores, &c2, (uint64_t)Q_BATCH * topk)) return rc;
-      s.out_cap = (uint64_t)Q_BATCH * topk;
-    }
-    const uint64_t hneed = (uint64_t)nqt * nch * topk * 256;
-    if (!s.hs || s.heap_cap < hneed) {
-      uint64_t c1 = s.heap_cap, c2 = s.heap_cap;
-      if (int rc = grow(h, &s.hs, &c1, hneed)) return rc;
-      if (int rc = grow(h, &s.hi, &c2, hneed)) return rc;
-      s.heap_cap = hneed;
-    }
-    qh.assign(rows, NONE);
+    qh.resize(m);
     for (uint32_t i = 0; i < m; ++i) qh[i] = nodes ? nodes[b + i] : b + i;
-    HIPCHK(hipMemcpyAsync(s.qnodes, qh.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    const uint64_t ae = (uint64_t)rows * k16;
-    hipLaunchKernelGGL(k_build_aq, dim3((uint32_t)((ae + 255) / 256)), dim3(256), 0, h->stream, rows, g.K, g.ld, k16, h->d.gamma,
-                       s.inv, s.beta, s.qnodes, s.aq);
-    hipLaunchKernelGGL(k_topk_tiles, dim3(nqt, nch), dim3(256), 0, h->stream, g.n, g.K, g.ld, k16, topk, nch, h->d.gamma, s.inv,
-                       s.aq, s.qnodes, h->d.rowptr, s.scol, s.hs, s.hi);
-    hipLaunchKernelGGL(k_topk_merge, dim3(m), dim3(256), 0, h->stream, topk, nch, lp, s.hs, s.hi, s.scores, s.ids);
+    TileBatch tb;   // at most MERGE_MAX / (4 topk) chunks: the merge sorts the 4 x nch x topk heap entries of a query in LDS
+    if (int rc = begin_tile_batch(h, qh, std::max<uint32_t>(1, MERGE_MAX / (4 * topk)), &tb)) return rc;
+    uint32_t L = 4 * tb.nch * topk, lp = 1;
+    while (lp < L) lp <<= 1;
+    const uint64_t oneed = (uint64_t)Q_BATCH * topk, hneed = (uint64_t)tb.nqt * tb.nch * topk * 256;
+    if (int rc = reserve(h, s.ids, oneed)) return rc;
+    if (int rc = reserve(h, s.scores, oneed)) return rc;
+    if (int rc = reserve(h, s.hs, hneed)) return rc;
+    if (int rc = reserve(h, s.hi, hneed)) return rc;
+    hipLaunchKernelGGL(k_topk_tiles, dim3(tb.nqt, tb.nch), dim3(256), 0, h->stream, g.n, g.K, g.ld, tb.k16, topk, tb.nch,
+                       h->d.gamma, s.inv, s.aq.p, s.qnodes.p, h->d.rowptr, s.scol, s.hs.p, s.hi.p);
+    hipLaunchKernelGGL(k_topk_merge, dim3(m), dim3(256), 0, h->stream, topk, tb.nch, lp, s.hs.p, s.hi.p, s.scores.p, s.ids.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ids + (size_t)b * topk, s.ids, (size_t)m * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(scores + (size_t)b * topk, s.scores, (size_t)m * topk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ids + (size_t)b * topk, s.ids.p, (size_t)m * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(scores + (size_t)b * topk, s.scores.p, (size_t)m * topk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   return 0;
@@ -511,63 +457,33 @@ int svils_predict_links(svils_handle *h, const uint32_t *nodes, uint32_t nnodes,
 
 int svils_rank_links(svils_handle *h, const uint32_t *pairs, uint64_t npairs, uint32_t *above, uint32_t *tied, uint32_t *ncand,
                      double *score) {
-  if (int rc = check_handle(h, "svils_rank_links")) return rc;
-  if (npairs && !pairs) return fail(SVILS_ERR_ARG, "svils_rank_links: null argument");
-  const Geometry &g = h->geo;
-  for (uint64_t i = 0; i < npairs; ++i) {
-    const uint32_t p = pairs[2 * i], q = pairs[2 * i + 1];
-    if (p >= g.n || q >= g.n) return fail(SVILS_ERR_ARG, "svils_rank_links: pair %llu = (%u, %u): node id >= n = %u", (unsigned long long)i, p, q, g.n);
-    if (p == q) return fail(SVILS_ERR_ARG, "svils_rank_links: pair %llu = (%u, %u): p == q", (unsigned long long)i, p, q);
-  }
+  if (int rc = check_pair_handle(h, "svils_rank_links", true)) return rc;
+  if (int rc = check_pairs(h, "svils_rank_links", pairs, npairs)) return rc;
   if (!npairs) return 0;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = prepare(h)) return rc;
-  int cus = 0;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-  if (cus <= 0) cus = 256;
+  const Geometry &g = h->geo;
   svils_handle::PredictScratch &s = h->pred;
-  const uint32_t k16 = (g.K + 15u) & ~15u;
-  std::vector<uint32_t> ph, qh, ch;
-  std::vector<double> th;
+  std::vector<uint32_t> ph, qh;
   for (uint64_t b = 0; b < npairs; b += Q_BATCH) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(Q_BATCH, npairs - b);
-    const uint32_t nqt = (m + PQ - 1) / PQ, rows = nqt * PQ;
-    // chunks as in svils_predict_links, without the merge's bound: the counts are sums over the chunks, whatever the cut
-    uint32_t nch = std::max<uint32_t>(1, (8u * (uint32_t)cus + nqt - 1) / nqt);
-    nch = std::min(nch, std::max<uint32_t>(1, g.n / PC));
-    if (int rc = grow(h, &s.qnodes, &s.q_cap, rows)) return rc;
-    if (int rc = grow(h, &s.aq, &s.aq_cap, (uint64_t)rows * k16)) return rc;
-    if (!s.rq || s.rank_cap < rows) {
-      uint64_t c1 = s.rank_cap, c2 = s.rank_cap, c3 = s.rank_cap;
-      if (int rc = grow(h, &s.rq, &c1, rows)) return rc;
-      if (int rc = grow(h, &s.rthr, &c2, rows)) return rc;
-      if (int rc = grow(h, &s.rcnt, &c3, 3 * (uint64_t)rows)) return rc;
-      s.rank_cap = rows;
-    }
-    ph.assign(rows, NONE);
-    qh.assign(rows, NONE);
-    for (uint32_t i = 0; i < m; ++i) { ph[i] = pairs[2 * (b + i)]; qh[i] = pairs[2 * (b + i) + 1]; }
-    HIPCHK(hipMemcpyAsync(s.qnodes, ph.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s.rq, qh.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(s.rcnt, 0, 3 * (size_t)rows * sizeof(uint32_t), h->stream));
-    const uint64_t ae = (uint64_t)rows * k16;
-    hipLaunchKernelGGL(k_build_aq, dim3((uint32_t)((ae + 255) / 256)), dim3(256), 0, h->stream, rows, g.K, g.ld, k16, h->d.gamma,
-                       s.inv, s.beta, s.qnodes, s.aq);
-    hipLaunchKernelGGL(k_rank_thresh, dim3(nqt), dim3(256), 0, h->stream, g.K, g.ld, k16, h->d.gamma, s.inv, s.aq, s.rq, s.rthr);
-    hipLaunchKernelGGL(k_rank_tiles, dim3(nqt, nch), dim3(256), 0, h->stream, g.n, g.K, g.ld, k16, nch, h->d.gamma, s.inv, s.aq,
-                       s.qnodes, s.rq, s.rthr, h->d.rowptr, s.scol, s.rcnt);
+    ph.resize(m);
+    for (uint32_t i = 0; i < m; ++i) ph[i] = pairs[2 * (b + i)];
+    TileBatch tb;   // no bound on the chunks: nothing is merged
+    if (int rc = begin_tile_batch(h, ph, UINT32_MAX, &tb)) return rc;
+    if (int rc = reserve(h, s.rq, tb.rows)) return rc;
+    if (int rc = reserve(h, s.rthr, tb.rows)) return rc;
+    if (int rc = reserve(h, s.rcnt, 3 * (uint64_t)tb.rows)) return rc;
+    qh.assign(tb.rows, NONE);
+    for (uint32_t i = 0; i < m; ++i) qh[i] = pairs[2 * (b + i) + 1];
+    HIPCHK(hipMemcpyAsync(s.rq.p, qh.data(), tb.rows * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(s.rcnt.p, 0, 3 * (size_t)tb.rows * sizeof(uint32_t), h->stream));
+    hipLaunchKernelGGL(k_rank_thresh, dim3(tb.nqt), dim3(256), 0, h->stream, g.K, g.ld, tb.k16, h->d.gamma, s.inv, s.aq.p, s.rq.p,
+                       s.rthr.p);
+    hipLaunchKernelGGL(k_rank_tiles, dim3(tb.nqt, tb.nch), dim3(256), 0, h->stream, g.n, g.K, g.ld, tb.k16, tb.nch, h->d.gamma,
+                       s.inv, s.aq.p, s.qnodes.p, s.rq.p, s.rthr.p, h->d.rowptr, s.scol, s.rcnt.p);
     HIPCHK(hipGetLastError());
-    ch.resize(3 * (size_t)m);
-    th.resize(m);
-    HIPCHK(hipMemcpyAsync(ch.data(), s.rcnt, 3 * (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(th.data(), s.rthr, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (uint32_t i = 0; i < m; ++i) {
-      if (above) above[b + i] = ch[3 * (size_t)i];
-      if (tied) tied[b + i] = ch[3 * (size_t)i + 1];
-      if (ncand) ncand[b + i] = ch[3 * (size_t)i + 2];
-      if (score) score[b + i] = th[i];
-    }
+    if (int rc = fetch_ranks(h, s.rcnt.p, s.rthr.p, m, b, above, tied, ncand, score)) return rc;
   }
   return 0;
 }

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from pair_cases import _bits, _lfr_setup, _random_pairs, _same, _state_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -106,12 +107,6 @@ def _graph_engine(n, links, k=2):
 def _both(pairs):
     pairs = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
     return np.ascontiguousarray(np.stack([pairs, pairs[:, ::-1]], 1).reshape(-1, 2))   # p -> q, q -> p, ...
-
-
-def _random_pairs(rng, n, m):
-    p = rng.integers(0, n, size=m)
-    q = (p + 1 + rng.integers(0, n - 1, size=m)) % n
-    return np.stack([p, q], 1).astype(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -219,10 +214,6 @@ def test_a_query_whose_candidates_overflow_the_list(big_hub):
         assert np.array_equal(a, b[::-1])
 
 
-def _bits(res):
-    return [np.ascontiguousarray(x).view(np.uint64 if x.dtype == np.float64 else x.dtype).copy() for x in res]
-
-
 def test_a_pair_does_not_depend_on_the_call_it_is_in(small):
     """more directed pairs than the kernel has workgroups (four per CU): every workgroup serves several pairs from one
     bitmap, so a bit left behind by one pair shows in the next"""
@@ -294,22 +285,6 @@ def test_arguments_and_null_outputs(small):
     with pytest.raises(_svils.SvilsError) as ei:
         bare.nbr_score(AA, pairs)
     assert ei.value.code == -1 and "graph" in str(ei.value)
-
-
-def _state_bits(eng):
-    g, lam, conv = eng.state()
-    c = eng.control()
-    ctl = (c.iter, c.annealing, c.write_comm, c.nh, c.prev_h, c.max_h, c.stopped, c.why, c.sweeps_done, c.rows)
-    return g.view(np.uint64).copy(), lam.view(np.uint64).copy(), conv, eng.rows().view(np.uint64).copy(), ctl
-
-
-def _same(a, b):
-    assert all(np.array_equal(x, y) for x, y in zip(a[:4], b[:4])) and a[4] == b[4]
-
-
-def _lfr_setup(graph_files):
-    from svinet_amd.host_api import Setup
-    return Setup(graph_files["lfr"], 1000, 28)
 
 
 def test_the_calls_do_not_disturb_the_sweeps(graph_files):

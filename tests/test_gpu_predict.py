@@ -10,27 +10,15 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from pair_cases import NONE, _lfr_setup, _nbrs, _pb, _random_links, _same, _state_bits
 
 pytestmark = pytest.mark.gpu
 
 SVINET = os.path.join(ROOT, "svinet_amd", "bin", "svinet")
-NONE = 0xFFFFFFFF
-
-
-def _pb(gamma, lam):
-    return gamma / gamma.sum(1, keepdims=True), lam[:, 0] / (lam[:, 0] + lam[:, 1])
 
 
 def _pair_ref(P, beta, pairs):
     return np.sum(P[pairs[:, 0]] * P[pairs[:, 1]] * beta, axis=1)
-
-
-def _nbrs(n, links):
-    nb = [[] for _ in range(n)]
-    for p, q in links:
-        nb[p].append(q)
-        nb[q].append(p)
-    return [np.array(sorted(set(x)), dtype=np.int64) for x in nb]
 
 
 def _check_topk(ids, sc, P, beta, nodes, k, nbrs):
@@ -64,20 +52,6 @@ def _check_topk(ids, sc, P, beta, nodes, k, nbrs):
             tol = 1e-12 * max(S[i, cid].max(), 1e-300)
             for q in set(got.tolist()) ^ set(order.tolist()):
                 assert abs(S[i, q] - kth) <= tol, (p, q, S[i, q], kth)
-
-
-def _lfr_setup(graph_files, k=28):
-    from svinet_amd.host_api import Setup
-    return Setup(graph_files["lfr"], 1000, k)
-
-
-def _random_links(rng, n, m):
-    a = rng.integers(0, n, size=3 * m)
-    b = rng.integers(0, n, size=3 * m)
-    e = np.stack([np.minimum(a, b), np.maximum(a, b)], 1)
-    e = e[e[:, 0] != e[:, 1]]
-    e = np.unique(e, axis=0)[:m]
-    return np.ascontiguousarray(e[np.lexsort((e[:, 1], e[:, 0]))], dtype=np.uint32)
 
 
 def _random_engine(n, k, m, seed, ties=False):
@@ -156,6 +130,18 @@ def test_topk_random_states(n, k, m, nq, topk, ties):
     np.testing.assert_allclose(pr, sc[:8, 0], rtol=1e-13)
 
 
+# (n, K, links, query nodes, topk), the tile-edge shapes of test_gpu_rank.SHAPES: n = 64 / 65 one candidate tile and one
+# node more; K = 1, 4, 16, 17 the padding to 16 columns; 1, 63, 64, 65 query nodes the edge of the query tile; topk = 70 is
+# more than the 64 candidates there can be, so the (NONE, -1.0) fill is checked
+@pytest.mark.parametrize("n,k,m,nq,topk", [(64, 4, 100, 63, 10), (65, 1, 100, 64, 70), (65, 16, 120, 65, 25), (300, 17, 900, 1, 10)])
+def test_topk_tile_edges(n, k, m, nq, topk):
+    eng, links, gamma, lam = _random_engine(n, k, m, seed=1000 + n + k)
+    P, beta = _pb(gamma, lam)
+    nodes = np.random.default_rng(nq).choice(n, size=nq, replace=False).astype(np.uint32)
+    ids, sc = eng.predict_links(topk, nodes)
+    _check_topk(ids, sc, P, beta, nodes, topk, _nbrs(n, links))
+
+
 def test_topk_many_chunks():
     n, k = 200000, 512
     eng, links, gamma, lam = _random_engine(n, k, 4 * n, seed=5)
@@ -180,17 +166,6 @@ def test_sentinel_fill_and_held_out_candidates(graph_files):
     assert len(v1)
     for p, q, _ in v1:
         assert q in ids[p] and p in ids[q]
-
-
-def _state_bits(eng):
-    g, lam, conv = eng.state()
-    c = eng.control()
-    ctl = (c.iter, c.annealing, c.write_comm, c.nh, c.prev_h, c.max_h, c.stopped, c.why, c.sweeps_done, c.rows)
-    return g.view(np.uint64).copy(), lam.view(np.uint64).copy(), conv, eng.rows().view(np.uint64).copy(), ctl
-
-
-def _same(a, b):
-    assert all(np.array_equal(x, y) for x, y in zip(a[:4], b[:4])) and a[4] == b[4]
 
 
 def test_prediction_does_not_disturb_the_sweeps(graph_files):

@@ -17,33 +17,12 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from pair_cases import NONE, _bits, _lfr_setup, _nbrs, _pb, _random_links, _random_pairs, _same, _state_bits
 
 pytestmark = pytest.mark.gpu
 
 SVINET = os.path.join(ROOT, "svinet_amd", "bin", "svinet")
-NONE = 0xFFFFFFFF
 EPS = 1e-12
-
-
-def _pb(gamma, lam):
-    return gamma / gamma.sum(1, keepdims=True), lam[:, 0] / (lam[:, 0] + lam[:, 1])
-
-
-def _nbrs(n, links):
-    nb = [[] for _ in range(n)]
-    for p, q in np.asarray(links).tolist():
-        nb[p].append(q)
-        nb[q].append(p)
-    return [np.array(sorted(set(x)), dtype=np.int64) for x in nb]
-
-
-def _random_links(rng, n, m):
-    a = rng.integers(0, n, size=3 * m)
-    b = rng.integers(0, n, size=3 * m)
-    e = np.stack([np.minimum(a, b), np.maximum(a, b)], 1)
-    e = e[e[:, 0] != e[:, 1]]
-    e = np.unique(e, axis=0)[:m]
-    return np.ascontiguousarray(e[np.lexsort((e[:, 1], e[:, 0]))], dtype=np.uint32)
 
 
 def _hub_links(rng, n, m, hub):
@@ -67,12 +46,6 @@ def _engine(n, k, links, gamma, lam):
     eng.set_graph(links)
     eng.set_state(gamma, lam)
     return eng
-
-
-def _random_pairs(rng, n, m):
-    p = rng.integers(0, n, size=m)
-    q = (p + 1 + rng.integers(0, n - 1, size=m)) % n
-    return np.stack([p, q], 1).astype(np.uint32)
 
 
 def _rank_ref(P, beta, nbrs, pairs, eps=EPS):
@@ -206,10 +179,6 @@ def test_candidates_and_arguments():
     assert ei.value.code == -1
 
 
-def _bits(res):
-    return [np.ascontiguousarray(x).view(np.uint64 if x.dtype == np.float64 else x.dtype).copy() for x in res]
-
-
 def test_a_pair_does_not_depend_on_the_rest_of_the_call():
     n, k = 2000, 37
     links, gamma, lam = _random_state(n, k, 8000, seed=k)
@@ -225,22 +194,6 @@ def test_a_pair_does_not_depend_on_the_rest_of_the_call():
         assert np.array_equal(a, b[where])
     for a, b in zip(alone, _bits(eng.rank_links(mine))):
         assert np.array_equal(a, b)
-
-
-def _state_bits(eng):
-    g, lam, conv = eng.state()
-    c = eng.control()
-    ctl = (c.iter, c.annealing, c.write_comm, c.nh, c.prev_h, c.max_h, c.stopped, c.why, c.sweeps_done, c.rows)
-    return g.view(np.uint64).copy(), lam.view(np.uint64).copy(), conv, eng.rows().view(np.uint64).copy(), ctl
-
-
-def _same(a, b):
-    assert all(np.array_equal(x, y) for x, y in zip(a[:4], b[:4])) and a[4] == b[4]
-
-
-def _lfr_setup(graph_files, k=28):
-    from svinet_amd.host_api import Setup
-    return Setup(graph_files["lfr"], 1000, k)
 
 
 def _heldout_directed(s):
