@@ -175,6 +175,7 @@ def test_empty_and_tiny_graphs():
 
 
 @pytest.mark.parametrize("k,no_elogpi", [(20, False), (64, False), (200, False), (64, True), (200, True), (500, True),
+                                         (100, True), (128, True),   # V = 2: the redo launch k_phi<2, false, true, 2> redoes a pass
                                          # the lane-per-link layout above K = 32: k_phi_lpl<18 / 20 / 28> (K = 49: seven padding columns)
                                          (33, False), (40, False), (49, False), (56, False)])
 def test_softmax_rows_that_underflow(k, no_elogpi, monkeypatch):

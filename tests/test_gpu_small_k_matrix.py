@@ -14,7 +14,7 @@ Every case asserts the side of each switch its graph is on (the library's formul
 count), and what the handle's launch counters show of it.  A case is two phases, each compared with the oracle in full:
 
   (a) 4 natural sweeps from the reference initialisation (annealing, every link on the full softmax);
-  (b) 5 sweeps from a seeded state (_seed) -- one at the natural _iter, whose prune() derives the active sets, then four at
+  (b) 5 sweeps from a seeded state (matrix_cases.seed_state) -- one at the natural _iter, whose prune() derives the active sets, then four at
       _iter = 1500 with annealing off: converged-node shortcuts, the active-set branch and the full softmax side by side.
 
 The oracle's own link counts must show that (b) reached those branches, or the case fails before any kernel runs.
@@ -23,7 +23,7 @@ The largest error each tier showed on an MI355X is recorded beside TOL below."""
 import numpy as np
 import pytest
 
-from oracle import oracle as O
+import matrix_cases as MC
 from test_gpu_properties import _synthetic
 
 pytestmark = pytest.mark.gpu
@@ -63,74 +63,17 @@ def _pairs(size):
     return _graphs[size]
 
 
-def _seed(n, k, lam):
-    """The state phase (b) starts from.  Nineteen nodes in twenty are concentrated on community 0 and dominate: a
-    link with one of them puts all of its phi there (their rows are the smallest off their own community).  Pairs of ring neighbours
-    (nodes 20 i + 5, 20 i + 6) share one of the other communities, so that every community keeps mass.  After one sweep
-    without the annealing scale the majority nodes have one active community (prune() marks them converged), the others a
-    few: links between two majority nodes take the active-set branch, links with one converged end the shortcuts, and
-    links among the rest the full softmax.  A quarter of the nodes carries its community as converged flag from the
-    start (community K among them: quirk Q2)."""
-    rng = np.random.default_rng(4000 + k)
-    home = np.zeros(n, dtype=np.int64)
-    minor = np.zeros(n, dtype=bool)
-    if k > 1:
-        first = np.arange(5, n - 1, 20)
-        home[first] = home[first + 1] = 1 + np.arange(first.size) % (k - 1)
-        minor[first] = minor[first + 1] = True
-    g = np.where(minor[:, None], 0.02, 0.005) * np.ones((n, k))
-    g[np.arange(n), home] = rng.uniform(20.0, 60.0, size=n)
-    conv = np.zeros(n, dtype=np.uint32)
-    idx = rng.choice(n, size=n // 4, replace=False)
-    conv[idx] = home[idx] + 1
-    return g, np.array(lam), conv
-
-
-def _snapshot(ref, counts, test):
-    return dict(gamma=ref.gamma, lam=ref.lam, conv=ref.converged, counts=list(counts), rows=ref.rows[1:],
-                member=ref.communities(), mphi=ref.mphi, iter=ref.iter, test_rows=ref.test_rows if test else None)
-
-
-def _test_pairs(ref_links):
-    """a test set: some training links, two non-links (one unordered)"""
-    return np.concatenate([ref_links[7::997], [[3, 900], [999, 4]]]).astype(np.uint32)
-
-
 def _oracle(k, size, test=False):
     """the oracle's trajectory of one (K, size): computed once, kept for the K the modes share"""
     key = (k, size, test)
     if key in _records:
         return _records[key]
-    n, pairs = SIZES[size], _pairs(size)
-    net = O.Network(n=n, pairs=pairs)
-    tp = None
-    if test:
-        tp = _test_pairs(O.LinkSampling(net, k, use_validation_stop=False).links)
-    ref = O.LinkSampling(net, k, use_validation_stop=False, test_pairs=tp)
-    rec = dict(links=ref.links, validation=ref.validation_sorted, gamma0=ref.gamma, lam0=ref.lam, ones=net.ones,
-               ones_prob=ref.ones_prob, eta=ref.eta, test_sorted=ref.test_sorted if test else None)
-    counts = []
-
-    def sweeps(m):
-        for _ in range(m):
-            assert ref.sweep() == 0
-            counts.append(ref.link_counts())
-
-    sweeps(NAT)
-    rec["a"] = _snapshot(ref, counts, test)
-    rec["seed"] = g, lam, conv = _seed(n, k, ref.lam)
-    ref.set_gamma(g); ref.set_lambda(lam); ref.set_converged(conv); ref.refresh()
-    ref.annealing = False
-    sweeps(1)
-    ref.iter = 1500
-    sweeps(REG - 1)
-    rec["b"] = _snapshot(ref, counts, test)
+    rec = MC.trajectory(SIZES[size], _pairs(size), k, NAT, REG, test=test)
     # the condition on the seeded state, from the oracle alone: phase (b) reached the branches it is there for
-    reg = counts[NAT:]
+    reg = rec["b"]["counts"][NAT:]
     assert any(c[0] > 0 for c in reg) and any(c[2] > 0 for c in reg), reg
     if k >= 20:
         assert any(c[1] > 0 for c in reg), reg
-    assert np.isfinite(rec["b"]["gamma"]).all() and (rec["b"]["gamma"] > 0).all()
     if size == "M" and k in MODE_KS:
         _records[key] = rec
     return rec
@@ -138,56 +81,17 @@ def _oracle(k, size, test=False):
 
 def _engine(rec, k, size, **kw):
     """a handle on the oracle's inputs (its links, held-out pairs and initial state)"""
-    from svinet_amd._svils import Engine
-    eng = Engine(SIZES[size], k, ones=rec["ones"], ones_prob=rec["ones_prob"], eta=rec["eta"], use_validation_stop=False, **kw)
-    eng.set_graph(rec["links"])
-    eng.set_validation(rec["validation"])
-    eng.set_state(rec["gamma0"], rec["lam0"])
-    if rec["test_sorted"] is not None:
-        eng.set_test(rec["test_sorted"])
-    return eng
-
-
-def _rel(a, b):
-    return float(np.max(np.abs(a - b) / np.abs(b)))
+    return MC.engine_on(rec, SIZES[size], k, **kw)
 
 
 def _compare(tag, want, eng, lo=0, hi=None, counts=True):
     """the state of `eng` against an oracle snapshot; [lo, hi): the rows the handle owns (tags, stored indicators)"""
-    g, lam, conv = eng.state()
-    rows = eng.rows()
-    mphi = eng.aux(2)[lo:hi]
-    wm = want["mphi"][lo:hi]
-    err = (_rel(g, want["gamma"]), _rel(lam, want["lam"]))
-    assert err[0] < TOL["state"] and err[1] < TOL["state"], (tag, err)
-    assert np.array_equal(conv, want["conv"]), tag
-    assert eng.control().iter == want["iter"], tag
-    if counts:
-        st = eng.sweep_stats(0, len(want["counts"]))
-        assert [tuple(int(x) for x in r) for r in st] == want["counts"], tag
-    assert np.array_equal(rows[:, 0], want["rows"][:, 0]), tag
-    np.testing.assert_allclose(rows[:, 1:], want["rows"][:, 1:], rtol=TOL["rows_rtol"], atol=TOL["rows_atol"], err_msg=str(tag))
-    assert np.array_equal(eng.communities()[lo:hi], want["member"][lo:hi]), tag
-    np.testing.assert_allclose(mphi, wm, rtol=TOL["mphi_rtol"], atol=TOL["mphi_atol"], err_msg=str(tag))
-    if want["test_rows"] is not None:
-        tr = eng.test_rows(0, want["test_rows"].shape[0])
-        assert np.array_equal(tr[:, 0], want["test_rows"][:, 0]), tag
-        np.testing.assert_allclose(tr[:, 1:], want["test_rows"][:, 1:], rtol=TOL["rows_rtol"], atol=TOL["rows_atol"], err_msg=str(tag))
+    MC.compare(tag, want, eng, TOL, lo=lo, hi=hi, counts=counts)
 
 
 def _two_phases(rec, engines, sweep, check):
     """phases (a) and (b) on `engines` (every handle of a run), `sweep(m)` running m sweeps on all of them"""
-    sweep(NAT)
-    check("a", rec["a"])
-    g, lam, conv = rec["seed"]
-    for e in engines:
-        e.set_state(g, lam, conv)
-        e.set_control(annealing=0)
-    sweep(1)
-    for e in engines:
-        e.set_control(iter=1500)
-    sweep(REG - 1)
-    check("b", rec["b"])
+    MC.two_phases(rec, engines, sweep, check, REG)
 
 
 def _block_shapes(k, nodes, links, cus):
@@ -281,15 +185,9 @@ def test_forced_options_against_oracle(k, option, value):
 def test_phase_split_sweeps_against_oracle(k):
     """sweeps split at their exchange points (svils_sweep_phase): K-vectors through k_colreduce at every K, the stored
     mean indicators in the s3 pass, a stand-alone classification per sweep"""
-    from svinet_amd import _svils
     rec = _oracle(k, "M")
     eng = _engine(rec, k, "M")
-
-    def sweep(m):
-        for _ in range(m):
-            for ph in (_svils.PHASE_A, _svils.PHASE_B, _svils.PHASE_EXPAND, _svils.PHASE_C, _svils.PHASE_D):
-                eng.sweep_phase(ph)
-
+    sweep = MC.phase_split_sweeps(eng)
     _two_phases(rec, [eng], sweep, lambda phase, want: _compare((k, "M", "phases", phase), want, eng))
     eng.close()
 
@@ -303,14 +201,6 @@ def test_full_window_unit_steps_against_oracle(k):
     eng.set_stochastic(batch_nodes=0, tau0=1.0, kappa=0.0)
     _two_phases(rec, [eng], eng.step, lambda phase, want: _compare((k, "M", "step", phase), want, eng))
     eng.close()
-
-
-def _exchange_sum(ts):
-    tot = ts[0].clone()
-    for t in ts[1:]:
-        tot += t
-    for t in ts:
-        t.copy_(tot)
 
 
 # node blocks of the M graph: a handle shapes its finalise launch by the nodes, its s3 launch by the links of ITS block, so
@@ -327,16 +217,12 @@ def test_three_virtual_node_blocks_against_oracle(k):
     (768 threads on rank 0 at K = 25), K-vectors through k_colreduce at every K (caller-driven phases do not fold).
     Each rank's side of the two switches is asserted from its block, and the ranks' link counts add up to the oracle's."""
     import torch
-    from svinet_amd import _svils
     from svinet_amd.host_api import Setup
-    from svinet_amd.sharded import HipShard
     rec = _oracle(k, "M")
     setup = Setup(n=SIZES["M"], k=k, pairs=_pairs("M"))
     assert np.array_equal(setup.links, rec["links"]) and np.array_equal(setup.gamma, rec["gamma0"])
-    world = 3
-    shards = [HipShard(setup, r, world, 0, bounds=BLOCK_BOUNDS, use_validation_stop=False) for r in range(world)]
-    bounds, bm = shards[0].bounds.astype(np.int64), shards[0].bmax
-    assert list(bounds) == BLOCK_BOUNDS
+    shards, sync = MC.node_blocks(setup, BLOCK_BOUNDS)
+    world, bounds = len(shards), shards[0].bounds.astype(np.int64)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     for r in range(world):
         lo, hi = int(bounds[r]), int(bounds[r + 1])
@@ -344,45 +230,10 @@ def test_three_virtual_node_blocks_against_oracle(k):
         s3_threads, fin_waves = _block_shapes(k, hi - lo, owned, cus)
         assert (fin_waves == 12) == (r == 0 and k in (25, 49, 56)), (k, r, hi - lo, cus)
         assert s3_threads == (1024 if k <= 20 else 768 if (r == 0 and k == 25) else 512), (k, r, owned)
-
-    def sync():
-        for s in shards:
-            s.engine.synchronize()
-        torch.cuda.synchronize()
-
-    def sweep(m):
-        for _ in range(m):
-            for s in shards:
-                s.phase(_svils.PHASE_A)
-                s.phase(_svils.PHASE_B_LIGHT)
-            sync()
-            _exchange_sum([s.kvec_a for s in shards])
-            for dst in range(world):
-                for src in range(world):
-                    if src != dst:
-                        shards[dst].gstage[src * bm:(src + 1) * bm].copy_(shards[src].gstage[src * bm:(src + 1) * bm])
-            sync()
-            for s in shards:
-                s.phase(_svils.PHASE_EXPAND_ALL)
-                s.phase(_svils.PHASE_C)
-            sync()
-            _exchange_sum([s.kvec_c for s in shards])
-            sync()
-            for s in shards:
-                s.phase(_svils.PHASE_D)
-        sync()
+    sweep = MC.staged_block_sweeps(shards, sync)
 
     def check(phase, want):
-        states = [s.engine.state() for s in shards]
-        for r, s in enumerate(shards):
-            # a rank tags and stores indicators for its own rows
-            _compare((k, "M", "block%d" % r, phase), want, s.engine, lo=int(bounds[r]), hi=int(bounds[r + 1]), counts=False)
-        # ... and counts the links of its own rows (each link with the rank that owns its first end): the sum is the oracle's
-        nsw = len(want["counts"])
-        tot = sum(s.engine.sweep_stats(0, nsw).astype(np.int64) for s in shards)
-        assert [tuple(int(x) for x in row) for row in tot] == want["counts"], (k, phase)
-        for g, lam, conv in states[1:]:
-            assert np.array_equal(g, states[0][0]) and np.array_equal(lam, states[0][1])
+        MC.compare_blocks((k, "M", phase), want, shards, TOL)
 
     _two_phases(rec, [s.engine for s in shards], sweep, check)
     for s in shards:
