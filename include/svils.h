@@ -41,6 +41,7 @@ extern "C" {
                                     on a sweep path reads the environment); svils_gather_communities ends the no-wait window of "After the stop";
                                     (additive, same version) svils_link_prob / svils_predict_links: link prediction from the state;
                                     (additive, same version) svils_findk_*: -findk, the estimate of the number of communities;
+                                    (additive, same version) svils_batch_*: -batch-gpu, all-pairs batch inference;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
                                     resource-allocation scores of pairs, the model-free baselines of svils_rank_links */
@@ -624,6 +625,51 @@ int svils_lc_get_links(svils_lc *h, uint32_t *colour, uint8_t *flags, uint64_t c
 int svils_lc_get_gml(svils_lc *h, uint64_t *count, uint32_t *edges);
 /* device milliseconds of the last run's node pass, link pass (with the recheck) and counts (with the GML list); -1: not run */
 int svils_lc_get_timing(svils_lc *h, double ms[3]);
+
+/* ---- -batch-gpu: all-pairs batch variational inference (an ADDITION of ABI 8; a handle of its own) ---------------------
+ * The reference's MMSBInfer::batch_infer (src/mmsbinfer.cc:833-930): coordinate ascent over ALL n (n - 1) / 2 pairs, the
+ * exact model -link-sampling approximates.  One sweep is the loop body (:846-889):
+ *   Elogpi / Elogbeta   set_dir_exp (src/mmsbinfer.hh:563-580) of gamma and lambda, on the device
+ *   pair pass           every pair p < q outside the skip set: PhiComp::update_phis_until_conv (src/mmsbinfer.hh:104-203),
+ *                       the Jacobi fixed point of the two indicator vectors from 1 / k, at most 50 rounds, the exit tested
+ *                       on odd rounds (mean |new - old| < 1e-5 on both sides), normalised by the plain sum
+ *   accumulation        gamma_next[p] += phi1, gamma_next[q] += phi2, lambda_next[k][y ? 0 : 1] += phi1[k] phi2[k] on top of
+ *                       alpha and eta (:868-876): per-tile partial sums added in a fixed order, no floating-point atomics,
+ *                       so a sweep is bitwise reproducible run to run
+ * The device holds y(p, q) and the skip set as two n x n bit matrices: 2 * n * ceil(n / 32) * 4 bytes (256 MiB at
+ * n = SVILS_BATCH_MAX_N).  Without a HIP device svils_batch_create answers SVILS_ERR_DEVICE ("no CPU path"); every other
+ * entry point answers a null handle the same way, and SVILS_ERR_ARG with a device. */
+#define SVILS_BATCH_MAX_K 256      /* the (W, V) table of the pair kernel ends here (svils_batch_variant) */
+#define SVILS_BATCH_MAX_N 32768    /* bit matrices: 2 * n * ceil(n / 32) * 4 bytes = 256 MiB here; state 4 * n * k * 8 bytes */
+typedef struct svils_batch svils_batch;
+/* alpha, eta0, eta1, epsilon: src/env.hh:344-395 (epsilon in (0, 1)).  SVILS_ERR_ARG: n < 2, k < 2, a parameter <= 0;
+ * SVILS_ERR_UNSUPPORTED: k > SVILS_BATCH_MAX_K or n > SVILS_BATCH_MAX_N (checked before any device call) */
+int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double eta0, double eta1, double epsilon,
+                       svils_batch **out);
+int svils_batch_destroy(svils_batch *h);
+/* links [nlinks][2]: y(p, q) = 1 (Network::y); skip [nskip][2]: the held-out and validation pairs batch_infer leaves out
+ * (:851-853).  Every pair has p < q < n; a self pair, p > q, a node >= n or a pair repeated inside its list: SVILS_ERR_ARG */
+int svils_batch_set_graph(svils_batch *h, const uint32_t *links, uint64_t nlinks, const uint32_t *skip, uint64_t nskip);
+/* gamma [n][k], lambda [k][2] (init_gamma / init_lambda, :372-397); every value > 0 */
+int svils_batch_set_state(svils_batch *h, const double *gamma, const double *lambda);
+int svils_batch_get_state(svils_batch *h, double *gamma, double *lambda);   /* either may be null; waits for the sweeps */
+/* nsweeps passes of the loop body (:846-889), enqueued.  A pair whose normaliser is not > 0 (the reference's
+ * assert(s > .0), src/mmsbinfer.hh:139) is counted on the device: the next call that waits for the device
+ * (svils_batch_get_state, svils_batch_pair_loglik) then answers SVILS_ERR_UNSUPPORTED with "phi normaliser underflow" */
+int svils_batch_sweep(svils_batch *h, uint32_t nsweeps);
+/* edge_likelihood (src/mmsbinfer.hh:634-668) of m pairs (p, q, y) on the current state: out[i] = log(max(s, 1e-30)), s the
+ * sum over z of pi_p pi_q beta_z for y = 1 and the k x k sum with epsilon off the diagonal for y = 0.  The caller adds them
+ * (heldout_likelihood, src/mmsbinfer.cc:2086-2174, in its std::map order) */
+int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t *y, uint64_t m, double *out);
+/* of the last sweep, counted by the pair kernel: pairs visited, fixed-point rounds over all of them, the most rounds of one
+ * pair, pairs whose normaliser underflowed (this one since the last svils_batch_set_state); any pointer may be null */
+int svils_batch_get_stats(svils_batch *h, uint64_t *pairs_done, uint64_t *rounds_total, uint32_t *rounds_max,
+                          uint64_t *underflow_pairs);
+/* device milliseconds of the last sweep: Elogpi / Elogbeta, the pair pass, the reductions (hipEvent brackets; -1: none yet) */
+int svils_batch_get_timing(svils_batch *h, double ms[3]);
+/* the pair kernel's instantiation for k: a group of W lanes per pair, V values per lane, W * V >= k.  No device needed.
+ * SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_BATCH_MAX_K */
+int svils_batch_variant(uint32_t k, uint32_t *w, uint32_t *v);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * Every tunable of the library is a row of ONE table: key, the SVILS_* environment variable that sets its default, the

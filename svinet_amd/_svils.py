@@ -40,7 +40,10 @@ EXPORTS = (
     "svils_lc_create", "svils_lc_destroy", "svils_lc_set_graph", "svils_lc_set_model", "svils_lc_run", "svils_lc_get_nodes",
     "svils_lc_get_degrees", "svils_lc_get_pi", "svils_lc_get_communities", "svils_lc_get_links", "svils_lc_get_gml",
     "svils_lc_get_timing",
+    "svils_batch_create", "svils_batch_destroy", "svils_batch_set_graph", "svils_batch_set_state", "svils_batch_get_state",
+    "svils_batch_sweep", "svils_batch_pair_loglik", "svils_batch_get_stats", "svils_batch_get_timing", "svils_batch_variant",
 )
+BATCH_MAX_K, BATCH_MAX_N = 256, 32768   # SVILS_BATCH_MAX_K, SVILS_BATCH_MAX_N
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
 NBR_CN, NBR_AA, NBR_RA = range(3)   # svils_nbr_measure
 
@@ -184,6 +187,16 @@ def load():
     L.svils_lc_get_links.argtypes = [vp, vp, vp, vp]
     L.svils_lc_get_gml.argtypes = [vp, C.POINTER(C.c_uint64), vp]
     L.svils_lc_get_timing.argtypes = [vp, vp]
+    L.svils_batch_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(vp)]
+    L.svils_batch_destroy.argtypes = [vp]
+    L.svils_batch_set_graph.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+    L.svils_batch_set_state.argtypes = [vp, vp, vp]
+    L.svils_batch_get_state.argtypes = [vp, vp, vp]
+    L.svils_batch_sweep.argtypes = [vp, C.c_uint32]
+    L.svils_batch_pair_loglik.argtypes = [vp, vp, vp, C.c_uint64, vp]
+    L.svils_batch_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.svils_batch_get_timing.argtypes = [vp, vp]
+    L.svils_batch_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):
@@ -607,3 +620,64 @@ def option_table():
     rows = load().svils_option_table().decode().strip().split("\n")
     head = rows[0].split("\t")
     return [dict(zip(head, r.split("\t"))) for r in rows[1:]]
+
+
+def batch_variant(k):
+    """svils_batch_variant: (W, V) of the pair kernel of -batch-gpu for k; no device needed"""
+    w, v = C.c_uint32(), C.c_uint32()
+    _chk(load().svils_batch_variant(k, C.byref(w), C.byref(v)))
+    return w.value, v.value
+
+
+class Batch:
+    """One svils_batch handle: the body of MMSBInfer::batch_infer (all pairs) on the device."""
+
+    def __init__(self, n, k, alpha, eta, epsilon=1e-30, device=0):
+        self._h = C.c_void_p()
+        self.n, self.k = n, k
+        _chk(load().svils_batch_create(device, n, k, alpha, eta[0], eta[1], epsilon, C.byref(self._h)))
+
+    def set_graph(self, links, skip=()):
+        links = np.ascontiguousarray(links, dtype=np.uint32).reshape(-1, 2)
+        skip = np.ascontiguousarray(skip, dtype=np.uint32).reshape(-1, 2)
+        _chk(load().svils_batch_set_graph(self._h, links.ctypes.data, links.shape[0], skip.ctypes.data, skip.shape[0]))
+
+    def set_state(self, gamma, lam):
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64).reshape(self.n, self.k)
+        lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(self.k, 2)
+        _chk(load().svils_batch_set_state(self._h, gamma.ctypes.data, lam.ctypes.data))
+
+    def state(self):
+        g, lam = np.empty((self.n, self.k)), np.empty((self.k, 2))
+        _chk(load().svils_batch_get_state(self._h, g.ctypes.data, lam.ctypes.data))
+        return g, lam
+
+    def sweep(self, nsweeps=1):
+        _chk(load().svils_batch_sweep(self._h, nsweeps))
+
+    def pair_loglik(self, pairs, y):
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        y = np.ascontiguousarray(y, dtype=np.uint8).reshape(-1)
+        assert y.shape[0] == pairs.shape[0]
+        out = np.empty(pairs.shape[0])
+        _chk(load().svils_batch_pair_loglik(self._h, pairs.ctypes.data, y.ctypes.data, pairs.shape[0], out.ctypes.data))
+        return out
+
+    def stats(self):
+        """(pairs_done, rounds_total, rounds_max, underflow_pairs) of the last sweep"""
+        a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+        _chk(load().svils_batch_get_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
+
+    def timing(self):
+        """device ms of the last sweep: dir_exp, pair pass, reductions"""
+        ms = np.zeros(3)
+        _chk(load().svils_batch_get_timing(self._h, ms.ctypes.data))
+        return ms
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().svils_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close

@@ -38,6 +38,8 @@ typedef struct {
   int32_t eta_type;        // 0 uniform, 1 fromdata, 2 sparse, 3 dense
   int32_t accuracy;
   int32_t defer_gamma;     // 1: no host init_gamma2 (the caller draws on the device: svih_init_links / svih_init_streams -> svils_init_gamma)
+  int32_t batch_device;    // svih_batch_from_file: 1 = the device backend of the -batch engine (-batch-gpu), on `device`
+  int32_t device;
 } svih_options;
 
 struct svih_setup {
@@ -78,6 +80,7 @@ void svih_options_default(svih_options *o, uint32_t n, uint32_t k) {
   memset(o, 0, sizeof *o);
   o->n = n; o->k = k; o->seed = 0; o->heldout_ratio = 0.01; o->link_thresh = 0.5;
   o->lt_min_deg = 0; o->eta_type = 0; o->accuracy = 0; o->defer_gamma = 0;
+  o->batch_device = 0; o->device = 0;
 }
 svih_setup *svih_setup_from_file(const char *path, const svih_options *o) { return make_setup(o, path, nullptr, 0); }
 svih_setup *svih_setup_from_pairs(const int32_t *pairs, uint64_t nlines, const svih_options *o) {
@@ -160,6 +163,8 @@ svih_batch *svih_batch_from_file(const char *path, const svih_options *o) {
   a.n = o->n;
   a.k = o->k;
   a.batch = true;
+  a.batch_gpu = o->batch_device != 0;
+  a.device = o->device;
   a.rand_seed = o->seed;
   a.hol_ratio = o->heldout_ratio;
   a.eta_type = eta_names[(o->eta_type >= 0 && o->eta_type < 4) ? o->eta_type : 0];
@@ -169,7 +174,10 @@ svih_batch *svih_batch_from_file(const char *path, const svih_options *o) {
   b->net.reset(new Network(*b->env));
   if (b->net->read(path) < 0) { delete b; return nullptr; }
   b->env->n = b->net->n() - b->net->singles();
-  b->eng.reset(new MMSBBatch(*b->env, *b->net));
+  if (svils_rc([&] { b->eng.reset(new MMSBBatch(*b->env, *b->net)); return 0; })) {   // svils_last_error() keeps the library's text
+    delete b;
+    return nullptr;
+  }
   return b;
 }
 void svih_batch_free(svih_batch *b) { delete b; }
@@ -183,8 +191,8 @@ uint64_t svih_batch_nvalidation(const svih_batch *b) { return b->eng->validation
 const uint32_t *svih_batch_validation(const svih_batch *b) { return b->eng->validation_edges().data(); }
 uint64_t svih_batch_nrows(const svih_batch *b) { return b->eng->heldout_rows().size() / 10; }
 const double *svih_batch_rows(const svih_batch *b) { return b->eng->heldout_rows().data(); }
-void svih_batch_sweep(svih_batch *b) { b->eng->sweep(); }
-int svih_batch_report(svih_batch *b) { return b->eng->report() ? 1 : 0; }
+int svih_batch_sweep(svih_batch *b) { return svils_rc([&] { b->eng->sweep(); return 0; }); }   // < 0: a svils_error of the device backend
+int svih_batch_report(svih_batch *b) { return svils_rc([&] { return b->eng->report() ? 1 : 0; }); }
 double svih_batch_eta0(const svih_batch *b) { return b->env->eta0; }
 double svih_batch_eta1(const svih_batch *b) { return b->env->eta1; }
 double svih_batch_ones_prob(const svih_batch *b) { return b->env->ones_prob; }

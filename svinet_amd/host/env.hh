@@ -18,6 +18,7 @@ class Env {
     std::string datfname = "network.dat";
     std::string label = "mmsb";
     bool batch = false, link_sampling = false;
+    bool batch_gpu = false;             // -batch-gpu: -batch with its sweeps and pair likelihoods on the device (svils_batch_*)
     bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
     bool load = false;
@@ -106,6 +107,7 @@ class Env {
   int comm_rfd;
   std::vector<int> comm_wfds;
   bool batch_mode, link_sampling, findk;
+  bool batch_device;                 // -batch-gpu: MMSBBatch drives a svils_batch handle instead of its host loops
   bool gml, lcstats;
   bool strid;
   volatile int terminate;

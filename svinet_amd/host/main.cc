@@ -106,6 +106,8 @@ static void usage() {
           "\t-k <K>\t\tnumber of communities\n\n"
           "\t-link-sampling\tinference using link sampling (the MI355X engine of this build)\n\n"
           "\t-batch\t\trun batch variational inference over all pairs (host CPU, small graphs)\n\n"
+          "\t-batch-gpu\t-batch with every sweep and pair likelihood on the GPU: same output directory and files, -k <= 256,\n"
+          "\t\t\t-n <= 32768.  Single GPU; without one the run fails (no fall-back to the host engine)\n\n"
           "\t-findk\t\testimate the number of communities (label propagation over a top-5 sparse gamma, on the GPU);\n"
           "\t\t\tpick -k for -link-sampling from the lines of its communities.txt.  Single GPU; -k only sets alpha = 1/k\n\n"
           "\t-gml\t\tgenerate a GML format file that visualizes link communities: reads gamma.txt and lambda.txt of the\n"
@@ -180,6 +182,7 @@ int main(int argc, char **argv) {
     else if (is("-force") || is("-online") || is("-nodelay")) {}
     else if (is("-file")) { need(i); a.datfname = argv[++i]; }
     else if (is("-batch")) { a.batch = true; a.link_sampling = false; a.rfreq = 1; }
+    else if (is("-batch-gpu")) { a.batch = true; a.batch_gpu = true; a.link_sampling = false; a.rfreq = 1; }
     else if (is("-link-sampling")) { a.link_sampling = true; a.batch = false; a.rfreq = 1; }
     else if (is("-findk")) { a.findk = true; }
     else if (is("-gml")) { a.gml = true; }
@@ -266,6 +269,16 @@ int main(int argc, char **argv) {
     }
   }
   if (a.findk && refused(a, kFindK, "-findk")) return 2;
+  if (a.batch_gpu) {                                     // the limits of svils_batch_create, before anything is read
+    if (a.k > SVILS_BATCH_MAX_K) {
+      fprintf(stderr, "error: -batch-gpu holds -k <= %d (SVILS_BATCH_MAX_K); -k %u is refused\n", SVILS_BATCH_MAX_K, a.k);
+      return 2;
+    }
+    if (a.n > SVILS_BATCH_MAX_N) {
+      fprintf(stderr, "error: -batch-gpu holds -n <= %d (SVILS_BATCH_MAX_N); -n %u is refused\n", SVILS_BATCH_MAX_N, a.n);
+      return 2;
+    }
+  }
   if (a.adamic_adar) {                                   // baselines of link ranks (svils_nbr_score / svils_nbr_rank)
     if (refused(a, kPrediction, "-adamic-adar") || refused(a, kBaselines, "-adamic-adar")) return 2;
     if (!a.link_sampling || (a.predict_pairs_fname.empty() && a.rank_pairs_fname.empty() && !a.rank_heldout)) {
@@ -442,8 +455,13 @@ run:
   }
   if (a.batch) {                             // src/main.cc:354-358
     printf("+ running mmsb batch inference\n");
-    MMSBBatch mmsb(env, network);
-    mmsb.batch_infer();
+    try {                                    // -batch-gpu: a failed svils_batch_* call ends the run (no host fall-back)
+      MMSBBatch mmsb(env, network);
+      mmsb.batch_infer();
+    } catch (const SvilsError &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return -1;
+    }
     exit(0);
   }
   LinkSampling ls(env, network);

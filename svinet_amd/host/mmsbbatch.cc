@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <set>
 #include <sstream>
 
 #include "util.hh"
@@ -46,6 +47,7 @@ MMSBBatch::MMSBBatch(Env &env, Network &network)
     lambda_[2 * k + 1] = lambdanext_[2 * k + 1] = env.eta1;
   }
   set_dir_exp();
+  if (env_.batch_device) attach_device();
   if (env_.write_files) {
     // files the reference's constructor opens (:62-166); the ones this path never writes stay empty
     for (const char *f : {"/stats.txt", "/time.txt", "/convergence.txt", "/cmap.txt", "/training.txt",
@@ -66,6 +68,55 @@ MMSBBatch::MMSBBatch(Env &env, Network &network)
 MMSBBatch::~MMSBBatch() {
   if (hf_) fclose(hf_);
   if (vf_) fclose(vf_);
+  if (dev_) svils_batch_destroy(dev_);
+}
+
+// ---------------------------------------------------------------------------
+// the device backend (include/svils.h: svils_batch_*)
+// ---------------------------------------------------------------------------
+void MMSBBatch::device_failed(const char *what, int rc) {
+  if (strstr(svils_last_error(), "phi normaliser underflow")) {   // the host loops' error line and exit status (phis())
+    fprintf(stderr, "error: %s\n", svils_last_error());
+    exit(-1);
+  }
+  throw_svils(what, rc);
+}
+
+void MMSBBatch::attach_device() {
+  if (int rc = svils_batch_create(env_.device, n_, k_, env_.alpha, env_.eta0, env_.eta1, env_.epsilon, &dev_))
+    device_failed("svils_batch_create", rc);
+  std::set<Edge> links(network_.edges().begin(), network_.edges().end()), skip;
+  for (const auto &it : heldout_map_) skip.insert(it.first);
+  for (const auto &it : validation_map_) skip.insert(it.first);
+  std::vector<uint32_t> l, s;
+  for (const Edge &e : links) { l.push_back(e.first); l.push_back(e.second); }
+  for (const Edge &e : skip) { s.push_back(e.first); s.push_back(e.second); }
+  if (int rc = svils_batch_set_graph(dev_, l.data(), l.size() / 2, s.data(), s.size() / 2)) device_failed("svils_batch_set_graph", rc);
+  if (int rc = svils_batch_set_state(dev_, gamma_.data(), lambda_.data())) device_failed("svils_batch_set_state", rc);
+}
+
+void MMSBBatch::fetch_state() {
+  if (!dev_ || !host_stale_) return;
+  if (int rc = svils_batch_get_state(dev_, gamma_.data(), lambda_.data())) device_failed("svils_batch_get_state", rc);
+  host_stale_ = false;
+}
+
+std::vector<double> MMSBBatch::pair_likelihoods(const std::map<Edge, bool> &pairs) {
+  std::vector<double> u(pairs.size());
+  size_t i = 0;
+  if (!dev_) {
+    for (const auto &it : pairs) u[i++] = edge_likelihood(it.first.first, it.first.second, network_.y(it.first.first, it.first.second) ? 1 : 0);
+    return u;
+  }
+  std::vector<uint32_t> pq(2 * pairs.size());
+  std::vector<uint8_t> y(pairs.size());
+  for (const auto &it : pairs) {
+    pq[2 * i] = it.first.first;
+    pq[2 * i + 1] = it.first.second;
+    y[i++] = network_.y(it.first.first, it.first.second) ? 1 : 0;
+  }
+  if (int rc = svils_batch_pair_loglik(dev_, pq.data(), y.data(), pairs.size(), u.data())) device_failed("svils_batch_pair_loglik", rc);
+  return u;
 }
 
 // ---------------------------------------------------------------------------
@@ -233,6 +284,12 @@ void MMSBBatch::phis(uint32_t p, uint32_t q, int y, double *phi1, double *phi2) 
 }
 
 void MMSBBatch::sweep() {                                   // src/mmsbinfer.cc:846-889
+  if (dev_) {
+    if (int rc = svils_batch_sweep(dev_, 1)) device_failed("svils_batch_sweep", rc);
+    host_stale_ = true;
+    iter_++;
+    return;
+  }
   set_dir_exp();
   std::vector<double> phi1(k_), phi2(k_);
   for (uint32_t p = 0; p < n_; ++p)
@@ -280,9 +337,11 @@ bool MMSBBatch::heldout_likelihood() {                      // src/mmsbinfer.cc:
   if (env_.accuracy) return false;
   uint32_t k = 0, kzeros = 0, kones = 0;
   double s = 0, szeros = 0, sones = 0;
+  const std::vector<double> us = pair_likelihoods(heldout_map_);
+  size_t at = 0;
   for (const auto &it : heldout_map_) {
     const int y = network_.y(it.first.first, it.first.second) ? 1 : 0;
-    const double u = edge_likelihood(it.first.first, it.first.second, y);
+    const double u = us[at++];
     s += u;
     k++;
     if (y) { sones += u; kones++; } else { szeros += u; kzeros++; }
@@ -330,9 +389,11 @@ void MMSBBatch::validation_likelihood(double *av) {         // src/mmsbinfer.cc:
   if (env_.accuracy) return;
   uint32_t k = 0, kzeros = 0, kones = 0;
   double s = 0, szeros = 0, sones = 0;
+  const std::vector<double> us = pair_likelihoods(validation_map_);
+  size_t at = 0;
   for (const auto &it : validation_map_) {
     const int y = network_.y(it.first.first, it.first.second) ? 1 : 0;
-    const double u = edge_likelihood(it.first.first, it.first.second, y);
+    const double u = us[at++];
     s += u;
     k++;
     if (y) { sones += u; kones++; } else { szeros += u; kzeros++; }
@@ -346,7 +407,7 @@ void MMSBBatch::validation_likelihood(double *av) {         // src/mmsbinfer.cc:
 }
 
 bool MMSBBatch::report() {                                  // src/mmsbinfer.cc:895-905
-  set_dir_exp();
+  if (!dev_) set_dir_exp();                                 // (the device forms Elogpi / Elogbeta at the head of its sweep)
   if (heldout_likelihood()) return true;
   validation_likelihood(nullptr);
   return false;
@@ -383,6 +444,7 @@ int MMSBBatch::batch_infer() {
 // ---------------------------------------------------------------------------
 void MMSBBatch::do_on_stop() {
   if (!env_.write_files) return;
+  fetch_state();
   save_model();
   compute_and_log_groups();
 }

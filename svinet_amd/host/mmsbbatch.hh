@@ -3,9 +3,15 @@
 // `svinet -file F -n N -k K -batch` in the reference constructs MMSBInfer and runs
 // MMSBInfer::batch_infer() (src/main.cc:354-358): coordinate-ascent variational inference
 // over ALL n(n-1)/2 pairs, on the CPU, single-threaded.  It is a different engine from the
-// link-sampling hot path this repo accelerates; it is provided here as plumbing only (same
-// flags, same output directory and file formats) and, like the reference's, it runs on the
-// host.  It is NOT a fallback for `-link-sampling`: that path has no CPU route in this repo.
+// link-sampling hot path this repo accelerates (same flags, same output directory and file
+// formats).  Two backends, chosen at construction by Env::batch_device:
+//   host    (-batch)      the reference's loops restated, single-threaded, as plumbing;
+//   device  (-batch-gpu)  every sweep and every pair likelihood through the svils_batch_* entry
+//                         points of include/svils.h (csrc/svils_batch.hip); the samplers,
+//                         init_gamma, the sums in std::map order, the stop rule and the writers
+//                         stay here.  A failed svils_batch_* call throws SvilsError (util.hh); no
+//                         HIP device is such a failure -- there is no fall-back to the host loops.
+// It is NOT a fallback for `-link-sampling`: that path has no CPU route in this repo.
 //
 // Seam mirrored:   MMSBInfer mmsb(env, network);  mmsb.batch_infer();
 //
@@ -24,6 +30,7 @@
 #include "env.hh"
 #include "network.hh"
 #include "rng.hh"
+#include "svils.h"
 
 namespace svinet {
 
@@ -44,8 +51,8 @@ class MMSBBatch {
   uint32_t n() const { return n_; }
   uint32_t k() const { return k_; }
   uint32_t iter() const { return iter_; }
-  std::vector<double> &gamma() { return gamma_; }         // [n][k]
-  std::vector<double> &lambda() { return lambda_; }       // [k][2]
+  std::vector<double> &gamma() { fetch_state(); return gamma_; }     // [n][k]
+  std::vector<double> &lambda() { fetch_state(); return lambda_; }   // [k][2]
   const std::vector<uint32_t> &heldout_edges() const { return heldout_edges_; }         // [H][2], acceptance order
   const std::vector<uint32_t> &validation_edges() const { return validation_edges_; }   // [V][2]
   const std::vector<double> &heldout_rows() const { return rows_; }                     // [rows][10]
@@ -54,6 +61,11 @@ class MMSBBatch {
   double edge_likelihood(uint32_t p, uint32_t q, int y) const;                          // src/mmsbinfer.hh:634-668
 
  private:
+  void attach_device();                                   // the svils_batch handle: graph, skip set, state
+  void fetch_state();                                     // device backend: gamma_ / lambda_ follow the device
+  [[noreturn]] void device_failed(const char *what, int rc);
+  // edge_likelihood of every pair of a held-out map, in its order
+  std::vector<double> pair_likelihoods(const std::map<Edge, bool> &pairs);
   void init_heldout();
   void set_sample(int s, bool heldout);
   void get_random_edge(bool heldout_flag, bool stratified, int family, Edge &e);
@@ -85,6 +97,8 @@ class MMSBBatch {
   double spare_ = 0;
   time_t start_time_;
   FILE *hf_ = nullptr, *vf_ = nullptr;
+  svils_batch *dev_ = nullptr;       // the device backend (null: host loops)
+  bool host_stale_ = false;          // the device has swept since gamma_ / lambda_ were fetched
 };
 
 }  // namespace svinet

@@ -20,7 +20,8 @@ ETA_TYPES = {"uniform": 0, "fromdata": 1, "sparse": 2, "dense": 3}
 class Options(C.Structure):
     _fields_ = [("n", C.c_uint32), ("k", C.c_uint32), ("seed", C.c_double),
                 ("heldout_ratio", C.c_double), ("link_thresh", C.c_double),
-                ("lt_min_deg", C.c_uint32), ("eta_type", C.c_int32), ("accuracy", C.c_int32), ("defer_gamma", C.c_int32)]
+                ("lt_min_deg", C.c_uint32), ("eta_type", C.c_int32), ("accuracy", C.c_int32), ("defer_gamma", C.c_int32),
+                ("batch_device", C.c_int32), ("device", C.c_int32)]
 
 
 _lib = None
@@ -198,9 +199,11 @@ class Setup:
 
 class BatchEngine:
     """The `-batch` engine of the host library (svinet_amd/host/mmsbbatch.cc): the reference's
-    all-pairs CPU engine MMSBInfer::batch_infer (src/mmsbinfer.cc:833-930), plumbing only."""
+    all-pairs engine MMSBInfer::batch_infer (src/mmsbinfer.cc:833-930).  on_device=False: its host loops (plumbing only);
+    on_device=True: the sweeps and pair likelihoods run through svils_batch_* on `device` (-batch-gpu) -- SvilsError
+    without a HIP device, never the host loops instead."""
 
-    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, eta_type="uniform"):
+    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, eta_type="uniform", on_device=False, device=0):
         L = load()
         vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
         if not hasattr(L, "_batch_ready"):
@@ -208,7 +211,7 @@ class BatchEngine:
             L.svih_batch_from_file.restype = vp
             for name, res in (("free", None), ("n", u32), ("iter", u32), ("gamma", P(dbl)), ("lambda", P(dbl)),
                               ("nheldout", u64), ("heldout", P(u32)), ("nvalidation", u64),
-                              ("validation", P(u32)), ("nrows", u64), ("rows", P(dbl)), ("sweep", None),
+                              ("validation", P(u32)), ("nrows", u64), ("rows", P(dbl)), ("sweep", C.c_int),
                               ("report", C.c_int), ("eta0", dbl), ("eta1", dbl), ("ones_prob", dbl),
                               ("edges", P(u32)), ("ones", u32)):
                 f = getattr(L, "svih_batch_" + name)
@@ -218,8 +221,13 @@ class BatchEngine:
         o = Options()
         L.svih_options_default(C.byref(o), n, k)
         o.seed, o.heldout_ratio, o.eta_type = seed, heldout_ratio, ETA_TYPES[eta_type]
+        o.batch_device, o.device = int(bool(on_device)), device
         self._h = L.svih_batch_from_file(os.fsencode(path), C.byref(o))
         if not self._h:
+            if on_device:   # (as FindK: an unreadable file and a failed svils_batch_* call both end here)
+                err = _svils.load().svils_last_error().decode("utf-8", "replace")
+                raise _svils.SvilsError(-2 if "no HIP device" in err else -1,
+                                        "BatchEngine: cannot read %r or the device backend failed: %s" % (path, err))
             raise IOError("cannot read network %r" % (path,))
         self.n, self.k = L.svih_batch_n(self._h), k
         self.eta = (L.svih_batch_eta0(self._h), L.svih_batch_eta1(self._h))
@@ -245,10 +253,15 @@ class BatchEngine:
         return load().svih_batch_iter(self._h)
 
     def sweep(self):
-        load().svih_batch_sweep(self._h)
+        rc = load().svih_batch_sweep(self._h)
+        if rc < 0:
+            _svils._chk(rc)
 
     def report(self):
-        return bool(load().svih_batch_report(self._h))
+        rc = load().svih_batch_report(self._h)
+        if rc < 0:
+            _svils._chk(rc)
+        return bool(rc)
 
     def close(self):
         if getattr(self, "_h", None):
