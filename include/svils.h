@@ -516,7 +516,10 @@ int svils_gather_communities(svils_handle *h);
 typedef enum {
   SVILS_KPHASE_DEN = 0, SVILS_KPHASE_PHI = 1, SVILS_KPHASE_FIN = 2, SVILS_KPHASE_LAMBDA = 3, SVILS_KPHASE_STOP = 4,
   SVILS_KPHASE_INIT_ROWS = 5, SVILS_KPHASE_INIT_EXPAND = 6,
-  SVILS_KPHASE_DENMAX = 7   /* log-domain mode only: before DEN, followed by a MAX (not SUM) of SVILS_KSH_DMAX */
+  SVILS_KPHASE_DENMAX = 7,  /* log-domain mode only: before DEN, followed by a MAX (not SUM) of SVILS_KSH_DMAX */
+  /* not part of a sweep: the partial dot products of the held-out pairs alone, after svils_ksh_init_state or between two
+   * sweeps -- what svils_validation_row launches on a K-sharded handle, for callers that SUM SVILS_KSH_VDOT themselves */
+  SVILS_KPHASE_VDOT = 8
 } svils_kphase;
 typedef enum { SVILS_KSH_DEN = 0, SVILS_KSH_ROWX = 1, SVILS_KSH_Q2 = 2, SVILS_KSH_VDOT = 3, SVILS_KSH_DMAX = 4,
                /* link_thresh < 1/2 only (argmax tagging, src/linksampling.cc:704-717, src/matrix.hh:521-532): the lowest

@@ -230,7 +230,7 @@ def balance_node_blocks(links, n, world, node_weight=-1.0):
     b = np.zeros(world + 1, dtype=np.uint32)
     _chk(load().svils_balance_node_blocks(links.ctypes.data, links.shape[0], n, world, float(node_weight), b.ctypes.data))
     return b
-KPHASE_DEN, KPHASE_PHI, KPHASE_FIN, KPHASE_LAMBDA, KPHASE_STOP, KPHASE_INIT_ROWS, KPHASE_INIT_EXPAND, KPHASE_DENMAX = range(8)
+KPHASE_DEN, KPHASE_PHI, KPHASE_FIN, KPHASE_LAMBDA, KPHASE_STOP, KPHASE_INIT_ROWS, KPHASE_INIT_EXPAND, KPHASE_DENMAX, KPHASE_VDOT = range(9)
 KSH_DEN, KSH_ROWX, KSH_Q2, KSH_VDOT, KSH_DMAX, KSH_EARG = range(6)
 
 

@@ -10,8 +10,9 @@ int svils_ksweep_phase(svils_handle *h, svils_kphase phase) {
   if (!h) return fail(SVILS_ERR_ARG, "svils_ksweep_phase: null handle");
   if (!h->d.ksh) return fail(SVILS_ERR_ARG, "svils_ksweep_phase: not a K-sharded handle (svils_config.k_total)");
   if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "svils_ksweep_phase: set graph and state first");
-  if ((int)phase < 0 || (int)phase > 7) return fail(SVILS_ERR_ARG, "svils_ksweep_phase: unknown phase %d", (int)phase);
+  if ((int)phase < 0 || (int)phase > 8) return fail(SVILS_ERR_ARG, "svils_ksweep_phase: unknown phase %d", (int)phase);
   if (phase == SVILS_KPHASE_DENMAX && !h->d.ksh_log) return fail(SVILS_ERR_ARG, "svils_ksweep_phase: DENMAX belongs to the log-domain mode (svils_ksh_log_domain)");
+  if (phase == SVILS_KPHASE_VDOT && h->step_open) return fail(SVILS_ERR_ARG, "svils_ksweep_phase: VDOT belongs between two steps, not inside one");
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->stoch && ((int)phase <= 4 || phase == SVILS_KPHASE_DENMAX)) {
     // mini-batch step over the window of nodes every rank shares (open_step: window geometry, item ranges, the

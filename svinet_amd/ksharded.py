@@ -26,12 +26,21 @@ def column_slices(k, world):
 
 
 class KShard:
-    def __init__(self, setup, rank, world, device_index=0, log_domain=None, **engine_kw):
-        """log_domain: None = the library's default (on above K = 700), True / False forces it"""
+    def __init__(self, setup, rank, world, device_index=0, log_domain=None, bounds=None, **engine_kw):
+        """log_domain: None = the library's default (on above K = 700), True / False forces it
+        bounds: world + 1 ascending column bounds from 0 to setup.k (rank r holds [bounds[r], bounds[r + 1]), no slice
+        empty); None = column_slices (as even as possible).  The slice width selects a rank's kernels, so ranks of
+        unequal slices run different instantiations side by side."""
         import torch
         self.torch = torch
         self.rank, self.world = rank, world
-        self.k0, self.k1 = column_slices(setup.k, world)[rank]
+        if bounds is None:
+            self.k0, self.k1 = column_slices(setup.k, world)[rank]
+        else:
+            b = [int(x) for x in bounds]
+            if len(b) != world + 1 or b[0] != 0 or b[-1] != setup.k or any(lo >= hi for lo, hi in zip(b, b[1:])):
+                raise ValueError("bounds: need %d ascending column bounds from 0 to %d, got %r" % (world + 1, setup.k, b))
+            self.k0, self.k1 = b[rank], b[rank + 1]
         from ._svils import Engine
         args = dict(ones=setup.ones, ones_prob=setup.ones_prob, eta=setup.eta,
                     link_thresh=setup.link_thresh, lt_min_deg=setup.lt_min_deg, device=device_index,
@@ -41,6 +50,8 @@ class KShard:
         self.engine = e = Engine(setup.n, setup.k, **args)
         e.set_graph(setup.links)
         e.set_validation(setup.validation_sorted)
+        self.validation = np.asarray(setup.validation_sorted, dtype=np.uint32).reshape(-1, 3)
+        self.ones_prob = args["ones_prob"]
         if getattr(setup, "host_gamma", True):
             e.set_state(np.ascontiguousarray(setup.gamma[:, self.k0:self.k1]), np.ascontiguousarray(setup.lam[self.k0:self.k1]))
         else:   # init_gamma2 on the device: this rank's column slice of every link's draws (svils_init_gamma)
@@ -96,6 +107,36 @@ def init_virtual(shards):
     _sum_virtual(shards, _svils.KSH_ROWX)
     for s in shards:
         s.engine.ksweep_phase(_svils.KPHASE_INIT_EXPAND)
+
+
+def validation_row_virtual(shards):
+    """svils_validation_row for virtual ranks (the library's own is collective over a communicator): the partial dot
+    products of every slice (phase VDOT: k_vdot_ksh alone), summed, then the log terms of validation_likelihood
+    (src/linksampling.cc:966-1002) on the host in pair order -> the row's ten numbers.  After init_virtual or between
+    two sweeps.  The host part restates the library's own finish (ksh_validation_row_finish, svils_kshard.hip: the 1e-30
+    clamp, sums in pair order, the ten fields), which the native-rank drivers exercise; handles without held-out pairs have
+    no such row."""
+    if shards[0].buf[_svils.KSH_VDOT] is None:
+        raise ValueError("validation_row_virtual: the handles have no held-out pairs")
+    for s in shards:
+        s.engine.ksweep_phase(_svils.KPHASE_VDOT)
+    _sum_virtual(shards, _svils.KSH_VDOT)
+    s = shards[0]
+    pq = s.buf[_svils.KSH_VDOT].cpu().numpy()
+    y = s.validation[:, 2] != 0
+    terms = np.log(np.maximum(np.where(y, pq, 1.0 - pq), 1e-30))
+    sz = so = 0.0
+    for t, one in zip(terms.tolist(), y.tolist()):
+        if one:
+            so += t
+        else:
+            sz += t
+    ko = int(np.count_nonzero(y))
+    kz = y.size - ko
+    mean0, mean1 = sz / kz, so / ko
+    zp, op = 1 - float(s.ones_prob), float(s.ones_prob)
+    return np.array([s.engine.control().iter, (sz + so) / y.size, y.size, mean0, kz, mean1, ko, zp * mean0, op * mean1,
+                     zp * mean0 + op * mean1])
 
 
 def sweep_virtual(shards, nsweeps=1):

@@ -38,7 +38,8 @@ def seed_state(n, k, lam):
 
 def snapshot(ref, counts, test=False):
     return dict(gamma=ref.gamma, lam=ref.lam, conv=ref.converged, counts=list(counts), rows=ref.rows[1:],
-                member=ref.communities(), mphi=ref.mphi, iter=ref.iter, test_rows=ref.test_rows if test else None)
+                member=ref.communities(), mphi=ref.mphi, iter=ref.iter, annealing=ref.annealing,
+                test_rows=ref.test_rows if test else None)
 
 
 def test_pairs_of(ref_links):
@@ -49,16 +50,18 @@ def test_pairs_of(ref_links):
 test_pairs_of.__test__ = False
 
 
-def trajectory(n, pairs, k, nat, reg, test=False, **ref_kw):
+def trajectory(n, pairs, k, nat, reg, test=False, seed=None, **ref_kw):
     """the oracle's trajectory of one (graph, K): its inputs, the seeded state and a snapshot after each phase; the link
-    counts of every sweep are in the snapshots (dense, active-set, shortcut)"""
+    counts of every sweep are in the snapshots (dense, active-set, shortcut).  seed(n, k, lam) -> (gamma, lambda, flags):
+    the state phase (b) starts from (seed_state when None); "b1" is the snapshot after the first sweep from it, "row0" the
+    constructor's likelihood row."""
     net = O.Network(n=n, pairs=pairs)
     tp = None
     if test:
         tp = test_pairs_of(O.LinkSampling(net, k, use_validation_stop=False, **ref_kw).links)
     ref = O.LinkSampling(net, k, use_validation_stop=False, test_pairs=tp, **ref_kw)
     rec = dict(links=ref.links, validation=ref.validation_sorted, gamma0=ref.gamma, lam0=ref.lam, ones=net.ones,
-               ones_prob=ref.ones_prob, eta=ref.eta, test_sorted=ref.test_sorted if test else None)
+               ones_prob=ref.ones_prob, eta=ref.eta, test_sorted=ref.test_sorted if test else None, row0=ref.rows[0])
     counts = []
 
     def sweeps(m):
@@ -68,10 +71,11 @@ def trajectory(n, pairs, k, nat, reg, test=False, **ref_kw):
 
     sweeps(nat)
     rec["a"] = snapshot(ref, counts, test)
-    rec["seed"] = g, lam, conv = seed_state(n, k, ref.lam)
+    rec["seed"] = g, lam, conv = (seed or seed_state)(n, k, ref.lam)
     ref.set_gamma(g); ref.set_lambda(lam); ref.set_converged(conv); ref.refresh()
     ref.annealing = False
     sweeps(1)
+    rec["b1"] = snapshot(ref, counts, test)
     ref.iter = 1500
     sweeps(reg - 1)
     rec["b"] = snapshot(ref, counts, test)
@@ -123,13 +127,17 @@ def compare(tag, want, eng, tol, lo=0, hi=None, counts=True):
     return dict(gamma=err[0], lam=err[1], rows=err_rows, mphi=err_m)
 
 
-def two_phases(rec, engines, sweep, check, reg):
-    """phases (a) and (b) on `engines` (every handle of a run), `sweep(m)` running m sweeps on all of them"""
+def two_phases(rec, engines, sweep, check, reg, seed=None):
+    """phases (a) and (b) on `engines` (every handle of a run), `sweep(m)` running m sweeps on all of them;
+    seed(engine, gamma, lambda, flags) puts the seeded state on a handle (set_state when None: a handle of all columns)"""
     sweep(len(rec["a"]["counts"]))
     check("a", rec["a"])
     g, lam, conv = rec["seed"]
     for e in engines:
-        e.set_state(g, lam, conv)
+        if seed is None:
+            e.set_state(g, lam, conv)
+        else:
+            seed(e, g, lam, conv)
         e.set_control(annealing=0)
     sweep(1)
     for e in engines:
@@ -216,3 +224,40 @@ def compare_blocks(tag, want, shards, tol):
     for g, lam, conv in states[1:]:
         assert np.array_equal(g, states[0][0]) and np.array_equal(lam, states[0][1])
     return {key: max(e[key] for e in errs) for key in errs[0]}
+
+
+# ------------------------------------------------------------------------------------------------- column slices
+def compare_slices(tag, want, shards, tol, skip=0):
+    """K-sharded ranks (svinet_amd/ksharded.py: every rank the columns [k0, k1) of all rows) against a snapshot: gamma,
+    lambda and the communities put together from the slices, the stored mean indicators slice by slice; flags, _iter,
+    the annealing flag, sweeps_done, the per-sweep link counts and the likelihood rows are replicated -- all of them on
+    every rank.  skip: sweeps of the snapshot these handles did not run (a fresh handle set to the seeded state).
+    -> the relative errors, as compare(), and under "ranks" those of every rank's own columns (gamma, lambda, indicators)"""
+    states = [s.engine.state() for s in shards]
+    g = np.concatenate([st[0] for st in states], 1)
+    lam = np.concatenate([st[1] for st in states], 0)
+    err = (rel(g, want["gamma"]), rel(lam, want["lam"]))
+    assert err[0] < tol["state"] and err[1] < tol["state"], (tag, err)
+    nsw = len(want["counts"]) - skip
+    wr = want["rows"][skip:]
+    err_rows = err_m = 0.0
+    ranks = []
+    for s, st in zip(shards, states):
+        who = tag + ("rank%d" % s.rank,)
+        assert np.array_equal(st[2], want["conv"]), who
+        c = s.engine.control()
+        assert (c.iter, bool(c.annealing), c.sweeps_done) == (want["iter"], want["annealing"], nsw), who
+        stats = s.engine.sweep_stats(0, nsw)
+        assert [tuple(int(x) for x in r) for r in stats] == want["counts"][skip:], who
+        rows = s.engine.rows()
+        assert np.array_equal(rows[:, 0], wr[:, 0]), who
+        np.testing.assert_allclose(rows[:, 1:], wr[:, 1:], rtol=tol["rows_rtol"], atol=tol["rows_atol"], err_msg=str(who))
+        mphi, wm = s.engine.aux(2), want["mphi"][:, s.k0:s.k1]
+        np.testing.assert_allclose(mphi, wm, rtol=tol["mphi_rtol"], atol=tol["mphi_atol"], err_msg=str(who))
+        err_rows = max(err_rows, float(np.max(np.abs(rows[:, 1:] - wr[:, 1:]) / np.maximum(np.abs(wr[:, 1:]), 1e-300))))
+        ranks.append((rel(st[0], want["gamma"][:, s.k0:s.k1]), rel(st[1], want["lam"][s.k0:s.k1]),
+                      float(np.max(np.abs(mphi - wm) / np.maximum(np.abs(wm), 1e-9)))))
+        err_m = max(err_m, ranks[-1][2])
+    member = np.concatenate([s.engine.communities() for s in shards], 1)
+    assert np.array_equal(member, want["member"]), tag
+    return dict(gamma=err[0], lam=err[1], rows=err_rows, mphi=err_m, ranks=ranks)
