@@ -42,6 +42,7 @@ extern "C" {
                                     (additive, same version) svils_link_prob / svils_predict_links: link prediction from the state;
                                     (additive, same version) svils_findk_*: -findk, the estimate of the number of communities;
                                     (additive, same version) svils_batch_*: -batch-gpu, all-pairs batch inference;
+                                    (additive, same version) svils_batch_step_node / svils_batch_step_pairs: -rnode / -rpair, sampled-pair steps;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
                                     resource-allocation scores of pairs, the model-free baselines of svils_rank_links */
@@ -668,11 +669,41 @@ int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t
  * pair, pairs whose normaliser underflowed (this one since the last svils_batch_set_state); any pointer may be null */
 int svils_batch_get_stats(svils_batch *h, uint64_t *pairs_done, uint64_t *rounds_total, uint32_t *rounds_max,
                           uint64_t *underflow_pairs);
-/* device milliseconds of the last sweep: Elogpi / Elogbeta, the pair pass, the reductions (hipEvent brackets; -1: none yet) */
+/* device milliseconds of the last sweep: Elogpi / Elogbeta, the pair pass, the reductions (hipEvent brackets; -1: none yet).
+ * After a call of svils_batch_step_node / svils_batch_step_pairs: ms[0] brackets all steps of that call, ms[1] = ms[2] = -1 */
 int svils_batch_get_timing(svils_batch *h, double ms[3]);
 /* the pair kernel's instantiation for k: a group of W lanes per pair, V values per lane, W * V >= k.  No device needed.
  * SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_BATCH_MAX_K */
 int svils_batch_variant(uint32_t k, uint32_t *w, uint32_t *v);
+
+/* ---- -rnode / -rpair: sampled-pair steps on the svils_batch handle (an ADDITION of ABI 8) -------------------------------
+ * The reference's MMSBInfer::infer (src/mmsbinfer.cc:459-740): the Robbins-Monro version of the model batch_infer fits.
+ * The caller draws the mini-batches (get_subsample, :1912-1945) and the step sizes; one step (:513-642, process()
+ * :1092-1190) is
+ *   Elogpi / Elogbeta   those of the current gamma and lambda
+ *   pair pass           the fixed point of svils_batch_sweep for every pair of the mini-batch outside the skip set, y from
+ *                       the bit matrix; gammat[p] += phi1, gammat[q] += phi2, lambdat[k][y ? 0 : 1] += phi1[k] phi2[k]
+ *   gamma               for EVERY node i: gamma_i = (1 - rho_gamma) gamma_i + rho_gamma (alpha + scale gammat_i) (:578-600);
+ *                       a node no pair touched moves towards alpha
+ *   lambda              rho_lambda >= 0: lambda = (1 - rho_lambda) lambda + rho_lambda (eta + scale lambdat) (:613-637);
+ *                       rho_lambda < 0: lambda is left bit for bit (the reference's delayed learning, :613)
+ * nsteps steps are enqueued on the handle's stream in order and nothing waits for them; the getters do.  No
+ * floating-point atomics: every sum has one owner and a fixed order, so a step is bitwise reproducible and the result does
+ * not depend on how a run of steps is cut into calls.  Steps and sweeps may be mixed on one handle.
+ * svils_batch_get_stats then covers all steps of the last call.  SVILS_ERR_ARG: a null array, rho_gamma outside (0, 1],
+ * rho_lambda > 1, a scale that is not a positive number, no graph or no state.
+ *
+ * svils_batch_step_node: step s takes every pair (nodes[s], j), j != nodes[s], outside the skip set
+ * (get_randomnode_edges, :1867-1876); the caller passes scale = n / 2.  Three launches per step. */
+int svils_batch_step_node(svils_batch *h, uint32_t nsteps, const uint32_t *nodes, double scale, const double *rho_gamma,
+                          const double *rho_lambda);
+/* svils_batch_step_pairs: step s takes pairs[off[s] .. off[s + 1]) as given ([.][2], p < q < n); a pair listed twice
+ * counts twice.  scale[s] is the reference's scale / mbsize (:566-568, :587, :631).  A listed pair of the skip set, a
+ * self pair, p > q, a node >= n: SVILS_ERR_ARG, checked before anything is enqueued (the state is untouched).  Three
+ * launches per step, two while lambda is left alone.  The lists travel through a pinned staging area: a call waits for
+ * the previous call's copy (not for its steps) to have left it */
+int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off, const uint32_t *pairs, const double *scale,
+                           const double *rho_gamma, const double *rho_lambda);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * Every tunable of the library is a row of ONE table: key, the SVILS_* environment variable that sets its default, the

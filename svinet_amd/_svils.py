@@ -42,6 +42,7 @@ EXPORTS = (
     "svils_lc_get_timing",
     "svils_batch_create", "svils_batch_destroy", "svils_batch_set_graph", "svils_batch_set_state", "svils_batch_get_state",
     "svils_batch_sweep", "svils_batch_pair_loglik", "svils_batch_get_stats", "svils_batch_get_timing", "svils_batch_variant",
+    "svils_batch_step_node", "svils_batch_step_pairs",
 )
 BATCH_MAX_K, BATCH_MAX_N = 256, 32768   # SVILS_BATCH_MAX_K, SVILS_BATCH_MAX_N
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
@@ -197,6 +198,8 @@ def load():
     L.svils_batch_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.svils_batch_get_timing.argtypes = [vp, vp]
     L.svils_batch_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.svils_batch_step_node.argtypes = [vp, C.c_uint32, vp, C.c_double, vp, vp]
+    L.svils_batch_step_pairs.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):
@@ -655,6 +658,27 @@ class Batch:
     def sweep(self, nsweeps=1):
         _chk(load().svils_batch_sweep(self._h, nsweeps))
 
+    def step_node(self, nodes, scale, rho_gamma, rho_lambda):
+        """svils_batch_step_node: one step per entry of `nodes`, enqueued; rho_lambda < 0 leaves lambda alone"""
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1)
+        rg = np.ascontiguousarray(rho_gamma, dtype=np.float64).reshape(-1)
+        rl = np.ascontiguousarray(rho_lambda, dtype=np.float64).reshape(-1)
+        assert rg.shape == rl.shape == nodes.shape
+        _chk(load().svils_batch_step_node(self._h, nodes.shape[0], nodes.ctypes.data, scale, rg.ctypes.data, rl.ctypes.data))
+
+    def step_pairs(self, lists, scale, rho_gamma, rho_lambda):
+        """svils_batch_step_pairs: one step per pair list ([m][2], p < q) of `lists`, enqueued"""
+        lists = [np.ascontiguousarray(l, dtype=np.uint32).reshape(-1, 2) for l in lists]
+        off = np.zeros(len(lists) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([l.shape[0] for l in lists])
+        pairs = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros((0, 2)), dtype=np.uint32)
+        sc = np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+        rg = np.ascontiguousarray(rho_gamma, dtype=np.float64).reshape(-1)
+        rl = np.ascontiguousarray(rho_lambda, dtype=np.float64).reshape(-1)
+        assert sc.shape == rg.shape == rl.shape == (len(lists),)
+        _chk(load().svils_batch_step_pairs(self._h, len(lists), off.ctypes.data, pairs.ctypes.data, sc.ctypes.data, rg.ctypes.data,
+                                           rl.ctypes.data))
+
     def pair_loglik(self, pairs, y):
         pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
         y = np.ascontiguousarray(y, dtype=np.uint8).reshape(-1)
@@ -664,13 +688,13 @@ class Batch:
         return out
 
     def stats(self):
-        """(pairs_done, rounds_total, rounds_max, underflow_pairs) of the last sweep"""
+        """(pairs_done, rounds_total, rounds_max, underflow_pairs) of the last sweep, or of all steps of the last step call"""
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64()
         _chk(load().svils_batch_get_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
 
     def timing(self):
-        """device ms of the last sweep: dir_exp, pair pass, reductions"""
+        """device ms of the last sweep: dir_exp, pair pass, reductions; after a step call: (all its steps, -1, -1)"""
         ms = np.zeros(3)
         _chk(load().svils_batch_get_timing(self._h, ms.ctypes.data))
         return ms

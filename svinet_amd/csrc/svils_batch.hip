@@ -18,6 +18,15 @@
 //
 // No floating-point atomics: every sum has one owner and a fixed order, so a sweep is bitwise reproducible.  The tiles of
 // a sweep go through the partial buffers in batches of at most BATCH_TILES.
+//
+// -rnode / -rpair: the sampled-pair steps of MMSBInfer::infer (src/mmsbinfer.cc:459-740) on the same handle (DESIGN.md
+// section 4g), one fixed chain of launches per step, queued without a host round trip:
+//
+//   k_batch_step_node<W,V>  node step: group j holds pair (a, j), blends gamma_j and writes Elogpi_j itself; phi_a and the
+//                           lambda terms leave as per-wavefront partials
+//   k_batch_step_phi<W,V>   pair step: group e holds the e-th listed pair; phi to the step's buffer, lambda partials
+//   k_batch_step_rows<W,V>  pair step: group i adds node i's phi vectors in list order, blends gamma_i, writes Elogpi_i
+//   k_batch_step_tail       block k: the partials of community k in a fixed order; gamma_a[k] (node steps), lambda[k], Elogbeta[k]
 #include "svils_devutil.h"
 #include "svils_tool.h"
 
@@ -324,6 +333,297 @@ __global__ __launch_bounds__(256) void k_batch_pair_ll(uint64_t m, uint32_t K, d
   if (lane == 0) out[x] = log(s < 1e-30 ? 1e-30 : s);
 }
 
+// ---- sampled-pair steps (svils_batch_step_node / svils_batch_step_pairs) ----------------------
+// The fixed point of k_batch_pairs for the one pair a group of W lanes holds: the same constants, Jacobi order, odd-round
+// exit test and underflow rule.  Called by whole wavefronts; a group with valid = false runs along with zero vectors.
+template <int W, int V>
+__device__ __forceinline__ void pair_fixed_point(const double (&elp)[V], const double (&elq)[V], const double (&ef)[V], double le,
+                                                 const bool (&kval)[V], uint32_t K, bool valid, double (&p1)[V], double (&p2)[V],
+                                                 uint32_t &rounds, bool &under) {
+  const double invK = 1.0 / (double)K, dK = (double)K;
+  double o1[V], o2[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    p1[v] = p2[v] = kval[v] ? invK : 0.0;
+    o1[v] = o2[v] = 0.0;
+  }
+  bool live = valid;
+  rounds = 0;
+  under = false;
+  for (uint32_t i = 0; i < MAX_ROUNDS; ++i) {
+    if (!__ballot(live)) break;
+    if ((i & 1) == 0) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        o1[v] = live ? p1[v] : o1[v];
+        o2[v] = live ? p2[v] : o2[v];
+      }
+    }
+    double e[2 * V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      e[v] = (elp[v] + ef[v] * p2[v]) + (1.0 - p2[v]) * le;
+      e[V + v] = (elq[v] + ef[v] * p1[v]) + (1.0 - p1[v]) * le;
+    }
+    exp_neg_n<2 * V>(e);
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      e[v] = kval[v] ? e[v] : 0.0;
+      e[V + v] = kval[v] ? e[V + v] : 0.0;
+      s1 += e[v];
+      s2 += e[V + v];
+    }
+    s1 = group_sum<W>(s1);
+    s2 = group_sum<W>(s2);
+    const bool ok = s1 > 0.0 && s2 > 0.0;
+    if (live && !ok) {
+      under = true;
+      live = false;
+    }
+    const double r1 = fast_rcp(ok ? s1 : 1.0), r2 = fast_rcp(ok ? s2 : 1.0);
+    double m1 = 0.0, m2 = 0.0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      e[v] *= r1;
+      e[V + v] *= r2;
+      m1 += fabs(e[v] - o1[v]);
+      m2 += fabs(e[V + v] - o2[v]);
+      p1[v] = live ? e[v] : p1[v];
+      p2[v] = live ? e[V + v] : p2[v];
+    }
+    rounds += live;
+    if (i & 1) {
+      m1 = group_sum<W>(m1);
+      m2 = group_sum<W>(m2);
+      if (m1 / dK < MEAN_CHANGE_THRESH && m2 / dK < MEAN_CHANGE_THRESH) live = false;
+    }
+  }
+}
+
+// the counters of a wavefront's groups (lane lw == 0 of a group carries its pair's) into the handle's five
+__device__ inline void count_pairs(unsigned long long *ctr, uint32_t lane, uint32_t npairs, uint32_t rtot, uint32_t rmax, uint32_t under) {
+  npairs = wave_sum_u32(npairs);
+  rtot = wave_sum_u32(rtot);
+  under = wave_sum_u32(under);
+  rmax = wave_max_u32(rmax);
+  if (lane == 0) {
+    if (npairs) atomicAdd(&ctr[0], (unsigned long long)npairs);
+    if (rtot) atomicAdd(&ctr[1], (unsigned long long)rtot);
+    if (rmax) atomicMax(&ctr[2], (unsigned long long)rmax);
+    if (under) { atomicAdd(&ctr[3], (unsigned long long)under); atomicAdd(&ctr[4], (unsigned long long)under); }
+  }
+}
+
+// a group's new row: gamma = (1 - rho) gamma + rho (alpha + scale t), then Elogpi of it.  Only groups with row < n store.
+template <int W, int V>
+__device__ __forceinline__ void blend_row(bool row_ok, size_t row, uint32_t K, uint32_t lw, const bool (&kval)[V], const double (&t)[V],
+                                          double rho, double alpha, double scale, double *__restrict__ gamma, double *__restrict__ elogpi,
+                                          const double2 *logtab) {
+  double gn[V], s = 0.0;
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const bool ok = row_ok && kval[v];
+    const double g = ok ? gamma[row * K + v * W + lw] : 0.0;
+    gn[v] = ok ? (1.0 - rho) * g + rho * (alpha + scale * t[v]) : 0.0;
+    s += gn[v];
+  }
+  s = group_sum<W>(s);
+  const double ps = digamma(row_ok ? s : 1.0, logtab);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const bool ok = row_ok && kval[v];
+    const double el = digamma(ok ? gn[v] : 1.0, logtab) - ps;
+    if (ok) {
+      gamma[row * K + v * W + lw] = gn[v];
+      elogpi[row * K + v * W + lw] = el;
+    }
+  }
+}
+
+struct StepArgs {
+  uint32_t n, K, nw;
+  const uint32_t *adj, *skip;
+  double *gamma, *elogpi;           // [n][K]: the kernel that owns a row writes both
+  const double *elogbeta;
+  double logeps, alpha, scale, rho;
+  double *part_a, *pl;              // per-wavefront partials: [wavefront][K] (node steps), [wavefront][K][2]
+  unsigned long long *ctr;
+  const double *gtab;
+  // node steps
+  uint32_t a;
+  // pair steps
+  uint32_t m;                       // pairs of the step
+  const uint32_t *pairs;            // [m][2]
+  const uint32_t *noff, *ent;       // [n + 1] offsets into ent; ent[x] = 2 e + side, every node's in list order
+  double *phi;                      // [m][2][K]
+};
+
+// Node step, first launch: group j holds the pair (a, j).  Row a and Elogpi_a are only read; row j belongs to its group,
+// which blends it and writes Elogpi_j (a skipped pair: with phi = 0).  phi_a and the lambda terms leave per wavefront.
+template <int W, int V>
+__global__ __launch_bounds__(256) void k_batch_step_node(StepArgs x) {
+  constexpr int G = 64 / W;
+  __shared__ double2 logtab[128];
+  load_logtab(logtab, x.gtab);
+  __syncthreads();
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / W, lw = lane % W;
+  const uint32_t K = x.K, n = x.n, a = x.a;
+  const uint32_t wv = blockIdx.x * 4 + wave, j = wv * G + g;
+  const bool row_ok = j < n && j != a;
+  bool valid = row_ok, y = false;
+  if (row_ok) {
+    const uint32_t p = min(a, j), q = max(a, j);
+    const size_t wd = (size_t)p * x.nw + (q >> 5);
+    const uint32_t bit = 1u << (q & 31);
+    valid = (x.skip[wd] & bit) == 0;
+    y = (x.adj[wd] & bit) != 0;
+  }
+  bool kval[V];
+  double ela[V], elj[V], ef[V], pa[V], pj[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const uint32_t k = v * W + lw;
+    kval[v] = k < K;
+    ela[v] = kval[v] ? x.elogpi[(size_t)a * K + k] : 0.0;
+    elj[v] = kval[v] && row_ok ? x.elogpi[(size_t)j * K + k] : 0.0;
+    ef[v] = kval[v] ? x.elogbeta[2 * k + (y ? 0 : 1)] : 0.0;
+  }
+  uint32_t rounds;
+  bool under;
+  pair_fixed_point<W, V>(ela, elj, ef, y ? x.logeps : 0.0, kval, K, valid, pa, pj, rounds, under);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    pa[v] = valid ? pa[v] : 0.0;
+    pj[v] = valid ? pj[v] : 0.0;
+  }
+  blend_row<W, V>(row_ok, j, K, lw, kval, pj, x.rho, x.alpha, x.scale, x.gamma, x.elogpi, logtab);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const double pp = pa[v] * pj[v];
+    const double sa = cross_group_sum<W>(pa[v]);
+    const double t0 = cross_group_sum<W>(y ? pp : 0.0), t1 = cross_group_sum<W>(y ? 0.0 : pp);
+    if (g == 0 && kval[v]) {
+      const uint32_t k = v * W + lw;
+      x.part_a[(size_t)wv * K + k] = sa;
+      x.pl[((size_t)wv * K + k) * 2] = t0;
+      x.pl[((size_t)wv * K + k) * 2 + 1] = t1;
+    }
+  }
+  const bool cnt = valid && lw == 0;
+  count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt && under);
+}
+
+// Pair step, first launch: group e holds the e-th listed pair; phi goes to the step's buffer, the lambda terms leave per wavefront
+template <int W, int V>
+__global__ __launch_bounds__(256) void k_batch_step_phi(StepArgs x) {
+  constexpr int G = 64 / W;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / W, lw = lane % W;
+  const uint32_t K = x.K, wv = blockIdx.x * 4 + wave, e = wv * G + g;
+  const bool valid = e < x.m;
+  uint32_t p = 0, q = 0;
+  bool y = false;
+  if (valid) {
+    p = x.pairs[2 * (size_t)e];
+    q = x.pairs[2 * (size_t)e + 1];
+    y = (x.adj[(size_t)p * x.nw + (q >> 5)] & (1u << (q & 31))) != 0;
+  }
+  bool kval[V];
+  double elp[V], elq[V], ef[V], p1[V], p2[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const uint32_t k = v * W + lw;
+    kval[v] = k < K;
+    elp[v] = kval[v] && valid ? x.elogpi[(size_t)p * K + k] : 0.0;
+    elq[v] = kval[v] && valid ? x.elogpi[(size_t)q * K + k] : 0.0;
+    ef[v] = kval[v] ? x.elogbeta[2 * k + (y ? 0 : 1)] : 0.0;
+  }
+  uint32_t rounds;
+  bool under;
+  pair_fixed_point<W, V>(elp, elq, ef, y ? x.logeps : 0.0, kval, K, valid, p1, p2, rounds, under);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const uint32_t k = v * W + lw;
+    const double q1 = valid ? p1[v] : 0.0, q2 = valid ? p2[v] : 0.0;
+    if (valid && kval[v]) {
+      x.phi[(2 * (size_t)e) * K + k] = q1;
+      x.phi[(2 * (size_t)e + 1) * K + k] = q2;
+    }
+    const double pp = q1 * q2;
+    const double t0 = cross_group_sum<W>(y ? pp : 0.0), t1 = cross_group_sum<W>(y ? 0.0 : pp);
+    if (g == 0 && kval[v]) {
+      x.pl[((size_t)wv * K + k) * 2] = t0;
+      x.pl[((size_t)wv * K + k) * 2 + 1] = t1;
+    }
+  }
+  const bool cnt = valid && lw == 0;
+  count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt && under);
+}
+
+// Pair step, second launch: group i owns node i -- its phi vectors of the step added in list order, then the blend and Elogpi_i
+template <int W, int V>
+__global__ __launch_bounds__(256) void k_batch_step_rows(StepArgs x) {
+  constexpr int G = 64 / W;
+  __shared__ double2 logtab[128];
+  load_logtab(logtab, x.gtab);
+  __syncthreads();
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / W, lw = lane % W;
+  const uint32_t K = x.K, i = (blockIdx.x * 4 + wave) * G + g;
+  const bool row_ok = i < x.n;
+  bool kval[V];
+  double t[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    kval[v] = (uint32_t)(v * W) + lw < K;
+    t[v] = 0.0;
+  }
+  if (row_ok)
+    for (uint32_t o = x.noff[i]; o < x.noff[i + 1]; ++o) {
+      const double *ph = x.phi + (size_t)x.ent[o] * K;
+#pragma unroll
+      for (int v = 0; v < V; ++v) t[v] += kval[v] ? ph[v * W + lw] : 0.0;
+    }
+  blend_row<W, V>(row_ok, i, K, lw, kval, t, x.rho, x.alpha, x.scale, x.gamma, x.elogpi, logtab);
+}
+
+// Last launch of a step, block k: the nwv per-wavefront partials of community k -- every thread its entries in ascending
+// order, then a fixed tree over the threads.  Node steps (part_a non-null) blend gamma[a][k] here; rho_l >= 0 blends
+// lambda[k] and renews Elogbeta[k], rho_l < 0 leaves both alone.
+__global__ __launch_bounds__(256) void k_batch_step_tail(uint32_t K, uint32_t nwv, const double *__restrict__ part_a,
+                                                         const double *__restrict__ pl, double *__restrict__ gamma_a, double alpha,
+                                                         double eta0, double eta1, double scale, double rho_g, double rho_l,
+                                                         double *__restrict__ lam, double *__restrict__ elogbeta,
+                                                         const double *__restrict__ gtab) {
+  __shared__ double red[3][256];
+  const uint32_t k = blockIdx.x, t = threadIdx.x;
+  double sa = 0.0, s0 = 0.0, s1 = 0.0;
+  for (uint32_t w = t; w < nwv; w += 256) {
+    if (part_a) sa += part_a[(size_t)w * K + k];
+    s0 += pl[((size_t)w * K + k) * 2];
+    s1 += pl[((size_t)w * K + k) * 2 + 1];
+  }
+  red[0][t] = sa;
+  red[1][t] = s0;
+  red[2][t] = s1;
+  __syncthreads();
+  for (uint32_t o = 128; o > 0; o >>= 1) {
+    if (t < o) { red[0][t] += red[0][t + o]; red[1][t] += red[1][t + o]; red[2][t] += red[2][t + o]; }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  if (part_a) gamma_a[k] = (1.0 - rho_g) * gamma_a[k] + rho_g * (alpha + scale * red[0][0]);
+  if (rho_l >= 0.0) {
+    const double2 *tab = reinterpret_cast<const double2 *>(gtab);
+    const double l0 = (1.0 - rho_l) * lam[2 * k] + rho_l * (eta0 + scale * red[1][0]);
+    const double l1 = (1.0 - rho_l) * lam[2 * k + 1] + rho_l * (eta1 + scale * red[2][0]);
+    lam[2 * k] = l0;
+    lam[2 * k + 1] = l1;
+    const double ps = digamma(l0 + l1, tab);
+    elogbeta[2 * k] = digamma(l0, tab) - ps;
+    elogbeta[2 * k + 1] = digamma(l1, tab) - ps;
+  }
+}
+
 }  // namespace
 
 // events: ev[0] sweep begin, ev[1] Elogpi / Elogbeta done, then per launch of the pair kernel ev[2 + 2 b] (pairs done) and
@@ -348,6 +648,17 @@ struct svils_batch : ToolHandle {
   std::vector<uint32_t> h_tiles;
   bool have_graph = false, have_state = false, timed = false;
   uint32_t nlaunch = 0;                                           // launches of the last sweep
+  // sampled-pair steps.  HANDLE scope, grown on demand: the per-wavefront partials, one step's phi, a call's lists
+  bool timed_steps = false;                                       // the last timed call was a step call: ev[0] .. ev[1] bracket it
+  bool elog_fresh = false;                                        // Elogpi / Elogbeta are those of gamma / lambda
+  std::vector<uint32_t> h_skip;                                   // the skip bits, to refuse a listed skipped pair
+  double *st_part = nullptr, *st_pl = nullptr, *st_phi = nullptr;
+  uint32_t *st_lists = nullptr;                                   // a call's pairs [total][2], entries [2 total], offsets [nsteps][n + 1]
+  size_t cap_part = 0, cap_pl = 0, cap_phi = 0, cap_lists = 0;
+  uint32_t *pin = nullptr;                                        // pinned staging of st_lists; ev_copy: its last copy has left it
+  size_t cap_pin = 0;
+  hipEvent_t ev_copy = nullptr;
+  bool copy_pending = false;
 };
 
 namespace {
@@ -412,7 +723,84 @@ int one_sweep(svils_batch *h) {
   std::swap(h->gamma, h->gnext);   // gamma = gamma_next (:883-886); later launches take the new pointers
   std::swap(h->lam, h->lnext);
   h->timed = true;
+  h->timed_steps = false;
+  h->elog_fresh = false;
   return 0;
+}
+
+// ---- sampled-pair steps: host side ----
+template <class T>
+int grow(svils_batch *h, T **p, size_t *cap, size_t need) {
+  if (need <= *cap) return 0;
+  HIPCHK(hipStreamSynchronize(h->st));   // the steps in flight still use the old buffer
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  if (int rc = h->dalloc(ToolHandle::HANDLE, p, need)) return rc;
+  *cap = need;
+  return 0;
+}
+
+#define STEP_DISPATCH(KERNEL, NBLOCKS, ARGS)                                                                                   \
+  switch (h->w) {                                                                                                              \
+    case 1: hipLaunchKernelGGL((KERNEL<1, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                  \
+    case 2: hipLaunchKernelGGL((KERNEL<2, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                  \
+    case 4: hipLaunchKernelGGL((KERNEL<4, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                  \
+    case 8: hipLaunchKernelGGL((KERNEL<8, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                  \
+    case 16: hipLaunchKernelGGL((KERNEL<16, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                \
+    case 32: hipLaunchKernelGGL((KERNEL<32, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                \
+    case 64: hipLaunchKernelGGL((KERNEL<64, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                \
+    default: return fail(SVILS_ERR_UNSUPPORTED, "%s: no step kernel for W = %u", name, h->w); /* a missing kernel is an error */ \
+  }
+
+// what both step entry points check of their handle and step sizes
+int check_steps(svils_batch *h, const char *name, uint32_t nsteps, const double *rho_gamma, const double *rho_lambda) {
+  if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "%s: set the graph and the state first", name);
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    if (!(rho_gamma[s] > 0.0 && rho_gamma[s] <= 1.0)) return fail(SVILS_ERR_ARG, "%s: rho_gamma[%u] is not in (0, 1]", name, s);
+    if (!(rho_lambda[s] <= 1.0)) return fail(SVILS_ERR_ARG, "%s: rho_lambda[%u] is not <= 1 (negative: lambda is left alone)", name, s);
+  }
+  return 0;
+}
+
+// Elogpi / Elogbeta of the current state if a sweep or set_state came in between; the counters of the call start at zero
+int begin_steps(svils_batch *h) {
+  if (!h->elog_fresh) {
+    hipLaunchKernelGGL(k_batch_dir_exp, dim3(blocks(h->n, 4)), dim3(256), 0, h->st, h->n, h->k, h->gamma, h->gtab, h->elogpi);
+    hipLaunchKernelGGL(k_batch_beta, dim3(blocks(h->k, 256)), dim3(256), 0, h->st, h->k, h->lam, h->gtab, h->elogbeta);
+    HIPCHK(hipGetLastError());
+    h->elog_fresh = true;
+  }
+  HIPCHK(hipMemsetAsync(h->ctr, 0, 4 * sizeof(unsigned long long), h->st));
+  HIPCHK(hipEventRecord(h->ev[0], h->st));
+  return 0;
+}
+
+int end_steps(svils_batch *h) {
+  HIPCHK(hipEventRecord(h->ev[1], h->st));
+  h->timed = h->timed_steps = true;
+  return 0;
+}
+
+StepArgs step_args(svils_batch *h, double scale, double rho) {
+  StepArgs x{};
+  x.n = h->n;
+  x.K = h->k;
+  x.nw = h->nw;
+  x.adj = h->adj;
+  x.skip = h->skip;
+  x.gamma = h->gamma;
+  x.elogpi = h->elogpi;
+  x.elogbeta = h->elogbeta;
+  x.logeps = std::log(h->epsilon);
+  x.alpha = h->alpha;
+  x.scale = scale;
+  x.rho = rho;
+  x.part_a = h->st_part;
+  x.pl = h->st_pl;
+  x.ctr = h->ctr;
+  x.gtab = h->gtab;
+  return x;
 }
 
 }  // namespace
@@ -475,6 +863,12 @@ int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double 
 }
 
 int svils_batch_destroy(svils_batch *h) {
+  if (h && h->st) {   // the steps' staging area and its event are not in a scope
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->st);
+    if (h->pin) (void)hipHostFree(h->pin);
+    if (h->ev_copy) (void)hipEventDestroy(h->ev_copy);
+  }
   delete h;   // ~ToolHandle: waits for the stream, frees both scopes
   return 0;
 }
@@ -536,6 +930,7 @@ int svils_batch_set_graph(svils_batch *h, const uint32_t *links, uint64_t nlinks
     return rc;
   }
   h->h_tiles.swap(tiles);
+  h->h_skip.swap(skp);
   h->ntiles = ntiles;
   h->nrb = nrb;
   h->batch = batch;
@@ -557,6 +952,7 @@ int svils_batch_set_state(svils_batch *h, const double *gamma, const double *lam
   HIPCHK(hipMemcpy(h->lam, lambda, 2 * (size_t)h->k * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemset(h->ctr, 0, 5 * sizeof(unsigned long long)));
   h->have_state = true;
+  h->elog_fresh = false;
   return 0;
 }
 
@@ -575,6 +971,123 @@ int svils_batch_sweep(svils_batch *h, uint32_t nsweeps) {
   for (uint32_t s = 0; s < nsweeps; ++s)
     if (int rc = one_sweep(h)) return rc;
   return 0;
+}
+
+int svils_batch_step_node(svils_batch *h, uint32_t nsteps, const uint32_t *nodes, double scale, const double *rho_gamma,
+                          const double *rho_lambda) {
+  const char *name = "svils_batch_step_node";
+  if (int rc = check(h, name)) return rc;
+  if (nsteps && (!nodes || !rho_gamma || !rho_lambda)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
+  if (!(scale > 0.0) || !std::isfinite(scale)) return fail(SVILS_ERR_ARG, "%s: scale is not a positive number", name);
+  if (int rc = check_steps(h, name, nsteps, rho_gamma, rho_lambda)) return rc;
+  for (uint32_t s = 0; s < nsteps; ++s)
+    if (nodes[s] >= h->n) return fail(SVILS_ERR_ARG, "%s: nodes[%u] = %u is not < n = %u", name, s, nodes[s], h->n);
+  if (!nsteps) return 0;
+  const uint32_t n = h->n, K = h->k, G = 64 / h->w, nb = blocks(n, 4 * G), nwv = 4 * nb;
+  if (int rc = grow(h, &h->st_part, &h->cap_part, (size_t)nwv * K)) return rc;
+  if (int rc = grow(h, &h->st_pl, &h->cap_pl, (size_t)nwv * K * 2)) return rc;
+  if (int rc = begin_steps(h)) return rc;
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    StepArgs x = step_args(h, scale, rho_gamma[s]);
+    x.a = nodes[s];
+    STEP_DISPATCH(k_batch_step_node, nb, x)
+    double *ga = h->gamma + (size_t)x.a * K;
+    hipLaunchKernelGGL(k_batch_step_tail, dim3(K), dim3(256), 0, h->st, K, nwv, h->st_part, h->st_pl, ga, h->alpha, h->eta0, h->eta1,
+                       scale, rho_gamma[s], rho_lambda[s], h->lam, h->elogbeta, h->gtab);
+    hipLaunchKernelGGL(k_batch_dir_exp, dim3(1), dim3(256), 0, h->st, 1u, K, ga, h->gtab, h->elogpi + (size_t)x.a * K);
+    HIPCHK(hipGetLastError());
+  }
+  return end_steps(h);
+}
+
+int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off, const uint32_t *pairs, const double *scale,
+                           const double *rho_gamma, const double *rho_lambda) {
+  const char *name = "svils_batch_step_pairs";
+  if (int rc = check(h, name)) return rc;
+  if (nsteps && (!off || !scale || !rho_gamma || !rho_lambda)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
+  if (!nsteps) return 0;
+  if (int rc = check_steps(h, name, nsteps, rho_gamma, rho_lambda)) return rc;
+  if (off[0] != 0) return fail(SVILS_ERR_ARG, "%s: off[0] is not 0", name);
+  uint64_t most = 0;
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    if (off[s + 1] < off[s]) return fail(SVILS_ERR_ARG, "%s: off[%u] decreases", name, s + 1);
+    if (!(scale[s] > 0.0) || !std::isfinite(scale[s])) return fail(SVILS_ERR_ARG, "%s: scale[%u] is not a positive number", name, s);
+    most = std::max(most, off[s + 1] - off[s]);
+  }
+  const uint64_t total = off[nsteps];
+  if (total && !pairs) return fail(SVILS_ERR_ARG, "%s: null argument", name);
+  if (total >= ((uint64_t)1 << 30)) return fail(SVILS_ERR_UNSUPPORTED, "%s: more than 2^30 pairs in one call", name);
+  const uint32_t n = h->n, K = h->k, G = 64 / h->w;
+  // checked before anything is enqueued
+  for (uint32_t s = 0; s < nsteps; ++s)
+    for (uint64_t e = off[s]; e < off[s + 1]; ++e) {
+      const uint32_t p = pairs[2 * e], q = pairs[2 * e + 1];
+      if (p >= q || q >= n)
+        return fail(SVILS_ERR_ARG, "%s: pair %llu of step %u (%u, %u) is not a pair p < q < n = %u", name, (unsigned long long)(e - off[s]), s, p, q, n);
+      if (h->h_skip[(size_t)p * h->nw + (q >> 5)] & (1u << (q & 31)))
+        return fail(SVILS_ERR_ARG, "%s: pair %llu of step %u (%u, %u) is in the skip set", name, (unsigned long long)(e - off[s]), s, p, q);
+    }
+  // the call's lists go through pinned memory in one copy, so that the call need not wait for it; the staging area is
+  // free again once the previous call's copy has left it
+  const size_t nlists = 4 * (size_t)total + (size_t)nsteps * (n + 1);
+  if (h->copy_pending) {
+    HIPCHK(hipEventSynchronize(h->ev_copy));
+    h->copy_pending = false;
+  }
+  if (!h->ev_copy) HIPCHK(hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
+  if (nlists > h->cap_pin) {
+    if (h->pin) (void)hipHostFree(h->pin);
+    h->pin = nullptr;
+    h->cap_pin = 0;
+    HIPCHK(hipHostMalloc((void **)&h->pin, nlists * sizeof(uint32_t), hipHostMallocDefault));
+    h->cap_pin = nlists;
+  }
+  uint32_t *const pin_pairs = h->pin, *const pin_ent = h->pin + 2 * total, *const pin_noff = h->pin + 4 * total;
+  if (total) std::memcpy(pin_pairs, pairs, 2 * total * sizeof(uint32_t));
+  std::memset(pin_noff, 0, (size_t)nsteps * (n + 1) * sizeof(uint32_t));
+  // every node's (pair, side) entries of a step in list order: a counting sort per step
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    uint32_t *no = pin_noff + (size_t)s * (n + 1);
+    const uint32_t *pr = pairs + 2 * off[s];
+    const uint32_t m = (uint32_t)(off[s + 1] - off[s]);
+    for (uint32_t e = 0; e < m; ++e) {
+      ++no[pr[2 * e] + 1];
+      ++no[pr[2 * e + 1] + 1];
+    }
+    for (uint32_t i = 0; i < n; ++i) no[i + 1] += no[i];
+    std::vector<uint32_t> at(no, no + n);
+    uint32_t *en = pin_ent + 2 * off[s];
+    for (uint32_t e = 0; e < m; ++e) {
+      en[at[pr[2 * e]]++] = 2 * e;
+      en[at[pr[2 * e + 1]]++] = 2 * e + 1;
+    }
+  }
+  const uint32_t nwv_most = 4 * blocks(std::max<uint64_t>(most, 1), 4 * G);
+  if (int rc = grow(h, &h->st_pl, &h->cap_pl, (size_t)nwv_most * K * 2)) return rc;
+  if (int rc = grow(h, &h->st_phi, &h->cap_phi, 2 * (size_t)most * K)) return rc;
+  if (int rc = grow(h, &h->st_lists, &h->cap_lists, nlists)) return rc;
+  // ordered behind the steps of earlier calls, which read the device copy, by the stream
+  HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nlists * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipEventRecord(h->ev_copy, h->st));
+  h->copy_pending = true;
+  if (int rc = begin_steps(h)) return rc;
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    const uint32_t m = (uint32_t)(off[s + 1] - off[s]);
+    StepArgs x = step_args(h, scale[s], rho_gamma[s]);
+    x.m = m;
+    x.pairs = h->st_lists + 2 * off[s];
+    x.ent = h->st_lists + 2 * total + 2 * off[s];
+    x.noff = h->st_lists + 4 * total + (size_t)s * (n + 1);
+    x.phi = h->st_phi;
+    const uint32_t nb = blocks(m, 4 * G);
+    if (m) { STEP_DISPATCH(k_batch_step_phi, nb, x) }
+    STEP_DISPATCH(k_batch_step_rows, blocks(n, 4 * G), x)
+    if (rho_lambda[s] >= 0.0)
+      hipLaunchKernelGGL(k_batch_step_tail, dim3(K), dim3(256), 0, h->st, K, 4 * nb, (const double *)nullptr, h->st_pl, (double *)nullptr,
+                         h->alpha, h->eta0, h->eta1, scale[s], rho_gamma[s], rho_lambda[s], h->lam, h->elogbeta, h->gtab);
+    HIPCHK(hipGetLastError());
+  }
+  return end_steps(h);
 }
 
 int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t *y, uint64_t m, double *out) {
@@ -628,8 +1141,8 @@ int svils_batch_get_timing(svils_batch *h, double ms[3]) {
   if (!ms) return fail(SVILS_ERR_ARG, "svils_batch_get_timing: null argument");
   HIPCHK(hipStreamSynchronize(h->st));
   ms[0] = h->elapsed_ms(0, 1, h->timed);
-  ms[1] = ms[2] = h->timed ? 0.0 : -1.0;
-  for (uint32_t b = 0; h->timed && b < h->nlaunch; ++b) {
+  ms[1] = ms[2] = h->timed && !h->timed_steps ? 0.0 : -1.0;
+  for (uint32_t b = 0; h->timed && !h->timed_steps && b < h->nlaunch; ++b) {
     ms[1] += h->elapsed_ms(1 + 2 * b, 2 + 2 * b, true);   // (the first launch's bracket includes the fill)
     ms[2] += h->elapsed_ms(2 + 2 * b, 3 + 2 * b, true);
   }

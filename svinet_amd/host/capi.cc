@@ -40,6 +40,9 @@ typedef struct {
   int32_t defer_gamma;     // 1: no host init_gamma2 (the caller draws on the device: svih_init_links / svih_init_streams -> svils_init_gamma)
   int32_t batch_device;    // svih_batch_from_file: 1 = the device backend of the -batch engine (-batch-gpu), on `device`
   int32_t device;
+  int32_t sampled;         // svih_batch_from_file: 0 = -batch; 1 -rnode, 2 -rpair, 3 -rpair -stratified (batch_device: on the device)
+  int32_t nodelay;         // ... with -nodelay
+  double tau0, kappa, nodetau0, nodekappa;   // their step sizes (svih_options_default: 1024, 0.9, 1024, 0.5)
 } svih_options;
 
 struct svih_setup {
@@ -81,6 +84,8 @@ void svih_options_default(svih_options *o, uint32_t n, uint32_t k) {
   o->n = n; o->k = k; o->seed = 0; o->heldout_ratio = 0.01; o->link_thresh = 0.5;
   o->lt_min_deg = 0; o->eta_type = 0; o->accuracy = 0; o->defer_gamma = 0;
   o->batch_device = 0; o->device = 0;
+  const Env::Args d;
+  o->sampled = 0; o->nodelay = 0; o->tau0 = d.tau0; o->kappa = d.kappa; o->nodetau0 = d.nodetau0; o->nodekappa = d.nodekappa;
 }
 svih_setup *svih_setup_from_file(const char *path, const svih_options *o) { return make_setup(o, path, nullptr, 0); }
 svih_setup *svih_setup_from_pairs(const int32_t *pairs, uint64_t nlines, const svih_options *o) {
@@ -162,8 +167,18 @@ svih_batch *svih_batch_from_file(const char *path, const svih_options *o) {
   Env::Args a;
   a.n = o->n;
   a.k = o->k;
-  a.batch = true;
-  a.batch_gpu = o->batch_device != 0;
+  if (o->sampled) {
+    a.rnode = o->sampled == 1;
+    a.rpair = o->sampled >= 2;
+    a.stratified = o->sampled == 3;
+    a.nodelay = o->nodelay != 0;
+    a.host_loops = o->batch_device == 0;
+    a.rfreq = 100;
+    a.tau0 = o->tau0; a.kappa = o->kappa; a.nodetau0 = o->nodetau0; a.nodekappa = o->nodekappa;
+  } else {
+    a.batch = true;
+    a.batch_gpu = o->batch_device != 0;
+  }
   a.device = o->device;
   a.rand_seed = o->seed;
   a.hol_ratio = o->heldout_ratio;
@@ -178,8 +193,23 @@ svih_batch *svih_batch_from_file(const char *path, const svih_options *o) {
     delete b;
     return nullptr;
   }
+  b->eng->keep_schedule(o->sampled != 0);
   return b;
 }
+// the sampled-pair engines: nsteps iterations (drawn, then run); the schedule of every executed iteration
+int svih_batch_step(svih_batch *b, uint32_t nsteps) { return svils_rc([&] { b->eng->step(nsteps); return 0; }); }
+uint64_t svih_batch_nschedule(const svih_batch *b) { return b->eng->schedule().size(); }
+// out[5]: node, family, scale, rho_gamma, rho_lambda; returns the number of pairs of the iteration's mini-batch, and with
+// pairs non-null copies them ([m][2]; -rnode: the pairs of the start node outside the held-out sets)
+uint64_t svih_batch_schedule(const svih_batch *b, uint64_t i, double *out, uint32_t *pairs) {
+  const MMSBBatch::Drawn &d = b->eng->schedule()[i];
+  if (out) { out[0] = d.node; out[1] = d.family; out[2] = d.scale; out[3] = d.rho_gamma; out[4] = d.rho_lambda; }
+  const std::vector<uint32_t> np = b->env->randomnode ? b->eng->node_pairs(d.node) : std::vector<uint32_t>();
+  const std::vector<uint32_t> &pq = b->env->randomnode ? np : d.pairs;
+  if (pairs && !pq.empty()) memcpy(pairs, pq.data(), pq.size() * sizeof(uint32_t));
+  return pq.size() / 2;
+}
+double svih_batch_total_pairs(const svih_batch *b) { return (double)b->env->total_pairs; }
 void svih_batch_free(svih_batch *b) { delete b; }
 uint32_t svih_batch_n(const svih_batch *b) { return b->eng->n(); }
 uint32_t svih_batch_iter(const svih_batch *b) { return b->eng->iter(); }

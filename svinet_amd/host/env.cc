@@ -65,7 +65,8 @@ Env::Env(const Args &a)
       use_init_communities(a.init_comm), init_communities_fname(a.init_comm_fname),
       nmi(a.nmi), ground_truth_fname(a.ground_truth_fname),
       datfname(a.datfname), label(a.label), gpus(a.gpus), rank(a.rank), kshard(a.kshard), sharded((a.sharded || a.gpus > 1) && !a.kshard), comm_rfd(a.comm_rfd), comm_wfds(a.comm_wfds),
-      batch_mode(a.batch), link_sampling(a.link_sampling), findk(a.findk), batch_device(a.batch && a.batch_gpu), gml(a.gml), lcstats(a.lcstats), strid(a.strid),
+      batch_mode(a.batch), link_sampling(a.link_sampling), findk(a.findk), batch_device((a.batch && a.batch_gpu) || ((a.rnode || a.rpair) && !a.host_loops)),
+      randomnode(a.rnode), randompair(a.rpair), stratified(a.stratified), delaylearn((a.rnode || a.rpair) && !a.nodelay), s(a.n / 2), gml(a.gml), lcstats(a.lcstats), strid(a.strid),
       terminate(0), total_pairs(0), ones_prob(0), zeros_prob(1),
       device(a.device), sweep_batch(a.sweep_batch), write_files(a.write_files),
       minibatch(a.minibatch), tau0(a.tau0), kappa(a.kappa), nodetau0(a.nodetau0), nodekappa(a.nodekappa),
@@ -90,6 +91,13 @@ Env::Env(const Args &a)
   if (batch_mode) { sa << "-batch"; if (!gml) reportfreq = 1; }   // the reference names no directory for -gml (the block is skipped)
   else if (link_sampling) sa << "-linksampling";
   else if (findk) sa << "-findk";
+  else if (sampled()) {   // src/env.hh:529-546 (undirected is always set there: the dash is always written)
+    sa << "-";
+    if (stratified) sa << "S";
+    if (delaylearn) sa << "U";
+    if (randompair) sa << "rpair";
+    if (randomnode) sa << "rnode";
+  }
   if (a.nthreads > 0) sa << "-T" << a.nthreads;
   const std::string name = gml ? std::string("gml") : sa.str();
   prefix = a.outdir_root.empty() ? name : a.outdir_root + "/" + name;
@@ -122,10 +130,10 @@ Env::Env(const Args &a)
   plog("sbm_alpha", alpha);
   plog("heldout_ratio", heldout_ratio);
   plog("precision_ratio", 0.001);
-  plog("stratified", false);
-  plog("delaylearn", false);
+  plog("stratified", stratified);
+  plog("delaylearn", delaylearn);
   plog("nolambda", false);
-  plog("randomnode", false);
+  plog("randomnode", randomnode);
   plog("gen", false);
   plog("undirected", true);
   plog("gap", false);
@@ -150,8 +158,8 @@ Env::Env(const Args &a)
   plog("test_file_location", load_test_fname);
   plog("reportfreq", reportfreq);
   plog("eta_type", eta_type);
-  if (minibatch) {   // keys of this build (mini-batch mode), after the reference's
-    plog("link_sampling_minibatch_nodes", minibatch);
+  if (minibatch || sampled()) {   // keys of this build (mini-batch mode, the sampled-pair engines), after the reference's
+    if (minibatch) plog("link_sampling_minibatch_nodes", minibatch);
     plog("tau0", tau0);
     plog("kappa", kappa);
     plog("nodetau0", nodetau0);

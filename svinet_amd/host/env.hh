@@ -19,6 +19,10 @@ class Env {
     std::string label = "mmsb";
     bool batch = false, link_sampling = false;
     bool batch_gpu = false;             // -batch-gpu: -batch with its sweeps and pair likelihoods on the device (svils_batch_*)
+    // -rnode / -rpair / -rpair -stratified: sampled-pair SVI of the exact model (MMSBInfer::infer, src/mmsbinfer.cc:459-740);
+    // -nodelay: lambda learns from the first iteration (src/env.hh:487-490); -host-loops: the plain C++ loops instead of the device
+    bool rnode = false, rpair = false, stratified = false, nodelay = false, host_loops = false;
+    double scale = 1;                   // -scale (src/env.hh:357): only 1 is implemented
     bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
     bool load = false;
@@ -107,7 +111,10 @@ class Env {
   int comm_rfd;
   std::vector<int> comm_wfds;
   bool batch_mode, link_sampling, findk;
-  bool batch_device;                 // -batch-gpu: MMSBBatch drives a svils_batch handle instead of its host loops
+  bool batch_device;                 // -batch-gpu, and -rnode / -rpair without -host-loops: MMSBBatch drives a svils_batch handle
+  bool randomnode, randompair, stratified, delaylearn;   // the sampled-pair engines (src/env.hh:485-501)
+  bool sampled() const { return randomnode || randompair; }
+  uint32_t s;                        // their mini-batch size n / 2 (src/env.hh:321; -rpair only)
   bool gml, lcstats;
   bool strid;
   volatile int terminate;

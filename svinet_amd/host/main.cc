@@ -5,7 +5,8 @@
 // so -rfreq must follow it).  Engines: -link-sampling (the MI355X path), -findk (the
 // estimate of the number of communities, also on the device), -gml / -lcstats (the
 // link communities of a fitted model's gamma.txt / lambda.txt, on the device) and the
-// reference's small all-pairs CPU engine -batch (plumbing only); the
+// reference's small all-pairs CPU engine -batch (plumbing only), with
+// -batch-gpu, -rnode, -rpair and -rpair -stratified the same model on the device; the
 // flags that select the reference's other engines are recognised and rejected
 // with a message instead of being silently ignored.  -adamic-adar (src/main.cc:173), which
 // the reference wires to two of those engines, is here an option of the link-prediction
@@ -54,7 +55,8 @@ static void forward_handler(int sig) {
 // The single-GPU tool modes refuse the flags of the fitting paths.  Every flag a mode may refuse, in the order the checks
 // name them: a mode reports the first one set among its own.
 enum : unsigned { F_BATCH = 1, F_GPUS = 2, F_KSHARD = 4, F_SHARDED = 8, F_MINIBATCH = 16, F_PAIRS = 32, F_RECOMMEND = 64, F_K2048 = 128,
-                  F_RANKPAIRS = 256, F_RANKHELDOUT = 512, F_ADAMIC = 1024 };
+                  F_RANKPAIRS = 256, F_RANKHELDOUT = 512, F_ADAMIC = 1024, F_LINKSAMPLING = 2048, F_FINDK = 4096, F_GML = 8192,
+                  F_LCSTATS = 16384 };
 
 struct ToolMode {
   unsigned refuses;   // F_* bits
@@ -73,10 +75,19 @@ static const ToolMode kBaselines = {         // -adamic-adar beside them: sums i
     F_MINIBATCH,
     "error: %1$s is not available with %2$s (the relabelled device ids would change the order in which a score is summed)\n"};
 
+static const ToolMode kSampled = {           // -rnode / -rpair: an engine of its own on one GPU
+    F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND |
+        F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
+    "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
+
 // true (the refusal printed) when a flag `mode` refuses is set
 static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) {
   const struct { unsigned bit; bool set; const char *name; } flags[] = {
       {F_BATCH, a.batch, "-batch"},
+      {F_LINKSAMPLING, a.link_sampling, "-link-sampling"},
+      {F_FINDK, a.findk, "-findk"},
+      {F_GML, a.gml, "-gml"},
+      {F_LCSTATS, a.lcstats, "-lcstats"},
       {F_GPUS, a.gpus > 1, "-gpus N > 1"},
       {F_KSHARD, a.kshard, "-kshard"},
       {F_SHARDED, a.sharded, "-sharded"},
@@ -108,6 +119,14 @@ static void usage() {
           "\t-batch\t\trun batch variational inference over all pairs (host CPU, small graphs)\n\n"
           "\t-batch-gpu\t-batch with every sweep and pair likelihood on the GPU: same output directory and files, -k <= 256,\n"
           "\t\t\t-n <= 32768.  Single GPU; without one the run fails (no fall-back to the host engine)\n\n"
+          "\t-rnode\t\tstochastic variational inference of the model of -batch, one random node per iteration: the\n"
+          "\t\t\tn - 1 pairs of the node are the mini-batch.  On the GPU (-k <= 256, -n <= 32768; without one the run fails);\n"
+          "\t\t\ta report every 100 iterations unless -rfreq came before it; step sizes -tau0 -kappa -nodetau0 -nodekappa\n\n"
+          "\t-rpair\t\tthe same with n / 2 random pairs per iteration; not with -rnode\n\n"
+          "\t-stratified\twith -rpair: mini-batches alternate between non-links and links (with -rnode or alone: refused)\n\n"
+          "\t-nodelay\twith -rnode / -rpair: learn lambda from the first iteration (default: once iterations x n / 2 exceed the\n"
+          "\t\t\tnumber of pairs)\n\n"
+          "\t-host-loops\twith -rnode / -rpair: the host CPU loops instead of the GPU (small graphs)\n\n"
           "\t-findk\t\testimate the number of communities (label propagation over a top-5 sparse gamma, on the GPU);\n"
           "\t\t\tpick -k for -link-sampling from the lines of its communities.txt.  Single GPU; -k only sets alpha = 1/k\n\n"
           "\t-gml\t\tgenerate a GML format file that visualizes link communities: reads gamma.txt and lambda.txt of the\n"
@@ -179,7 +198,13 @@ int main(int argc, char **argv) {
     const char *f = argv[i];
     auto is = [&](const char *s) { return strcmp(f, s) == 0; };
     if (is("-help")) { usage(); exit(0); }
-    else if (is("-force") || is("-online") || is("-nodelay")) {}
+    else if (is("-force") || is("-online")) {}
+    else if (is("-nodelay")) { a.nodelay = true; }
+    else if (is("-rnode")) { a.rnode = true; if (a.rfreq == 1) a.rfreq = 100; }   // src/main.cc:141-163
+    else if (is("-rpair")) { a.rpair = true; if (a.rfreq == 1) a.rfreq = 100; }
+    else if (is("-stratified")) { a.stratified = true; if (a.rfreq == 1) a.rfreq = 100; }
+    else if (is("-host-loops")) { a.host_loops = true; }
+    else if (is("-scale")) { need(i); a.scale = atof(argv[++i]); }
     else if (is("-file")) { need(i); a.datfname = argv[++i]; }
     else if (is("-batch")) { a.batch = true; a.link_sampling = false; a.rfreq = 1; }
     else if (is("-batch-gpu")) { a.batch = true; a.batch_gpu = true; a.link_sampling = false; a.rfreq = 1; }
@@ -233,11 +258,10 @@ int main(int argc, char **argv) {
     else if (is("-adamic-adar")) { a.adamic_adar = true; }
     else if (is("-recommend")) { need(i); a.recommend = atoi(argv[++i]); if (a.recommend == 0) a.recommend = -1; }
     else if (is("-init-communities")) { need(i); a.init_comm = true; a.init_comm_fname = argv[++i]; }   // src/main.cc:237-239
-    else if (is("-stopthresh") || is("-inf") || is("-scale") || is("-itype") || is("-groups-file")) {
+    else if (is("-stopthresh") || is("-inf") || is("-itype") || is("-groups-file")) {
       need(i); ++i;   // value flags of other engines: consumed, no effect on this path
     }
-    else if (is("-gen") || is("-ppc") || is("-stratified") ||
-             is("-rnode") || is("-rpair") || is("-orig") || is("-infset") || is("-single") ||
+    else if (is("-gen") || is("-ppc") || is("-orig") || is("-infset") || is("-single") ||
              is("-preprocess") || is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
       unsupported = true;
@@ -245,12 +269,41 @@ int main(int argc, char **argv) {
     }
     // unknown flags are ignored, as in the reference
   }
-  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats)) {
+  const bool sampled = a.rnode || a.rpair;
+  if (a.stratified && !sampled && !unsupported) {        // alone, or beside another engine: the reference's stratified engines
+    unsupported = true;
+    unsupported_flag = "-stratified";
+  }
+  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || sampled)) {
     fprintf(stderr,
             "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk, -gml, -lcstats)%s%s.\n"
             "Use the reference build for the other engines.\n",
             unsupported ? "; unsupported option " : "", unsupported ? unsupported_flag.c_str() : "");
     return 2;
+  }
+  if (sampled) {                                         // -rnode / -rpair / -rpair -stratified (MMSBInfer::infer)
+    const char *flag = a.rnode ? "-rnode" : "-rpair";
+    if (a.rnode && a.stratified) {
+      fprintf(stderr, "error: -stratified -rnode is a different engine of the reference (FastAMM2) and is not implemented here\n");
+      return 2;
+    }
+    if (a.rnode && a.rpair) {
+      fprintf(stderr, "error: -rnode is not available with -rpair (one engine per run)\n");
+      return 2;
+    }
+    if (refused(a, kSampled, flag)) return 2;
+    if (a.scale != 1) {
+      fprintf(stderr, "error: %s is not available with -scale other than 1 (subsampling of the non-links is not implemented)\n", flag);
+      return 2;
+    }
+    if (!a.host_loops && a.k > SVILS_BATCH_MAX_K) {      // the limits of svils_batch_create, before anything is read
+      fprintf(stderr, "error: %s holds -k <= %d (SVILS_BATCH_MAX_K); -k %u is refused\n", flag, SVILS_BATCH_MAX_K, a.k);
+      return 2;
+    }
+    if (!a.host_loops && a.n > SVILS_BATCH_MAX_N) {
+      fprintf(stderr, "error: %s holds -n <= %d (SVILS_BATCH_MAX_N); -n %u is refused\n", flag, SVILS_BATCH_MAX_N, a.n);
+      return 2;
+    }
   }
   if (a.gml || a.lcstats) {
     const char *flag = a.lcstats ? "-lcstats" : "-gml";   // the reference runs -lcstats when both are given (src/main.cc:307-318)
@@ -453,11 +506,11 @@ run:
     fprintf(stderr, "error: %s\n", e.what());
     return -1;
   }
-  if (a.batch) {                             // src/main.cc:354-358
-    printf("+ running mmsb batch inference\n");
-    try {                                    // -batch-gpu: a failed svils_batch_* call ends the run (no host fall-back)
+  if (a.batch || sampled) {                  // src/main.cc:354-358; -rnode / -rpair: :373-377
+    printf(sampled ? "+ running mmsb inference\n" : "+ running mmsb batch inference\n");
+    try {                                    // the device backends: a failed svils_batch_* call ends the run (no host fall-back)
       MMSBBatch mmsb(env, network);
-      mmsb.batch_infer();
+      if (sampled) mmsb.infer(); else mmsb.batch_infer();
     } catch (const SvilsError &e) {
       fprintf(stderr, "error: %s\n", e.what());
       return -1;

@@ -1,5 +1,6 @@
 #include "mmsbbatch.hh"
 
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdlib>
@@ -309,6 +310,135 @@ void MMSBBatch::sweep() {                                   // src/mmsbinfer.cc:
   lambda_ = lambdanext_;
   for (uint32_t k = 0; k < k_; ++k) { lambdanext_[2 * k] = env_.eta0; lambdanext_[2 * k + 1] = env_.eta1; }
   iter_++;
+}
+
+// ---------------------------------------------------------------------------
+// -rnode / -rpair: MMSBInfer::infer (src/mmsbinfer.cc:459-740)
+// ---------------------------------------------------------------------------
+std::vector<uint32_t> MMSBBatch::node_pairs(uint32_t a) const {   // :1867-1876
+  std::vector<uint32_t> out;
+  for (uint32_t i = 0; i < n_; ++i) {
+    if (i == a) continue;
+    const Edge e = a < i ? Edge(a, i) : Edge(i, a);
+    if (!edge_ok(e, false, false, 0)) continue;
+    out.push_back(e.first);
+    out.push_back(e.second);
+  }
+  return out;
+}
+
+MMSBBatch::Drawn MMSBBatch::draw() {
+  Drawn d;
+  const uint32_t it = drawn_++, mbsize = env_.s;             // _env.m = 1 (:483-485)
+  d.family = family_;
+  if (env_.randomnode) {                                     // get_subsample, :1931-1936
+    d.node = rng_.uniform_int(n_);
+    d.scale = (double)n_ / 2;                                // :576
+  } else {
+    do {                                                     // :1926-1930, :1941
+      Edge e;
+      get_random_edge(false, env_.stratified, family_, e);
+      d.pairs.push_back(e.first);
+      d.pairs.push_back(e.second);
+    } while (d.pairs.size() / 2 < mbsize);
+    double scale = (double)env_.total_pairs;                 // :566-568
+    if (env_.stratified) scale = env_.total_pairs * (family_ ? ones_prob_ : zeros_prob_);
+    d.scale = scale / mbsize;                                // :587, :631
+  }
+  d.rho_gamma = pow(env_.nodetau0 + 1 + (double)it / 100, -1 * env_.nodekappa);   // :584 with :18; _nodec[i] = the iteration
+  if (!env_.delaylearn || (uint64_t)it * env_.s > env_.total_pairs) {               // :613
+    if (!delay_reported_) {
+      lambda_start_iter_ = it;
+      Env::plog("learning lambda since (time)", (int)duration());
+      Env::plog("learning lambda since (iter)", it);
+      Env::plog("lambda start iter", lambda_start_iter_);
+      delay_reported_ = true;
+    }
+    d.rho_lambda = pow(env_.tau0 + 1 + (it - lambda_start_iter_ + 1), -1 * env_.kappa);   // :622 with :17
+  }
+  if (env_.stratified) family_ = family_ ? 0 : 1;            // :682-683
+  return d;
+}
+
+void MMSBBatch::step_host(const Drawn &d) {                  // :513-642, process() :1092-1190 with subsample_scale = 1
+  set_dir_exp();
+  const std::vector<uint32_t> pairs = env_.randomnode ? node_pairs(d.node) : d.pairs;
+  std::vector<double> gammat((size_t)n_ * k_, 0.0), lambdat(2 * (size_t)k_, 0.0), phi1(k_), phi2(k_);
+  for (size_t x = 0; x + 1 < pairs.size(); x += 2) {
+    const uint32_t p = pairs[x], q = pairs[x + 1];
+    const int y = network_.y(p, q) ? 1 : 0;
+    phis(p, q, y, phi1.data(), phi2.data());
+    for (uint32_t k = 0; k < k_; ++k) {
+      gammat[(size_t)p * k_ + k] += phi1[k];
+      gammat[(size_t)q * k_ + k] += phi2[k];
+      lambdat[2 * k + (y ? 0 : 1)] += phi1[k] * phi2[k];
+    }
+  }
+  for (size_t x = 0; x < gamma_.size(); ++x)
+    gamma_[x] = (1 - d.rho_gamma) * gamma_[x] + d.rho_gamma * (env_.alpha + d.scale * gammat[x]);
+  if (d.rho_lambda >= 0)
+    for (uint32_t k = 0; k < k_; ++k) {
+      lambda_[2 * k] = (1 - d.rho_lambda) * lambda_[2 * k] + d.rho_lambda * (env_.eta0 + d.scale * lambdat[2 * k]);
+      lambda_[2 * k + 1] = (1 - d.rho_lambda) * lambda_[2 * k + 1] + d.rho_lambda * (env_.eta1 + d.scale * lambdat[2 * k + 1]);
+    }
+}
+
+void MMSBBatch::step(uint32_t nsteps) {
+  std::vector<Drawn> chunk(nsteps);
+  for (Drawn &d : chunk) d = draw();
+  if (!dev_) {
+    for (const Drawn &d : chunk) step_host(d);
+  } else if (nsteps) {
+    std::vector<double> rg(nsteps), rl(nsteps);
+    for (uint32_t s = 0; s < nsteps; ++s) { rg[s] = chunk[s].rho_gamma; rl[s] = chunk[s].rho_lambda; }
+    if (env_.randomnode) {
+      std::vector<uint32_t> nodes(nsteps);
+      for (uint32_t s = 0; s < nsteps; ++s) nodes[s] = chunk[s].node;
+      if (int rc = svils_batch_step_node(dev_, nsteps, nodes.data(), chunk[0].scale, rg.data(), rl.data())) device_failed("svils_batch_step_node", rc);
+    } else {
+      std::vector<uint64_t> off(nsteps + 1, 0);
+      std::vector<uint32_t> pairs;
+      std::vector<double> scale(nsteps);
+      for (uint32_t s = 0; s < nsteps; ++s) {
+        pairs.insert(pairs.end(), chunk[s].pairs.begin(), chunk[s].pairs.end());
+        off[s + 1] = pairs.size() / 2;
+        scale[s] = chunk[s].scale;
+      }
+      if (int rc = svils_batch_step_pairs(dev_, nsteps, off.data(), pairs.data(), scale.data(), rg.data(), rl.data()))
+        device_failed("svils_batch_step_pairs", rc);
+    }
+    host_stale_ = true;
+  }
+  iter_ += nsteps;
+  if (keep_schedule_)
+    for (Drawn &d : chunk) schedule_.push_back(std::move(d));
+}
+
+int MMSBBatch::infer() {
+  for (;;) {
+    if (env_.max_iterations && iter_ > env_.max_iterations) {
+      printf("+ Quitting: reached max iterations.\n");
+      Env::plog("maxiterations reached", true);
+      do_on_stop();                                          // as batch_infer(): a bounded run leaves its model
+      return 0;
+    }
+    // drawing never depends on the state: everything up to the next report goes to the device in one call
+    uint32_t todo = env_.reportfreq - iter_ % env_.reportfreq;
+    if (env_.max_iterations) todo = std::min(todo, env_.max_iterations + 1 - iter_);
+    step(todo);
+    if (iter_ % env_.reportfreq == 0) {                      // :709-738
+      if (report()) {
+        do_on_stop();
+        return 1;
+      }
+      printf("\riteration = %d took %d secs", iter_, duration());
+      fflush(stdout);
+      if (env_.terminate) {
+        do_on_stop();
+        env_.terminate = 0;
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------

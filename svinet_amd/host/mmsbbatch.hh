@@ -13,6 +13,12 @@
 //                         HIP device is such a failure -- there is no fall-back to the host loops.
 // It is NOT a fallback for `-link-sampling`: that path has no CPU route in this repo.
 //
+// -rnode / -rpair / -rpair -stratified (Env::sampled()) run MMSBInfer::infer() (src/mmsbinfer.cc:459-740) on the same
+// object: the Robbins-Monro version of the same model, one mini-batch of pairs per iteration (infer(), step()).  The
+// samplers, likelihoods, stop rule and writers are the ones above; the mini-batches are drawn here from the same MT19937
+// stream (get_subsample, :1912-1945) and never depend on the state, so a whole report interval is drawn first and handed
+// to the device in one call (svils_batch_step_node / svils_batch_step_pairs); -host-loops runs the restated loops instead.
+//
 // Seam mirrored:   MMSBInfer mmsb(env, network);  mmsb.batch_infer();
 //
 // Where the reference reads members it never initialises (`_iter`, `_ones_prob`,
@@ -47,6 +53,22 @@ class MMSBBatch {
   // the report step (:895-905); returns true when the stop rule fired
   bool report();
   void do_on_stop();                                      // :743-752
+
+  // the sampled-pair engines.  infer(): as batch_infer(), a report every reportfreq iterations
+  int infer();
+  // one drawn iteration: its start node (-rnode) or pair list, the factor of gammat / lambdat (scale, or scale / mbsize),
+  // the step sizes (rho_lambda < 0: lambda waits, :613) and the family it was drawn from
+  struct Drawn {
+    uint32_t node = 0;
+    std::vector<uint32_t> pairs;     // [m][2], p < q
+    double scale = 0, rho_gamma = 0, rho_lambda = -1;
+    int family = 0;
+  };
+  void step(uint32_t nsteps);                             // draws nsteps iterations, then runs them (:476-642)
+  void keep_schedule(bool on) { keep_schedule_ = on; }   // library callers: every executed iteration stays in schedule()
+  const std::vector<Drawn> &schedule() const { return schedule_; }
+  // the pairs of a node's mini-batch (get_randomnode_edges, :1867-1876), [m][2]
+  std::vector<uint32_t> node_pairs(uint32_t a) const;
 
   uint32_t n() const { return n_; }
   uint32_t k() const { return k_; }
@@ -97,6 +119,14 @@ class MMSBBatch {
   double spare_ = 0;
   time_t start_time_;
   FILE *hf_ = nullptr, *vf_ = nullptr;
+  Drawn draw();                                           // get_subsample and the step sizes of iteration iter_ + drawn so far
+  void step_host(const Drawn &d);
+  int family_ = 0;                                        // _family, alternating under -stratified (:682-683)
+  uint32_t drawn_ = 0;                                    // iterations drawn: the next one is number drawn_
+  uint32_t lambda_start_iter_ = 0;
+  bool delay_reported_ = false;
+  bool keep_schedule_ = false;
+  std::vector<Drawn> schedule_;
   svils_batch *dev_ = nullptr;       // the device backend (null: host loops)
   bool host_stale_ = false;          // the device has swept since gamma_ / lambda_ were fetched
 };

@@ -21,7 +21,8 @@ class Options(C.Structure):
     _fields_ = [("n", C.c_uint32), ("k", C.c_uint32), ("seed", C.c_double),
                 ("heldout_ratio", C.c_double), ("link_thresh", C.c_double),
                 ("lt_min_deg", C.c_uint32), ("eta_type", C.c_int32), ("accuracy", C.c_int32), ("defer_gamma", C.c_int32),
-                ("batch_device", C.c_int32), ("device", C.c_int32)]
+                ("batch_device", C.c_int32), ("device", C.c_int32), ("sampled", C.c_int32), ("nodelay", C.c_int32),
+                ("tau0", C.c_double), ("kappa", C.c_double), ("nodetau0", C.c_double), ("nodekappa", C.c_double)]
 
 
 _lib = None
@@ -203,7 +204,10 @@ class BatchEngine:
     on_device=True: the sweeps and pair likelihoods run through svils_batch_* on `device` (-batch-gpu) -- SvilsError
     without a HIP device, never the host loops instead."""
 
-    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, eta_type="uniform", on_device=False, device=0):
+    _SAMPLED = 0
+
+    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, eta_type="uniform", on_device=False, device=0, nodelay=False,
+                 **step_sizes):
         L = load()
         vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
         if not hasattr(L, "_batch_ready"):
@@ -213,15 +217,24 @@ class BatchEngine:
                               ("nheldout", u64), ("heldout", P(u32)), ("nvalidation", u64),
                               ("validation", P(u32)), ("nrows", u64), ("rows", P(dbl)), ("sweep", C.c_int),
                               ("report", C.c_int), ("eta0", dbl), ("eta1", dbl), ("ones_prob", dbl),
-                              ("edges", P(u32)), ("ones", u32)):
+                              ("edges", P(u32)), ("ones", u32), ("nschedule", u64), ("total_pairs", dbl)):
                 f = getattr(L, "svih_batch_" + name)
                 f.argtypes = [vp]
                 f.restype = res
+            L.svih_batch_step.argtypes = [vp, u32]
+            L.svih_batch_step.restype = C.c_int
+            L.svih_batch_schedule.argtypes = [vp, u64, vp, vp]
+            L.svih_batch_schedule.restype = u64
             L._batch_ready = True
         o = Options()
         L.svih_options_default(C.byref(o), n, k)
         o.seed, o.heldout_ratio, o.eta_type = seed, heldout_ratio, ETA_TYPES[eta_type]
         o.batch_device, o.device = int(bool(on_device)), device
+        o.sampled, o.nodelay = self._SAMPLED, int(bool(nodelay))
+        for key, value in step_sizes.items():   # tau0, kappa, nodetau0, nodekappa
+            if key not in ("tau0", "kappa", "nodetau0", "nodekappa"):
+                raise TypeError("unexpected argument %r" % key)
+            setattr(o, key, value)
         self._h = L.svih_batch_from_file(os.fsencode(path), C.byref(o))
         if not self._h:
             if on_device:   # (as FindK: an unreadable file and a failed svils_batch_* call both end here)
@@ -235,6 +248,7 @@ class BatchEngine:
         self.heldout = _arr(L.svih_batch_heldout(self._h), (L.svih_batch_nheldout(self._h), 2), np.uint32)
         self.validation = _arr(L.svih_batch_validation(self._h), (L.svih_batch_nvalidation(self._h), 2), np.uint32)
         self.edges = _arr(L.svih_batch_edges(self._h), (L.svih_batch_ones(self._h), 2), np.uint32)
+        self.total_pairs = L.svih_batch_total_pairs(self._h)
 
     @property
     def gamma(self):
@@ -269,6 +283,41 @@ class BatchEngine:
             self._h = None
 
     __del__ = close
+
+
+class SampledEngine(BatchEngine):
+    """The sampled-pair engines of the host library: the reference's MMSBInfer::infer (src/mmsbinfer.cc:459-740) for
+    mode "rnode", "rpair" or "rpair-stratified".  on_device=False: its host loops (-host-loops); on_device=True: the steps
+    and pair likelihoods run through svils_batch_step_* on `device`.  step(nsteps) draws nsteps iterations and runs them;
+    schedule lists, per executed iteration, what was drawn: dict(node, family, pairs [m][2], scale, rho_gamma, rho_lambda)
+    -- scale is the factor of gammat (n / 2, or scale / mbsize), rho_lambda < 0 an iteration that leaves lambda alone."""
+
+    MODES = {"rnode": 1, "rpair": 2, "rpair-stratified": 3}
+
+    def __init__(self, path, n, k, mode, on_device=False, nodelay=False, **kw):
+        self._SAMPLED = self.MODES[mode]
+        self.mode = mode
+        super().__init__(path, n, k, on_device=on_device, nodelay=nodelay, **kw)
+
+    def sweep(self):
+        raise TypeError("a SampledEngine steps; BatchEngine sweeps")
+
+    def step(self, nsteps=1):
+        rc = load().svih_batch_step(self._h, nsteps)
+        if rc < 0:
+            _svils._chk(rc)
+
+    @property
+    def schedule(self):
+        L, out = load(), []
+        for i in range(L.svih_batch_nschedule(self._h)):
+            head = np.zeros(5)
+            m = L.svih_batch_schedule(self._h, i, head.ctypes.data, None)
+            pairs = np.zeros((m, 2), dtype=np.uint32)
+            L.svih_batch_schedule(self._h, i, None, pairs.ctypes.data)
+            out.append(dict(node=int(head[0]), family=int(head[1]), pairs=pairs, scale=float(head[2]), rho_gamma=float(head[3]),
+                            rho_lambda=float(head[4])))
+        return out
 
 
 class FindK:
