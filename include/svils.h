@@ -43,6 +43,7 @@ extern "C" {
                                     (additive, same version) svils_findk_*: -findk, the estimate of the number of communities;
                                     (additive, same version) svils_batch_*: -batch-gpu, all-pairs batch inference;
                                     (additive, same version) svils_batch_step_node / svils_batch_step_pairs: -rnode / -rpair, sampled-pair steps;
+                                    (additive, same version) svils_batch_step_star / svils_batch_set_star_chain / svils_batch_get_expectations: -infset, informative-set steps;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
                                     resource-allocation scores of pairs, the model-free baselines of svils_rank_links */
@@ -670,7 +671,7 @@ int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t
 int svils_batch_get_stats(svils_batch *h, uint64_t *pairs_done, uint64_t *rounds_total, uint32_t *rounds_max,
                           uint64_t *underflow_pairs);
 /* device milliseconds of the last sweep: Elogpi / Elogbeta, the pair pass, the reductions (hipEvent brackets; -1: none yet).
- * After a call of svils_batch_step_node / svils_batch_step_pairs: ms[0] brackets all steps of that call, ms[1] = ms[2] = -1 */
+ * After a call of svils_batch_step_node / svils_batch_step_pairs / svils_batch_step_star: ms[0] brackets all steps of that call, ms[1] = ms[2] = -1 */
 int svils_batch_get_timing(svils_batch *h, double ms[3]);
 /* the pair kernel's instantiation for k: a group of W lanes per pair, V values per lane, W * V >= k.  No device needed.
  * SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_BATCH_MAX_K */
@@ -704,6 +705,37 @@ int svils_batch_step_node(svils_batch *h, uint32_t nsteps, const uint32_t *nodes
  * the previous call's copy (not for its steps) to have left it */
 int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off, const uint32_t *pairs, const double *scale,
                            const double *rho_gamma, const double *rho_lambda);
+
+/* ---- -infset: informative-set steps on the svils_batch handle (an ADDITION of ABI 8) -----------------------------------
+ * The reference's FastAMM::infer (src/fastamm.cc:565-616) with opt_process / opt_process_noninf (:915-1126).  Step s is a
+ * star: the start node a = start[s] and the entries off[s] .. off[s + 1) -- partner[e] = j, y[e] the pair's link bit,
+ * rho_partner[e] the step size of row j.  One step:
+ *   pair pass   every listed pair (a, j): the fixed point of svils_batch_sweep from the current Elogpi / Elogbeta
+ *   gamma_j     (1 - rho_partner) gamma_j + rho_partner (alpha + scale[s] phi_j), Elogpi_j renewed
+ *   gamma_a     (1 - rho_start[s]) gamma_a + rho_start[s] (alpha + scale[s] sum phi_a), Elogpi_a renewed
+ *   lambda      rho_lambda[s] >= 0: (1 - rho_lambda) lambda + rho_lambda (eta + scale[s] (sum_{y=1} phi phi', sum_{y=0} phi phi')),
+ *               Elogbeta renewed; rho_lambda[s] < 0: lambda and Elogbeta are left bit for bit
+ * No other row of gamma is written.  A step without entries moves row a towards alpha and lambda towards eta (a start
+ * node whose pairs are all held out).  The caller draws the stars and counts the times a node was touched, hence every
+ * rho (:594).  The steps of a call run as a chain in ONE workgroup, step after step inside a launch (DESIGN.md section
+ * 4h); a call cuts its chain into launches of at most 64 steps (svils_batch_set_star_chain: another length up to 1024; 0: the
+ * default) and the result does not depend on where the cuts fall, nor on how the steps are cut into calls.  No
+ * floating-point atomics.  Enqueued, nothing waits; svils_batch_get_stats / svils_batch_get_timing cover the call as for
+ * the other steps; the lists travel through the pinned staging area of svils_batch_step_pairs.
+ * SVILS_ERR_ARG, checked before anything is enqueued (the state is untouched): a null array, no graph or no state, a
+ * node >= n, a partner equal to its step's start, a partner listed twice within a step, a listed pair of the skip set, a
+ * y that disagrees with the graph, a rho outside (0, 1] (rho_lambda: > 1), a scale that is not a positive number */
+int svils_batch_step_star(svils_batch *h, uint32_t nsteps, const uint32_t *start, const uint64_t *off, const uint32_t *partner,
+                          const uint8_t *y, const double *rho_partner, const double *rho_start, const double *scale,
+                          const double *rho_lambda);
+/* steps per launch of the star chain: 1 .. SVILS_BATCH_STAR_CHAIN_MAX, 0 the default of 64; more: SVILS_ERR_ARG (a longer
+ * chain is a longer kernel on a machine others share).  Results do not depend on it */
+#define SVILS_BATCH_STAR_CHAIN_MAX 1024
+int svils_batch_set_star_chain(svils_batch *h, uint32_t max_steps);
+/* Elogpi [n][k] and Elogbeta [k][2] as the step kernels read them: those of the current gamma / lambda, renewed first if a
+ * sweep or svils_batch_set_state came since the last step call (what the next step call would do), else the ones the steps
+ * maintain row by row.  Waits for the stream.  Either pointer may be null.  SVILS_ERR_ARG: no state */
+int svils_batch_get_expectations(svils_batch *h, double *elogpi, double *elogbeta);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * Every tunable of the library is a row of ONE table: key, the SVILS_* environment variable that sets its default, the

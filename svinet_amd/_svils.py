@@ -42,9 +42,11 @@ EXPORTS = (
     "svils_lc_get_timing",
     "svils_batch_create", "svils_batch_destroy", "svils_batch_set_graph", "svils_batch_set_state", "svils_batch_get_state",
     "svils_batch_sweep", "svils_batch_pair_loglik", "svils_batch_get_stats", "svils_batch_get_timing", "svils_batch_variant",
-    "svils_batch_step_node", "svils_batch_step_pairs",
+    "svils_batch_step_node", "svils_batch_step_pairs", "svils_batch_step_star", "svils_batch_set_star_chain",
+    "svils_batch_get_expectations",
 )
 BATCH_MAX_K, BATCH_MAX_N = 256, 32768   # SVILS_BATCH_MAX_K, SVILS_BATCH_MAX_N
+BATCH_STAR_CHAIN_MAX = 1024             # SVILS_BATCH_STAR_CHAIN_MAX
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
 NBR_CN, NBR_AA, NBR_RA = range(3)   # svils_nbr_measure
 
@@ -200,6 +202,9 @@ def load():
     L.svils_batch_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.svils_batch_step_node.argtypes = [vp, C.c_uint32, vp, C.c_double, vp, vp]
     L.svils_batch_step_pairs.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.svils_batch_step_star.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.svils_batch_set_star_chain.argtypes = [vp, C.c_uint32]
+    L.svils_batch_get_expectations.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):
@@ -678,6 +683,35 @@ class Batch:
         assert sc.shape == rg.shape == rl.shape == (len(lists),)
         _chk(load().svils_batch_step_pairs(self._h, len(lists), off.ctypes.data, pairs.ctypes.data, sc.ctypes.data, rg.ctypes.data,
                                            rl.ctypes.data))
+
+    def step_star(self, steps):
+        """svils_batch_step_star: one informative-set step per entry of `steps`, enqueued as one chain.  A step is a dict:
+        start, partner [m], y [m], rho_partner [m], rho_start, scale, rho_lambda (< 0 leaves lambda alone)"""
+        ns = len(steps)
+        parts = [np.ascontiguousarray(s["partner"], dtype=np.uint32).reshape(-1) for s in steps]
+        off = np.zeros(ns + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([p.shape[0] for p in parts])
+
+        def cat(key, dtype):
+            a = [np.ascontiguousarray(s[key], dtype=dtype).reshape(-1) for s in steps]
+            assert all(x.shape == p.shape for x, p in zip(a, parts))
+            return np.ascontiguousarray(np.concatenate(a) if a else np.zeros(0), dtype=dtype)
+
+        partner, y, rp = cat("partner", np.uint32), cat("y", np.uint8), cat("rho_partner", np.float64)
+        start = np.array([s["start"] for s in steps], dtype=np.uint32)
+        rs, sc, rl = (np.array([s[key] for s in steps], dtype=np.float64) for key in ("rho_start", "scale", "rho_lambda"))
+        _chk(load().svils_batch_step_star(self._h, ns, start.ctypes.data, off.ctypes.data, partner.ctypes.data, y.ctypes.data,
+                                          rp.ctypes.data, rs.ctypes.data, sc.ctypes.data, rl.ctypes.data))
+
+    def set_star_chain(self, max_steps):
+        """steps per launch of the star chain (0: the default, at most BATCH_STAR_CHAIN_MAX); results do not depend on it"""
+        _chk(load().svils_batch_set_star_chain(self._h, max_steps))
+
+    def expectations(self):
+        """svils_batch_get_expectations: Elogpi [n][k], Elogbeta [k][2] as the step kernels read them"""
+        ep, eb = np.empty((self.n, self.k)), np.empty((self.k, 2))
+        _chk(load().svils_batch_get_expectations(self._h, ep.ctypes.data, eb.ctypes.data))
+        return ep, eb
 
     def pair_loglik(self, pairs, y):
         pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)

@@ -27,6 +27,10 @@
 //   k_batch_step_phi<W,V>   pair step: group e holds the e-th listed pair; phi to the step's buffer, lambda partials
 //   k_batch_step_rows<W,V>  pair step: group i adds node i's phi vectors in list order, blends gamma_i, writes Elogpi_i
 //   k_batch_step_tail       block k: the partials of community k in a fixed order; gamma_a[k] (node steps), lambda[k], Elogbeta[k]
+//
+// -infset: the informative-set steps of FastAMM::infer (src/fastamm.cc:549-672) on the same handle:
+//
+//   k_batch_star_chain<W,V> a chain of star steps in one workgroup of one launch, a barrier between steps
 #include "svils_devutil.h"
 #include "svils_tool.h"
 
@@ -624,6 +628,133 @@ __global__ __launch_bounds__(256) void k_batch_step_tail(uint32_t K, uint32_t nw
   }
 }
 
+// ---- informative-set steps (svils_batch_step_star) ---------------------------------------------
+// FastAMM::infer (src/fastamm.cc:565-616) with opt_process / opt_process_noninf (:915-1126): a step is a star -- a start
+// node a and the listed partners j -- and moves only the rows it names, each with its own step size.  A chain of steps
+// runs in ONE workgroup of ONE launch: step t + 1 reads rows step t wrote, and between them stands a __syncthreads(),
+// not a launch.  Passes of STAR_WAVES x 64 / W entries run over a step's list; group e of a pass holds pair (a, j_e),
+// blends gamma_j and writes Elogpi_j itself (a partner is listed once per step: one owner per row); phi_a and the lambda
+// terms stay in the group's registers across the passes, leave per wavefront to LDS and are added there in ascending
+// wavefront order by thread k.  The kernel waits on nothing but its own barriers.  gamma / Elogpi / lambda / Elogbeta are
+// read and written here: plain pointers, plain loads.
+constexpr int STAR_THREADS = 512, STAR_WAVES = STAR_THREADS / 64;
+constexpr uint32_t STAR_CHAIN = 64;   // steps per launch unless svils_batch_set_star_chain says otherwise
+constexpr uint32_t STAR_CHAIN_MAX = SVILS_BATCH_STAR_CHAIN_MAX;   // ... and the most it may say
+
+struct StarArgs {
+  uint32_t K, s0, s1;                         // the launch runs steps [s0, s1) of the call
+  double *gamma, *elogpi, *lam, *elogbeta;
+  const double *gtab;
+  double logeps, alpha, eta0, eta1;
+  const uint32_t *off, *start, *partner;      // [nsteps + 1], [nsteps], [total]
+  const uint8_t *y;                           // [total]
+  const double *rho_partner, *rho_start, *scale, *rho_lambda;   // [total], [nsteps] x 3
+  unsigned long long *ctr;
+};
+
+template <int W, int V>
+__global__ __launch_bounds__(STAR_THREADS) void k_batch_star_chain(StarArgs x) {
+  constexpr int G = 64 / W, WV = W * V;
+  constexpr uint32_t P = STAR_WAVES * G;      // entries per pass
+  __shared__ double2 logtab[128];
+  __shared__ double part[STAR_WAVES][3][WV];  // per wavefront: phi_a, the y = 1 and the y = 0 lambda terms
+  __shared__ double rowa[WV];                 // the new gamma_a
+  load_logtab(logtab, x.gtab);
+  __syncthreads();
+  const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63, g = lane / W, lw = lane % W, K = x.K;
+  bool kval[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) kval[v] = (uint32_t)(v * W) + lw < K;
+  uint32_t npairs = 0, rtot = 0, rmax = 0, nunder = 0;
+  for (uint32_t s = x.s0; s < x.s1; ++s) {
+    const uint32_t a = x.start[s], e0 = x.off[s], e1 = x.off[s + 1];
+    const double scale = x.scale[s];
+    double ela[V], ef0[V], ef1[V], acc[V], l0[V], l1[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const uint32_t k = v * W + lw;
+      ela[v] = kval[v] ? x.elogpi[(size_t)a * K + k] : 0.0;
+      ef1[v] = kval[v] ? x.elogbeta[2 * k] : 0.0;
+      ef0[v] = kval[v] ? x.elogbeta[2 * k + 1] : 0.0;
+      acc[v] = l0[v] = l1[v] = 0.0;
+    }
+    for (uint32_t base = e0; base < e1; base += P) {   // the same trip count in every wavefront
+      const uint32_t e = base + wave * G + g;
+      const bool valid = e < e1;
+      const uint32_t j = valid ? x.partner[e] : 0;
+      const bool y = valid && x.y[e] != 0;
+      const double rho = valid ? x.rho_partner[e] : 1.0;
+      double elj[V], ef[V], pa[V], pj[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        elj[v] = kval[v] && valid ? x.elogpi[(size_t)j * K + v * W + lw] : 0.0;
+        ef[v] = y ? ef1[v] : ef0[v];
+      }
+      uint32_t rounds;
+      bool under;
+      pair_fixed_point<W, V>(ela, elj, ef, y ? x.logeps : 0.0, kval, K, valid, pa, pj, rounds, under);
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        pa[v] = valid ? pa[v] : 0.0;
+        pj[v] = valid ? pj[v] : 0.0;
+      }
+      blend_row<W, V>(valid, j, K, lw, kval, pj, rho, x.alpha, scale, x.gamma, x.elogpi, logtab);
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        const double pp = pa[v] * pj[v];
+        acc[v] += pa[v];
+        l0[v] += y ? pp : 0.0;
+        l1[v] += y ? 0.0 : pp;
+      }
+      const bool cnt = valid && lw == 0;
+      npairs += cnt;
+      rtot += cnt ? rounds : 0;
+      rmax = max(rmax, cnt ? rounds : 0);
+      nunder += cnt && under;
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const double sa = cross_group_sum<W>(acc[v]), t0 = cross_group_sum<W>(l0[v]), t1 = cross_group_sum<W>(l1[v]);
+      if (g == 0) {
+        part[wave][0][v * W + lw] = sa;
+        part[wave][1][v * W + lw] = t0;
+        part[wave][2][v * W + lw] = t1;
+      }
+    }
+    __syncthreads();
+    if (t < K) {   // thread k: the wavefronts' partials of community k in ascending order; gamma_a[k], lambda[k], Elogbeta[k]
+      double sa = 0.0, s0 = 0.0, s1 = 0.0;
+      for (int w = 0; w < STAR_WAVES; ++w) {
+        sa += part[w][0][t];
+        s0 += part[w][1][t];
+        s1 += part[w][2][t];
+      }
+      const double rho_a = x.rho_start[s], rho_l = x.rho_lambda[s];
+      const double ga = (1.0 - rho_a) * x.gamma[(size_t)a * K + t] + rho_a * (x.alpha + scale * sa);
+      x.gamma[(size_t)a * K + t] = ga;
+      rowa[t] = ga;
+      if (rho_l >= 0.0) {
+        const double n0 = (1.0 - rho_l) * x.lam[2 * t] + rho_l * (x.eta0 + scale * s0);
+        const double n1 = (1.0 - rho_l) * x.lam[2 * t + 1] + rho_l * (x.eta1 + scale * s1);
+        x.lam[2 * t] = n0;
+        x.lam[2 * t + 1] = n1;
+        const double ps = digamma(n0 + n1, logtab);
+        x.elogbeta[2 * t] = digamma(n0, logtab) - ps;
+        x.elogbeta[2 * t + 1] = digamma(n1, logtab) - ps;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {   // Elogpi_a as k_batch_dir_exp forms it
+      double rs = 0.0;
+      for (uint32_t k = lane; k < K; k += 64) rs += rowa[k];
+      const double ps = digamma(wave_sum_f64(rs), logtab);
+      for (uint32_t k = lane; k < K; k += 64) x.elogpi[(size_t)a * K + k] = digamma(rowa[k], logtab) - ps;
+    }
+    __syncthreads();   // the next step reads what this one wrote
+  }
+  count_pairs(x.ctr, lane, npairs, rtot, rmax, nunder);
+}
+
 }  // namespace
 
 // events: ev[0] sweep begin, ev[1] Elogpi / Elogbeta done, then per launch of the pair kernel ev[2 + 2 b] (pairs done) and
@@ -652,6 +783,8 @@ struct svils_batch : ToolHandle {
   bool timed_steps = false;                                       // the last timed call was a step call: ev[0] .. ev[1] bracket it
   bool elog_fresh = false;                                        // Elogpi / Elogbeta are those of gamma / lambda
   std::vector<uint32_t> h_skip;                                   // the skip bits, to refuse a listed skipped pair
+  std::vector<uint32_t> h_adj;                                    // the link bits, to refuse a star entry whose y disagrees: fetched by the first star call
+  uint32_t star_chain = STAR_CHAIN;                               // steps per launch of k_batch_star_chain
   double *st_part = nullptr, *st_pl = nullptr, *st_phi = nullptr;
   uint32_t *st_lists = nullptr;                                   // a call's pairs [total][2], entries [2 total], offsets [nsteps][n + 1]
   size_t cap_part = 0, cap_pl = 0, cap_phi = 0, cap_lists = 0;
@@ -667,6 +800,8 @@ void free_graph(svils_batch *h) {
   h->release(ToolHandle::GRAPH);
   h->have_graph = false;
   h->ll_cap = 0;
+  std::vector<uint32_t>().swap(h->h_skip);   // the host copies of the graph's bits go with it
+  std::vector<uint32_t>().swap(h->h_adj);
 }
 
 template <int W>
@@ -764,13 +899,17 @@ int check_steps(svils_batch *h, const char *name, uint32_t nsteps, const double 
 }
 
 // Elogpi / Elogbeta of the current state if a sweep or set_state came in between; the counters of the call start at zero
+int renew_expectations(svils_batch *h) {
+  if (h->elog_fresh) return 0;
+  hipLaunchKernelGGL(k_batch_dir_exp, dim3(blocks(h->n, 4)), dim3(256), 0, h->st, h->n, h->k, h->gamma, h->gtab, h->elogpi);
+  hipLaunchKernelGGL(k_batch_beta, dim3(blocks(h->k, 256)), dim3(256), 0, h->st, h->k, h->lam, h->gtab, h->elogbeta);
+  HIPCHK(hipGetLastError());
+  h->elog_fresh = true;
+  return 0;
+}
+
 int begin_steps(svils_batch *h) {
-  if (!h->elog_fresh) {
-    hipLaunchKernelGGL(k_batch_dir_exp, dim3(blocks(h->n, 4)), dim3(256), 0, h->st, h->n, h->k, h->gamma, h->gtab, h->elogpi);
-    hipLaunchKernelGGL(k_batch_beta, dim3(blocks(h->k, 256)), dim3(256), 0, h->st, h->k, h->lam, h->gtab, h->elogbeta);
-    HIPCHK(hipGetLastError());
-    h->elog_fresh = true;
-  }
+  if (int rc = renew_expectations(h)) return rc;
   HIPCHK(hipMemsetAsync(h->ctr, 0, 4 * sizeof(unsigned long long), h->st));
   HIPCHK(hipEventRecord(h->ev[0], h->st));
   return 0;
@@ -779,6 +918,23 @@ int begin_steps(svils_batch *h) {
 int end_steps(svils_batch *h) {
   HIPCHK(hipEventRecord(h->ev[1], h->st));
   h->timed = h->timed_steps = true;
+  return 0;
+}
+
+// the pinned staging area for a call's lists, nwords uint32 wide: free again once the previous call's copy has left it
+int reserve_pin(svils_batch *h, size_t nwords) {
+  if (h->copy_pending) {
+    HIPCHK(hipEventSynchronize(h->ev_copy));
+    h->copy_pending = false;
+  }
+  if (!h->ev_copy) HIPCHK(hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
+  if (nwords > h->cap_pin) {
+    if (h->pin) (void)hipHostFree(h->pin);
+    h->pin = nullptr;
+    h->cap_pin = 0;
+    HIPCHK(hipHostMalloc((void **)&h->pin, nwords * sizeof(uint32_t), hipHostMallocDefault));
+    h->cap_pin = nwords;
+  }
   return 0;
 }
 
@@ -1030,18 +1186,7 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
   // the call's lists go through pinned memory in one copy, so that the call need not wait for it; the staging area is
   // free again once the previous call's copy has left it
   const size_t nlists = 4 * (size_t)total + (size_t)nsteps * (n + 1);
-  if (h->copy_pending) {
-    HIPCHK(hipEventSynchronize(h->ev_copy));
-    h->copy_pending = false;
-  }
-  if (!h->ev_copy) HIPCHK(hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
-  if (nlists > h->cap_pin) {
-    if (h->pin) (void)hipHostFree(h->pin);
-    h->pin = nullptr;
-    h->cap_pin = 0;
-    HIPCHK(hipHostMalloc((void **)&h->pin, nlists * sizeof(uint32_t), hipHostMallocDefault));
-    h->cap_pin = nlists;
-  }
+  if (int rc = reserve_pin(h, nlists)) return rc;
   uint32_t *const pin_pairs = h->pin, *const pin_ent = h->pin + 2 * total, *const pin_noff = h->pin + 4 * total;
   if (total) std::memcpy(pin_pairs, pairs, 2 * total * sizeof(uint32_t));
   std::memset(pin_noff, 0, (size_t)nsteps * (n + 1) * sizeof(uint32_t));
@@ -1085,6 +1230,127 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
     if (rho_lambda[s] >= 0.0)
       hipLaunchKernelGGL(k_batch_step_tail, dim3(K), dim3(256), 0, h->st, K, 4 * nb, (const double *)nullptr, h->st_pl, (double *)nullptr,
                          h->alpha, h->eta0, h->eta1, scale[s], rho_gamma[s], rho_lambda[s], h->lam, h->elogbeta, h->gtab);
+    HIPCHK(hipGetLastError());
+  }
+  return end_steps(h);
+}
+
+int svils_batch_set_star_chain(svils_batch *h, uint32_t max_steps) {
+  if (int rc = check(h, "svils_batch_set_star_chain")) return rc;
+  if (max_steps > STAR_CHAIN_MAX)   // a longer chain is a longer kernel on a shared machine
+    return fail(SVILS_ERR_ARG, "svils_batch_set_star_chain: %u steps per launch exceed the most, %u", max_steps, STAR_CHAIN_MAX);
+  h->star_chain = max_steps ? max_steps : STAR_CHAIN;
+  return 0;
+}
+
+int svils_batch_get_expectations(svils_batch *h, double *elogpi, double *elogbeta) {
+  const char *name = "svils_batch_get_expectations";
+  if (int rc = check(h, name)) return rc;
+  if (!h->have_state) return fail(SVILS_ERR_ARG, "%s: no state", name);
+  if (int rc = renew_expectations(h)) return rc;   // what the next step call would do first
+  if (int rc = settle(h, name)) return rc;
+  if (elogpi) HIPCHK(hipMemcpy(elogpi, h->elogpi, (size_t)h->n * h->k * sizeof(double), hipMemcpyDeviceToHost));
+  if (elogbeta) HIPCHK(hipMemcpy(elogbeta, h->elogbeta, 2 * (size_t)h->k * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int svils_batch_step_star(svils_batch *h, uint32_t nsteps, const uint32_t *start, const uint64_t *off, const uint32_t *partner,
+                          const uint8_t *y, const double *rho_partner, const double *rho_start, const double *scale,
+                          const double *rho_lambda) {
+  const char *name = "svils_batch_step_star";
+  if (int rc = check(h, name)) return rc;
+  if (nsteps && (!start || !off || !rho_start || !scale || !rho_lambda)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
+  if (!nsteps) return 0;
+  if (int rc = check_steps(h, name, nsteps, rho_start, rho_lambda)) return rc;
+  if (off[0] != 0) return fail(SVILS_ERR_ARG, "%s: off[0] is not 0", name);
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    if (off[s + 1] < off[s]) return fail(SVILS_ERR_ARG, "%s: off[%u] decreases", name, s + 1);
+    if (!(scale[s] > 0.0) || !std::isfinite(scale[s])) return fail(SVILS_ERR_ARG, "%s: scale[%u] is not a positive number", name, s);
+    if (start[s] >= h->n) return fail(SVILS_ERR_ARG, "%s: start[%u] = %u is not < n = %u", name, s, start[s], h->n);
+  }
+  const uint64_t total = off[nsteps];
+  if (total && (!partner || !y || !rho_partner)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
+  if (total >= ((uint64_t)1 << 30)) return fail(SVILS_ERR_UNSUPPORTED, "%s: more than 2^30 entries in one call", name);
+  const uint32_t n = h->n, K = h->k;
+  if (total && h->h_adj.empty()) {   // the link bits come back once per graph, for handles that take star steps
+    std::vector<uint32_t> bits((size_t)n * h->nw);
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipMemcpy(bits.data(), h->adj, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    h->h_adj.swap(bits);
+  }
+  // checked before anything is enqueued; seen[j] = s + 1: j is a partner of step s already (one owner per row)
+  std::vector<uint32_t> seen(n, 0);
+  for (uint32_t s = 0; s < nsteps; ++s)
+    for (uint64_t e = off[s]; e < off[s + 1]; ++e) {
+      const uint32_t a = start[s], j = partner[e];
+      const unsigned long long x = e - off[s];
+      if (j >= n || j == a) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u pairs node %u with %u (n = %u)", name, x, s, a, j, n);
+      if (seen[j] == s + 1) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u lists partner %u twice", name, x, s, j);
+      seen[j] = s + 1;
+      const uint32_t p = std::min(a, j), q = std::max(a, j), bit = 1u << (q & 31);
+      const size_t wd = (size_t)p * h->nw + (q >> 5);
+      if (h->h_skip[wd] & bit) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) is in the skip set", name, x, s, p, q);
+      if (((h->h_adj[wd] & bit) != 0) != (y[e] != 0))
+        return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) has y = %u, the graph says otherwise", name, x, s, p, q, (unsigned)y[e]);
+      if (!(rho_partner[e] > 0.0 && rho_partner[e] <= 1.0))
+        return fail(SVILS_ERR_ARG, "%s: rho_partner of entry %llu of step %u is not in (0, 1]", name, x, s);
+    }
+  // the call's lists in one copy through the pinned staging area, doubles first: rho_partner [total], rho_start, scale,
+  // rho_lambda [nsteps] each; then off [nsteps + 1] (as uint32), start [nsteps], partner [total]; then y [total] bytes
+  const size_t ndbl = (size_t)total + 3 * (size_t)nsteps;
+  const size_t nwords = 2 * ndbl + (size_t)nsteps + 1 + nsteps + (size_t)total + ((size_t)total + 3) / 4;
+  if (int rc = reserve_pin(h, nwords)) return rc;
+  double *const pd = reinterpret_cast<double *>(h->pin);
+  uint32_t *const pu = h->pin + 2 * ndbl;
+  if (total) std::memcpy(pd, rho_partner, total * sizeof(double));
+  std::memcpy(pd + total, rho_start, nsteps * sizeof(double));
+  std::memcpy(pd + total + nsteps, scale, nsteps * sizeof(double));
+  std::memcpy(pd + total + 2 * (size_t)nsteps, rho_lambda, nsteps * sizeof(double));
+  for (uint32_t s = 0; s <= nsteps; ++s) pu[s] = (uint32_t)off[s];
+  std::memcpy(pu + nsteps + 1, start, nsteps * sizeof(uint32_t));
+  if (total) std::memcpy(pu + 2 * (size_t)nsteps + 1, partner, total * sizeof(uint32_t));
+  if (total) std::memcpy(pu + 2 * (size_t)nsteps + 1 + total, y, total);
+  if (int rc = grow(h, &h->st_lists, &h->cap_lists, nwords)) return rc;
+  HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nwords * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipEventRecord(h->ev_copy, h->st));
+  h->copy_pending = true;
+  if (int rc = begin_steps(h)) return rc;
+  StarArgs x{};
+  x.K = K;
+  x.gamma = h->gamma;
+  x.elogpi = h->elogpi;
+  x.lam = h->lam;
+  x.elogbeta = h->elogbeta;
+  x.gtab = h->gtab;
+  x.logeps = std::log(h->epsilon);
+  x.alpha = h->alpha;
+  x.eta0 = h->eta0;
+  x.eta1 = h->eta1;
+  const double *dd = reinterpret_cast<const double *>(h->st_lists);
+  const uint32_t *du = h->st_lists + 2 * ndbl;
+  x.rho_partner = dd;
+  x.rho_start = dd + total;
+  x.scale = dd + total + nsteps;
+  x.rho_lambda = dd + total + 2 * (size_t)nsteps;
+  x.off = du;
+  x.start = du + nsteps + 1;
+  x.partner = du + 2 * (size_t)nsteps + 1;
+  x.y = reinterpret_cast<const uint8_t *>(du + 2 * (size_t)nsteps + 1 + total);
+  x.ctr = h->ctr;
+  // a chain is cut into launches of at most star_chain steps: no kernel runs long, and a step does the same wherever the cut falls
+  for (uint32_t s0 = 0; s0 < nsteps; s0 += h->star_chain) {
+    x.s0 = s0;
+    x.s1 = (uint32_t)std::min<uint64_t>(nsteps, (uint64_t)s0 + h->star_chain);
+    switch (h->w) {
+      case 1: hipLaunchKernelGGL((k_batch_star_chain<1, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
+      case 2: hipLaunchKernelGGL((k_batch_star_chain<2, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
+      case 4: hipLaunchKernelGGL((k_batch_star_chain<4, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
+      case 8: hipLaunchKernelGGL((k_batch_star_chain<8, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
+      case 16: hipLaunchKernelGGL((k_batch_star_chain<16, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
+      case 32: hipLaunchKernelGGL((k_batch_star_chain<32, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
+      case 64: hipLaunchKernelGGL((k_batch_star_chain<64, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
+      default: return fail(SVILS_ERR_UNSUPPORTED, "%s: no star kernel for W = %u", name, h->w);   // a missing kernel is an error
+    }
     HIPCHK(hipGetLastError());
   }
   return end_steps(h);

@@ -43,6 +43,7 @@ typedef struct {
   int32_t sampled;         // svih_batch_from_file: 0 = -batch; 1 -rnode, 2 -rpair, 3 -rpair -stratified (batch_device: on the device)
   int32_t nodelay;         // ... with -nodelay
   double tau0, kappa, nodetau0, nodekappa;   // their step sizes (svih_options_default: 1024, 0.9, 1024, 0.5)
+  double inf_epsilon;      // svih_infset_from_file: the chance of a non-informative step (svih_options_default: 1e-4)
 } svih_options;
 
 struct svih_setup {
@@ -85,6 +86,7 @@ void svih_options_default(svih_options *o, uint32_t n, uint32_t k) {
   o->lt_min_deg = 0; o->eta_type = 0; o->accuracy = 0; o->defer_gamma = 0;
   o->batch_device = 0; o->device = 0;
   const Env::Args d;
+  o->inf_epsilon = d.inf_epsilon;
   o->sampled = 0; o->nodelay = 0; o->tau0 = d.tau0; o->kappa = d.kappa; o->nodetau0 = d.nodetau0; o->nodekappa = d.nodekappa;
 }
 svih_setup *svih_setup_from_file(const char *path, const svih_options *o) { return make_setup(o, path, nullptr, 0); }
@@ -162,12 +164,18 @@ struct svih_batch {
   std::unique_ptr<MMSBBatch> eng;
 };
 
-svih_batch *svih_batch_from_file(const char *path, const svih_options *o) {
+// neighbors non-null: the -infset engine with the informative sets of that file
+static svih_batch *make_batch(const char *path, const svih_options *o, const char *neighbors) {
   static const char *eta_names[] = {"uniform", "fromdata", "sparse", "dense"};
   Env::Args a;
   a.n = o->n;
   a.k = o->k;
-  if (o->sampled) {
+  if (neighbors) {
+    a.infset = true;
+    a.host_loops = o->batch_device == 0;
+    a.inf_epsilon = o->inf_epsilon;
+    a.tau0 = o->tau0; a.kappa = o->kappa; a.nodetau0 = o->nodetau0; a.nodekappa = o->nodekappa;
+  } else if (o->sampled) {
     a.rnode = o->sampled == 1;
     a.rpair = o->sampled >= 2;
     a.stratified = o->sampled == 3;
@@ -188,14 +196,42 @@ svih_batch *svih_batch_from_file(const char *path, const svih_options *o) {
   b->env.reset(new Env(a));
   b->net.reset(new Network(*b->env));
   if (b->net->read(path) < 0) { delete b; return nullptr; }
+  if (neighbors && b->net->load_neighborhood_sets(neighbors)) { delete b; return nullptr; }
   b->env->n = b->net->n() - b->net->singles();
   if (svils_rc([&] { b->eng.reset(new MMSBBatch(*b->env, *b->net)); return 0; })) {   // svils_last_error() keeps the library's text
     delete b;
     return nullptr;
   }
-  b->eng->keep_schedule(o->sampled != 0);
+  b->eng->keep_schedule(o->sampled != 0 || neighbors);
   return b;
 }
+svih_batch *svih_batch_from_file(const char *path, const svih_options *o) { return make_batch(path, o, nullptr); }
+// the -infset engine (svih_batch_step steps it; its schedule: svih_batch_nstars / svih_batch_star)
+svih_batch *svih_infset_from_file(const char *path, const char *neighbors, const svih_options *o) { return make_batch(path, o, neighbors); }
+// -preprocess: the informative sets of the graph of `path` (declared n nodes) into `out` in the reference's format; 0, or -1
+int svih_preprocess(const char *path, uint32_t n, const char *out) {
+  Env::Args a;
+  a.n = n;
+  a.k = 2;
+  a.write_files = false;
+  Env env(a);
+  Network net(env);
+  if (net.read(path) < 0) return -1;
+  return net.write_neighborhood_sets(out) ? 0 : -1;
+}
+uint64_t svih_batch_nstars(const svih_batch *b) { return b->eng->stars().size(); }
+// out[5]: start, kind, scale, rho_start, rho_lambda; returns the number of entries and with non-null arrays copies them
+uint64_t svih_batch_star(const svih_batch *b, uint64_t i, double *out, uint32_t *partner, uint8_t *y, double *rho_partner) {
+  const MMSBBatch::Star &d = b->eng->stars()[i];
+  if (out) { out[0] = d.start; out[1] = d.kind; out[2] = d.scale; out[3] = d.rho_start; out[4] = d.rho_lambda; }
+  const size_t m = d.partner.size();
+  if (partner && m) memcpy(partner, d.partner.data(), m * sizeof(uint32_t));
+  if (y && m) memcpy(y, d.y.data(), m);
+  if (rho_partner && m) memcpy(rho_partner, d.rho_partner.data(), m * sizeof(double));
+  return m;
+}
+const uint32_t *svih_batch_node_counts(const svih_batch *b) { return b->eng->node_counts().data(); }
+const uint32_t *svih_batch_shuffled(const svih_batch *b) { return b->eng->shuffled_nodes().data(); }
 // the sampled-pair engines: nsteps iterations (drawn, then run); the schedule of every executed iteration
 int svih_batch_step(svih_batch *b, uint32_t nsteps) { return svils_rc([&] { b->eng->step(nsteps); return 0; }); }
 uint64_t svih_batch_nschedule(const svih_batch *b) { return b->eng->schedule().size(); }

@@ -23,6 +23,10 @@ class Env {
     // -nodelay: lambda learns from the first iteration (src/env.hh:487-490); -host-loops: the plain C++ loops instead of the device
     bool rnode = false, rpair = false, stratified = false, nodelay = false, host_loops = false;
     double scale = 1;                   // -scale (src/env.hh:357): only 1 is implemented
+    // -infset: informative-set SVI (FastAMM::infer, src/fastamm.cc:549-672); -preprocess: its pass over the graph that writes
+    // neighbors.bin (Network::set_neighborhood_sets, src/network.cc:558-686).  Both name the directory -infset (src/env.hh:523)
+    bool infset = false, preprocess = false;
+    double inf_epsilon = 0.0001;        // _inf_epsilon (src/fastamm.cc:18): library callers only
     bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
     bool load = false;
@@ -111,9 +115,11 @@ class Env {
   int comm_rfd;
   std::vector<int> comm_wfds;
   bool batch_mode, link_sampling, findk;
-  bool batch_device;                 // -batch-gpu, and -rnode / -rpair without -host-loops: MMSBBatch drives a svils_batch handle
+  bool batch_device;                 // -batch-gpu, and -rnode / -rpair / -infset without -host-loops: MMSBBatch drives a svils_batch handle
   bool randomnode, randompair, stratified, delaylearn;   // the sampled-pair engines (src/env.hh:485-501)
   bool sampled() const { return randomnode || randompair; }
+  bool infset, preprocess;           // -infset / -preprocess (src/env.hh:325, :436)
+  double inf_epsilon;                // the chance of a non-informative step
   uint32_t s;                        // their mini-batch size n / 2 (src/env.hh:321; -rpair only)
   bool gml, lcstats;
   bool strid;

@@ -6,7 +6,7 @@
 // estimate of the number of communities, also on the device), -gml / -lcstats (the
 // link communities of a fitted model's gamma.txt / lambda.txt, on the device) and the
 // reference's small all-pairs CPU engine -batch (plumbing only), with
-// -batch-gpu, -rnode, -rpair and -rpair -stratified the same model on the device; the
+// -batch-gpu, -rnode, -rpair, -rpair -stratified and -infset (with its -preprocess pass) the same model on the device; the
 // flags that select the reference's other engines are recognised and rejected
 // with a message instead of being silently ignored.  -adamic-adar (src/main.cc:173), which
 // the reference wires to two of those engines, is here an option of the link-prediction
@@ -56,7 +56,7 @@ static void forward_handler(int sig) {
 // name them: a mode reports the first one set among its own.
 enum : unsigned { F_BATCH = 1, F_GPUS = 2, F_KSHARD = 4, F_SHARDED = 8, F_MINIBATCH = 16, F_PAIRS = 32, F_RECOMMEND = 64, F_K2048 = 128,
                   F_RANKPAIRS = 256, F_RANKHELDOUT = 512, F_ADAMIC = 1024, F_LINKSAMPLING = 2048, F_FINDK = 4096, F_GML = 8192,
-                  F_LCSTATS = 16384 };
+                  F_LCSTATS = 16384, F_RNODE = 32768, F_RPAIR = 65536, F_STRATIFIED = 131072 };
 
 struct ToolMode {
   unsigned refuses;   // F_* bits
@@ -80,6 +80,11 @@ static const ToolMode kSampled = {           // -rnode / -rpair: an engine of it
         F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
 
+static const ToolMode kInfset = {            // -infset / -preprocess: an engine of its own on one GPU
+    F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
+        F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
+    "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
+
 // true (the refusal printed) when a flag `mode` refuses is set
 static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) {
   const struct { unsigned bit; bool set; const char *name; } flags[] = {
@@ -88,6 +93,9 @@ static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) 
       {F_FINDK, a.findk, "-findk"},
       {F_GML, a.gml, "-gml"},
       {F_LCSTATS, a.lcstats, "-lcstats"},
+      {F_RNODE, a.rnode, "-rnode"},
+      {F_RPAIR, a.rpair, "-rpair"},
+      {F_STRATIFIED, a.stratified, "-stratified"},
       {F_GPUS, a.gpus > 1, "-gpus N > 1"},
       {F_KSHARD, a.kshard, "-kshard"},
       {F_SHARDED, a.sharded, "-sharded"},
@@ -126,7 +134,13 @@ static void usage() {
           "\t-stratified\twith -rpair: mini-batches alternate between non-links and links (with -rnode or alone: refused)\n\n"
           "\t-nodelay\twith -rnode / -rpair: learn lambda from the first iteration (default: once iterations x n / 2 exceed the\n"
           "\t\t\tnumber of pairs)\n\n"
-          "\t-host-loops\twith -rnode / -rpair: the host CPU loops instead of the GPU (small graphs)\n\n"
+          "\t-host-loops\twith -rnode / -rpair / -infset: the host CPU loops instead of the GPU (small graphs)\n\n"
+          "\t-infset\t\tinference using informative set sampling: an iteration takes a random node, its links and the\n"
+          "\t\t\tnon-links -preprocess chose for it (rarely: 200 other non-links) and moves only their rows.  Reads neighbors.bin\n"
+          "\t\t\tof the working directory.  On the GPU, a report interval per launch chain (-k <= 256, -n <= 32768; without\n"
+          "\t\t\tone the run fails); give -rfreq (default 1: a report after every iteration)\n\n"
+          "\t-preprocess\tpreprocess to run informative set sampling: writes neighbors.bin (per node up to 100 two-hop\n"
+          "\t\t\tnon-neighbours) into the run's output directory and exits; host CPU, threaded\n\n"
           "\t-findk\t\testimate the number of communities (label propagation over a top-5 sparse gamma, on the GPU);\n"
           "\t\t\tpick -k for -link-sampling from the lines of its communities.txt.  Single GPU; -k only sets alpha = 1/k\n\n"
           "\t-gml\t\tgenerate a GML format file that visualizes link communities: reads gamma.txt and lambda.txt of the\n"
@@ -261,8 +275,11 @@ int main(int argc, char **argv) {
     else if (is("-stopthresh") || is("-inf") || is("-itype") || is("-groups-file")) {
       need(i); ++i;   // value flags of other engines: consumed, no effect on this path
     }
-    else if (is("-gen") || is("-ppc") || is("-orig") || is("-infset") || is("-single") ||
-             is("-preprocess") || is("-gp") || is("-disjoint") ||
+    else if (is("-infset")) { a.infset = true; }             // src/main.cc:189-190, :214-216: rfreq stays as it is
+    else if (is("-preprocess")) { a.preprocess = true; }
+    else if (is("-randzeros")) {}                            // ignored: the informative sets are the two-hop ones
+    else if (is("-gen") || is("-ppc") || is("-orig") || is("-single") ||
+             is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
       unsupported = true;
       unsupported_flag = f;
@@ -270,11 +287,28 @@ int main(int argc, char **argv) {
     // unknown flags are ignored, as in the reference
   }
   const bool sampled = a.rnode || a.rpair;
+  const bool infset = a.infset || a.preprocess;
+  if (infset && !unsupported) {                          // -infset / -preprocess (FastAMM): an engine of its own
+    const char *flag = a.preprocess ? "-preprocess" : "-infset";
+    if (refused(a, kInfset, flag)) return 2;
+    if (a.scale != 1) {
+      fprintf(stderr, "error: %s is not available with -scale other than 1 (subsampling of the non-links is not implemented)\n", flag);
+      return 2;
+    }
+    if (!a.preprocess && !a.host_loops && a.k > SVILS_BATCH_MAX_K) {   // the limits of svils_batch_create, before anything is read
+      fprintf(stderr, "error: -infset holds -k <= %d (SVILS_BATCH_MAX_K); -k %u is refused\n", SVILS_BATCH_MAX_K, a.k);
+      return 2;
+    }
+    if (!a.preprocess && !a.host_loops && a.n > SVILS_BATCH_MAX_N) {
+      fprintf(stderr, "error: -infset holds -n <= %d (SVILS_BATCH_MAX_N); -n %u is refused\n", SVILS_BATCH_MAX_N, a.n);
+      return 2;
+    }
+  }
   if (a.stratified && !sampled && !unsupported) {        // alone, or beside another engine: the reference's stratified engines
     unsupported = true;
     unsupported_flag = "-stratified";
   }
-  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || sampled)) {
+  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || sampled || infset)) {
     fprintf(stderr,
             "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk, -gml, -lcstats)%s%s.\n"
             "Use the reference build for the other engines.\n",
@@ -506,11 +540,31 @@ run:
     fprintf(stderr, "error: %s\n", e.what());
     return -1;
   }
-  if (a.batch || sampled) {                  // src/main.cc:354-358; -rnode / -rpair: :373-377
-    printf(sampled ? "+ running mmsb inference\n" : "+ running mmsb batch inference\n");
+  if (a.preprocess) {                        // src/network.cc:148-151: <outdir>/neighbors.bin, then exit
+    const std::string out = Env::file_str("/neighbors.bin");
+    if (!network.write_neighborhood_sets(out)) {
+      fprintf(stderr, "error: cannot write %s: %s\n", out.c_str(), strerror(errno));
+      return -1;
+    }
+    printf("+ wrote %s\n", out.c_str());
+    exit(0);
+  }
+  if (infset) {                              // src/network.cc:151-152, :689-696: neighbors.bin of the working directory
+    const int rc = network.load_neighborhood_sets("neighbors.bin");
+    if (rc == -1) {
+      fprintf(stderr, "error: cannot find neighbors.bin from preprocessing the network\n");
+      return -1;
+    }
+    if (rc) {
+      fprintf(stderr, "error: neighbors.bin does not belong to this network (run -preprocess on the same file and -n)\n");
+      return -1;
+    }
+  }
+  if (a.batch || sampled || infset) {        // src/main.cc:354-358; -rnode / -rpair: :373-377; -infset: :361-366
+    printf(infset ? "+ running mmsb inference (with infset network option)\n" : sampled ? "+ running mmsb inference\n" : "+ running mmsb batch inference\n");
     try {                                    // the device backends: a failed svils_batch_* call ends the run (no host fall-back)
       MMSBBatch mmsb(env, network);
-      if (sampled) mmsb.infer(); else mmsb.batch_infer();
+      if (sampled || infset) mmsb.infer(); else mmsb.batch_infer();
     } catch (const SvilsError &e) {
       fprintf(stderr, "error: %s\n", e.what());
       return -1;

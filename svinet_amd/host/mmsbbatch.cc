@@ -17,6 +17,7 @@ namespace {
 const double kNegInit = -2147483647.0;     // _max_t/_max_h/_max_v/_prev_h, src/mmsbinfer.cc:33-38
 const uint32_t kOnlineIterations = 50;     // src/env.hh:415
 const double kMeanChangeThresh = 0.00001;  // src/env.hh:337
+const uint32_t kNoninfSetsize = 200;       // _noninf_setsize, src/fastamm.cc:18
 
 // psi(x), x > 0: recurrence up to x >= 6, then the asymptotic series (double accurate)
 double digamma(double x) {
@@ -40,12 +41,22 @@ MMSBBatch::MMSBBatch(Env &env, Network &network)
       start_time_(time(0)) {
   fprintf(stdout, "+ initialization begin\n+ running inference on %d nodes\n", n_);
   Env::plog("inference n", n_);
+  if (env_.infset) {                                        // src/fastamm.cc:64-66, :85: the shuffle draws before the sampler
+    Env::plog("inf_epsilon", env_.inf_epsilon);
+    Env::plog("noninf_setsize", kNoninfSetsize);
+    shuffle_nodes();
+    nodec_.assign(n_, 0);
+  }
   init_heldout();
   printf("+ heldout sets created\n");
-  init_gamma();
-  for (uint32_t k = 0; k < k_; ++k) {                       // init_lambda, :389-397
-    lambda_[2 * k] = lambdanext_[2 * k] = env.eta0;
-    lambda_[2 * k + 1] = lambdanext_[2 * k + 1] = env.eta1;
+  if (env_.infset) {
+    init_gamma_lambda_infset();
+  } else {
+    init_gamma();
+    for (uint32_t k = 0; k < k_; ++k) {                     // init_lambda, :389-397
+      lambda_[2 * k] = lambdanext_[2 * k] = env.eta0;
+      lambda_[2 * k + 1] = lambdanext_[2 * k + 1] = env.eta1;
+    }
   }
   set_dir_exp();
   if (env_.batch_device) attach_device();
@@ -54,6 +65,8 @@ MMSBBatch::MMSBBatch(Env &env, Network &network)
     for (const char *f : {"/stats.txt", "/time.txt", "/convergence.txt", "/cmap.txt", "/training.txt",
                           "/training-edges.txt", "/logl.txt", "/modularity.txt"})
       fclose(open_or_die(Env::file_str(f), f + 1));
+    if (env_.infset)                                        // src/fastamm.cc:99, :241 (PRECISION_SAMPLE is off: both stay empty)
+      for (const char *f : {"/precision-pairs.txt", "/precision.txt"}) fclose(open_or_die(Env::file_str(f), f + 1));
     hf_ = open_or_die(Env::file_str("/heldout.txt"), "heldout");
     vf_ = open_or_die(Env::file_str("/validation.txt"), "validation");
   }
@@ -154,7 +167,7 @@ void MMSBBatch::set_sample(int s, bool heldout) {
   while (c0 < p || c1 < p) {
     Edge e;
     if (c0 == p) get_random_edge(false, true, 1, e);        // enough non-links: draw links only
-    else get_random_edge(heldout, false, 0, e);
+    else get_random_edge(heldout && !env_.infset, false, 0, e);   // FastAMM's edge_ok always looks at both maps (src/fastamm.hh:592-613)
     const bool y = network_.y(e.first, e.second);
     if ((!y && c0 < p) || (y && c1 < p)) {
       (y ? c1 : c0)++;
@@ -179,10 +192,11 @@ void MMSBBatch::init_heldout() {
   Env::plog("heldout ratio", env_.heldout_ratio);
   Env::plog("heldout edges (1s and 0s)", (uint32_t)heldout_map_.size());
   if (!env_.write_files) return;
-  FILE *f = open_or_die(Env::file_str("/heldout-edges.txt"), "heldout edges");
+  // (FastAMM names them -pairs, src/fastamm.cc:87-97)
+  FILE *f = open_or_die(Env::file_str(env_.infset ? "/heldout-pairs.txt" : "/heldout-edges.txt"), "heldout edges");
   fprintf(f, "%s\n", edgelist_s(heldout_edges_).c_str());
   fclose(f);
-  f = open_or_die(Env::file_str("/validation-edges.txt"), "validation edges");
+  f = open_or_die(Env::file_str(env_.infset ? "/validation-pairs.txt" : "/validation-edges.txt"), "validation edges");
   fprintf(f, "%s\n", edgelist_s(validation_edges_).c_str());
   fclose(f);
 }
@@ -383,7 +397,139 @@ void MMSBBatch::step_host(const Drawn &d) {                  // :513-642, proces
     }
 }
 
+// ---------------------------------------------------------------------------
+// -infset: FastAMM (src/fastamm.cc).  _iter and _lambda_start_iter are never initialised there: both are 0 here
+// ---------------------------------------------------------------------------
+void MMSBBatch::shuffle_nodes() {                           // :506-511; gsl_ran_shuffle: i from n - 1 down, j = uniform_int(i + 1)
+  shuffled_.resize(n_);
+  for (uint32_t i = 0; i < n_; ++i) shuffled_[i] = i;
+  for (uint32_t i = n_ - 1; i > 0; --i) std::swap(shuffled_[i], shuffled_[rng_.uniform_int(i + 1)]);
+}
+
+void MMSBBatch::init_gamma_lambda_infset() {                // :514-546 (k < 100 for gamma, k <= 100 for lambda)
+  const double vg = k_ < 100 ? 1.0 : 100.0 / k_, vl = k_ <= 100 ? 1.0 : 100.0 / k_;
+  for (size_t i = 0; i < gamma_.size(); ++i) gamma_[i] = ran_gamma(100 * vg, 0.01);
+  for (uint32_t k = 0; k < k_; ++k)
+    for (uint32_t t = 0; t < 2; ++t) lambda_[2 * k + t] = lambdanext_[2 * k + t] = (t ? env_.eta1 : env_.eta0) + ran_gamma(100 * vl, 0.01);
+}
+
+MMSBBatch::Star MMSBBatch::draw_star() {
+  Star d;
+  const uint32_t it = drawn_++;
+  d.kind = rng_.uniform() < env_.inf_epsilon ? 1 : 0;       // gsl_ran_bernoulli (:574)
+  const uint32_t a = d.start = rng_.uniform_int(n_);        // :917, :1054
+  auto take = [&](uint32_t j, bool y) {
+    d.partner.push_back(j);
+    d.y.push_back(y ? 1 : 0);
+  };
+  auto ok = [&](uint32_t j) { return edge_ok(a < j ? Edge(a, j) : Edge(j, a), false, false, 0); };
+  const std::vector<uint32_t> &zeros = network_.sparse_zeros(a);
+  if (d.kind == 0) {                                        // opt_process: the links (:925-979), then the informative set (:988-1041)
+    for (uint32_t j : network_.get_edges(a))
+      if (ok(j)) take(j, true);
+    for (uint32_t j : zeros)
+      if (ok(j)) take(j, false);
+    d.scale = (double)n_ / 2;                               // :587-588
+  } else {                                                  // opt_process_noninf (:1062-1090)
+    // inf_map.find(node)->second on a missing key reads as false with libstdc++: a node outside the informative set.
+    // The reference walks on until it has 200 pairs, round the shuffled order again if need be (a node then listed
+    // twice); here the walk ends after one lap, so that a partner is listed once
+    std::set<uint32_t> inf(zeros.begin(), zeros.end());
+    uint32_t q = (uint32_t)((int)((double)rng_.uniform_int(n_) / kNoninfSetsize)) * kNoninfSetsize;
+    for (uint32_t seen = 0; seen < n_ && d.partner.size() < kNoninfSetsize; ++seen, q = (q + 1) % n_) {
+      const uint32_t node = shuffled_[q];
+      if (node == a || network_.y(a, node) || !ok(node) || inf.count(node)) continue;
+      take(node, false);
+    }
+    d.scale = ((double)n_ * (double)n_) / (2 * env_.inf_epsilon * kNoninfSetsize);
+  }
+  // every row of the star moves with the step size of its own counter (:592-602); the counters are part of the draw
+  d.rho_start = pow(env_.nodetau0 + 1 + nodec_[a], -1 * env_.nodekappa);
+  nodec_[a]++;
+  for (uint32_t j : d.partner) {
+    d.rho_partner.push_back(pow(env_.nodetau0 + 1 + nodec_[j], -1 * env_.nodekappa));
+    nodec_[j]++;
+  }
+  d.rho_lambda = pow(env_.tau0 + 1 + (it - lambda_start_iter_ + 1), -1 * env_.kappa);   // :605 (nolambda is never set here)
+  return d;
+}
+
+// FPhiComp (src/fastamm.hh) normalises by log-sum-exp where PhiComp divides by the sum: the same fixed point at rounding
+// level, so phis() above stands for both
+void MMSBBatch::star_host(const Star &d) {
+  const uint32_t a = d.start, K = k_;
+  auto row_exp = [&](uint32_t i) {                          // set_dir_exp(a, _gamma, _Elogpi), :921, :943
+    const double *g = &gamma_[(size_t)i * K];
+    double s = 0;
+    for (uint32_t k = 0; k < K; ++k) s += g[k];
+    const double ps = digamma(s);
+    for (uint32_t k = 0; k < K; ++k) elogpi_[(size_t)i * K + k] = digamma(g[k]) - ps;
+  };
+  for (uint32_t k = 0; k < K; ++k) {                        // set_dir_exp(_lambda, _Elogbeta), :566
+    const double ps = digamma(lambda_[2 * k] + lambda_[2 * k + 1]);
+    elogbeta_[2 * k] = digamma(lambda_[2 * k]) - ps;
+    elogbeta_[2 * k + 1] = digamma(lambda_[2 * k + 1]) - ps;
+  }
+  row_exp(a);
+  std::vector<double> ta(K, 0.0), tj(K), lambdat(2 * (size_t)K, 0.0), phi1(K), phi2(K);
+  auto blend = [&](uint32_t i, double rho, const std::vector<double> &t) {   // :594-598
+    for (uint32_t k = 0; k < K; ++k)
+      gamma_[(size_t)i * K + k] = (1 - rho) * gamma_[(size_t)i * K + k] + rho * (env_.alpha + d.scale * t[k]);
+  };
+  for (size_t e = 0; e < d.partner.size(); ++e) {
+    const uint32_t j = d.partner[e], p = std::min(a, j), q = std::max(a, j);
+    const int y = d.y[e];
+    row_exp(j);
+    phis(p, q, y, phi1.data(), phi2.data());
+    const std::vector<double> &pa = p == a ? phi1 : phi2, &pj = p == a ? phi2 : phi1;
+    for (uint32_t k = 0; k < K; ++k) {
+      ta[k] += pa[k];
+      tj[k] = pj[k];
+      lambdat[2 * k + (y ? 0 : 1)] += phi1[k] * phi2[k];
+    }
+    blend(j, d.rho_partner[e], tj);                         // a partner is listed once: its gammat is this pair's phi
+  }
+  blend(a, d.rho_start, ta);
+  if (d.rho_lambda >= 0)                                    // :604-616
+    for (uint32_t k = 0; k < K; ++k) {
+      lambda_[2 * k] = (1 - d.rho_lambda) * lambda_[2 * k] + d.rho_lambda * (env_.eta0 + d.scale * lambdat[2 * k]);
+      lambda_[2 * k + 1] = (1 - d.rho_lambda) * lambda_[2 * k + 1] + d.rho_lambda * (env_.eta1 + d.scale * lambdat[2 * k + 1]);
+    }
+}
+
+void MMSBBatch::step_stars(uint32_t nsteps) {
+  std::vector<Star> chunk(nsteps);
+  for (Star &d : chunk) d = draw_star();
+  if (!dev_) {
+    for (const Star &d : chunk) star_host(d);
+  } else if (nsteps) {
+    std::vector<uint32_t> start(nsteps), partner;
+    std::vector<uint64_t> off(nsteps + 1, 0);
+    std::vector<uint8_t> y;
+    std::vector<double> rp, rs(nsteps), sc(nsteps), rl(nsteps);
+    for (uint32_t s = 0; s < nsteps; ++s) {
+      const Star &d = chunk[s];
+      start[s] = d.start;
+      partner.insert(partner.end(), d.partner.begin(), d.partner.end());
+      y.insert(y.end(), d.y.begin(), d.y.end());
+      rp.insert(rp.end(), d.rho_partner.begin(), d.rho_partner.end());
+      off[s + 1] = partner.size();
+      rs[s] = d.rho_start;
+      sc[s] = d.scale;
+      rl[s] = d.rho_lambda;
+    }
+    if (int rc = svils_batch_step_star(dev_, nsteps, start.data(), off.data(), partner.data(), y.data(), rp.data(), rs.data(), sc.data(),
+                                       rl.data()))
+      device_failed("svils_batch_step_star", rc);
+    host_stale_ = true;
+  }
+  iter_ += nsteps;
+  if (keep_schedule_)
+    for (Star &d : chunk) stars_.push_back(std::move(d));
+}
+
 void MMSBBatch::step(uint32_t nsteps) {
+  if (env_.infset) return step_stars(nsteps);
   std::vector<Drawn> chunk(nsteps);
   for (Drawn &d : chunk) d = draw();
   if (!dev_) {
@@ -419,7 +565,9 @@ int MMSBBatch::infer() {
     if (env_.max_iterations && iter_ > env_.max_iterations) {
       printf("+ Quitting: reached max iterations.\n");
       Env::plog("maxiterations reached", true);
-      do_on_stop();                                          // as batch_infer(): a bounded run leaves its model
+      // The reference exits here without saving, MMSBInfer and FastAMM alike (src/fastamm.cc:559-563).  This build saves the
+      // model, for -infset as for -rnode / -rpair and batch_infer(): a bounded run leaves usable output
+      do_on_stop();
       return 0;
     }
     // drawing never depends on the state: everything up to the next report goes to the device in one call

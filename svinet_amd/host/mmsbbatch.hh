@@ -19,6 +19,14 @@
 // stream (get_subsample, :1912-1945) and never depend on the state, so a whole report interval is drawn first and handed
 // to the device in one call (svils_batch_step_node / svils_batch_step_pairs); -host-loops runs the restated loops instead.
 //
+// -infset (Env::infset) runs FastAMM::infer() (src/fastamm.cc:549-672) on the same object: informative-set sampling.  An
+// iteration is a star -- a random start node with its links and its informative non-links (the set -preprocess wrote
+// for it, Network::sparse_zeros), or with chance 1e-4 up to 200 non-informative non-links -- and moves only the rows of
+// the star, each with the step size of its own counter.  What differs from the engines above is here (the node shuffle
+// before the held-out sampler, init_gamma / init_lambda of :514-546, the draw, the restated step); the samplers, the
+// fixed point, the likelihoods, the stop rule and the writers are the ones above.  A whole report interval is drawn
+// first, counters and step sizes included, and handed to the device in one svils_batch_step_star call.
+//
 // Seam mirrored:   MMSBInfer mmsb(env, network);  mmsb.batch_infer();
 //
 // Where the reference reads members it never initialises (`_iter`, `_ones_prob`,
@@ -69,6 +77,20 @@ class MMSBBatch {
   const std::vector<Drawn> &schedule() const { return schedule_; }
   // the pairs of a node's mini-batch (get_randomnode_edges, :1867-1876), [m][2]
   std::vector<uint32_t> node_pairs(uint32_t a) const;
+  // -infset: one drawn iteration of FastAMM::infer -- the start node, kind 0 (its links and informative non-links,
+  // opt_process) or 1 (non-informative non-links, opt_process_noninf), the partners in the reference's order with the
+  // pair's y and the partner's step size, the start node's step size, scale and lambda's step size
+  struct Star {
+    uint32_t start = 0;
+    int kind = 0;
+    std::vector<uint32_t> partner;
+    std::vector<uint8_t> y;
+    std::vector<double> rho_partner;
+    double rho_start = 0, scale = 0, rho_lambda = -1;
+  };
+  const std::vector<Star> &stars() const { return stars_; }               // with keep_schedule: every executed iteration
+  const std::vector<uint32_t> &node_counts() const { return nodec_; }     // _nodec: times a node's row was moved
+  const std::vector<uint32_t> &shuffled_nodes() const { return shuffled_; }
 
   uint32_t n() const { return n_; }
   uint32_t k() const { return k_; }
@@ -127,6 +149,14 @@ class MMSBBatch {
   bool delay_reported_ = false;
   bool keep_schedule_ = false;
   std::vector<Drawn> schedule_;
+  // -infset (FastAMM, src/fastamm.cc)
+  void shuffle_nodes();                                   // :506-511
+  void init_gamma_lambda_infset();                        // :514-546
+  Star draw_star();                                       // :574-605 with the lists of opt_process / opt_process_noninf
+  void star_host(const Star &d);                          // :565-616, the restated loops
+  void step_stars(uint32_t nsteps);
+  std::vector<uint32_t> shuffled_, nodec_;
+  std::vector<Star> stars_;
   svils_batch *dev_ = nullptr;       // the device backend (null: host loops)
   bool host_stale_ = false;          // the device has swept since gamma_ / lambda_ were fetched
 };

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <thread>
 #include <vector>
 #include <string>
 
@@ -154,6 +155,86 @@ void Network::read_pairs(const int32_t *pairs, uint64_t nlines) {
   edges_.reserve(nlines);
   for (uint64_t i = 0; i < nlines; ++i) add_line((uint32_t)pairs[2 * i], (uint32_t)pairs[2 * i + 1]);
   set_env_variables();
+}
+
+std::vector<std::vector<uint32_t> > Network::neighborhood_sets() const {
+  const uint32_t n = declared_n_, limit = 100, per_visit = 10;   // src/network.cc:562, :630
+  std::vector<std::vector<uint32_t> > sets(n);
+  const uint32_t nthreads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  auto work = [&](uint32_t tid) {
+    std::vector<uint32_t> taken(n, UINT32_MAX);   // taken[p] == i: p is in node i's set
+    std::vector<char> exhausted;
+    for (uint32_t i = tid; i < n; i += nthreads) {
+      const std::vector<uint32_t> &v = adj_[i];
+      if (v.empty()) continue;
+      std::vector<uint32_t> &zeros = sets[i];
+      exhausted.assign(v.size(), 0);
+      uint32_t mm = 0, nexhausted = 0;
+      size_t j = 0;
+      do {
+        const uint32_t q = v[j];
+        if (q != i && !exhausted[j]) {
+          const std::vector<uint32_t> &u = adj_[q];
+          size_t k = 0;
+          uint32_t c = 0;
+          for (; k < u.size() && mm < limit; ++k) {   // every visit scans from the front (:618)
+            const uint32_t p = u[k];
+            if (p == i || taken[p] == i || y(i, p)) continue;
+            zeros.push_back(p);
+            taken[p] = i;
+            ++mm;
+            if (++c >= per_visit) break;             // k stays: a scan that ends here has not run off the end
+          }
+          if (k == u.size()) { exhausted[j] = 1; ++nexhausted; }
+        }
+        j = (j + 1) % v.size();
+      } while (mm < limit && nexhausted < v.size());
+    }
+  };
+  std::vector<std::thread> pool;
+  for (uint32_t t = 1; t < nthreads; ++t) pool.emplace_back(work, t);
+  work(0);
+  for (std::thread &t : pool) t.join();
+  return sets;
+}
+
+bool Network::write_neighborhood_sets(const std::string &path) const {
+  const std::vector<std::vector<uint32_t> > sets = neighborhood_sets();
+  FILE *f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  bool ok = true;
+  for (uint32_t i = 0; i < declared_n_; ++i) {
+    const uint64_t sz = sets[i].size();              // the reference writes a long unsigned: 8 bytes
+    ok = ok && fwrite(&i, sizeof i, 1, f) == 1 && fwrite(&sz, sizeof sz, 1, f) == 1;
+    if (sz) ok = ok && fwrite(sets[i].data(), sizeof(uint32_t), sz, f) == sz;
+  }
+  return fclose(f) == 0 && ok;
+}
+
+int Network::load_neighborhood_sets(const std::string &path) {
+  FILE *f = fopen(path.c_str(), "rb");
+  if (!f) return -1;
+  const uint32_t n = declared_n_;
+  std::vector<std::vector<uint32_t> > sets(n);
+  std::vector<uint32_t> seen(n, UINT32_MAX);
+  bool ok = true;
+  for (uint32_t i = 0; ok && i < n; ++i) {
+    uint32_t nid = 0;
+    uint64_t sz = 0;
+    ok = fread(&nid, sizeof nid, 1, f) == 1 && nid == i && fread(&sz, sizeof sz, 1, f) == 1 && sz < n;
+    if (!ok) break;
+    sets[i].resize(sz);
+    ok = !sz || fread(sets[i].data(), sizeof(uint32_t), sz, f) == sz;
+    for (uint32_t p : sets[i]) {
+      if (!ok) break;
+      ok = p < n && p != i && seen[p] != i && !y(i, p);
+      if (ok) seen[p] = i;
+    }
+  }
+  fclose(f);
+  if (!ok) return -2;
+  sparse_zeros_.swap(sets);
+  return 0;
 }
 
 void Network::deg_stats(uint32_t &max, double &avg) const {

@@ -45,6 +45,19 @@ class Network {
   // arithmetic), ones_prob/zeros_prob and eta0/eta1 from -eta-type
   void set_env_variables();
 
+  // -preprocess: Network::set_neighborhood_sets (src/network.cc:558-686).  Per node the neighbours are walked round-robin;
+  // a visit takes at most 10 not-yet-taken two-hop non-neighbours in the neighbour's adjacency order; a neighbour is
+  // exhausted once a scan runs off its end; the walk ends at 100 taken or when every neighbour is exhausted.  The nodes
+  // are independent and are spread over threads.  Returns node i's set at [i]
+  std::vector<std::vector<uint32_t> > neighborhood_sets() const;
+  // ... written as the reference writes them: per node its uint32 id, an 8-byte count, the uint32 ids.  false: cannot write
+  bool write_neighborhood_sets(const std::string &path) const;
+  // -infset: Network::load_neighborhood_sets (src/network.cc:689-719) from `path`.  0: loaded; -1: no such file; -2: the
+  // file does not belong to this graph (a node id out of order, an entry that is the node, a neighbour, listed twice or
+  // >= n, a short file): the reference asserts on some of these and runs on with the others
+  int load_neighborhood_sets(const std::string &path);
+  const std::vector<uint32_t> &sparse_zeros(uint32_t p) const { return sparse_zeros_[p]; }
+
  private:
   bool add_line(uint32_t id1, uint32_t id2);
   bool intern(uint32_t id, uint32_t *seq);
@@ -57,6 +70,7 @@ class Network {
   FlatIdMap id2seq_;          // external id -> sequence id
   FlatPairSet pair_set_;      // the links read so far (both directions of a pair are one key)
   std::map<std::string, uint32_t> str2id_;
+  std::vector<std::vector<uint32_t> > sparse_zeros_;   // the informative sets of -infset (neighbors.bin)
 };
 
 }  // namespace svinet

@@ -22,7 +22,8 @@ class Options(C.Structure):
                 ("heldout_ratio", C.c_double), ("link_thresh", C.c_double),
                 ("lt_min_deg", C.c_uint32), ("eta_type", C.c_int32), ("accuracy", C.c_int32), ("defer_gamma", C.c_int32),
                 ("batch_device", C.c_int32), ("device", C.c_int32), ("sampled", C.c_int32), ("nodelay", C.c_int32),
-                ("tau0", C.c_double), ("kappa", C.c_double), ("nodetau0", C.c_double), ("nodekappa", C.c_double)]
+                ("tau0", C.c_double), ("kappa", C.c_double), ("nodetau0", C.c_double), ("nodekappa", C.c_double),
+                ("inf_epsilon", C.c_double)]
 
 
 _lib = None
@@ -205,6 +206,11 @@ class BatchEngine:
     without a HIP device, never the host loops instead."""
 
     _SAMPLED = 0
+    _STEP_SIZES = ("tau0", "kappa", "nodetau0", "nodekappa")   # the keyword arguments beyond the named ones
+
+    def _open(self, L, path, o):
+        """the engine's handle (a subclass with another constructor of the host library overrides this)"""
+        return L.svih_batch_from_file(os.fsencode(path), C.byref(o))
 
     def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, eta_type="uniform", on_device=False, device=0, nodelay=False,
                  **step_sizes):
@@ -225,17 +231,27 @@ class BatchEngine:
             L.svih_batch_step.restype = C.c_int
             L.svih_batch_schedule.argtypes = [vp, u64, vp, vp]
             L.svih_batch_schedule.restype = u64
+            L.svih_infset_from_file.argtypes = [C.c_char_p, C.c_char_p, P(Options)]
+            L.svih_infset_from_file.restype = vp
+            L.svih_batch_nstars.argtypes = [vp]
+            L.svih_batch_nstars.restype = u64
+            L.svih_batch_star.argtypes = [vp, u64, vp, vp, vp, vp]
+            L.svih_batch_star.restype = u64
+            for name in ("node_counts", "shuffled"):
+                f = getattr(L, "svih_batch_" + name)
+                f.argtypes = [vp]
+                f.restype = P(u32)
             L._batch_ready = True
         o = Options()
         L.svih_options_default(C.byref(o), n, k)
         o.seed, o.heldout_ratio, o.eta_type = seed, heldout_ratio, ETA_TYPES[eta_type]
         o.batch_device, o.device = int(bool(on_device)), device
         o.sampled, o.nodelay = self._SAMPLED, int(bool(nodelay))
-        for key, value in step_sizes.items():   # tau0, kappa, nodetau0, nodekappa
-            if key not in ("tau0", "kappa", "nodetau0", "nodekappa"):
+        for key, value in step_sizes.items():
+            if key not in self._STEP_SIZES:
                 raise TypeError("unexpected argument %r" % key)
             setattr(o, key, value)
-        self._h = L.svih_batch_from_file(os.fsencode(path), C.byref(o))
+        self._h = self._open(L, path, o)
         if not self._h:
             if on_device:   # (as FindK: an unreadable file and a failed svils_batch_* call both end here)
                 err = _svils.load().svils_last_error().decode("utf-8", "replace")
@@ -318,6 +334,73 @@ class SampledEngine(BatchEngine):
             out.append(dict(node=int(head[0]), family=int(head[1]), pairs=pairs, scale=float(head[2]), rho_gamma=float(head[3]),
                             rho_lambda=float(head[4])))
         return out
+
+
+def preprocess(path, n, out):
+    """-preprocess: the informative sets of the graph of `path` (n declared nodes) written to `out` (neighbors.bin, the
+    reference's format: per node uint32 id, 8-byte count, uint32 ids)"""
+    L = load()
+    L.svih_preprocess.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p]
+    L.svih_preprocess.restype = C.c_int
+    if L.svih_preprocess(os.fsencode(path), n, os.fsencode(out)) != 0:
+        raise IOError("cannot read %r or write %r" % (path, out))
+
+
+def read_neighbors(path, n):
+    """the sets of a neighbors.bin -> list of n uint32 arrays"""
+    raw = open(path, "rb").read()
+    out, at = [], 0
+    for i in range(n):
+        node = int(np.frombuffer(raw, np.uint32, 1, at)[0])
+        count = int(np.frombuffer(raw, np.uint64, 1, at + 4)[0])
+        assert node == i
+        out.append(np.frombuffer(raw, np.uint32, count, at + 12).copy())
+        at += 12 + 4 * count
+    assert at == len(raw)
+    return out
+
+
+class InfsetEngine(BatchEngine):
+    """The -infset engine of the host library: the reference's FastAMM::infer (src/fastamm.cc:549-672), informative-set
+    sampling, with the sets of `neighbors` (a neighbors.bin of preprocess()).  on_device=False: its host loops
+    (-host-loops); on_device=True: the steps run through svils_batch_step_star on `device`, one call per step(nsteps).
+    schedule lists, per executed iteration, what was drawn: dict(start, kind (0 links + informative set, 1
+    non-informative), partner [m], y [m], rho_partner [m], rho_start, scale, rho_lambda); node_counts are the times every
+    node's row was moved, shuffled the node order the non-informative steps walk.  inf_epsilon: the chance of kind 1."""
+
+    _STEP_SIZES = BatchEngine._STEP_SIZES + ("inf_epsilon",)
+
+    def __init__(self, path, n, k, neighbors, on_device=False, **kw):
+        self._neighbors = neighbors
+        super().__init__(path, n, k, on_device=on_device, **kw)
+
+    def _open(self, L, path, o):
+        return L.svih_infset_from_file(os.fsencode(path), os.fsencode(self._neighbors), C.byref(o))
+
+    def sweep(self):
+        raise TypeError("an InfsetEngine steps; BatchEngine sweeps")
+
+    step = SampledEngine.step
+
+    @property
+    def schedule(self):
+        L, out = load(), []
+        for i in range(L.svih_batch_nstars(self._h)):
+            head = np.zeros(5)
+            m = L.svih_batch_star(self._h, i, head.ctypes.data, None, None, None)
+            partner, y, rho = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint8), np.zeros(m)
+            L.svih_batch_star(self._h, i, None, partner.ctypes.data, y.ctypes.data, rho.ctypes.data)
+            out.append(dict(start=int(head[0]), kind=int(head[1]), partner=partner, y=y, rho_partner=rho, scale=float(head[2]),
+                            rho_start=float(head[3]), rho_lambda=float(head[4])))
+        return out
+
+    @property
+    def node_counts(self):
+        return _arr(load().svih_batch_node_counts(self._h), (self.n,), np.uint32)
+
+    @property
+    def shuffled(self):
+        return _arr(load().svih_batch_shuffled(self._h), (self.n,), np.uint32)
 
 
 class FindK:
