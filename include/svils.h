@@ -44,6 +44,7 @@ extern "C" {
                                     (additive, same version) svils_batch_*: -batch-gpu, all-pairs batch inference;
                                     (additive, same version) svils_batch_step_node / svils_batch_step_pairs: -rnode / -rpair, sampled-pair steps;
                                     (additive, same version) svils_batch_step_star / svils_batch_set_star_chain / svils_batch_get_expectations: -infset, informative-set steps;
+                                    (additive, same version) svils_orig_*: -orig, the full K x K blockmodel over all ordered pairs;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
                                     resource-allocation scores of pairs, the model-free baselines of svils_rank_links */
@@ -736,6 +737,61 @@ int svils_batch_set_star_chain(svils_batch *h, uint32_t max_steps);
  * sweep or svils_batch_set_state came since the last step call (what the next step call would do), else the ones the steps
  * maintain row by row.  Waits for the stream.  Either pointer may be null.  SVILS_ERR_ARG: no state */
 int svils_batch_get_expectations(svils_batch *h, double *elogpi, double *elogbeta);
+
+/* ---- -orig: the full K x K blockmodel (an ADDITION of ABI 8; a handle of its own) ---------------------------------------
+ * The reference's MMSBInferOrig::batch_infer (src/mmsbinferorig.cc:212-294; fixed point PhiComp2,
+ * src/mmsbinferorig.hh:110-220): the mixed-membership blockmodel of Airoldi et al. with a K x K matrix beta of block
+ * rates, coordinate ascent over every ORDERED pair (p, q), p != q.  One sweep: Elogpi = psi(max(gamma, 1e-30)) -
+ * psi(row sum) (:601-622); for every ordered pair outside the skip list, from phi1 = phi2 = 1 / K, up to 50 rounds of
+ *   next1[g] ~ exp(Elogpi_p[g] + sum_h L_y[g][h] phi2[h]),  next2[g] ~ exp(Elogpi_q[g] + sum_h L_y[g][h] phi1[h])
+ * (L_1 = log beta, L_0 = log(1 - beta); both from the OLD vectors, L_y NOT transposed for the second side, normalised by
+ * the plain sum), the old vectors saved at even rounds and the exit -- mean |next - old| < 1e-5 on both sides -- tested
+ * at odd ones; then gamma_next[p] += phi1, gamma_next[q] += phi2 on top of alpha, num += y phi1 phi2^T, tot += phi1
+ * phi2^T, and afterwards gamma = gamma_next, beta = num / tot.  The matrix-shaped parts run on v_mfma_f64_16x16x4_f64, a
+ * wavefront owning 16 pairs (svinet_amd/csrc/svils_orig.hip).  No floating-point atomics: two runs
+ * on the same device are bitwise equal and svils_orig_sweep(h, 3) equals three svils_orig_sweep(h, 1).
+ * Bounded launches: a sweep is cut into launches of whole p rows whose phi vectors fill at most 256 MiB -- at most
+ * max(n, 2^24 / KP) ordered pairs per launch, KP = 16 ceil(k / 16) -- so no launch grows with n^2.
+ * Degenerate cases are counted, never asserted: a pair whose normaliser is not > 0 is counted; a beta entry outside (0, 1)
+ * after the update (a block that saw only links or only non-links: num == tot bitwise, or num == 0) is counted and raises
+ * a device flag -- sweeps already in the queue then leave the state alone, and the next call that waits
+ * (svils_orig_get_state, svils_orig_pair_loglik) answers SVILS_ERR_UNSUPPORTED naming the cause; svils_orig_set_state
+ * lowers the flag.  Without a HIP device svils_orig_create answers SVILS_ERR_DEVICE ("no CPU path"); every other entry
+ * point answers a null handle the same way, and SVILS_ERR_ARG with a device. */
+#define SVILS_ORIG_MAX_K 64                   /* the instantiations of the pair kernel end here (svils_orig_variant) */
+#define SVILS_ORIG_MAX_N SVILS_BATCH_MAX_N    /* bit matrices for y and the skip list, as the batch handle's */
+typedef struct svils_orig svils_orig;
+/* SVILS_ERR_ARG: n < 2, k < 2, alpha <= 0; SVILS_ERR_UNSUPPORTED: k > SVILS_ORIG_MAX_K or n > SVILS_ORIG_MAX_N (checked
+ * before any device call) */
+int svils_orig_create(int device, uint32_t n, uint32_t k, double alpha, svils_orig **out);
+int svils_orig_destroy(svils_orig *h);
+/* links [nlinks][2], p < q < n: y(p, q) = y(q, p) = 1.  skip [nskip][2]: ORDERED pairs (p != q, either orientation; the
+ * two orientations are separate entries) the sweep leaves out.  SVILS_ERR_ARG: a self pair, a node >= n, a link with
+ * p > q, a pair repeated inside its list */
+int svils_orig_set_graph(svils_orig *h, const uint32_t *links, uint64_t nlinks, const uint32_t *skip, uint64_t nskip);
+/* p rows per launch from the next svils_orig_set_graph on: at most `rows` (never more than the bound above admits), 0 the
+ * default.  Results agree to rounding whatever the value: a column sum of gamma is added launch by launch */
+int svils_orig_set_launch_rows(svils_orig *h, uint32_t rows);
+/* gamma [n][k], beta [k][k].  SVILS_ERR_ARG: a gamma that is negative or not finite, a beta outside (0, 1) */
+int svils_orig_set_state(svils_orig *h, const double *gamma, const double *beta);
+/* either may be null; waits for the sweeps.  With the degenerate flag up the state of the last applied sweep is still
+ * copied out, then SVILS_ERR_UNSUPPORTED comes back */
+int svils_orig_get_state(svils_orig *h, double *gamma, double *beta);
+/* nsweeps sweeps, enqueued; nothing waits */
+int svils_orig_sweep(svils_orig *h, uint32_t nsweeps);
+/* edge_likelihood (:563-587) of pairs [m][2] (ordered, p != q) with y [m]: log sum_g sum_h pi_p[g] pi_q[h]
+ * (y ? beta_gh : 1 - beta_gh), pi = gamma / row sum.  No clamp.  Waits */
+int svils_orig_pair_loglik(svils_orig *h, const uint32_t *pairs, const uint8_t *y, uint64_t m, double *out);
+/* of the last svils_orig_sweep call (all its sweeps): pairs visited, rounds over all pairs, most rounds of one pair, pairs
+ * whose normaliser was not > 0; and since the last svils_orig_set_state: beta entries that left (0, 1).  Any pointer may
+ * be null; waits */
+int svils_orig_get_stats(svils_orig *h, uint64_t *pairs_done, uint64_t *rounds_total, uint32_t *rounds_max,
+                         uint64_t *bad_normalisers, uint64_t *bad_betas);
+/* device ms of the last sweep: Elogpi and the log tables, the pair pass, the reductions (-1 before the first sweep) */
+int svils_orig_get_timing(svils_orig *h, double ms[3]);
+/* host only: the instantiation of the pair kernel for k -- padded K, pairs per wavefront, 1 if the log tables live in LDS
+ * (0: in registers).  SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_ORIG_MAX_K */
+int svils_orig_variant(uint32_t k, uint32_t *padded_k, uint32_t *pairs_per_wave, uint32_t *tables_in_lds);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * Every tunable of the library is a row of ONE table: key, the SVILS_* environment variable that sets its default, the

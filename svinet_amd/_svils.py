@@ -44,7 +44,11 @@ EXPORTS = (
     "svils_batch_sweep", "svils_batch_pair_loglik", "svils_batch_get_stats", "svils_batch_get_timing", "svils_batch_variant",
     "svils_batch_step_node", "svils_batch_step_pairs", "svils_batch_step_star", "svils_batch_set_star_chain",
     "svils_batch_get_expectations",
+    "svils_orig_create", "svils_orig_destroy", "svils_orig_set_graph", "svils_orig_set_state", "svils_orig_get_state",
+    "svils_orig_sweep", "svils_orig_pair_loglik", "svils_orig_get_stats", "svils_orig_get_timing", "svils_orig_variant",
+    "svils_orig_set_launch_rows",
 )
+ORIG_MAX_K, ORIG_MAX_N = 64, 32768      # SVILS_ORIG_MAX_K, SVILS_ORIG_MAX_N
 BATCH_MAX_K, BATCH_MAX_N = 256, 32768   # SVILS_BATCH_MAX_K, SVILS_BATCH_MAX_N
 BATCH_STAR_CHAIN_MAX = 1024             # SVILS_BATCH_STAR_CHAIN_MAX
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
@@ -205,6 +209,18 @@ def load():
     L.svils_batch_step_star.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.svils_batch_set_star_chain.argtypes = [vp, C.c_uint32]
     L.svils_batch_get_expectations.argtypes = [vp, vp, vp]
+    L.svils_orig_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(vp)]
+    L.svils_orig_destroy.argtypes = [vp]
+    L.svils_orig_set_graph.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+    L.svils_orig_set_state.argtypes = [vp, vp, vp]
+    L.svils_orig_get_state.argtypes = [vp, vp, vp]
+    L.svils_orig_sweep.argtypes = [vp, C.c_uint32]
+    L.svils_orig_pair_loglik.argtypes = [vp, vp, vp, C.c_uint64, vp]
+    L.svils_orig_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]
+    L.svils_orig_get_timing.argtypes = [vp, vp]
+    L.svils_orig_set_launch_rows.argtypes = [vp, C.c_uint32]
+    L.svils_orig_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):
@@ -736,6 +752,76 @@ class Batch:
     def close(self):
         if getattr(self, "_h", None):
             load().svils_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def orig_variant(k):
+    """svils_orig_variant: (padded K, pairs per wavefront, log tables in LDS) of the pair kernel of -orig for k; no device needed"""
+    kp, ppw, lds = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _chk(load().svils_orig_variant(k, C.byref(kp), C.byref(ppw), C.byref(lds)))
+    return kp.value, ppw.value, bool(lds.value)
+
+
+class Orig:
+    """One svils_orig handle: the body of MMSBInferOrig::batch_infer (the full K x K blockmodel, all ordered pairs) on the device."""
+
+    def __init__(self, n, k, alpha, device=0):
+        self._h = C.c_void_p()
+        self.n, self.k = n, k
+        _chk(load().svils_orig_create(device, n, k, alpha, C.byref(self._h)))
+
+    def set_graph(self, links, skip=()):
+        """links [m][2] with p < q; skip: ORDERED pairs left out in that orientation only"""
+        links = np.ascontiguousarray(links, dtype=np.uint32).reshape(-1, 2)
+        skip = np.ascontiguousarray(skip, dtype=np.uint32).reshape(-1, 2)
+        _chk(load().svils_orig_set_graph(self._h, links.ctypes.data, links.shape[0], skip.ctypes.data, skip.shape[0]))
+
+    def set_launch_rows(self, rows):
+        """p rows per launch of the pair pass from the next set_graph on (0: as many as the library's bound admits)"""
+        _chk(load().svils_orig_set_launch_rows(self._h, rows))
+
+    def set_state(self, gamma, beta):
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64).reshape(self.n, self.k)
+        beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(self.k, self.k)
+        _chk(load().svils_orig_set_state(self._h, gamma.ctypes.data, beta.ctypes.data))
+
+    def state(self, check=True):
+        """(gamma, beta); check=False returns them even where the degenerate flag makes svils_orig_get_state answer an error"""
+        g, b = np.empty((self.n, self.k)), np.empty((self.k, self.k))
+        rc = load().svils_orig_get_state(self._h, g.ctypes.data, b.ctypes.data)
+        if check or rc != -4:
+            _chk(rc)
+        return g, b
+
+    def sweep(self, nsweeps=1):
+        _chk(load().svils_orig_sweep(self._h, nsweeps))
+
+    def pair_loglik(self, pairs, y):
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        y = np.ascontiguousarray(y, dtype=np.uint8).reshape(-1)
+        assert y.shape[0] == pairs.shape[0]
+        out = np.empty(pairs.shape[0])
+        _chk(load().svils_orig_pair_loglik(self._h, pairs.ctypes.data, y.ctypes.data, pairs.shape[0], out.ctypes.data))
+        return out
+
+    def stats(self):
+        """(pairs visited, rounds over all pairs, most rounds of a pair, normalisers not > 0) of the last sweep() call, and the
+        beta entries that left (0, 1) since the state was set"""
+        a, b, c, d, e = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _chk(load().svils_orig_get_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
+        return a.value, b.value, c.value, d.value, e.value
+
+    def timing(self):
+        """device ms of the last sweep: Elogpi and log tables, pair pass, reductions"""
+        ms = np.zeros(3)
+        _chk(load().svils_orig_get_timing(self._h, ms.ctypes.data))
+        return ms
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().svils_orig_destroy(self._h)
             self._h = None
 
     __del__ = close

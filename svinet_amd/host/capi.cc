@@ -12,6 +12,7 @@
 #include "svils.h"
 #include "linksampling.hh"
 #include "mmsbbatch.hh"
+#include "mmsbinferorig.hh"
 #include "network.hh"
 #include "nmi.hh"
 
@@ -264,6 +265,60 @@ double svih_batch_eta1(const svih_batch *b) { return b->env->eta1; }
 double svih_batch_ones_prob(const svih_batch *b) { return b->env->ones_prob; }
 const uint32_t *svih_batch_edges(const svih_batch *b) { return &b->net->edges()[0].first; }
 uint32_t svih_batch_ones(const svih_batch *b) { return b->net->ones(); }
+
+// ---- the -orig engine (MMSBInferOrig): on_device 0 = the host loops, 1 = svils_orig_* on `device` ----
+struct svih_orig {
+  std::unique_ptr<Env> env;
+  std::unique_ptr<Network> net;
+  std::unique_ptr<MMSBInferOrig> eng;
+};
+svih_orig *svih_orig_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t itype,
+                               int32_t on_device, int32_t device) {
+  Env::Args a;
+  a.n = n;
+  a.k = k;
+  a.orig = true;
+  a.itype = itype;
+  a.host_loops = on_device == 0;
+  a.device = device;
+  a.rand_seed = seed;
+  a.hol_ratio = heldout_ratio;
+  a.write_files = false;
+  svih_orig *b = new svih_orig();
+  b->env.reset(new Env(a));
+  b->net.reset(new Network(*b->env));
+  if (b->net->read(path) < 0) { delete b; return nullptr; }
+  b->env->n = b->net->n() - b->net->singles();
+  if (svils_rc([&] { b->eng.reset(new MMSBInferOrig(*b->env, *b->net, itype)); return 0; })) {   // svils_last_error() keeps the library's text
+    delete b;
+    return nullptr;
+  }
+  return b;
+}
+void svih_orig_free(svih_orig *b) { delete b; }
+uint32_t svih_orig_n(const svih_orig *b) { return b->eng->n(); }
+uint32_t svih_orig_iter(const svih_orig *b) { return b->eng->iter(); }
+int svih_orig_gamma(svih_orig *b, double *out) {
+  return svils_rc([&] { memcpy(out, b->eng->gamma().data(), b->eng->gamma().size() * sizeof(double)); return 0; });
+}
+int svih_orig_beta(svih_orig *b, double *out) {
+  return svils_rc([&] { memcpy(out, b->eng->beta().data(), b->eng->beta().size() * sizeof(double)); return 0; });
+}
+uint64_t svih_orig_nheldout(const svih_orig *b) { return b->eng->heldout_edges().size() / 2; }
+const uint32_t *svih_orig_heldout(const svih_orig *b) { return b->eng->heldout_edges().data(); }
+uint64_t svih_orig_nvalidation(const svih_orig *b) { return b->eng->validation_edges().size() / 2; }
+const uint32_t *svih_orig_validation(const svih_orig *b) { return b->eng->validation_edges().data(); }
+uint64_t svih_orig_nrows(const svih_orig *b) { return b->eng->rows().size() / 8; }
+const double *svih_orig_rows(const svih_orig *b) { return b->eng->rows().data(); }
+uint64_t svih_orig_rounds_total(const svih_orig *b) { return b->eng->rounds_total(); }
+int svih_orig_sweep(svih_orig *b) { return svils_rc([&] { b->eng->sweep(); return 0; }); }   // < 0: a svils_error of the device backend
+int svih_orig_report(svih_orig *b) { return svils_rc([&] { b->eng->report(); return 0; }); }
+int svih_orig_set_state(svih_orig *b, const double *gamma, const double *beta) {
+  return svils_rc([&] { b->eng->set_state(gamma, beta); return 0; });
+}
+void svih_orig_skip_also(svih_orig *b, const uint32_t *pairs, uint64_t m) { b->eng->skip_also(std::vector<uint32_t>(pairs, pairs + 2 * m)); }
+const uint32_t *svih_orig_edges(const svih_orig *b) { return &b->net->edges()[0].first; }
+uint32_t svih_orig_ones(const svih_orig *b) { return b->net->ones(); }
 
 // tests: how many of `count` values differ between the writers' fixed-point formatter (fixedfmt.hh) and printf's
 // "%.5f" / "%.3f" -- the values come as they are, the test chooses them

@@ -27,6 +27,10 @@ class Env {
     // neighbors.bin (Network::set_neighborhood_sets, src/network.cc:558-686).  Both name the directory -infset (src/env.hh:523)
     bool infset = false, preprocess = false;
     double inf_epsilon = 0.0001;        // _inf_epsilon (src/fastamm.cc:18): library callers only
+    // -orig: the full K x K blockmodel (MMSBInferOrig::batch_infer, src/mmsbinferorig.cc:212-294); -itype: its beta start
+    // (0: init_beta1, > 0: init_beta2).  On the device unless -host-loops is given
+    bool orig = false;
+    int itype = 0;
     bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
     bool load = false;
@@ -120,6 +124,8 @@ class Env {
   bool sampled() const { return randomnode || randompair; }
   bool infset, preprocess;           // -infset / -preprocess (src/env.hh:325, :436)
   double inf_epsilon;                // the chance of a non-informative step
+  bool orig, orig_device;            // -orig; without -host-loops MMSBInferOrig drives a svils_orig handle
+  int itype;                         // -itype (src/main.cc:193-194), read by -orig alone
   uint32_t s;                        // their mini-batch size n / 2 (src/env.hh:321; -rpair only)
   bool gml, lcstats;
   bool strid;

@@ -6,7 +6,8 @@
 // estimate of the number of communities, also on the device), -gml / -lcstats (the
 // link communities of a fitted model's gamma.txt / lambda.txt, on the device) and the
 // reference's small all-pairs CPU engine -batch (plumbing only), with
-// -batch-gpu, -rnode, -rpair, -rpair -stratified and -infset (with its -preprocess pass) the same model on the device; the
+// -batch-gpu, -rnode, -rpair, -rpair -stratified and -infset (with its -preprocess pass) the same model on the device, and
+// -orig, the blockmodel with a full K x K matrix of block rates (MMSBInferOrig), on the device as well; the
 // flags that select the reference's other engines are recognised and rejected
 // with a message instead of being silently ignored.  -adamic-adar (src/main.cc:173), which
 // the reference wires to two of those engines, is here an option of the link-prediction
@@ -28,6 +29,8 @@
 #include "lcstats.hh"
 #include "linksampling.hh"
 #include "mmsbbatch.hh"
+#include "mmsbinferorig.hh"
+#include "util.hh"
 #include "network.hh"
 
 using namespace svinet;
@@ -81,6 +84,11 @@ static const ToolMode kSampled = {           // -rnode / -rpair: an engine of it
     "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
 
 static const ToolMode kInfset = {            // -infset / -preprocess: an engine of its own on one GPU
+    F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
+        F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
+    "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
+
+static const ToolMode kOrig = {              // -orig: an engine of its own on one GPU
     F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
         F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
@@ -141,6 +149,10 @@ static void usage() {
           "\t\t\tone the run fails); give -rfreq (default 1: a report after every iteration)\n\n"
           "\t-preprocess\tpreprocess to run informative set sampling: writes neighbors.bin (per node up to 100 two-hop\n"
           "\t\t\tnon-neighbours) into the run's output directory and exits; host CPU, threaded\n\n"
+          "\t-orig\t\tthe mixed-membership blockmodel with a full K x K matrix of block rates (Airoldi et al.): batch\n"
+          "\t\t\tvariational inference over all ordered pairs, on the GPU (-k <= 64, -n <= 32768; without one the run fails,\n"
+          "\t\t\t-host-loops runs the host CPU loops).  Needs -max-iterations N: N sweeps, then gamma.txt and beta.txt.\n"
+          "\t\t\t-itype 0 (default) starts beta at random, -itype 1 from the link density\n\n"
           "\t-findk\t\testimate the number of communities (label propagation over a top-5 sparse gamma, on the GPU);\n"
           "\t\t\tpick -k for -link-sampling from the lines of its communities.txt.  Single GPU; -k only sets alpha = 1/k\n\n"
           "\t-gml\t\tgenerate a GML format file that visualizes link communities: reads gamma.txt and lambda.txt of the\n"
@@ -272,13 +284,15 @@ int main(int argc, char **argv) {
     else if (is("-adamic-adar")) { a.adamic_adar = true; }
     else if (is("-recommend")) { need(i); a.recommend = atoi(argv[++i]); if (a.recommend == 0) a.recommend = -1; }
     else if (is("-init-communities")) { need(i); a.init_comm = true; a.init_comm_fname = argv[++i]; }   // src/main.cc:237-239
-    else if (is("-stopthresh") || is("-inf") || is("-itype") || is("-groups-file")) {
+    else if (is("-orig")) { a.orig = true; }                   // src/main.cc:187-188
+    else if (is("-itype")) { need(i); a.itype = atoi(argv[++i]); }   // :193-194: read by -orig alone
+    else if (is("-stopthresh") || is("-inf") || is("-groups-file")) {
       need(i); ++i;   // value flags of other engines: consumed, no effect on this path
     }
     else if (is("-infset")) { a.infset = true; }             // src/main.cc:189-190, :214-216: rfreq stays as it is
     else if (is("-preprocess")) { a.preprocess = true; }
     else if (is("-randzeros")) {}                            // ignored: the informative sets are the two-hop ones
-    else if (is("-gen") || is("-ppc") || is("-orig") || is("-single") ||
+    else if (is("-gen") || is("-ppc") || is("-single") ||
              is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
       unsupported = true;
@@ -304,11 +318,34 @@ int main(int argc, char **argv) {
       return 2;
     }
   }
+  if (a.orig && !unsupported) {                          // -orig (MMSBInferOrig): an engine of its own; refusals before anything is read or created
+    if (refused(a, kOrig, "-orig")) return 2;
+    const struct { bool set; const char *name; } more[] = {
+        {a.batch_gpu, "-batch-gpu"}, {a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.load, "-load"},
+        {a.val_load, "-load-validation"}, {a.test_load, "-load-test"}, {a.init_comm, "-init-communities"}, {a.scale != 1, "-scale"}};
+    for (const auto &m : more)
+      if (m.set) {
+        fprintf(stderr, kOrig.fmt, "-orig", m.name);
+        return 2;
+      }
+    if (a.max_iterations == 0) {
+      fprintf(stderr, "error: -orig needs -max-iterations N: the reference's loop never ends and its stop rule is compiled out\n");
+      return 2;
+    }
+    if (!a.host_loops && a.k > SVILS_ORIG_MAX_K) {       // the limits of svils_orig_create
+      fprintf(stderr, "error: -orig holds -k <= %d (SVILS_ORIG_MAX_K) unless -host-loops is given; -k %u is refused\n", SVILS_ORIG_MAX_K, a.k);
+      return 2;
+    }
+    if (!a.host_loops && a.n > SVILS_ORIG_MAX_N) {
+      fprintf(stderr, "error: -orig holds -n <= %d (SVILS_ORIG_MAX_N) unless -host-loops is given; -n %u is refused\n", SVILS_ORIG_MAX_N, a.n);
+      return 2;
+    }
+  }
   if (a.stratified && !sampled && !unsupported) {        // alone, or beside another engine: the reference's stratified engines
     unsupported = true;
     unsupported_flag = "-stratified";
   }
-  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || sampled || infset)) {
+  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || sampled || infset || a.orig)) {
     fprintf(stderr,
             "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk, -gml, -lcstats)%s%s.\n"
             "Use the reference build for the other engines.\n",
@@ -559,6 +596,17 @@ run:
       fprintf(stderr, "error: neighbors.bin does not belong to this network (run -preprocess on the same file and -n)\n");
       return -1;
     }
+  }
+  if (a.orig) {                              // src/main.cc:330-334 (Airoldi et al.)
+    printf("+ running mmsb orig inference\n");
+    try {                                    // the device backend: a failed svils_orig_* call ends the run (no host fall-back)
+      MMSBInferOrig mmsb(env, network, a.itype);
+      mmsb.batch_infer();
+    } catch (const SvilsError &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return -1;
+    }
+    exit(0);
   }
   if (a.batch || sampled || infset) {        // src/main.cc:354-358; -rnode / -rpair: :373-377; -infset: :361-366
     printf(infset ? "+ running mmsb inference (with infset network option)\n" : sampled ? "+ running mmsb inference\n" : "+ running mmsb batch inference\n");

@@ -1,0 +1,105 @@
+// mmsbinferorig.hh -- the reference's `-orig` engine: the mixed-membership blockmodel of Airoldi et al. with a full
+// K x K matrix of block rates, the only model of the package that can describe disassortative structure.
+//
+// `svinet -file F -n N -k K -orig` in the reference constructs MMSBInferOrig and runs MMSBInferOrig::batch_infer()
+// (src/main.cc:330-334, src/mmsbinferorig.cc:212-294): coordinate ascent over every ORDERED pair (p, q), p != q, the
+// fixed point of a pair being PhiComp2::update_phis_until_conv (src/mmsbinferorig.hh:110-226).  Two backends, chosen at
+// construction by Env::orig_device:
+//   device  (default)      every sweep and every pair likelihood through the svils_orig_* entry points of include/svils.h
+//                          (csrc/svils_orig.hip); the samplers, the starts, the sums in std::map order and the writers
+//                          stay here.  A failed svils_orig_* call throws SvilsError (util.hh); no HIP device is such a
+//                          failure -- there is no fall-back to the host loops.
+//   host    (-host-loops)  the reference's loops restated, single-threaded, as plumbing (what the CPU tests run).
+//
+// Seam mirrored:   MMSBInferOrig mmsb(env, network, itype);  mmsb.batch_infer();
+//
+// Quirks of the reference that are kept:
+//   - training skips only the HELD-OUT map, and only in the orientation the pair was drawn in (:231-235): the reverse
+//     orientation of a held-out pair and both orientations of the validation pairs are trained on;
+//   - both sides of a pair's update use L_y[g][h] with the other side's vector: the matrix is not transposed for the
+//     second side (:129-137);
+//   - the held-out and validation pairs are kept in the order drawn (no p < q), and the files list sequence ids.
+// Departures, all forced:
+//   - the reference's loop never ends and its stop rule is compiled out (:499-522): here -orig requires
+//     -max-iterations N, runs N sweeps, then writes gamma.txt (this project's format) and beta.txt (K lines of K values);
+//   - `_iter` is never initialised there; it starts at 0 here;
+//   - the reference never seeds this engine; -seed is honoured here when given;
+//   - the reference's printf of every beta entry is dropped;
+//   - gsl_ran_gamma: the same Marsaglia-Tsang recipe as mmsbbatch.cc over the same MT19937 stream with a polar Box-Muller
+//     Gaussian, so the distribution matches and the stream does not.
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <ctime>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "env.hh"
+#include "network.hh"
+#include "rng.hh"
+#include "svils.h"
+
+namespace svinet {
+
+class MMSBInferOrig {
+ public:
+  MMSBInferOrig(Env &env, Network &network, int itype);
+  ~MMSBInferOrig();
+
+  // env.max_iterations sweeps, a report every env.reportfreq of them, then gamma.txt and beta.txt; returns 0
+  int batch_infer();
+  void sweep();    // one pass of :217-271 (iter() advances)
+  void report();   // :276-290: groups.txt, communities.txt, summary.txt, a heldout.txt and a validation.txt row
+
+  uint32_t n() const { return n_; }
+  uint32_t k() const { return k_; }
+  uint32_t iter() const { return iter_; }
+  std::vector<double> &gamma() { fetch_state(); return gamma_; }   // [n][k]
+  std::vector<double> &beta() { fetch_state(); return beta_; }     // [k][k]
+  const std::vector<uint32_t> &heldout_edges() const { return heldout_edges_; }         // [H][2], as drawn
+  const std::vector<uint32_t> &validation_edges() const { return validation_edges_; }   // [V][2]
+  const std::vector<double> &rows() const { return rows_; }   // [rows][8]: which (0 held-out, 1 validation), iter, a, k, a0, k0, a1, k1
+  uint64_t rounds_total() const { return rounds_total_; }     // rounds over all pairs of the last sweep
+  double edge_likelihood(uint32_t p, uint32_t q, int y) const;   // :563-587, host
+  // library callers: another start, gamma [n][k] and beta [k][k] (as svils_orig_set_state checks them on the device)
+  void set_state(const double *gamma, const double *beta);
+  // -host-loops only (tests): also skip these ordered pairs
+  void skip_also(const std::vector<uint32_t> &pairs);
+
+ private:
+  void attach_device();
+  void fetch_state();
+  void init_heldout();
+  void set_sample(int s, bool heldout);
+  void init_gamma();
+  void init_beta1();
+  void init_beta2();
+  double ran_gamma(double a, double b);
+  double ran_gaussian();
+  void sweep_host();
+  void likelihood_row(const std::map<Edge, bool> &pairs, FILE *f, int which);
+  void compute_and_log_groups();
+  void save_model();
+  uint32_t duration() const { return (uint32_t)(time(0) - start_time_); }
+
+  Env &env_;
+  Network &network_;
+  uint32_t n_, k_;
+  int itype_;
+  uint32_t iter_ = 0;
+  double total_pairs_, ones_prob_;
+  GslMt19937 rng_;
+  std::map<Edge, bool> heldout_map_, validation_map_, extra_skip_;
+  std::vector<uint32_t> heldout_edges_, validation_edges_;
+  std::vector<double> gamma_, beta_, rows_;
+  uint64_t rounds_total_ = 0;
+  bool have_spare_ = false;
+  double spare_ = 0;
+  time_t start_time_;
+  FILE *hf_ = nullptr, *vf_ = nullptr;
+  svils_orig *dev_ = nullptr;   // the device backend (null: host loops)
+  bool host_stale_ = false;     // the device has swept since gamma_ / beta_ were fetched
+};
+
+}  // namespace svinet

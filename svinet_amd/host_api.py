@@ -301,6 +301,104 @@ class BatchEngine:
     __del__ = close
 
 
+class OrigEngine:
+    """The `-orig` engine of the host library (svinet_amd/host/mmsbinferorig.cc): the reference's MMSBInferOrig::batch_infer
+    (src/mmsbinferorig.cc:212-294), the blockmodel with a full K x K matrix of block rates.  on_device=True: the sweeps and
+    pair likelihoods run through svils_orig_* on `device` -- SvilsError without a HIP device, never the host loops
+    instead; on_device=False: the host loops (-host-loops)."""
+
+    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, itype=0, on_device=True, device=0):
+        L = load()
+        vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
+        if not hasattr(L, "_orig_ready"):
+            L.svih_orig_from_file.argtypes = [C.c_char_p, u32, u32, dbl, dbl, C.c_int32, C.c_int32, C.c_int32]
+            L.svih_orig_from_file.restype = vp
+            for name, res in (("free", None), ("n", u32), ("iter", u32), ("nheldout", u64), ("heldout", P(u32)),
+                              ("nvalidation", u64), ("validation", P(u32)), ("nrows", u64), ("rows", P(dbl)),
+                              ("rounds_total", u64), ("sweep", C.c_int), ("report", C.c_int), ("edges", P(u32)), ("ones", u32)):
+                f = getattr(L, "svih_orig_" + name)
+                f.argtypes = [vp]
+                f.restype = res
+            for name in ("gamma", "beta"):
+                f = getattr(L, "svih_orig_" + name)
+                f.argtypes = [vp, vp]
+                f.restype = C.c_int
+            L.svih_orig_set_state.argtypes = [vp, vp, vp]
+            L.svih_orig_set_state.restype = C.c_int
+            L.svih_orig_skip_also.argtypes = [vp, vp, u64]
+            L.svih_orig_skip_also.restype = None
+            L._orig_ready = True
+        self._h = L.svih_orig_from_file(os.fsencode(path), n, k, seed, heldout_ratio, itype, int(bool(on_device)), device)
+        if not self._h:
+            if on_device:
+                err = _svils.load().svils_last_error().decode("utf-8", "replace")
+                raise _svils.SvilsError(-2 if "no HIP device" in err else -1,
+                                        "OrigEngine: cannot read %r or the device backend failed: %s" % (path, err))
+            raise IOError("cannot read network %r" % (path,))
+        self.n, self.k = L.svih_orig_n(self._h), k
+        self.heldout = _arr(L.svih_orig_heldout(self._h), (L.svih_orig_nheldout(self._h), 2), np.uint32)
+        self.validation = _arr(L.svih_orig_validation(self._h), (L.svih_orig_nvalidation(self._h), 2), np.uint32)
+        self.edges = _arr(L.svih_orig_edges(self._h), (L.svih_orig_ones(self._h), 2), np.uint32)
+
+    def _state(self, name, shape):
+        out = np.empty(shape)
+        rc = getattr(load(), "svih_orig_" + name)(self._h, out.ctypes.data)
+        if rc < 0:
+            _svils._chk(rc)
+        return out
+
+    @property
+    def gamma(self):
+        return self._state("gamma", (self.n, self.k))
+
+    @property
+    def beta(self):
+        return self._state("beta", (self.k, self.k))
+
+    @property
+    def rows(self):
+        """[rows][8]: which (0 held-out, 1 validation), iter, mean, count, mean of the non-links, count, mean of the links, count"""
+        return _arr(load().svih_orig_rows(self._h), (load().svih_orig_nrows(self._h), 8), np.float64)
+
+    @property
+    def iter(self):
+        return load().svih_orig_iter(self._h)
+
+    @property
+    def rounds_total(self):
+        """host loops: the rounds over all pairs of the last sweep"""
+        return load().svih_orig_rounds_total(self._h)
+
+    def set_state(self, gamma, beta):
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64).reshape(self.n, self.k)
+        beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(self.k, self.k)
+        rc = load().svih_orig_set_state(self._h, gamma.ctypes.data, beta.ctypes.data)
+        if rc < 0:
+            _svils._chk(rc)
+
+    def skip_also(self, pairs):
+        """host loops: leave these ordered pairs out as well (tests)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        load().svih_orig_skip_also(self._h, pairs.ctypes.data, pairs.shape[0])
+
+    def sweep(self):
+        rc = load().svih_orig_sweep(self._h)
+        if rc < 0:
+            _svils._chk(rc)
+
+    def report(self):
+        rc = load().svih_orig_report(self._h)
+        if rc < 0:
+            _svils._chk(rc)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().svih_orig_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 class SampledEngine(BatchEngine):
     """The sampled-pair engines of the host library: the reference's MMSBInfer::infer (src/mmsbinfer.cc:459-740) for
     mode "rnode", "rpair" or "rpair-stratified".  on_device=False: its host loops (-host-loops); on_device=True: the steps
