@@ -789,6 +789,47 @@ int svils_orig_get_stats(svils_orig *h, uint64_t *pairs_done, uint64_t *rounds_t
                          uint64_t *bad_normalisers, uint64_t *bad_betas);
 /* device ms of the last sweep: Elogpi and the log tables, the pair pass, the reductions (-1 before the first sweep) */
 int svils_orig_get_timing(svils_orig *h, double ms[3]);
+/* ---- link prediction from a fitted -orig state (an ADDITION of ABI 8; nothing a sweep reads is written) ------------------
+ * score(p, c) = sum_g sum_h pi_p[g] beta[g][h] pi_c[h], pi_x = gamma_x / sum_k gamma_xk: the argument of the reference's
+ * edge_likelihood(p, c, 1) (src/mmsbinferorig.cc:563-587).  beta is not symmetric in general, so score(p, c) != score(c, p):
+ * "q among p's candidates" uses score(p, .), "p among q's candidates" uses score(q, .), and a scored pair (p, q) is scored
+ * in the orientation given.
+ * Candidates of p: every node c != p, except those where {p, c} is a link of the graph and NEITHER (p, c) NOR (c, p) is in
+ * the handle's skip list (a pair left out of training in either orientation IS a candidate: finding those is the point --
+ * the rule of svils_predict_links).  Note what the reference's own skip list is: a held-out pair in the orientation drawn
+ * (:231-235); the reverse orientation and the validation pairs are trained on.  A caller that wants to rank held-out links
+ * hands svils_orig_set_graph both orientations of every pair it holds out (the command line's -clean-holdout).
+ * The contracts are those of svils_link_prob / svils_predict_links / svils_rank_links: nodes == NULL means all n nodes
+ * (nnodes 0 or n); topk is 1 .. SVILS_PREDICT_MAX_TOPK; order is score descending, ties by ascending id; empty slots are
+ * UINT32_MAX / -1.0; above, tied and ncand are counted over the candidates c != q (q itself need not be one); any output
+ * pointer of svils_orig_rank_links may be NULL.  The calls enqueue on the handle's stream behind the sweeps already there
+ * and synchronise; results are bitwise deterministic and a row does not depend on the other rows of the call.
+ * All three calls get their scores from ONE device function (the 64 x 64 fp64 MFMA tile of svils_predict_links, fed with
+ * pi_p^T beta -- summed over g ascending -- and pi): svils_orig_link_prob(p, q) and score[] of svils_orig_rank_links are
+ * bitwise the score svils_orig_predict_links lists for q in p's row, and a node listed at place j has
+ * above <= j <= above + tied.  Against a plain fp64 evaluation the score differs by rounding only (two dot products of at
+ * most 64 positive terms: relative error below 2e-14).
+ * The state is read as it is when the call runs: a copy of pi is rebuilt whenever svils_orig_set_state or svils_orig_sweep
+ * came since it was built.
+ * Device scratch, allocated on first use: pi, n x 16 ceil(k / 16) doubles (at most 16 MB; freed by svils_orig_destroy); one
+ * bit matrix of the excluded pairs, adj & ~(skip | skip^T), n x ceil(n / 32) words (at most 128 MB; built once per graph,
+ * freed by the next svils_orig_set_graph or svils_orig_destroy); and per internal batch of 8192 query rows at most 4 MB of
+ * query rows, 384 MB of partial top-k heaps (svils_orig_predict_links only; 63 MB at topk = 10), 24 MB of results and 200 KB
+ * of thresholds and counters (freed by svils_orig_destroy).
+ * SVILS_ERR_ARG: a null handle, no graph or no state, a node id >= n, a pair with p == q, topk == 0 or
+ * > SVILS_PREDICT_MAX_TOPK, a null array that is needed.  SVILS_ERR_UNSUPPORTED, with the message of svils_orig_get_state:
+ * a state whose degenerate flag is up. */
+/* score of pairs[npairs][2] (ordered, p != q, both < n) -> prob[npairs] */
+int svils_orig_link_prob(svils_orig *h, const uint32_t *pairs, uint64_t npairs, double *prob);
+/* the top-k candidates of each query node -> ids[nnodes][topk], scores[nnodes][topk] */
+int svils_orig_predict_links(svils_orig *h, const uint32_t *nodes, uint32_t nnodes, uint32_t topk, uint32_t *ids, double *scores);
+/* for every directed pair (p, q): above[i] = #{candidates c != q of p : score(p, c) > s}, tied[i] = #{... == s}, ncand[i] =
+ * #{candidates c != q}, score[i] = s = score(p, q) */
+int svils_orig_rank_links(svils_orig *h, const uint32_t *pairs, uint64_t npairs, uint32_t *above, uint32_t *tied, uint32_t *ncand,
+                          double *score);
+/* device ms of the last of these three calls, from behind the sweeps it waited for to its last kernel (hipEvents on the
+ * handle's stream; a call of several internal batches includes the host's turn-round between them); -1 before the first */
+int svils_orig_get_query_timing(svils_orig *h, double *ms);
 /* host only: the instantiation of the pair kernel for k -- padded K, pairs per wavefront, 1 if the log tables live in LDS
  * (0: in registers).  SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_ORIG_MAX_K */
 int svils_orig_variant(uint32_t k, uint32_t *padded_k, uint32_t *pairs_per_wave, uint32_t *tables_in_lds);

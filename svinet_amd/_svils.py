@@ -46,7 +46,8 @@ EXPORTS = (
     "svils_batch_get_expectations",
     "svils_orig_create", "svils_orig_destroy", "svils_orig_set_graph", "svils_orig_set_state", "svils_orig_get_state",
     "svils_orig_sweep", "svils_orig_pair_loglik", "svils_orig_get_stats", "svils_orig_get_timing", "svils_orig_variant",
-    "svils_orig_set_launch_rows",
+    "svils_orig_set_launch_rows", "svils_orig_link_prob", "svils_orig_predict_links", "svils_orig_rank_links",
+    "svils_orig_get_query_timing",
 )
 ORIG_MAX_K, ORIG_MAX_N = 64, 32768      # SVILS_ORIG_MAX_K, SVILS_ORIG_MAX_N
 BATCH_MAX_K, BATCH_MAX_N = 256, 32768   # SVILS_BATCH_MAX_K, SVILS_BATCH_MAX_N
@@ -220,6 +221,10 @@ def load():
                                        C.POINTER(C.c_uint64)]
     L.svils_orig_get_timing.argtypes = [vp, vp]
     L.svils_orig_set_launch_rows.argtypes = [vp, C.c_uint32]
+    L.svils_orig_link_prob.argtypes = [vp, vp, C.c_uint64, vp]
+    L.svils_orig_predict_links.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.svils_orig_rank_links.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
+    L.svils_orig_get_query_timing.argtypes = [vp, vp]
     L.svils_orig_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         f = getattr(L, name)
@@ -819,9 +824,55 @@ class Orig:
         _chk(load().svils_orig_get_timing(self._h, ms.ctypes.data))
         return ms
 
+    def link_prob(self, pairs):
+        """score(p, q) = pi_p^T beta pi_q of ORDERED node pairs [m][2] (p != q) -> float64[m] (svils_orig_link_prob)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        out = np.zeros(pairs.shape[0], dtype=np.float64)
+        _chk(load().svils_orig_link_prob(self._h, pairs.ctypes.data, pairs.shape[0], out.ctypes.data))
+        return out
+
+    def predict_links(self, topk, nodes=None):
+        """the top-k candidates of each query node (all nodes when None) by score(p, .) -> (ids uint32[nq, topk], scores
+        float64[nq, topk]), as Engine.predict_links; a link is a candidate if either orientation of it is in the skip list
+        (svils_orig_predict_links)"""
+        if nodes is None:
+            nq, ptr = self.n, None
+        else:
+            nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1)
+            nq, ptr = nodes.shape[0], nodes.ctypes.data
+        ids = np.zeros((nq, max(int(topk), 1)), dtype=np.uint32)
+        scores = np.zeros((nq, max(int(topk), 1)), dtype=np.float64)
+        _chk(load().svils_orig_predict_links(self._h, ptr, nq if nodes is not None else 0, int(topk), ids.ctypes.data,
+                                             scores.ctypes.data))
+        return ids, scores
+
+    def rank_links(self, pairs):
+        """where q stands among the candidates of p by score(p, .), for directed pairs [m][2] -> (above, tied, ncand uint32[m],
+        score float64[m]), as Engine.rank_links (svils_orig_rank_links)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        m = pairs.shape[0]
+        above, tied, ncand = (np.zeros(m, dtype=np.uint32) for _ in range(3))
+        score = np.zeros(m, dtype=np.float64)
+        _chk(load().svils_orig_rank_links(self._h, pairs.ctypes.data, m, above.ctypes.data, tied.ctypes.data, ncand.ctypes.data,
+                                          score.ctypes.data))
+        return above, tied, ncand, score
+
+    def query_timing(self):
+        """device ms of the last link_prob / predict_links / rank_links call (-1 before the first)"""
+        ms = C.c_double()
+        _chk(load().svils_orig_get_query_timing(self._h, C.byref(ms)))
+        return ms.value
+
+    @classmethod
+    def borrowed(cls, handle, n, k):
+        """a view of a svils_orig handle that someone else owns (the host engine's): close() leaves it alone"""
+        self = cls.__new__(cls)
+        self._h, self.n, self.k, self._borrowed = C.c_void_p(handle), n, k, True
+        return self
+
     def close(self):
-        if getattr(self, "_h", None):
+        if getattr(self, "_h", None) and not getattr(self, "_borrowed", False):
             load().svils_orig_destroy(self._h)
-            self._h = None
+        self._h = None
 
     __del__ = close

@@ -241,7 +241,7 @@ int svils_nbr_rank(svils_handle *h, int measure, const uint32_t *pairs, uint64_t
     hipLaunchKernelGGL(k_nbr_rank, dim3(std::min(m, s.blocks)), dim3(256), 0, h->stream, m, n, words, h->d.rowptr, h->pred.scol,
                        s.w[measure], s.pairs.p, s.bitmap, s.score.p, s.cnt.p);
     HIPCHK(hipGetLastError());
-    if (int rc = fetch_ranks(h, s.cnt.p, s.score.p, m, b, above, tied, ncand, score)) return rc;
+    if (int rc = fetch_ranks(h->stream, s.cnt.p, s.score.p, m, b, above, tied, ncand, score)) return rc;
   }
   return 0;
 }

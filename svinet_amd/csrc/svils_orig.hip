@@ -27,12 +27,13 @@
 // No floating-point atomics: every sum has one owner and a fixed order, so a sweep is bitwise reproducible.  Once the flag is
 // up the pair pass, the reductions and k_orig_final of every later sweep return at once: the state stays as it is.
 #include "svils_devutil.h"
-#include "svils_tool.h"
+#include "svils_orig.h"
+
+using namespace svils_impl;
 
 namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64;
 
 constexpr uint32_t MAX_ROUNDS = 50;                 // src/env.hh: online_iterations
 constexpr double MEAN_CHANGE_THRESH = 0.00001;      // src/env.hh: meanchangethresh
@@ -40,7 +41,6 @@ constexpr uint32_t TILE_PAIRS = 16;                 // pairs per wavefront: the 
 constexpr uint32_t TILES_PER_BLOCK = 16;            // four per wavefront
 constexpr size_t PHI_BYTES = (size_t)256 << 20;     // phi1 and phi2 of one launch
 constexpr uint32_t ACC_WAVES = 256;                 // wavefronts (and partial sums) of k_orig_acc
-enum { CTR_PAIRS, CTR_ROUNDS, CTR_MAXR, CTR_NORM, CTR_BETA, CTR_FLAG, CTR_PENDING, CTR_COUNT };
 
 inline uint32_t padded_k(uint32_t k) { return (k + 15) / 16 * 16; }
 // row stride of the transposed log tables: 16 (mod 32) doubles, so the four lane groups of an A operand read take two LDS passes
@@ -383,50 +383,11 @@ __global__ __launch_bounds__(256) void k_orig_pair_ll(uint64_t m, uint32_t K, co
 
 }  // namespace
 
-using namespace svils_impl;
-
-struct svils_orig : ToolHandle {
-  uint32_t n = 0, k = 0, kp = 0, ld = 0, nw = 0;
-  double alpha = 0;
-  // HANDLE scope
-  double *gamma = nullptr, *gnext = nullptr, *elogpi = nullptr;   // [n][k]
-  double *beta = nullptr;                                         // [k][k]
-  double *tabs = nullptr;                                         // [2][kp][ld]
-  double *nt = nullptr;                                           // [2][kp kp] num, tot in the C/D layout
-  double *part = nullptr;                                         // [ACC_WAVES][2][kp kp]
-  double *gtab = nullptr;                                         // [128][2] log_tab's table
-  u64 *ctr = nullptr;                                             // [CTR_COUNT]
-  // GRAPH scope
-  uint32_t *adj = nullptr, *skip = nullptr;                       // [n][nw]
-  double *phi1 = nullptr, *phi2 = nullptr;                        // [rows n][kp]
-  uint8_t *yv = nullptr;                                          // [rows n]
-  uint32_t *ll_pairs = nullptr;                                   // svils_orig_pair_loglik: grown on demand
-  uint8_t *ll_y = nullptr;
-  double *ll_out = nullptr;
-  uint64_t ll_cap = 0;
-  uint32_t rows = 0, nlaunch = 0;                                 // p rows per launch, launches per sweep
-  uint32_t rows_req = 0;                                          // svils_orig_set_launch_rows: 0 = as many as the bound admits
-  bool have_graph = false, have_state = false, timed = false;
-};
-
 namespace {
 
 void free_graph(svils_orig *h) {
   h->release(ToolHandle::GRAPH);
   h->have_graph = false;
-}
-
-// waits for the stream; a raised degenerate flag becomes an error
-int settle(svils_orig *h, const char *name) {
-  u64 c[CTR_COUNT] = {0};
-  HIPCHK(hipMemcpyAsync(c, h->ctr, sizeof c, hipMemcpyDeviceToHost, h->st));
-  HIPCHK(hipStreamSynchronize(h->st));
-  if (c[CTR_PENDING])
-    return fail(SVILS_ERR_UNSUPPORTED,
-                "%s: %llu block rate(s) left (0, 1) after a sweep (a block saw only links or only non-links; %llu pair(s) with a "
-                "normaliser not > 0); later sweeps were not applied",
-                name, c[CTR_BETA], c[CTR_NORM]);
-  return 0;
 }
 
 template <int KP, bool LREG>
@@ -548,6 +509,7 @@ int svils_orig_destroy(svils_orig *h) {
     if (h->ll_pairs) (void)hipFree(h->ll_pairs);
     if (h->ll_y) (void)hipFree(h->ll_y);
     if (h->ll_out) (void)hipFree(h->ll_out);
+    free_queries(h);
   }
   delete h;   // ~ToolHandle: waits for the stream, frees both scopes
   return 0;
@@ -626,6 +588,7 @@ int svils_orig_set_state(svils_orig *h, const double *gamma, const double *beta)
   HIPCHK(hipMemcpy(h->beta, beta, kk * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemset(h->ctr, 0, CTR_COUNT * sizeof(u64)));
   h->have_state = true;
+  ++h->state_gen;
   return 0;
 }
 
@@ -642,6 +605,7 @@ int svils_orig_sweep(svils_orig *h, uint32_t nsweeps) {
   if (int rc = check(h, "svils_orig_sweep")) return rc;
   if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "svils_orig_sweep: set the graph and the state first");
   HIPCHK(hipMemsetAsync(h->ctr, 0, 4 * sizeof(u64), h->st));   // pairs, rounds, most rounds, normalisers: of this call
+  ++h->state_gen;   // before the first launch: a sweep call that fails half way has changed the state too
   for (uint32_t s = 0; s < nsweeps; ++s)
     if (int rc = one_sweep(h)) return rc;
   return 0;

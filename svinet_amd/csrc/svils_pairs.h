@@ -1,5 +1,5 @@
 // svils_pairs.h -- what the queries about node pairs share: svils_predict.hip (svils_link_prob, svils_predict_links,
-// svils_rank_links) and svils_nbr.hip (svils_nbr_score, svils_nbr_rank).  The refusals of include/svils.h in one order, the
+// svils_rank_links), svils_nbr.hip (svils_nbr_score, svils_nbr_rank) and, through svils_pairtiles.h, svils_orig_predict.hip.  The refusals of include/svils.h in one order, the
 // search in a sorted CSR row (svils_impl::sorted_rows), and the way a batch of ranks goes back to the caller.
 #pragma once
 #include "svils_handle.h"
@@ -33,10 +33,9 @@ inline int check_pair_handle(svils_handle *h, const char *name, bool need_state)
   return 0;
 }
 
-// ... and the pair lists it refuses: pairs[npairs][2], two different nodes each
-inline int check_pairs(const svils_handle *h, const char *name, const uint32_t *pairs, uint64_t npairs) {
+// ... and the pair lists it refuses: pairs[npairs][2], two different nodes < n each
+inline int check_pairs(uint32_t n, const char *name, const uint32_t *pairs, uint64_t npairs) {
   if (npairs && !pairs) return fail(SVILS_ERR_ARG, "%s: null argument", name);
-  const uint32_t n = h->geo.n;
   for (uint64_t i = 0; i < npairs; ++i) {
     const uint32_t p = pairs[2 * i], q = pairs[2 * i + 1];
     if (p >= n || q >= n) return fail(SVILS_ERR_ARG, "%s: pair %llu = (%u, %u): node id >= n = %u", name, (unsigned long long)i, p, q, n);
@@ -45,14 +44,18 @@ inline int check_pairs(const svils_handle *h, const char *name, const uint32_t *
   return 0;
 }
 
+inline int check_pairs(const svils_handle *h, const char *name, const uint32_t *pairs, uint64_t npairs) {
+  return check_pairs(h->geo.n, name, pairs, npairs);
+}
+
 // The end of a batch of m ranks: cnt[m][3] = above, tied, ncand and score[m] on the device go to entries b .. b + m - 1 of
-// the caller's arrays, any of which may be null.  Waits for the handle's stream.
-inline int fetch_ranks(svils_handle *h, const uint32_t *cnt, const double *dscore, uint32_t m, uint64_t b, uint32_t *above,
+// the caller's arrays, any of which may be null.  Waits for the stream.
+inline int fetch_ranks(hipStream_t stream, const uint32_t *cnt, const double *dscore, uint32_t m, uint64_t b, uint32_t *above,
                        uint32_t *tied, uint32_t *ncand, double *score) {
   std::vector<uint32_t> ch(3 * (size_t)m);
-  HIPCHK(hipMemcpyAsync(ch.data(), cnt, ch.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-  if (score) HIPCHK(hipMemcpyAsync(score + b, dscore, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpyAsync(ch.data(), cnt, ch.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  if (score) HIPCHK(hipMemcpyAsync(score + b, dscore, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
   for (uint32_t i = 0; i < m; ++i) {
     if (above) above[b + i] = ch[3 * (size_t)i];
     if (tied) tied[b + i] = ch[3 * (size_t)i + 1];

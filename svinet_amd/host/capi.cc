@@ -272,14 +272,16 @@ struct svih_orig {
   std::unique_ptr<Network> net;
   std::unique_ptr<MMSBInferOrig> eng;
 };
+// clean_holdout: -clean-holdout (both orientations of every held-out and validation pair are left out of training)
 svih_orig *svih_orig_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t itype,
-                               int32_t on_device, int32_t device) {
+                               int32_t on_device, int32_t device, int32_t clean_holdout) {
   Env::Args a;
   a.n = n;
   a.k = k;
   a.orig = true;
   a.itype = itype;
   a.host_loops = on_device == 0;
+  a.clean_holdout = clean_holdout != 0;
   a.device = device;
   a.rand_seed = seed;
   a.hol_ratio = heldout_ratio;
@@ -319,6 +321,8 @@ int svih_orig_set_state(svih_orig *b, const double *gamma, const double *beta) {
 void svih_orig_skip_also(svih_orig *b, const uint32_t *pairs, uint64_t m) { b->eng->skip_also(std::vector<uint32_t>(pairs, pairs + 2 * m)); }
 const uint32_t *svih_orig_edges(const svih_orig *b) { return &b->net->edges()[0].first; }
 uint32_t svih_orig_ones(const svih_orig *b) { return b->net->ones(); }
+// the engine's svils_orig handle, for the link queries of include/svils.h (null: host loops); the engine keeps owning it
+void *svih_orig_device(const svih_orig *b) { return b->eng->device(); }
 
 // tests: how many of `count` values differ between the writers' fixed-point formatter (fixedfmt.hh) and printf's
 // "%.5f" / "%.3f" -- the values come as they are, the test chooses them

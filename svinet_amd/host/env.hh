@@ -30,6 +30,8 @@ class Env {
     // -orig: the full K x K blockmodel (MMSBInferOrig::batch_infer, src/mmsbinferorig.cc:212-294); -itype: its beta start
     // (0: init_beta1, > 0: init_beta2).  On the device unless -host-loops is given
     bool orig = false;
+    // -clean-holdout (with -orig): both orientations of every held-out and validation pair are left out of training
+    bool clean_holdout = false;
     int itype = 0;
     bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
@@ -126,6 +128,7 @@ class Env {
   double inf_epsilon;                // the chance of a non-informative step
   bool orig, orig_device;            // -orig; without -host-loops MMSBInferOrig drives a svils_orig handle
   int itype;                         // -itype (src/main.cc:193-194), read by -orig alone
+  bool clean_holdout;                // -clean-holdout: -orig trains on no orientation of a held-out or validation pair
   uint32_t s;                        // their mini-batch size n / 2 (src/env.hh:321; -rpair only)
   bool gml, lcstats;
   bool strid;

@@ -15,6 +15,7 @@
 #include <sstream>
 
 #include "fixedfmt.hh"
+#include "pairfiles.hh"
 #include "svils.h"
 #include "util.hh"
 
@@ -401,51 +402,21 @@ void LinkSampling::load_test() {
   }
 }
 
-// -predict-pairs / -rank-pairs: "id<TAB>id" lines of external ids, parsed like -load-test; an unknown id or a pair of one node
-// ends the run
-void LinkSampling::load_pairs_file(const char *flag, const std::string &fname, std::vector<int> *ext, std::vector<uint32_t> *seq) const {
-  FILE *f = fopen(fname.c_str(), "r");
-  if (!f) {
-    fprintf(stderr, "error: cannot read %s file %s\n", flag, fname.c_str());
-    exit(2);
-  }
-  int a, b;
-  while (fscanf(f, "%d %d", &a, &b) == 2) {
-    uint32_t p, q;
-    if (!network_.id2seq((uint32_t)a, &p) || !network_.id2seq((uint32_t)b, &q)) {
-      fprintf(stderr, "error: %s: id %d or id %d not found in original network\n", flag, a, b);
-      exit(2);
-    }
-    if (p == q) {
-      fprintf(stderr, "error: %s: pair %d %d is one node\n", flag, a, b);
-      exit(2);
-    }
-    ext->push_back(a);
-    ext->push_back(b);
-    seq->push_back(p);
-    seq->push_back(q);
-  }
-  fclose(f);
-}
-
 void LinkSampling::load_predict_pairs() {
   if (!env_.predict_pairs_fname.empty()) {
-    load_pairs_file("-predict-pairs", env_.predict_pairs_fname, &pp_ext_, &pp_seq_);
+    load_pairs_file(network_, "-predict-pairs", env_.predict_pairs_fname, &pp_ext_, &pp_seq_);
     Env::plog("link prediction: pairs to score:", (uint32_t)(pp_seq_.size() / 2));
   }
   if (!env_.rank_pairs_fname.empty()) {
-    load_pairs_file("-rank-pairs", env_.rank_pairs_fname, &rp_ext_, &rp_seq_);
+    load_pairs_file(network_, "-rank-pairs", env_.rank_pairs_fname, &rp_ext_, &rp_seq_);
     Env::plog("link prediction: pairs to rank:", (uint32_t)(rp_seq_.size() / 2));
   }
 }
 
-// link-prob.txt (one line per -predict-pairs line, in input order: id_a, id_b, the network's y, link_prob) and
-// recommendations.txt (one line per node in groups.txt order: the node's id, then id and score of each of its -recommend
-// best candidates; an empty slot reads -1 -1.000000000e+00).  Under -minibatch the device holds the nodes relabelled
-// (dev_of_): pairs and queries go through the relabelling and results come back through seq_of_, so ties among
-// recommendations break by device id there.
+// link-prob.txt and recommendations.txt (pairfiles.hh).  Under -minibatch the device holds the nodes relabelled (dev_of_):
+// pairs and queries go through the relabelling and results come back through seq_of_, so ties among recommendations break
+// by device id there.
 void LinkSampling::write_predictions() {
-  const std::vector<uint32_t> &s2i = network_.seq2id();
   auto dev = [&](uint32_t seq) { return dev_of_.empty() ? seq : dev_of_[seq]; };
   if (!pp_seq_.empty()) {
     const size_t m = pp_seq_.size() / 2;
@@ -453,10 +424,7 @@ void LinkSampling::write_predictions() {
     for (size_t i = 0; i < 2 * m; ++i) pairs[i] = dev(pp_seq_[i]);
     std::vector<double> prob(m);
     if (svils_link_prob(h_, pairs.data(), m, prob.data())) die_svils("svils_link_prob");
-    FILE *f = open_or_die(Env::file_str("/link-prob.txt"), "link-prob");
-    for (size_t i = 0; i < m; ++i)
-      fprintf(f, "%d\t%d\t%d\t%.9e\n", pp_ext_[2 * i], pp_ext_[2 * i + 1], network_.y(pp_seq_[2 * i], pp_seq_[2 * i + 1]) ? 1 : 0, prob[i]);
-    fclose(f);
+    write_link_prob(network_, pp_ext_, pp_seq_, prob);
   }
   if (env_.recommend) {
     const uint32_t k = env_.recommend;
@@ -466,17 +434,7 @@ void LinkSampling::write_predictions() {
     std::vector<double> sc((size_t)n_ * k);
     if (svils_predict_links(h_, nodes.empty() ? nullptr : nodes.data(), nodes.empty() ? 0 : n_, k, ids.data(), sc.data()))
       die_svils("svils_predict_links");
-    FILE *f = open_or_die(Env::file_str("/recommendations.txt"), "recommendations");
-    for (uint32_t i = 0; i < n_; ++i) {
-      fprintf(f, "%d", (int)s2i[i]);
-      for (uint32_t j = 0; j < k; ++j) {
-        const uint32_t q = ids[(size_t)i * k + j];
-        if (q == 0xffffffffu) fprintf(f, "\t-1\t%.9e", sc[(size_t)i * k + j]);
-        else fprintf(f, "\t%d\t%.9e", (int)s2i[dev_of_.empty() ? q : seq_of_[q]], sc[(size_t)i * k + j]);
-      }
-      fprintf(f, "\n");
-    }
-    fclose(f);
+    write_recommendations(network_, n_, k, ids, sc, dev_of_.empty() ? nullptr : &seq_of_);
   }
 }
 
@@ -499,82 +457,28 @@ bool LinkSampling::held_out(uint32_t p, uint32_t q) const {
   return validation_map_.count(e) || test_map_.count(e);
 }
 
-// link-ranks.txt (one line per -rank-pairs line, in input order) and heldout-ranks.txt (-rank-heldout: the y = 1 pairs of
-// validation-edges.txt in its order, then those of test-edges.txt): id_p, id_q, the network's y, the score of (p, q), the
-// mid-rank of q among p's candidates (above + 1 + tied / 2 of svils_rank_links, "%.3f") and their count, the same for p among
-// q's.  link-ranks-summary.txt: a header and one line of values over the directed pairs (p -> q, then q -> p, in file order)
-// of the lines with y = 1 whose pair is held out, i.e. no training link -- of heldout-ranks.txt when that is written, of
-// link-ranks.txt otherwise; a direction without a candidate is left out.  The means are sequential double sums in that
-// order.  Under -minibatch the pairs go through the relabelling like those of -predict-pairs.
+// link-ranks.txt (one line per -rank-pairs line, in input order), heldout-ranks.txt (-rank-heldout: the y = 1 pairs of
+// validation-edges.txt in its order, then those of test-edges.txt) and link-ranks-summary.txt -- of heldout-ranks.txt when
+// that is written, of link-ranks.txt otherwise (the formats: pairfiles.hh).  Under -minibatch the pairs go through the
+// relabelling like those of -predict-pairs.
 // With -adamic-adar the same lists are ranked by the neighbourhood scores of the training graph (svils_nbr_rank):
 // link-ranks-aa.txt / heldout-ranks-aa.txt have the columns of their namesakes with the Adamic-Adar score and the ranks by
 // it, and link-ranks-baselines.txt holds the summary's line once per measure -- model (the values of link-ranks-summary.txt),
 // cn, aa, ra -- over the same selection of pairs, accumulated by the same code.
 void LinkSampling::write_ranks(const std::function<void(const char *)> &mark) {
-  const std::vector<uint32_t> &s2i = network_.seq2id();
-  auto dev = [&](uint32_t seq) { return dev_of_.empty() ? seq : dev_of_[seq]; };
-  // the summary of one ranking: sequential sums over the directed pairs in file order
-  struct Sum {
-    uint64_t cnt = 0, h1 = 0, h10 = 0, h100 = 0;
-    double auc = .0, mrr = .0, chance = .0;
-    void add(uint32_t above, uint32_t tied, uint32_t ncand) {
-      const double ahead_mid = (double)above + 0.5 * (double)tied;   // candidates ahead of the link, ties halved
-      const uint64_t ahead = (uint64_t)above + tied;
-      ++cnt;
-      auc += 1.0 - ahead_mid / (double)ncand;
-      mrr += 1.0 / (ahead_mid + 1.0);
-      h1 += ahead < 1;
-      h10 += ahead < 10;
-      h100 += ahead < 100;
-      chance += 10.0 / (double)ncand;
-    }
-    void print(FILE *f) const {
-      const double c = cnt ? (double)cnt : 1.0;
-      fprintf(f, "%llu\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\n", (unsigned long long)cnt, auc / c, mrr / c, (double)h1 / c,
-              (double)h10 / c, (double)h100 / c, chance / c);
-    }
-  };
   enum { MODEL = -1 };   // or a svils_nbr_measure
   // ranks `seq` by `measure`, returns the summary; fname: the per-pair file (nullptr: the summary only)
   auto rank = [&](int measure, const char *fname, const std::vector<uint32_t> &seq, const std::vector<int> *ext) {
     const size_t m = seq.size() / 2;
-    std::vector<uint32_t> pairs(4 * m), above(2 * m), tied(2 * m), ncand(2 * m);
+    const std::vector<uint32_t> pairs = directed_pairs(seq, [&](uint32_t x) { return dev_of_.empty() ? x : dev_of_[x]; });
+    std::vector<uint32_t> above(2 * m), tied(2 * m), ncand(2 * m);
     std::vector<double> sc(2 * m);
-    for (size_t i = 0; i < m; ++i) {
-      pairs[4 * i] = pairs[4 * i + 3] = dev(seq[2 * i]);
-      pairs[4 * i + 1] = pairs[4 * i + 2] = dev(seq[2 * i + 1]);
-    }
     if (measure == MODEL) {
       if (svils_rank_links(h_, pairs.data(), 2 * m, above.data(), tied.data(), ncand.data(), sc.data())) die_svils("svils_rank_links");
     } else if (svils_nbr_rank(h_, measure, pairs.data(), 2 * m, above.data(), tied.data(), ncand.data(), sc.data())) {
       die_svils("svils_nbr_rank");
     }
-    Sum sum;
-    std::string o;
-    {
-      RowOut out(o);
-      char num[64];
-      for (size_t i = 0; i < m; ++i) {
-        const uint32_t p = seq[2 * i], q = seq[2 * i + 1];
-        const bool y = network_.y(p, q);
-        out.integer(ext ? (*ext)[2 * i] : (long)s2i[p], '\t');
-        out.integer(ext ? (*ext)[2 * i + 1] : (long)s2i[q], '\t');
-        out.integer(y ? 1 : 0, '\t');
-        snprintf(num, sizeof num, "%.9e\t", sc[2 * i]);
-        out.text(num);
-        for (size_t d = 2 * i; d < 2 * i + 2; ++d) {
-          out.fixed<3>((double)above[d] + 0.5 * (double)tied[d] + 1.0, '\t');
-          out.integer((long)ncand[d], d == 2 * i ? '\t' : '\n');
-          if (y && held_out(p, q) && ncand[d] != 0) sum.add(above[d], tied[d], ncand[d]);
-        }
-      }
-    }
-    if (fname) {
-      FILE *f = open_or_die(Env::file_str(fname), fname + 1);
-      fwrite(o.data(), 1, o.size(), f);
-      fclose(f);
-    }
-    return sum;
+    return write_rank_file(network_, fname, seq, ext, above, tied, ncand, sc, [&](uint32_t p, uint32_t q) { return held_out(p, q); });
   };
   // the list the summary is about: the held-out links when they are ranked, the -rank-pairs file otherwise
   std::vector<uint32_t> ho;
@@ -584,22 +488,19 @@ void LinkSampling::write_ranks(const std::function<void(const char *)> &mark) {
         if ((*t)[i + 2]) { ho.push_back((*t)[i]); ho.push_back((*t)[i + 1]); }
   const std::vector<uint32_t> &last = env_.rank_heldout ? ho : rp_seq_;
   const std::vector<int> *last_ext = env_.rank_heldout ? nullptr : &rp_ext_;
-  Sum model;
+  RankSum model;
   if (!env_.rank_pairs_fname.empty()) model = rank(MODEL, "/link-ranks.txt", rp_seq_, &rp_ext_);
   if (env_.rank_heldout) model = rank(MODEL, "/heldout-ranks.txt", ho, nullptr);
-  FILE *f = open_or_die(Env::file_str("/link-ranks-summary.txt"), "link-ranks-summary");
-  fprintf(f, "pairs\tauc\tmrr\thits1\thits10\thits100\tchance10\n");
-  model.print(f);
-  fclose(f);
+  write_rank_summary(model);
   mark("link-ranks.txt / heldout-ranks.txt");
   if (!env_.adamic_adar) return;
-  Sum aa;
+  RankSum aa;
   if (!env_.rank_pairs_fname.empty()) aa = rank(SVILS_NBR_AA, "/link-ranks-aa.txt", rp_seq_, &rp_ext_);
   if (env_.rank_heldout) aa = rank(SVILS_NBR_AA, "/heldout-ranks-aa.txt", ho, nullptr);
-  const Sum cn = rank(SVILS_NBR_CN, nullptr, last, last_ext), ra = rank(SVILS_NBR_RA, nullptr, last, last_ext);
-  f = open_or_die(Env::file_str("/link-ranks-baselines.txt"), "link-ranks-baselines");
+  const RankSum cn = rank(SVILS_NBR_CN, nullptr, last, last_ext), ra = rank(SVILS_NBR_RA, nullptr, last, last_ext);
+  FILE *f = open_or_die(Env::file_str("/link-ranks-baselines.txt"), "link-ranks-baselines");
   fprintf(f, "measure\tpairs\tauc\tmrr\thits1\thits10\thits100\tchance10\n");
-  const struct { const char *name; const Sum *sum; } rows[] = {{"model", &model}, {"cn", &cn}, {"aa", &aa}, {"ra", &ra}};
+  const struct { const char *name; const RankSum *sum; } rows[] = {{"model", &model}, {"cn", &cn}, {"aa", &aa}, {"ra", &ra}};
   for (const auto &row : rows) {
     fprintf(f, "%s\t", row.name);
     row.sum->print(f);

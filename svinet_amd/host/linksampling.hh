@@ -80,7 +80,6 @@ class LinkSampling {
   void load_validation();
   void load_test();                            // -load-test
   void load_predict_pairs();                   // -predict-pairs / -rank-pairs: read and checked before any device work
-  void load_pairs_file(const char *flag, const std::string &fname, std::vector<int> *ext, std::vector<uint32_t> *seq) const;
   void write_predictions();                    // link-prob.txt / recommendations.txt from the final state
   // link-ranks.txt / heldout-ranks.txt / link-ranks-summary.txt from the final state, then the -adamic-adar files; `mark` is
   // called with the names of the files just written (the trace of do_on_stop_impl)

@@ -7,7 +7,8 @@
 // link communities of a fitted model's gamma.txt / lambda.txt, on the device) and the
 // reference's small all-pairs CPU engine -batch (plumbing only), with
 // -batch-gpu, -rnode, -rpair, -rpair -stratified and -infset (with its -preprocess pass) the same model on the device, and
-// -orig, the blockmodel with a full K x K matrix of block rates (MMSBInferOrig), on the device as well; the
+// -orig, the blockmodel with a full K x K matrix of block rates (MMSBInferOrig), on the device as well (with -clean-holdout
+// it answers the link-prediction flags too); the
 // flags that select the reference's other engines are recognised and rejected
 // with a message instead of being silently ignored.  -adamic-adar (src/main.cc:173), which
 // the reference wires to two of those engines, is here an option of the link-prediction
@@ -88,9 +89,12 @@ static const ToolMode kInfset = {            // -infset / -preprocess: an engine
         F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
 
-static const ToolMode kOrig = {              // -orig: an engine of its own on one GPU
+// -orig: an engine of its own on one GPU.  The link-prediction flags are not in this table: -orig answers them from its final
+// state (svils_orig_link_prob / _predict_links / _rank_links), under the conditions of orig_queries_refused below.
+// -adamic-adar stays refused: the neighbourhood baselines need the training CSR of a -link-sampling handle
+static const ToolMode kOrig = {
     F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
-        F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
+        F_MINIBATCH | F_ADAMIC,
     "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
 
 // true (the refusal printed) when a flag `mode` refuses is set
@@ -120,6 +124,28 @@ static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) 
       fprintf(stderr, mode.fmt, flag, f.name);
       return true;
     }
+  return false;
+}
+
+// -predict-pairs / -recommend / -rank-pairs / -rank-heldout beside -orig: true (the refusal printed) unless -clean-holdout is
+// given and the run is on the device.  The first flag set is the one named
+static bool orig_queries_refused(const Env::Args &a) {
+  const struct { bool set; const char *name; } q[] = {{!a.predict_pairs_fname.empty(), "-predict-pairs"}, {a.recommend != 0, "-recommend"},
+                                                      {!a.rank_pairs_fname.empty(), "-rank-pairs"}, {a.rank_heldout, "-rank-heldout"}};
+  for (const auto &f : q) {
+    if (!f.set) continue;
+    if (!a.clean_holdout) {
+      fprintf(stderr,
+              "error: %s beside -orig needs -clean-holdout: the reference's sweep trains on the reverse orientation of every held-out "
+              "pair and on both orientations of the validation pairs, so ranks and scores of those links would measure memorisation\n",
+              f.name);
+      return true;
+    }
+    if (a.host_loops) {
+      fprintf(stderr, "error: %s is not available with -orig -host-loops (the link queries run on the GPU; there is no host path)\n", f.name);
+      return true;
+    }
+  }
   return false;
 }
 
@@ -153,6 +179,11 @@ static void usage() {
           "\t\t\tvariational inference over all ordered pairs, on the GPU (-k <= 64, -n <= 32768; without one the run fails,\n"
           "\t\t\t-host-loops runs the host CPU loops).  Needs -max-iterations N: N sweeps, then gamma.txt and beta.txt.\n"
           "\t\t\t-itype 0 (default) starts beta at random, -itype 1 from the link density\n\n"
+          "\t-clean-holdout\twith -orig: leave both orientations of every held-out and every validation pair out of training\n"
+          "\t\t\t(the reference leaves out the held-out pairs alone, and only in the orientation drawn).  With it -orig answers\n"
+          "\t\t\t-predict-pairs, -recommend, -rank-pairs and -rank-heldout from its final state, on the GPU: the score of\n"
+          "\t\t\t(p, q) is pi_p^T beta pi_q in the listed orientation, the files are those of -link-sampling runs;\n"
+          "\t\t\t-rank-heldout ranks the links of heldout-edges.txt, then those of validation-edges.txt\n\n"
           "\t-findk\t\testimate the number of communities (label propagation over a top-5 sparse gamma, on the GPU);\n"
           "\t\t\tpick -k for -link-sampling from the lines of its communities.txt.  Single GPU; -k only sets alpha = 1/k\n\n"
           "\t-gml\t\tgenerate a GML format file that visualizes link communities: reads gamma.txt and lambda.txt of the\n"
@@ -189,7 +220,7 @@ static void usage() {
           "\t\t\tthe final state's link probability sum_z pi_pz pi_qz beta_z; writes link-prob.txt (id, id, y, probability)\n\n"
           "\t-recommend <k>\tlink prediction: the k (1 .. 256) most probable links of every node that are not training links,\n"
           "\t\t\tfrom the final state; writes recommendations.txt (one line per node, groups.txt order).  Both flags\n"
-          "\t\t\tbelong to single-GPU -link-sampling runs with -k <= 2048\n\n"
+          "\t\t\tbelong to single-GPU -link-sampling runs with -k <= 2048, and to -orig -clean-holdout runs\n\n"
           "\t-rank-pairs <file>\tlink prediction: where each pair of <file> (\"id<TAB>id\" lines of external ids) stands among the\n"
           "\t\t\tcandidates -recommend chooses from, in both directions; writes link-ranks.txt (id_p, id_q, y, score, mid-rank of q\n"
           "\t\t\tamong p's candidates and their count, the same for p among q's) and link-ranks-summary.txt (per-link AUC, MRR, hits@k)\n\n"
@@ -285,6 +316,7 @@ int main(int argc, char **argv) {
     else if (is("-recommend")) { need(i); a.recommend = atoi(argv[++i]); if (a.recommend == 0) a.recommend = -1; }
     else if (is("-init-communities")) { need(i); a.init_comm = true; a.init_comm_fname = argv[++i]; }   // src/main.cc:237-239
     else if (is("-orig")) { a.orig = true; }                   // src/main.cc:187-188
+    else if (is("-clean-holdout")) { a.clean_holdout = true; }
     else if (is("-itype")) { need(i); a.itype = atoi(argv[++i]); }   // :193-194: read by -orig alone
     else if (is("-stopthresh") || is("-inf") || is("-groups-file")) {
       need(i); ++i;   // value flags of other engines: consumed, no effect on this path
@@ -320,6 +352,7 @@ int main(int argc, char **argv) {
   }
   if (a.orig && !unsupported) {                          // -orig (MMSBInferOrig): an engine of its own; refusals before anything is read or created
     if (refused(a, kOrig, "-orig")) return 2;
+    if (orig_queries_refused(a)) return 2;
     const struct { bool set; const char *name; } more[] = {
         {a.batch_gpu, "-batch-gpu"}, {a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.load, "-load"},
         {a.val_load, "-load-validation"}, {a.test_load, "-load-test"}, {a.init_comm, "-init-communities"}, {a.scale != 1, "-scale"}};
@@ -340,6 +373,10 @@ int main(int argc, char **argv) {
       fprintf(stderr, "error: -orig holds -n <= %d (SVILS_ORIG_MAX_N) unless -host-loops is given; -n %u is refused\n", SVILS_ORIG_MAX_N, a.n);
       return 2;
     }
+  }
+  if (a.clean_holdout && !a.orig) {                      // the other engines hold their pairs out in both orientations already
+    fprintf(stderr, "error: -clean-holdout belongs to -orig runs (it changes which pairs the sweep of that engine leaves out)\n");
+    return 2;
   }
   if (a.stratified && !sampled && !unsupported) {        // alone, or beside another engine: the reference's stratified engines
     unsupported = true;

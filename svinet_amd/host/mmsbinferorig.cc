@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "pairfiles.hh"
 #include "util.hh"
 
 namespace svinet {
@@ -38,7 +39,10 @@ MMSBInferOrig::MMSBInferOrig(Env &env, Network &network, int itype)
   Env::plog("ones_prob", ones_prob_);
   Env::plog("zeros_prob", 1 - ones_prob_);
   Env::plog("itype", itype_);
+  if (!env_.predict_pairs_fname.empty()) load_pairs_file(network_, "-predict-pairs", env_.predict_pairs_fname, &pp_ext_, &pp_seq_);
+  if (!env_.rank_pairs_fname.empty()) load_pairs_file(network_, "-rank-pairs", env_.rank_pairs_fname, &rp_ext_, &rp_seq_);
   init_heldout();
+  init_skip();
   printf("+ done heldout\n");
   init_gamma();
   if (itype_ == 0) init_beta1(); else init_beta2();
@@ -76,7 +80,7 @@ void MMSBInferOrig::attach_device() {
     l.push_back(std::min(e.first, e.second));
     l.push_back(std::max(e.first, e.second));
   }
-  for (const auto &it : heldout_map_) { s.push_back(it.first.first); s.push_back(it.first.second); }   // the drawn orientation alone
+  for (const Edge &e : skip_) { s.push_back(e.first); s.push_back(e.second); }
   if (int rc = svils_orig_set_graph(dev_, l.data(), l.size() / 2, s.data(), s.size() / 2)) throw_svils("svils_orig_set_graph", rc);
   if (int rc = svils_orig_set_state(dev_, gamma_.data(), beta_.data())) throw_svils("svils_orig_set_state", rc);
 }
@@ -126,6 +130,18 @@ void MMSBInferOrig::set_sample(int s, bool heldout) {
       map[e] = true;
     }
   }
+}
+
+// The ordered pairs a sweep leaves out.  The reference: the held-out pairs in the orientation drawn, nothing else
+// (:231-235).  -clean-holdout: both orientations of every held-out and every validation pair
+void MMSBInferOrig::init_skip() {
+  for (const auto &it : heldout_map_) skip_.insert(it.first);
+  if (!env_.clean_holdout) return;
+  for (const std::map<Edge, bool> *m : {&heldout_map_, &validation_map_})
+    for (const auto &it : *m) {
+      skip_.insert(it.first);
+      skip_.insert(Edge(it.first.second, it.first.first));
+    }
 }
 
 void MMSBInferOrig::init_heldout() {
@@ -219,7 +235,7 @@ void MMSBInferOrig::sweep_host() {
     for (uint32_t q = 0; q < n_; ++q) {
       if (p == q) continue;
       const Edge e(p, q);
-      if (heldout_map_.count(e) || extra_skip_.count(e)) continue;   // this orientation alone (:231-235)
+      if (skip_.count(e) || extra_skip_.count(e)) continue;   // an ordered pair: init_skip
       const bool y = network_.y(p, q);
       const double *lf = y ? l1.data() : l0.data();
       for (uint32_t g = 0; g < K; ++g) { phi1[g] = phi2[g] = 1.0 / K; o1[g] = o2[g] = 0; }
@@ -350,7 +366,49 @@ int MMSBInferOrig::batch_infer() {
   }
   fetch_state();
   if (env_.write_files) save_model();
+  if (env_.write_files && dev_) run_queries();
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// link queries of the final state (include/svils.h: svils_orig_link_prob / _predict_links / _rank_links)
+// ---------------------------------------------------------------------------
+void MMSBInferOrig::run_queries() {
+  if (!pp_seq_.empty()) {
+    std::vector<double> prob(pp_seq_.size() / 2);
+    if (int rc = svils_orig_link_prob(dev_, pp_seq_.data(), prob.size(), prob.data())) throw_svils("svils_orig_link_prob", rc);
+    write_link_prob(network_, pp_ext_, pp_seq_, prob);
+  }
+  if (env_.recommend) {
+    const uint32_t k = env_.recommend;
+    std::vector<uint32_t> ids((size_t)n_ * k);
+    std::vector<double> sc((size_t)n_ * k);
+    if (int rc = svils_orig_predict_links(dev_, nullptr, 0, k, ids.data(), sc.data())) throw_svils("svils_orig_predict_links", rc);
+    write_recommendations(network_, n_, k, ids, sc, nullptr);
+  }
+  if (env_.rank_pairs_fname.empty() && !env_.rank_heldout) return;
+  auto held_out = [&](uint32_t p, uint32_t q) {   // left out of training (both orientations are: -clean-holdout)
+    const Edge e(p, q), r(q, p);
+    return heldout_map_.count(e) || heldout_map_.count(r) || validation_map_.count(e) || validation_map_.count(r);
+  };
+  auto rank = [&](const char *fname, const std::vector<uint32_t> &seq, const std::vector<int> *ext) {
+    const size_t m = seq.size() / 2;
+    const std::vector<uint32_t> pairs = directed_pairs(seq, nullptr);
+    std::vector<uint32_t> above(2 * m), tied(2 * m), ncand(2 * m);
+    std::vector<double> sc(2 * m);
+    if (int rc = svils_orig_rank_links(dev_, pairs.data(), 2 * m, above.data(), tied.data(), ncand.data(), sc.data()))
+      throw_svils("svils_orig_rank_links", rc);
+    return write_rank_file(network_, fname, seq, ext, above, tied, ncand, sc, held_out);
+  };
+  std::vector<uint32_t> ho;   // the y = 1 lines of heldout-edges.txt, then of validation-edges.txt, as listed
+  if (env_.rank_heldout)
+    for (const std::vector<uint32_t> *t : {&heldout_edges_, &validation_edges_})
+      for (size_t i = 0; i + 1 < t->size(); i += 2)
+        if (network_.y((*t)[i], (*t)[i + 1])) { ho.push_back((*t)[i]); ho.push_back((*t)[i + 1]); }
+  RankSum model;
+  if (!env_.rank_pairs_fname.empty()) model = rank("/link-ranks.txt", rp_seq_, &rp_ext_);
+  if (env_.rank_heldout) model = rank("/heldout-ranks.txt", ho, nullptr);
+  write_rank_summary(model);
 }
 
 // ---------------------------------------------------------------------------

@@ -15,7 +15,11 @@
 //
 // Quirks of the reference that are kept:
 //   - training skips only the HELD-OUT map, and only in the orientation the pair was drawn in (:231-235): the reverse
-//     orientation of a held-out pair and both orientations of the validation pairs are trained on;
+//     orientation of a held-out pair and both orientations of the validation pairs are trained on.  -clean-holdout
+//     (Env::clean_holdout) is this project's way out: the same draws, but both orientations of every held-out and every
+//     validation pair are left out, on the device and in the host loops alike.  The link queries of a fitted state
+//     (-predict-pairs, -recommend, -rank-pairs, -rank-heldout: run_queries) are offered with it only -- ranks of held-out
+//     links the sweep has trained on would measure memorisation;
 //   - both sides of a pair's update use L_y[g][h] with the other side's vector: the matrix is not transposed for the
 //     second side (:129-137);
 //   - the held-out and validation pairs are kept in the order drawn (no p < q), and the files list sequence ids.
@@ -32,6 +36,7 @@
 #include <cstdio>
 #include <ctime>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -50,6 +55,11 @@ class MMSBInferOrig {
   // env.max_iterations sweeps, a report every env.reportfreq of them, then gamma.txt and beta.txt; returns 0
   int batch_infer();
   void sweep();    // one pass of :217-271 (iter() advances)
+  // after the last sweep, device backend only: link-prob.txt, recommendations.txt, link-ranks.txt / heldout-ranks.txt and
+  // link-ranks-summary.txt for the flags given, in the formats of pairfiles.hh, from the final state.  A score is
+  // score(p, q) = pi_p^T beta pi_q in the listed orientation; the second direction's ranks use score(q, .)
+  void run_queries();
+  svils_orig *device() const { return dev_; }   // null: host loops
   void report();   // :276-290: groups.txt, communities.txt, summary.txt, a heldout.txt and a validation.txt row
 
   uint32_t n() const { return n_; }
@@ -71,6 +81,7 @@ class MMSBInferOrig {
   void attach_device();
   void fetch_state();
   void init_heldout();
+  void init_skip();
   void set_sample(int s, bool heldout);
   void init_gamma();
   void init_beta1();
@@ -91,6 +102,9 @@ class MMSBInferOrig {
   double total_pairs_, ones_prob_;
   GslMt19937 rng_;
   std::map<Edge, bool> heldout_map_, validation_map_, extra_skip_;
+  std::set<Edge> skip_;         // the ordered pairs a sweep leaves out (init_skip)
+  std::vector<int> pp_ext_, rp_ext_;        // -predict-pairs / -rank-pairs: the ids as given, and as sequence ids
+  std::vector<uint32_t> pp_seq_, rp_seq_;
   std::vector<uint32_t> heldout_edges_, validation_edges_;
   std::vector<double> gamma_, beta_, rows_;
   uint64_t rounds_total_ = 0;

@@ -305,13 +305,18 @@ class OrigEngine:
     """The `-orig` engine of the host library (svinet_amd/host/mmsbinferorig.cc): the reference's MMSBInferOrig::batch_infer
     (src/mmsbinferorig.cc:212-294), the blockmodel with a full K x K matrix of block rates.  on_device=True: the sweeps and
     pair likelihoods run through svils_orig_* on `device` -- SvilsError without a HIP device, never the host loops
-    instead; on_device=False: the host loops (-host-loops)."""
+    instead; on_device=False: the host loops (-host-loops).  clean_holdout=True (-clean-holdout): both orientations of every
+    held-out and every validation pair are left out of training, not the held-out pairs in the drawn orientation alone.
+    link_prob / predict_links / rank_links query the current state on the device (svils_orig_link_prob / _predict_links /
+    _rank_links) and return what the _svils.Engine methods of the same names return."""
 
-    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, itype=0, on_device=True, device=0):
+    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, itype=0, on_device=True, device=0, clean_holdout=False):
         L = load()
         vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
         if not hasattr(L, "_orig_ready"):
-            L.svih_orig_from_file.argtypes = [C.c_char_p, u32, u32, dbl, dbl, C.c_int32, C.c_int32, C.c_int32]
+            L.svih_orig_from_file.argtypes = [C.c_char_p, u32, u32, dbl, dbl, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+            L.svih_orig_device.argtypes = [vp]
+            L.svih_orig_device.restype = vp
             L.svih_orig_from_file.restype = vp
             for name, res in (("free", None), ("n", u32), ("iter", u32), ("nheldout", u64), ("heldout", P(u32)),
                               ("nvalidation", u64), ("validation", P(u32)), ("nrows", u64), ("rows", P(dbl)),
@@ -328,7 +333,8 @@ class OrigEngine:
             L.svih_orig_skip_also.argtypes = [vp, vp, u64]
             L.svih_orig_skip_also.restype = None
             L._orig_ready = True
-        self._h = L.svih_orig_from_file(os.fsencode(path), n, k, seed, heldout_ratio, itype, int(bool(on_device)), device)
+        self._h = L.svih_orig_from_file(os.fsencode(path), n, k, seed, heldout_ratio, itype, int(bool(on_device)), device,
+                                        int(bool(clean_holdout)))
         if not self._h:
             if on_device:
                 err = _svils.load().svils_last_error().decode("utf-8", "replace")
@@ -339,6 +345,21 @@ class OrigEngine:
         self.heldout = _arr(L.svih_orig_heldout(self._h), (L.svih_orig_nheldout(self._h), 2), np.uint32)
         self.validation = _arr(L.svih_orig_validation(self._h), (L.svih_orig_nvalidation(self._h), 2), np.uint32)
         self.edges = _arr(L.svih_orig_edges(self._h), (L.svih_orig_ones(self._h), 2), np.uint32)
+
+    def _device(self):
+        h = load().svih_orig_device(self._h)
+        if not h:
+            raise _svils.SvilsError(-4, "OrigEngine: the link queries run on the device (on_device=True); the host loops have none")
+        return _svils.Orig.borrowed(h, self.n, self.k)
+
+    def link_prob(self, pairs):
+        return self._device().link_prob(pairs)
+
+    def predict_links(self, topk, nodes=None):
+        return self._device().predict_links(topk, nodes)
+
+    def rank_links(self, pairs):
+        return self._device().rank_links(pairs)
 
     def _state(self, name, shape):
         out = np.empty(shape)
