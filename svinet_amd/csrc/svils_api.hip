@@ -276,14 +276,8 @@ int svils_create(const svils_config *cfg, svils_handle **out) {
     double *lt = nullptr;
     guard(dalloc(h, &lt, 256, false));
     if (!rc) {
-      // {1/c_i, ln c_i} at the centres of 128 equal sub-intervals of [1,2) (log_tab in svils_devutil.h)
-      double tab[256];
-      for (int i = 0; i < 128; ++i) {
-        const double c = 1.0 + (i + 0.5) / 128.0;
-        tab[2 * i] = 1.0 / c;
-        tab[2 * i + 1] = std::log(c);
-      }
-      if (hipMemcpy(lt, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "log table upload failed");
+      const std::vector<double> tab = log_table();
+      if (hipMemcpy(lt, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "log table upload failed");
       d.logtab = lt;
     }
   }

@@ -4,7 +4,7 @@
 //   k_batch_dir_exp    set_dir_exp (src/mmsbinfer.hh:563-580): one wavefront per node, Elogpi = psi(gamma) - psi(row sum)
 //   k_batch_beta       the same for lambda [k][2]
 //   k_batch_fill       gamma_next = alpha, lambda_next = eta (:887-888)
-//   k_batch_pairs<W,V> the pair pass (:846-880, PhiComp src/mmsbinfer.hh:104-203).  The pair triangle is cut into tiles of
+//   k_batch_pairs<W,V> the pair pass (:846-880).  The pair triangle is cut into tiles of
 //                      TA rows x 64 columns (TA = 4 A, A rows per wavefront: tile_rows()), one workgroup of 4 wavefronts
 //                      per tile; a group of W lanes holds one pair, V values per lane (k = v W + lw).  A wavefront walks the
 //                      64 columns in chunks of G = 64 / W -- group g owns column c G + g of the chunk and keeps its phi2 sum
@@ -18,6 +18,11 @@
 //
 // No floating-point atomics: every sum has one owner and a fixed order, so a sweep is bitwise reproducible.  The tiles of
 // a sweep go through the partial buffers in batches of at most BATCH_TILES.
+//
+// There is ONE fixed point in this file: pair_fixed_point<W,V> (PhiComp, src/mmsbinfer.hh:104-203), called by the pair pass,
+// by the step kernels and by the star chain below, with count_pairs for their counters -- sweeps and steps mixed on one
+// handle run the same arithmetic by construction.  And one launch table: launch_for_width maps the handle's lane width to
+// the <W, VARIANT_V> instantiation of whichever kernel the caller names.
 //
 // -rnode / -rpair: the sampled-pair steps of MMSBInfer::infer (src/mmsbinfer.cc:459-740) on the same handle (DESIGN.md
 // section 4g), one fixed chain of launches per step, queued without a host round trip:
@@ -33,14 +38,13 @@
 //   k_batch_star_chain<W,V> a chain of star steps in one workgroup of one launch, a barrier between steps
 #include "svils_devutil.h"
 #include "svils_tool.h"
+#include "svils_waveutil.h"
 
 namespace {
 
 constexpr uint32_t TILE_COLS = 64;
 constexpr uint32_t BATCH_TILES = 2048;              // tiles per launch of the pair kernel
 constexpr size_t BATCH_BYTES = (size_t)256 << 20;   // ... and at most this much of partial sums
-constexpr uint32_t MAX_ROUNDS = 50;                 // src/env.hh:415
-constexpr double MEAN_CHANGE_THRESH = 0.00001;      // src/env.hh:337
 
 // rows of a tile one wavefront owns: its row accumulators are A x (W V) doubles of LDS, 32 KiB per workgroup at most
 constexpr int rows_per_wave(int wv) { return wv <= 64 ? 16 : wv == 128 ? 8 : 4; }
@@ -52,19 +56,6 @@ inline uint32_t variant_w(uint32_t k) {
   return w;
 }
 constexpr uint32_t VARIANT_V = 4;
-
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-  return v;
-}
-__device__ inline uint32_t wave_max_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-  return v;
-}
-__device__ inline double wave_sum_f64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // one wavefront per node: lanes stride k, the row sum by a fixed butterfly
 __global__ __launch_bounds__(256) void k_batch_dir_exp(uint32_t n, uint32_t K, const double *__restrict__ gamma,
@@ -100,6 +91,91 @@ __global__ __launch_bounds__(256) void k_batch_fill(uint64_t nk, uint32_t K, dou
   if (x < K) { lnext[2 * x] = eta0; lnext[2 * x + 1] = eta1; }
 }
 
+// ---- the pair fixed point: PhiComp (src/mmsbinfer.hh:104-203), the ONE copy every kernel below runs -------------------
+// the start vector: 1 / K on the lanes that hold a community
+__device__ __forceinline__ double phi_start(bool kval, uint32_t K) { return kval ? 1.0 / (double)K : 0.0; }
+
+// The fixed point of the one pair a group of W lanes holds: Jacobi order (both updates from the previous round's vectors),
+// the exit test after every odd round, at most MAX_ROUNDS rounds; a pair whose normaliser is not > 0 leaves with what it
+// has and adds one to `under` (the reference asserts there).  p1 / p2 come in as phi_start -- the caller seeds them in the
+// loop that loads elp, which is what keeps k_batch_pairs at its registers (profiles/r19a_batch_refactor.md) -- and go out
+// as the pair's phi; `under` is only ever added to, in every lane of the group.  Called by whole wavefronts; a group with
+// valid = false runs along without a round.
+template <int W, int V>
+__device__ __forceinline__ void pair_fixed_point(const double (&elp)[V], const double (&elq)[V], const double (&ef)[V], double le,
+                                                 const bool (&kval)[V], uint32_t K, bool valid, double (&p1)[V], double (&p2)[V],
+                                                 uint32_t &rounds, uint32_t &under) {
+  const double dK = (double)K;
+  double o1[V], o2[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) o1[v] = o2[v] = 0.0;
+  bool live = valid;
+  rounds = 0;
+  for (uint32_t i = 0; i < MAX_ROUNDS; ++i) {
+    if (!__ballot(live)) break;
+    if ((i & 1) == 0) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        o1[v] = live ? p1[v] : o1[v];
+        o2[v] = live ? p2[v] : o2[v];
+      }
+    }
+    double e[2 * V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      e[v] = (elp[v] + ef[v] * p2[v]) + (1.0 - p2[v]) * le;
+      e[V + v] = (elq[v] + ef[v] * p1[v]) + (1.0 - p1[v]) * le;
+    }
+    exp_neg_n<2 * V>(e);
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      e[v] = kval[v] ? e[v] : 0.0;
+      e[V + v] = kval[v] ? e[V + v] : 0.0;
+      s1 += e[v];
+      s2 += e[V + v];
+    }
+    s1 = group_sum<W>(s1);
+    s2 = group_sum<W>(s2);
+    const bool ok = s1 > 0.0 && s2 > 0.0;
+    if (live && !ok) {
+      ++under;
+      live = false;
+    }
+    const double r1 = fast_rcp(ok ? s1 : 1.0), r2 = fast_rcp(ok ? s2 : 1.0);
+    double m1 = 0.0, m2 = 0.0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      e[v] *= r1;
+      e[V + v] *= r2;
+      m1 += fabs(e[v] - o1[v]);
+      m2 += fabs(e[V + v] - o2[v]);
+      p1[v] = live ? e[v] : p1[v];
+      p2[v] = live ? e[V + v] : p2[v];
+    }
+    rounds += live;
+    if (i & 1) {
+      m1 = group_sum<W>(m1);
+      m2 = group_sum<W>(m2);
+      if (m1 / dK < MEAN_CHANGE_THRESH && m2 / dK < MEAN_CHANGE_THRESH) live = false;
+    }
+  }
+}
+
+// the counters of a wavefront's groups (lane lw == 0 of a group carries its pair's) into the handle's five
+__device__ inline void count_pairs(unsigned long long *ctr, uint32_t lane, uint32_t npairs, uint32_t rtot, uint32_t rmax, uint32_t under) {
+  npairs = wave_sum_u32(npairs);
+  rtot = wave_sum_u32(rtot);
+  under = wave_sum_u32(under);
+  rmax = wave_max_u32(rmax);
+  if (lane == 0) {
+    if (npairs) atomicAdd(&ctr[0], (unsigned long long)npairs);
+    if (rtot) atomicAdd(&ctr[1], (unsigned long long)rtot);
+    if (rmax) atomicMax(&ctr[2], (unsigned long long)rmax);
+    if (under) { atomicAdd(&ctr[3], (unsigned long long)under); atomicAdd(&ctr[4], (unsigned long long)under); }
+  }
+}
+
 struct PairArgs {
   uint32_t n, K, nw, t0;            // nw: words per row of the bit matrices; t0: first tile of this launch
   const uint32_t *tiles;            // [T][2] (row block, column block)
@@ -132,7 +208,6 @@ __global__ __launch_bounds__(256) void k_batch_pairs(PairArgs x) {
 #pragma unroll
   for (int v = 0; v < V; ++v) l0[v] = l1[v] = 0.0;
   uint32_t npairs = 0, rtot = 0, rmax = 0, under = 0;
-  const double invK = 1.0 / (double)K, dK = (double)K;
 
   for (uint32_t c = 0; c < (uint32_t)W; ++c) {   // 64 / G chunks of G columns
     const uint32_t b = col0 + c * G + g;
@@ -155,67 +230,15 @@ __global__ __launch_bounds__(256) void k_batch_pairs(PairArgs x) {
         y = (x.adj[wd] & bit) != 0;
       }
       if (!__ballot(valid)) continue;   // the same in every lane
-      double elp[V], ef[V], p1[V], p2[V], o1[V], o2[V];
-      const double le = y ? x.logeps : 0.0;
+      double elp[V], ef[V], p1[V], p2[V];
 #pragma unroll
       for (int v = 0; v < V; ++v) {
         elp[v] = kval[v] ? x.elogpi[(size_t)a * K + v * W + lw] : 0.0;
         ef[v] = y ? ef1[v] : ef0[v];
-        p1[v] = p2[v] = kval[v] ? invK : 0.0;
-        o1[v] = o2[v] = 0.0;
+        p1[v] = p2[v] = phi_start(kval[v], K);
       }
-      bool live = valid;
-      uint32_t rounds = 0;
-      for (uint32_t i = 0; i < MAX_ROUNDS; ++i) {
-        if (!__ballot(live)) break;
-        if ((i & 1) == 0) {
-#pragma unroll
-          for (int v = 0; v < V; ++v) {
-            o1[v] = live ? p1[v] : o1[v];
-            o2[v] = live ? p2[v] : o2[v];
-          }
-        }
-        // both updates from the previous round's vectors: e[0..V) the new phi1 (from phi2), e[V..2V) the new phi2
-        double e[2 * V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          e[v] = (elp[v] + ef[v] * p2[v]) + (1.0 - p2[v]) * le;
-          e[V + v] = (elq[v] + ef[v] * p1[v]) + (1.0 - p1[v]) * le;
-        }
-        exp_neg_n<2 * V>(e);
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          e[v] = kval[v] ? e[v] : 0.0;
-          e[V + v] = kval[v] ? e[V + v] : 0.0;
-          s1 += e[v];
-          s2 += e[V + v];
-        }
-        s1 = group_sum<W>(s1);
-        s2 = group_sum<W>(s2);
-        const bool ok = s1 > 0.0 && s2 > 0.0;
-        if (live && !ok) {   // the reference asserts here; the pair leaves with what it has
-          under += lw == 0;
-          live = false;
-        }
-        const double r1 = fast_rcp(ok ? s1 : 1.0), r2 = fast_rcp(ok ? s2 : 1.0);
-        double m1 = 0.0, m2 = 0.0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          e[v] *= r1;
-          e[V + v] *= r2;
-          m1 += fabs(e[v] - o1[v]);
-          m2 += fabs(e[V + v] - o2[v]);
-          p1[v] = live ? e[v] : p1[v];
-          p2[v] = live ? e[V + v] : p2[v];
-        }
-        rounds += live;
-        if (i & 1) {
-          m1 = group_sum<W>(m1);
-          m2 = group_sum<W>(m2);
-          if (m1 / dK < MEAN_CHANGE_THRESH && m2 / dK < MEAN_CHANGE_THRESH) live = false;
-        }
-      }
+      uint32_t rounds;
+      pair_fixed_point<W, V>(elp, elq, ef, y ? x.logeps : 0.0, kval, K, valid, p1, p2, rounds, under);
       if (valid && lw == 0) {
         ++npairs;
         rtot += rounds;
@@ -250,16 +273,7 @@ __global__ __launch_bounds__(256) void k_batch_pairs(PairArgs x) {
       o[1] = t1;
     }
   }
-  npairs = wave_sum_u32(npairs);
-  rtot = wave_sum_u32(rtot);
-  under = wave_sum_u32(under);
-  rmax = wave_max_u32(rmax);
-  if (lane == 0) {
-    if (npairs) atomicAdd(&x.ctr[0], (unsigned long long)npairs);
-    if (rtot) atomicAdd(&x.ctr[1], (unsigned long long)rtot);
-    if (rmax) atomicMax(&x.ctr[2], (unsigned long long)rmax);
-    if (under) { atomicAdd(&x.ctr[3], (unsigned long long)under); atomicAdd(&x.ctr[4], (unsigned long long)under); }
-  }
+  count_pairs(x.ctr, lane, npairs, rtot, rmax, lw == 0 ? under : 0);
 }
 
 struct ReduceArgs {
@@ -338,86 +352,6 @@ __global__ __launch_bounds__(256) void k_batch_pair_ll(uint64_t m, uint32_t K, d
 }
 
 // ---- sampled-pair steps (svils_batch_step_node / svils_batch_step_pairs) ----------------------
-// The fixed point of k_batch_pairs for the one pair a group of W lanes holds: the same constants, Jacobi order, odd-round
-// exit test and underflow rule.  Called by whole wavefronts; a group with valid = false runs along with zero vectors.
-template <int W, int V>
-__device__ __forceinline__ void pair_fixed_point(const double (&elp)[V], const double (&elq)[V], const double (&ef)[V], double le,
-                                                 const bool (&kval)[V], uint32_t K, bool valid, double (&p1)[V], double (&p2)[V],
-                                                 uint32_t &rounds, bool &under) {
-  const double invK = 1.0 / (double)K, dK = (double)K;
-  double o1[V], o2[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    p1[v] = p2[v] = kval[v] ? invK : 0.0;
-    o1[v] = o2[v] = 0.0;
-  }
-  bool live = valid;
-  rounds = 0;
-  under = false;
-  for (uint32_t i = 0; i < MAX_ROUNDS; ++i) {
-    if (!__ballot(live)) break;
-    if ((i & 1) == 0) {
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        o1[v] = live ? p1[v] : o1[v];
-        o2[v] = live ? p2[v] : o2[v];
-      }
-    }
-    double e[2 * V];
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      e[v] = (elp[v] + ef[v] * p2[v]) + (1.0 - p2[v]) * le;
-      e[V + v] = (elq[v] + ef[v] * p1[v]) + (1.0 - p1[v]) * le;
-    }
-    exp_neg_n<2 * V>(e);
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      e[v] = kval[v] ? e[v] : 0.0;
-      e[V + v] = kval[v] ? e[V + v] : 0.0;
-      s1 += e[v];
-      s2 += e[V + v];
-    }
-    s1 = group_sum<W>(s1);
-    s2 = group_sum<W>(s2);
-    const bool ok = s1 > 0.0 && s2 > 0.0;
-    if (live && !ok) {
-      under = true;
-      live = false;
-    }
-    const double r1 = fast_rcp(ok ? s1 : 1.0), r2 = fast_rcp(ok ? s2 : 1.0);
-    double m1 = 0.0, m2 = 0.0;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      e[v] *= r1;
-      e[V + v] *= r2;
-      m1 += fabs(e[v] - o1[v]);
-      m2 += fabs(e[V + v] - o2[v]);
-      p1[v] = live ? e[v] : p1[v];
-      p2[v] = live ? e[V + v] : p2[v];
-    }
-    rounds += live;
-    if (i & 1) {
-      m1 = group_sum<W>(m1);
-      m2 = group_sum<W>(m2);
-      if (m1 / dK < MEAN_CHANGE_THRESH && m2 / dK < MEAN_CHANGE_THRESH) live = false;
-    }
-  }
-}
-
-// the counters of a wavefront's groups (lane lw == 0 of a group carries its pair's) into the handle's five
-__device__ inline void count_pairs(unsigned long long *ctr, uint32_t lane, uint32_t npairs, uint32_t rtot, uint32_t rmax, uint32_t under) {
-  npairs = wave_sum_u32(npairs);
-  rtot = wave_sum_u32(rtot);
-  under = wave_sum_u32(under);
-  rmax = wave_max_u32(rmax);
-  if (lane == 0) {
-    if (npairs) atomicAdd(&ctr[0], (unsigned long long)npairs);
-    if (rtot) atomicAdd(&ctr[1], (unsigned long long)rtot);
-    if (rmax) atomicMax(&ctr[2], (unsigned long long)rmax);
-    if (under) { atomicAdd(&ctr[3], (unsigned long long)under); atomicAdd(&ctr[4], (unsigned long long)under); }
-  }
-}
 
 // a group's new row: gamma = (1 - rho) gamma + rho (alpha + scale t), then Elogpi of it.  Only groups with row < n store.
 template <int W, int V>
@@ -492,9 +426,9 @@ __global__ __launch_bounds__(256) void k_batch_step_node(StepArgs x) {
     ela[v] = kval[v] ? x.elogpi[(size_t)a * K + k] : 0.0;
     elj[v] = kval[v] && row_ok ? x.elogpi[(size_t)j * K + k] : 0.0;
     ef[v] = kval[v] ? x.elogbeta[2 * k + (y ? 0 : 1)] : 0.0;
+    pa[v] = pj[v] = phi_start(kval[v], K);
   }
-  uint32_t rounds;
-  bool under;
+  uint32_t rounds, under = 0;
   pair_fixed_point<W, V>(ela, elj, ef, y ? x.logeps : 0.0, kval, K, valid, pa, pj, rounds, under);
 #pragma unroll
   for (int v = 0; v < V; ++v) {
@@ -515,7 +449,7 @@ __global__ __launch_bounds__(256) void k_batch_step_node(StepArgs x) {
     }
   }
   const bool cnt = valid && lw == 0;
-  count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt && under);
+  count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt ? under : 0);
 }
 
 // Pair step, first launch: group e holds the e-th listed pair; phi goes to the step's buffer, the lambda terms leave per wavefront
@@ -541,9 +475,9 @@ __global__ __launch_bounds__(256) void k_batch_step_phi(StepArgs x) {
     elp[v] = kval[v] && valid ? x.elogpi[(size_t)p * K + k] : 0.0;
     elq[v] = kval[v] && valid ? x.elogpi[(size_t)q * K + k] : 0.0;
     ef[v] = kval[v] ? x.elogbeta[2 * k + (y ? 0 : 1)] : 0.0;
+    p1[v] = p2[v] = phi_start(kval[v], K);
   }
-  uint32_t rounds;
-  bool under;
+  uint32_t rounds, under = 0;
   pair_fixed_point<W, V>(elp, elq, ef, y ? x.logeps : 0.0, kval, K, valid, p1, p2, rounds, under);
 #pragma unroll
   for (int v = 0; v < V; ++v) {
@@ -561,7 +495,7 @@ __global__ __launch_bounds__(256) void k_batch_step_phi(StepArgs x) {
     }
   }
   const bool cnt = valid && lw == 0;
-  count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt && under);
+  count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt ? under : 0);
 }
 
 // Pair step, second launch: group i owns node i -- its phi vectors of the step added in list order, then the blend and Elogpi_i
@@ -689,10 +623,10 @@ __global__ __launch_bounds__(STAR_THREADS) void k_batch_star_chain(StarArgs x) {
       for (int v = 0; v < V; ++v) {
         elj[v] = kval[v] && valid ? x.elogpi[(size_t)j * K + v * W + lw] : 0.0;
         ef[v] = y ? ef1[v] : ef0[v];
+        pa[v] = pj[v] = phi_start(kval[v], K);
       }
       uint32_t rounds;
-      bool under;
-      pair_fixed_point<W, V>(ela, elj, ef, y ? x.logeps : 0.0, kval, K, valid, pa, pj, rounds, under);
+      pair_fixed_point<W, V>(ela, elj, ef, y ? x.logeps : 0.0, kval, K, valid, pa, pj, rounds, nunder);
 #pragma unroll
       for (int v = 0; v < V; ++v) {
         pa[v] = valid ? pa[v] : 0.0;
@@ -710,7 +644,6 @@ __global__ __launch_bounds__(STAR_THREADS) void k_batch_star_chain(StarArgs x) {
       npairs += cnt;
       rtot += cnt ? rounds : 0;
       rmax = max(rmax, cnt ? rounds : 0);
-      nunder += cnt && under;
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -752,7 +685,7 @@ __global__ __launch_bounds__(STAR_THREADS) void k_batch_star_chain(StarArgs x) {
     }
     __syncthreads();   // the next step reads what this one wrote
   }
-  count_pairs(x.ctr, lane, npairs, rtot, rmax, nunder);
+  count_pairs(x.ctr, lane, npairs, rtot, rmax, lw == 0 ? nunder : 0);
 }
 
 }  // namespace
@@ -774,7 +707,6 @@ struct svils_batch : ToolHandle {
   uint32_t *ll_pairs = nullptr;                                   // svils_batch_pair_loglik: grown on demand
   uint8_t *ll_y = nullptr;
   double *ll_out = nullptr;
-  uint64_t ll_cap = 0;
   uint32_t ntiles = 0, nrb = 0, batch = 0;                        // batch: tiles per launch
   std::vector<uint32_t> h_tiles;
   bool have_graph = false, have_state = false, timed = false;
@@ -787,7 +719,6 @@ struct svils_batch : ToolHandle {
   uint32_t star_chain = STAR_CHAIN;                               // steps per launch of k_batch_star_chain
   double *st_part = nullptr, *st_pl = nullptr, *st_phi = nullptr;
   uint32_t *st_lists = nullptr;                                   // a call's pairs [total][2], entries [2 total], offsets [nsteps][n + 1]
-  size_t cap_part = 0, cap_pl = 0, cap_phi = 0, cap_lists = 0;
   uint32_t *pin = nullptr;                                        // pinned staging of st_lists; ev_copy: its last copy has left it
   size_t cap_pin = 0;
   hipEvent_t ev_copy = nullptr;
@@ -799,14 +730,29 @@ namespace {
 void free_graph(svils_batch *h) {
   h->release(ToolHandle::GRAPH);
   h->have_graph = false;
-  h->ll_cap = 0;
   std::vector<uint32_t>().swap(h->h_skip);   // the host copies of the graph's bits go with it
   std::vector<uint32_t>().swap(h->h_adj);
 }
 
+// The launch table, the one place that maps the handle's lane width to an instantiation: launch(Width<W>()) for W = h->w.
+// The caller's generic lambda names the kernel <decltype(w)::value, VARIANT_V>, its grid and its block.
 template <int W>
-void launch_pairs(svils_batch *h, uint32_t nt, const PairArgs &a) {
-  hipLaunchKernelGGL((k_batch_pairs<W, (int)VARIANT_V>), dim3(nt), dim3(256), 0, h->st, a);
+struct Width {
+  static constexpr int value = W;
+};
+template <class Launch>
+int launch_for_width(const svils_batch *h, const char *name, Launch &&launch) {
+  switch (h->w) {
+    case 1: launch(Width<1>()); break;
+    case 2: launch(Width<2>()); break;
+    case 4: launch(Width<4>()); break;
+    case 8: launch(Width<8>()); break;
+    case 16: launch(Width<16>()); break;
+    case 32: launch(Width<32>()); break;
+    case 64: launch(Width<64>()); break;
+    default: return fail(SVILS_ERR_UNSUPPORTED, "%s: no kernel for W = %u", name, h->w);   // a missing kernel is an error
+  }
+  return 0;
 }
 
 // waits for the stream; the sticky underflow counter becomes an error
@@ -835,16 +781,10 @@ int one_sweep(svils_batch *h) {
   for (uint32_t t0 = 0; t0 < h->ntiles; t0 += h->batch, ++b) {
     const uint32_t t1 = std::min(h->ntiles, t0 + h->batch), nt = t1 - t0;
     PairArgs a{n, K, h->nw, t0, h->tiles, h->adj, h->skip, h->elogpi, h->elogbeta, std::log(h->epsilon), h->pa, h->pb, h->pl, h->ctr};
-    switch (h->w) {
-      case 1: launch_pairs<1>(h, nt, a); break;
-      case 2: launch_pairs<2>(h, nt, a); break;
-      case 4: launch_pairs<4>(h, nt, a); break;
-      case 8: launch_pairs<8>(h, nt, a); break;
-      case 16: launch_pairs<16>(h, nt, a); break;
-      case 32: launch_pairs<32>(h, nt, a); break;
-      case 64: launch_pairs<64>(h, nt, a); break;
-      default: return fail(SVILS_ERR_UNSUPPORTED, "svils_batch_sweep: no pair kernel for W = %u", h->w);   // a missing kernel is an error
-    }
+    if (int rc = launch_for_width(h, "svils_batch_sweep", [&](auto w) {
+          hipLaunchKernelGGL((k_batch_pairs<decltype(w)::value, (int)VARIANT_V>), dim3(nt), dim3(256), 0, h->st, a);
+        }))
+      return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[2 + 2 * b], h->st));
     ReduceArgs r{n, K, h->ta, t0, t1, h->h_tiles[2 * (size_t)t0], h->h_tiles[2 * (size_t)(t1 - 1)], h->nrb, h->rowoff, h->jfirst,
@@ -864,30 +804,6 @@ int one_sweep(svils_batch *h) {
 }
 
 // ---- sampled-pair steps: host side ----
-template <class T>
-int grow(svils_batch *h, T **p, size_t *cap, size_t need) {
-  if (need <= *cap) return 0;
-  HIPCHK(hipStreamSynchronize(h->st));   // the steps in flight still use the old buffer
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (int rc = h->dalloc(ToolHandle::HANDLE, p, need)) return rc;
-  *cap = need;
-  return 0;
-}
-
-#define STEP_DISPATCH(KERNEL, NBLOCKS, ARGS)                                                                                   \
-  switch (h->w) {                                                                                                              \
-    case 1: hipLaunchKernelGGL((KERNEL<1, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                  \
-    case 2: hipLaunchKernelGGL((KERNEL<2, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                  \
-    case 4: hipLaunchKernelGGL((KERNEL<4, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                  \
-    case 8: hipLaunchKernelGGL((KERNEL<8, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                  \
-    case 16: hipLaunchKernelGGL((KERNEL<16, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                \
-    case 32: hipLaunchKernelGGL((KERNEL<32, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                \
-    case 64: hipLaunchKernelGGL((KERNEL<64, (int)VARIANT_V>), dim3(NBLOCKS), dim3(256), 0, h->st, ARGS); break;                \
-    default: return fail(SVILS_ERR_UNSUPPORTED, "%s: no step kernel for W = %u", name, h->w); /* a missing kernel is an error */ \
-  }
-
 // what both step entry points check of their handle and step sizes
 int check_steps(svils_batch *h, const char *name, uint32_t nsteps, const double *rho_gamma, const double *rho_lambda) {
   if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "%s: set the graph and the state first", name);
@@ -993,12 +909,6 @@ int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double 
   h->epsilon = epsilon;
   const auto scope = ToolHandle::HANDLE;
   const size_t nk = (size_t)n * k;
-  std::vector<double> tab(256);   // {1 / c_i, ln c_i} at the centres of 128 equal sub-intervals of [1, 2) (log_tab)
-  for (int i = 0; i < 128; ++i) {
-    const double c = 1.0 + (i + 0.5) / 128.0;
-    tab[2 * i] = 1.0 / c;
-    tab[2 * i + 1] = std::log(c);
-  }
   int rc = h->open(device, 2);
   if (!rc) rc = h->dalloc(scope, &h->gamma, nk);
   if (!rc) rc = h->dalloc(scope, &h->gnext, nk);
@@ -1007,7 +917,7 @@ int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double 
   if (!rc) rc = h->dalloc(scope, &h->lnext, 2 * (size_t)k);
   if (!rc) rc = h->dalloc(scope, &h->elogbeta, 2 * (size_t)k);
   if (!rc) rc = h->dalloc(scope, &h->ctr, 5);
-  if (!rc) rc = h->upload(scope, &h->gtab, tab);
+  if (!rc) rc = h->upload(scope, &h->gtab, log_table());
   if (!rc && hipMemsetAsync(h->ctr, 0, 5 * sizeof(unsigned long long), h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "svils_batch_create: memset failed");
   if (!rc && hipStreamSynchronize(h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "svils_batch_create: upload failed");
   if (rc) {
@@ -1065,11 +975,7 @@ int svils_batch_set_graph(svils_batch *h, const uint32_t *links, uint64_t nlinks
   const uint32_t nlaunch = (ntiles + batch - 1) / batch;
   HIPCHK(hipStreamSynchronize(h->st));
   free_graph(h);
-  while (h->ev.size() < 2 + 2 * (size_t)nlaunch) {
-    hipEvent_t e = nullptr;
-    HIPCHK(hipEventCreate(&e));
-    h->ev.push_back(e);
-  }
+  if (int rc = h->need_events(2 + 2 * (size_t)nlaunch)) return rc;
   const auto scope = ToolHandle::GRAPH;
   int rc = 0;
   if (!rc) rc = h->upload(scope, &h->adj, adj);
@@ -1140,13 +1046,16 @@ int svils_batch_step_node(svils_batch *h, uint32_t nsteps, const uint32_t *nodes
     if (nodes[s] >= h->n) return fail(SVILS_ERR_ARG, "%s: nodes[%u] = %u is not < n = %u", name, s, nodes[s], h->n);
   if (!nsteps) return 0;
   const uint32_t n = h->n, K = h->k, G = 64 / h->w, nb = blocks(n, 4 * G), nwv = 4 * nb;
-  if (int rc = grow(h, &h->st_part, &h->cap_part, (size_t)nwv * K)) return rc;
-  if (int rc = grow(h, &h->st_pl, &h->cap_pl, (size_t)nwv * K * 2)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_part, (size_t)nwv * K)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_pl, (size_t)nwv * K * 2)) return rc;
   if (int rc = begin_steps(h)) return rc;
   for (uint32_t s = 0; s < nsteps; ++s) {
     StepArgs x = step_args(h, scale, rho_gamma[s]);
     x.a = nodes[s];
-    STEP_DISPATCH(k_batch_step_node, nb, x)
+    if (int rc = launch_for_width(h, name, [&](auto w) {
+          hipLaunchKernelGGL((k_batch_step_node<decltype(w)::value, (int)VARIANT_V>), dim3(nb), dim3(256), 0, h->st, x);
+        }))
+      return rc;
     double *ga = h->gamma + (size_t)x.a * K;
     hipLaunchKernelGGL(k_batch_step_tail, dim3(K), dim3(256), 0, h->st, K, nwv, h->st_part, h->st_pl, ga, h->alpha, h->eta0, h->eta1,
                        scale, rho_gamma[s], rho_lambda[s], h->lam, h->elogbeta, h->gtab);
@@ -1208,9 +1117,9 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
     }
   }
   const uint32_t nwv_most = 4 * blocks(std::max<uint64_t>(most, 1), 4 * G);
-  if (int rc = grow(h, &h->st_pl, &h->cap_pl, (size_t)nwv_most * K * 2)) return rc;
-  if (int rc = grow(h, &h->st_phi, &h->cap_phi, 2 * (size_t)most * K)) return rc;
-  if (int rc = grow(h, &h->st_lists, &h->cap_lists, nlists)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_pl, (size_t)nwv_most * K * 2)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_phi, 2 * (size_t)most * K)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_lists, nlists)) return rc;
   // ordered behind the steps of earlier calls, which read the device copy, by the stream
   HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nlists * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
   HIPCHK(hipEventRecord(h->ev_copy, h->st));
@@ -1225,8 +1134,12 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
     x.noff = h->st_lists + 4 * total + (size_t)s * (n + 1);
     x.phi = h->st_phi;
     const uint32_t nb = blocks(m, 4 * G);
-    if (m) { STEP_DISPATCH(k_batch_step_phi, nb, x) }
-    STEP_DISPATCH(k_batch_step_rows, blocks(n, 4 * G), x)
+    if (int rc = launch_for_width(h, name, [&](auto w) {
+          constexpr int W = decltype(w)::value, V = (int)VARIANT_V;
+          if (m) hipLaunchKernelGGL((k_batch_step_phi<W, V>), dim3(nb), dim3(256), 0, h->st, x);
+          hipLaunchKernelGGL((k_batch_step_rows<W, V>), dim3(blocks(n, 4 * G)), dim3(256), 0, h->st, x);
+        }))
+      return rc;
     if (rho_lambda[s] >= 0.0)
       hipLaunchKernelGGL(k_batch_step_tail, dim3(K), dim3(256), 0, h->st, K, 4 * nb, (const double *)nullptr, h->st_pl, (double *)nullptr,
                          h->alpha, h->eta0, h->eta1, scale[s], rho_gamma[s], rho_lambda[s], h->lam, h->elogbeta, h->gtab);
@@ -1310,7 +1223,7 @@ int svils_batch_step_star(svils_batch *h, uint32_t nsteps, const uint32_t *start
   std::memcpy(pu + nsteps + 1, start, nsteps * sizeof(uint32_t));
   if (total) std::memcpy(pu + 2 * (size_t)nsteps + 1, partner, total * sizeof(uint32_t));
   if (total) std::memcpy(pu + 2 * (size_t)nsteps + 1 + total, y, total);
-  if (int rc = grow(h, &h->st_lists, &h->cap_lists, nwords)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_lists, nwords)) return rc;
   HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nwords * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
   HIPCHK(hipEventRecord(h->ev_copy, h->st));
   h->copy_pending = true;
@@ -1341,16 +1254,10 @@ int svils_batch_step_star(svils_batch *h, uint32_t nsteps, const uint32_t *start
   for (uint32_t s0 = 0; s0 < nsteps; s0 += h->star_chain) {
     x.s0 = s0;
     x.s1 = (uint32_t)std::min<uint64_t>(nsteps, (uint64_t)s0 + h->star_chain);
-    switch (h->w) {
-      case 1: hipLaunchKernelGGL((k_batch_star_chain<1, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
-      case 2: hipLaunchKernelGGL((k_batch_star_chain<2, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
-      case 4: hipLaunchKernelGGL((k_batch_star_chain<4, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
-      case 8: hipLaunchKernelGGL((k_batch_star_chain<8, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
-      case 16: hipLaunchKernelGGL((k_batch_star_chain<16, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
-      case 32: hipLaunchKernelGGL((k_batch_star_chain<32, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
-      case 64: hipLaunchKernelGGL((k_batch_star_chain<64, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x); break;
-      default: return fail(SVILS_ERR_UNSUPPORTED, "%s: no star kernel for W = %u", name, h->w);   // a missing kernel is an error
-    }
+    if (int rc = launch_for_width(h, name, [&](auto w) {
+          hipLaunchKernelGGL((k_batch_star_chain<decltype(w)::value, (int)VARIANT_V>), dim3(1), dim3(STAR_THREADS), 0, h->st, x);
+        }))
+      return rc;
     HIPCHK(hipGetLastError());
   }
   return end_steps(h);
@@ -1365,21 +1272,10 @@ int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t
       return fail(SVILS_ERR_ARG, "svils_batch_pair_loglik: pair %llu names a node >= n = %u", (unsigned long long)x, h->n);
   if (int rc = settle(h, "svils_batch_pair_loglik")) return rc;
   if (!m) return 0;
-  if (m > h->ll_cap) {   // GRAPH scope (the lists are the held-out sets of a graph); the stream is idle after settle()
-    if (h->ll_pairs) (void)hipFree(h->ll_pairs);
-    if (h->ll_y) (void)hipFree(h->ll_y);
-    if (h->ll_out) (void)hipFree(h->ll_out);
-    h->ll_pairs = nullptr;
-    h->ll_y = nullptr;
-    h->ll_out = nullptr;
-    h->ll_cap = 0;
-    const auto scope = ToolHandle::GRAPH;
-    int rc = h->dalloc(scope, &h->ll_pairs, 2 * (size_t)m);
-    if (!rc) rc = h->dalloc(scope, &h->ll_y, (size_t)m);
-    if (!rc) rc = h->dalloc(scope, &h->ll_out, (size_t)m);
-    if (rc) return rc;
-    h->ll_cap = m;
-  }
+  const auto scope = ToolHandle::GRAPH;   // the lists are the held-out sets of a graph
+  if (int rc = h->reserve(scope, &h->ll_pairs, 2 * (size_t)m)) return rc;
+  if (int rc = h->reserve(scope, &h->ll_y, (size_t)m)) return rc;
+  if (int rc = h->reserve(scope, &h->ll_out, (size_t)m)) return rc;
   HIPCHK(hipMemcpyAsync(h->ll_pairs, pairs, 2 * m * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
   HIPCHK(hipMemcpyAsync(h->ll_y, y, m, hipMemcpyHostToDevice, h->st));
   hipLaunchKernelGGL(k_batch_pair_ll, dim3(blocks(m, 4)), dim3(256), 0, h->st, m, h->k, h->epsilon, h->ll_pairs, h->ll_y, h->gamma,
@@ -1407,11 +1303,9 @@ int svils_batch_get_timing(svils_batch *h, double ms[3]) {
   if (!ms) return fail(SVILS_ERR_ARG, "svils_batch_get_timing: null argument");
   HIPCHK(hipStreamSynchronize(h->st));
   ms[0] = h->elapsed_ms(0, 1, h->timed);
-  ms[1] = ms[2] = h->timed && !h->timed_steps ? 0.0 : -1.0;
-  for (uint32_t b = 0; h->timed && !h->timed_steps && b < h->nlaunch; ++b) {
-    ms[1] += h->elapsed_ms(1 + 2 * b, 2 + 2 * b, true);   // (the first launch's bracket includes the fill)
-    ms[2] += h->elapsed_ms(2 + 2 * b, 3 + 2 * b, true);
-  }
+  const bool swept = h->timed && !h->timed_steps;
+  ms[1] = h->launches_ms(1, h->nlaunch, swept);   // (the first launch's bracket includes the fill)
+  ms[2] = h->launches_ms(2, h->nlaunch, swept);
   return 0;
 }
 

@@ -18,6 +18,7 @@
 // The sort order (count desc, label asc) is what the reference's qsort with cmppairval gives over a std::map's ascending
 // labels under glibc's merge sort: a stable descending sort.
 #include "svils_tool.h"
+#include "svils_waveutil.h"
 
 // No fused multiply-adds in this unit: the reference computes every product and sum separately (x86, no contraction);
 // an FMA inside `u > max` compares the exact product and moves the winning label of a tie in compute_and_log_groups.
@@ -34,19 +35,6 @@ constexpr uint32_t SENTINEL = 65535;       // compute_and_log_groups drops a lab
 
 __device__ inline uint64_t key_of(uint32_t count, uint32_t label) { return ((uint64_t)count << 32) | (uint64_t)(NONE - label); }
 __device__ inline uint32_t label_of(uint64_t key) { return NONE - (uint32_t)key; }
-
-__device__ inline uint64_t wave_max_u64(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t w = (uint64_t)__shfl_xor((long long)v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-  return v;
-}
 
 // nodes[] of training degree 1 .. 64; four per block of 256
 __global__ __launch_bounds__(256) void k_top_wave(uint32_t cnt, const uint32_t *__restrict__ nodes, const uint64_t *__restrict__ rowptr,

@@ -252,6 +252,17 @@ int reserve(svils_handle *h, DevBuf<T> &b, uint64_t need) {
   return 0;
 }
 
+// log_tab's table (svils_devutil.h): {1 / c_i, ln c_i} at the centres c_i of 128 equal sub-intervals of [1, 2)
+inline std::vector<double> log_table() {
+  std::vector<double> tab(256);
+  for (int i = 0; i < 128; ++i) {
+    const double c = 1.0 + (i + 0.5) / 128.0;
+    tab[2 * i] = 1.0 / c;
+    tab[2 * i + 1] = std::log(c);
+  }
+  return tab;
+}
+
 // compute units of a device; 256 (an MI355X) where the runtime does not say
 inline uint32_t cu_count(int device) {
   int cus = 0;

@@ -34,7 +34,6 @@ struct svils_orig : svils_impl::ToolHandle {
   uint32_t *ll_pairs = nullptr;                                   // svils_orig_pair_loglik: grown on demand
   uint8_t *ll_y = nullptr;
   double *ll_out = nullptr;
-  uint64_t ll_cap = 0;
   uint32_t rows = 0, nlaunch = 0;                                 // p rows per launch, launches per sweep
   uint32_t rows_req = 0;                                          // svils_orig_set_launch_rows: 0 = as many as the bound admits
   bool have_graph = false, have_state = false, timed = false;

@@ -28,6 +28,7 @@
 // up the pair pass, the reductions and k_orig_final of every later sweep return at once: the state stays as it is.
 #include "svils_devutil.h"
 #include "svils_orig.h"
+#include "svils_waveutil.h"
 
 using namespace svils_impl;
 
@@ -35,8 +36,6 @@ namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t MAX_ROUNDS = 50;                 // src/env.hh: online_iterations
-constexpr double MEAN_CHANGE_THRESH = 0.00001;      // src/env.hh: meanchangethresh
 constexpr uint32_t TILE_PAIRS = 16;                 // pairs per wavefront: the columns of one MFMA
 constexpr uint32_t TILES_PER_BLOCK = 16;            // four per wavefront
 constexpr size_t PHI_BYTES = (size_t)256 << 20;     // phi1 and phi2 of one launch
@@ -46,18 +45,6 @@ inline uint32_t padded_k(uint32_t k) { return (k + 15) / 16 * 16; }
 // row stride of the transposed log tables: 16 (mod 32) doubles, so the four lane groups of an A operand read take two LDS passes
 constexpr int tab_ld(int kp) { return kp % 32 == 0 ? kp + 16 : kp; }
 
-__device__ inline u64 wave_sum_u64(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o, 64);
-  return v;
-}
-__device__ inline uint32_t wave_max_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-  return v;
-}
-__device__ inline double wave_sum_f64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // the sum over the four lane groups of a pair (lanes c, c + 16, c + 32, c + 48): the same bits in all four
 __device__ inline double groups_sum(double v) {
   v += __shfl_xor(v, 16, 64);
@@ -387,7 +374,7 @@ namespace {
 
 void free_graph(svils_orig *h) {
   h->release(ToolHandle::GRAPH);
-  h->have_graph = false;
+  h->have_graph = false;   // (the lists of svils_orig_pair_loglik go with the graph)
 }
 
 template <int KP, bool LREG>
@@ -476,12 +463,6 @@ int svils_orig_create(int device, uint32_t n, uint32_t k, double alpha, svils_or
   h->alpha = alpha;
   const auto scope = ToolHandle::HANDLE;
   const size_t nk = (size_t)n * k, nnt = 2 * (size_t)h->kp * h->kp;
-  std::vector<double> tab(256);   // {1 / c_i, ln c_i} at the centres of 128 equal sub-intervals of [1, 2) (log_tab)
-  for (int i = 0; i < 128; ++i) {
-    const double c = 1.0 + (i + 0.5) / 128.0;
-    tab[2 * i] = 1.0 / c;
-    tab[2 * i + 1] = std::log(c);
-  }
   int rc = h->open(device, 2);
   if (!rc) rc = h->dalloc(scope, &h->gamma, nk);
   if (!rc) rc = h->dalloc(scope, &h->gnext, nk);
@@ -491,7 +472,7 @@ int svils_orig_create(int device, uint32_t n, uint32_t k, double alpha, svils_or
   if (!rc) rc = h->dalloc(scope, &h->nt, nnt);
   if (!rc) rc = h->dalloc(scope, &h->part, (size_t)ACC_WAVES * nnt);
   if (!rc) rc = h->dalloc(scope, &h->ctr, (size_t)CTR_COUNT);
-  if (!rc) rc = h->upload(scope, &h->gtab, tab);
+  if (!rc) rc = h->upload(scope, &h->gtab, log_table());
   if (!rc && hipMemsetAsync(h->ctr, 0, CTR_COUNT * sizeof(u64), h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "svils_orig_create: memset failed");
   if (!rc && hipStreamSynchronize(h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "svils_orig_create: upload failed");
   if (rc) {
@@ -503,12 +484,9 @@ int svils_orig_create(int device, uint32_t n, uint32_t k, double alpha, svils_or
 }
 
 int svils_orig_destroy(svils_orig *h) {
-  if (h && h->st) {   // the lists of svils_orig_pair_loglik are not in a scope
+  if (h && h->st) {   // the batch buffers of the link queries are not in a scope
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->st);
-    if (h->ll_pairs) (void)hipFree(h->ll_pairs);
-    if (h->ll_y) (void)hipFree(h->ll_y);
-    if (h->ll_out) (void)hipFree(h->ll_out);
     free_queries(h);
   }
   delete h;   // ~ToolHandle: waits for the stream, frees both scopes
@@ -545,11 +523,7 @@ int svils_orig_set_graph(svils_orig *h, const uint32_t *links, uint64_t nlinks, 
   const uint32_t nlaunch = (n + rows - 1) / rows;
   HIPCHK(hipStreamSynchronize(h->st));
   free_graph(h);
-  while (h->ev.size() < 2 + 2 * (size_t)nlaunch) {
-    hipEvent_t e = nullptr;
-    HIPCHK(hipEventCreate(&e));
-    h->ev.push_back(e);
-  }
+  if (int rc = h->need_events(2 + 2 * (size_t)nlaunch)) return rc;
   const auto scope = ToolHandle::GRAPH;
   const size_t nslots = (size_t)rows * n;
   int rc = 0;
@@ -621,18 +595,10 @@ int svils_orig_pair_loglik(svils_orig *h, const uint32_t *pairs, const uint8_t *
                   pairs[2 * x], pairs[2 * x + 1], h->n);
   if (int rc = settle(h, "svils_orig_pair_loglik")) return rc;
   if (!m) return 0;
-  if (m > h->ll_cap) {
-    // outside the scopes (svils_orig_destroy frees them); the stream is idle after settle()
-    if (h->ll_pairs) (void)hipFree(h->ll_pairs);
-    if (h->ll_y) (void)hipFree(h->ll_y);
-    if (h->ll_out) (void)hipFree(h->ll_out);
-    h->ll_pairs = nullptr; h->ll_y = nullptr; h->ll_out = nullptr;
-    h->ll_cap = 0;
-    HIPCHK(hipMalloc((void **)&h->ll_pairs, 2 * m * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&h->ll_y, m));
-    HIPCHK(hipMalloc((void **)&h->ll_out, m * sizeof(double)));
-    h->ll_cap = m;
-  }
+  const auto scope = ToolHandle::GRAPH;   // the lists are the held-out sets of a graph
+  if (int rc = h->reserve(scope, &h->ll_pairs, 2 * (size_t)m)) return rc;
+  if (int rc = h->reserve(scope, &h->ll_y, (size_t)m)) return rc;
+  if (int rc = h->reserve(scope, &h->ll_out, (size_t)m)) return rc;
   HIPCHK(hipMemcpyAsync(h->ll_pairs, pairs, 2 * m * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
   HIPCHK(hipMemcpyAsync(h->ll_y, y, m, hipMemcpyHostToDevice, h->st));
   hipLaunchKernelGGL(k_orig_pair_ll, dim3(blocks(m, 4)), dim3(256), 0, h->st, m, h->k, h->ll_pairs, h->ll_y, h->gamma, h->beta, h->ll_out);
@@ -661,11 +627,8 @@ int svils_orig_get_timing(svils_orig *h, double ms[3]) {
   if (!ms) return fail(SVILS_ERR_ARG, "svils_orig_get_timing: null argument");
   HIPCHK(hipStreamSynchronize(h->st));
   ms[0] = h->elapsed_ms(0, 1, h->timed);
-  ms[1] = ms[2] = h->timed ? 0.0 : -1.0;
-  for (uint32_t b = 0; h->timed && b < h->nlaunch; ++b) {
-    ms[1] += h->elapsed_ms(1 + 2 * (int)b, 2 + 2 * (int)b, true);
-    ms[2] += h->elapsed_ms(2 + 2 * (int)b, 3 + 2 * (int)b, true);
-  }
+  ms[1] = h->launches_ms(1, h->nlaunch, h->timed);
+  ms[2] = h->launches_ms(2, h->nlaunch, h->timed);
   return 0;
 }
 

@@ -1,9 +1,11 @@
-// svils_tool.h -- the scaffold of the standalone device handles that run on a fitted model or a graph (svils_findk,
-// svils_lc): one device, one stream, a fixed set of events, and device buffers tracked in two scopes -- the handle's
-// lifetime and the current graph's.
+// svils_tool.h -- the scaffold of the standalone device handles: one device, one stream, a set of events that only
+// grows, and device buffers tracked in two scopes -- the handle's lifetime and the current graph's.  A scope owns each
+// buffer once, with the element count it was allocated for; a buffer that has to grow is replaced through reserve().
 //
 //   svils_findk.hip   -findk: label propagation over a top-5 sparse gamma
 //   svils_lc.hip      -gml / -lcstats: the link communities of a fitted model
+//   svils_batch.hip   -batch-gpu / -rnode / -rpair / -infset: the exact model over all pairs, sampled pairs, stars
+//   svils_orig.hip    -orig: the full K x K blockmodel (svils_orig.h)
 //
 // Their buffers are not the sweep handle's (svils_handle.h: dalloc): exact size, not zeroed, no slack past the end, and
 // null for a count of 0.
@@ -45,14 +47,49 @@ struct ToolHandle {
     return 0;
   }
 
-  // *p = count elements of device memory, owned by scope s (release() frees it and nulls *p)
+  // at least nev events (a graph whose sweep takes more launches than the last one's)
+  int need_events(size_t nev) {
+    while (ev.size() < nev) {
+      hipEvent_t e = nullptr;
+      HIPCHK(hipEventCreate(&e));
+      ev.push_back(e);
+    }
+    return 0;
+  }
+
+  // *p = count elements of device memory, owned by scope s (release() frees it and nulls *p).  *p must not be owned already.
   template <class T>
   int dalloc(Scope s, T **p, size_t count) {
     *p = nullptr;
     if (!count) return 0;
     HIPCHK(hipMalloc((void **)p, count * sizeof(T)));
-    owned[s].push_back((void **)p);
+    owned[s].push_back({(void **)p, count});
     return 0;
+  }
+
+  // the elements scope s holds for *p: 0 if it holds none (never allocated, or released with the scope)
+  template <class T>
+  size_t capacity(Scope s, T *const *p) const {
+    for (const Owned &o : owned[s])
+      if (o.p == (void **)p) return o.count;
+    return 0;
+  }
+
+  // *p, owned by scope s, holds at least `need` elements: kept while it suffices, otherwise the stream is waited for (work
+  // in flight may still use the old buffer), the old buffer is freed and its entry dropped, and a new one is dalloc()ed --
+  // the scope lists *p once however often it grows.  The contents are not kept.
+  template <class T>
+  int reserve(Scope s, T **p, size_t need) {
+    if (need <= capacity(s, p)) return 0;
+    for (size_t i = 0; i < owned[s].size(); ++i)
+      if (owned[s][i].p == (void **)p) {
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(*p);
+        *p = nullptr;
+        owned[s].erase(owned[s].begin() + i);
+        break;
+      }
+    return dalloc(s, p, need);
   }
 
   // a dalloc()ed copy of v, queued on the stream
@@ -64,9 +101,9 @@ struct ToolHandle {
   }
 
   void release(Scope s) {
-    for (void **p : owned[s]) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
+    for (const Owned &o : owned[s]) {
+      if (*o.p) (void)hipFree(*o.p);
+      *o.p = nullptr;
     }
     owned[s].clear();
   }
@@ -76,9 +113,20 @@ struct ToolHandle {
     float t = 0;
     return timed && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : -1.0;
   }
+  // the sum over nlaunch launches of the brackets ev[first + 2 b] .. ev[first + 1 + 2 b], -1 where the sweep has not run
+  double launches_ms(int first, uint32_t nlaunch, bool timed) const {
+    if (!timed) return -1.0;
+    double ms = 0.0;
+    for (uint32_t b = 0; b < nlaunch; ++b) ms += elapsed_ms(first + 2 * (int)b, first + 1 + 2 * (int)b, true);
+    return ms;
+  }
 
  private:
-  std::vector<void **> owned[2];
+  struct Owned {
+    void **p;       // the handle's pointer
+    size_t count;   // elements allocated for it
+  };
+  std::vector<Owned> owned[2];
 };
 
 inline int no_device_or_null(const char *name) {

@@ -185,6 +185,32 @@ def test_pair_likelihoods_match_the_oracle(graph_files, k):
     assert abs(both[1] - B.edge_likelihood(g2, lam, 0, 1, 0)) < 1e-9
 
 
+def test_pair_likelihood_lists_regrow_and_go_with_the_graph(graph_files):
+    """the call's lists are grown on demand inside the graph's scope: 3 pairs, 50 (regrown), 3 (kept), a new graph (released
+    with the old one), 50 (allocated anew) -- every result is, byte for byte, that of a fresh handle's first call"""
+    s = Start(graph_files["assort"], 75, 5)
+    rs = np.random.RandomState(19)
+    pairs = np.array([(a, b) for a, b in np.sort(rs.randint(0, 75, size=(80, 2)), axis=1) if a != b][:50])
+    y = np.array([s.adj[a, b] for a, b in pairs], dtype=np.uint8)
+    assert len(pairs) == 50 and 0 < y.sum() < 50
+
+    def fresh(m):
+        d = _svils.Batch(s.n, s.k, s.alpha, s.eta)
+        d.set_state(s.gamma, s.lam)
+        out = d.pair_loglik(pairs[:m], y[:m])
+        d.close()
+        return out
+
+    ref = {m: fresh(m) for m in (3, 50)}
+    assert ref[50][:3].tobytes() == ref[3].tobytes()
+    for m in (3, 50, 3):
+        assert s.dev.pair_loglik(pairs[:m], y[:m]).tobytes() == ref[m].tobytes()
+    s.dev.set_graph(s.edges, sorted(s.skip))
+    assert s.dev.pair_loglik(pairs, y).tobytes() == ref[50].tobytes()
+    s.dev.sweep()                                                             # the handle still sweeps: the second graph is whole
+    assert s.dev.stats()[0] == s.trained
+
+
 def test_host_engine_with_both_backends(graph_files):
     a = BatchEngine(graph_files["assort"], 75, 4, heldout_ratio=0.1, eta_type="fromdata")
     b = BatchEngine(graph_files["assort"], 75, 4, heldout_ratio=0.1, eta_type="fromdata", on_device=True)

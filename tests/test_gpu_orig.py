@@ -186,6 +186,27 @@ def test_pair_loglik(case):
     assert dev.pair_loglik(np.zeros((0, 2)), np.zeros(0)).shape == (0,)
 
 
+def test_pair_loglik_lists_regrow_and_go_with_the_graph():
+    """tests/test_gpu_batch.py::test_pair_likelihood_lists_regrow_and_go_with_the_graph on this handle: 3 pairs, 50, 3, a new
+    graph, 50 -- every result is, byte for byte, that of a fresh handle's first call"""
+    k, n, seed = PEAKED[2]
+    links, gamma, beta, _ = _peaked_reference(k, n, seed)
+    adj = OC.adjacency(n, links)
+    rs = np.random.RandomState(seed + 1)
+    pairs = np.array([(a, b) for a, b in rs.randint(0, n, size=(80, 2)) if a != b][:50])
+    y = adj[pairs[:, 0], pairs[:, 1]].astype(np.uint8)
+    assert len(pairs) == 50 and 0 < y.sum() < 50
+    ref = {m: _device(n, k, links, (), gamma, beta).pair_loglik(pairs[:m], y[:m]) for m in (3, 50)}
+    assert ref[50][:3].tobytes() == ref[3].tobytes()
+    dev = _device(n, k, links, (), gamma, beta)
+    for m in (3, 50, 3):
+        assert dev.pair_loglik(pairs[:m], y[:m]).tobytes() == ref[m].tobytes()
+    dev.set_graph(links, ())
+    assert dev.pair_loglik(pairs, y).tobytes() == ref[50].tobytes()
+    dev.sweep(1)                                                              # the handle still sweeps: the second graph is whole
+    assert dev.stats()[0] == n * (n - 1)
+
+
 def test_a_block_that_saw_only_links_raises_the_flag():
     """a complete graph on 6 nodes, k = 3: num == tot bitwise, so every beta is exactly 1 after one sweep; the sweep behind
     it in the queue leaves the state alone, and the next call that waits names the cause"""

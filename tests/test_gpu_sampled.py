@@ -75,6 +75,28 @@ def test_steps_match_the_restatement_for_every_variant(graph_files, k):
         _pair_step(s, _draw_pairs(s, 37, 10 * k + c), c)
 
 
+@pytest.mark.parametrize("k", _variant_ks())
+def test_sweep_and_step_paths_run_the_same_rounds(graph_files, k):
+    """one fixed point behind both paths: from one start state a sweep, and on a second handle ONE pair step that lists every
+    trained pair (rho_gamma = 1, rho_lambda < 0: lambda and Elogbeta stay the start's), run each pair's fixed point from the
+    same Elogpi / Elogbeta.  The round counters are integers and are compared without a tolerance: a last-bit drift between
+    two copies of the loop moves a pair's exit, and these, before it shows at rtol 1e-7"""
+    s = Start(graph_files["assort"], 75, k)
+    s.dev.sweep()
+    swept = s.dev.stats()
+    pairs = np.array([(p, q) for p in range(s.n) for q in range(p + 1, s.n) if (p, q) not in s.skip], dtype=np.uint32)
+    assert len(pairs) == s.trained
+    d = _svils.Batch(s.n, k, s.alpha, s.eta)
+    d.set_graph(s.edges, sorted(s.skip))
+    d.set_state(s.gamma, s.lam)
+    d.step_pairs([pairs], [1.0], [1.0], [-1.0])
+    stepped = d.stats()
+    d.close()
+    assert stepped[0] == swept[0] == s.trained
+    assert stepped[1] == swept[1] and stepped[2] == swept[2]
+    assert stepped[3] == swept[3] == 0
+
+
 @pytest.mark.parametrize("k", [4, 5])
 @pytest.mark.parametrize("n", [10, 64, 65, 256, 257, 258])
 def test_steps_at_lane_group_and_workgroup_edges(tmp_path, n, k):
