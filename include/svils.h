@@ -44,6 +44,7 @@ extern "C" {
                                     (additive, same version) svils_batch_*: -batch-gpu, all-pairs batch inference;
                                     (additive, same version) svils_batch_step_node / svils_batch_step_pairs: -rnode / -rpair, sampled-pair steps;
                                     (additive, same version) svils_batch_step_star / svils_batch_set_star_chain / svils_batch_get_expectations: -infset, informative-set steps;
+                                    (additive, same version) svils_batch_elbo / svils_batch_set_elbo_tiles: -logl, the variational lower bound;
                                     (additive, same version) svils_orig_*: -orig, the full K x K blockmodel over all ordered pairs;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
@@ -737,6 +738,27 @@ int svils_batch_set_star_chain(svils_batch *h, uint32_t max_steps);
  * sweep or svils_batch_set_state came since the last step call (what the next step call would do), else the ones the steps
  * maintain row by row.  Waits for the stream.  Either pointer may be null.  SVILS_ERR_ARG: no state */
 int svils_batch_get_expectations(svils_batch *h, double *elogpi, double *elogbeta);
+
+/* ---- -logl: the variational lower bound on the svils_batch handle (an ADDITION of ABI 8) ---------------------------------
+ * The reference's approx_log_likelihood (src/mmsbinfer.cc:1948-2060, src/fastamm.cc:1129-1258) of the current state:
+ * s = G + P + N with Elogpi / Elogbeta of the current gamma / lambda (those svils_batch_get_expectations would return),
+ *   G   sum over k of lnGamma(eta0 + eta1) - lnGamma(eta0) - lnGamma(eta1) + sum_t (eta_t - 1) Elogbeta_kt
+ *       - [lnGamma(lambda_k0 + lambda_k1) - sum_t lnGamma(lambda_kt)] - sum_t (lambda_kt - 1) Elogbeta_kt
+ *   P   sum over every pair p < q outside the skip set, phi1 / phi2 the fixed point of svils_batch_sweep from 1 / k, of
+ *       sum_k phi1 phi2 elogf + [y = 1] log(epsilon) (S1 S2 - sum_k phi1 phi2) + sum_k phi1 Elogpi_p + sum_k phi2 Elogpi_q
+ *       - sum_k phi1 log phi1 - sum_k phi2 log phi2; an entry of phi that is exactly 0 adds 0 (the reference: NaN)
+ *   N   sum over p of lnGamma(k alpha) - k lnGamma(alpha) + (alpha - 1) sum_k Elogpi_pk
+ *       - [lnGamma(sum_k gamma_pk) - sum_k lnGamma(max(gamma_pk, 1e-30))] - sum_k (gamma_pk - 1) Elogpi_pk
+ * parts: total, G, P, N.  pairs_done / rounds_total (either may be null): the pairs of the pass and their fixed-point rounds.
+ * The pass has buffers and counters of its own: gamma, lambda, the expectations, svils_batch_get_stats and every later
+ * sweep or step are as without it.  Sums in a fixed order, no floating-point atomics: bitwise reproducible, and the same
+ * bits however svils_batch_set_elbo_tiles cuts the tiles into launches.  Waits for the device; svils_batch_get_timing
+ * called next gives the pass's device ms in ms[0], ms[1] = ms[2] = -1.  SVILS_ERR_ARG: null parts, no graph or no state;
+ * SVILS_ERR_UNSUPPORTED "phi normaliser underflow": a pair of the pass whose normaliser is not > 0 (parts untouched) */
+int svils_batch_elbo(svils_batch *h, double parts[4], uint64_t *pairs_done, uint64_t *rounds_total);
+/* tiles per launch of the pair pass of svils_batch_elbo: 1 .. 2048, 0 the default of 2048 (the sweep's bound); more:
+ * SVILS_ERR_ARG.  Results do not depend on it */
+int svils_batch_set_elbo_tiles(svils_batch *h, uint32_t tiles_per_launch);
 
 /* ---- -orig: the full K x K blockmodel (an ADDITION of ABI 8; a handle of its own) ---------------------------------------
  * The reference's MMSBInferOrig::batch_infer (src/mmsbinferorig.cc:212-294; fixed point PhiComp2,

@@ -43,7 +43,7 @@ EXPORTS = (
     "svils_batch_create", "svils_batch_destroy", "svils_batch_set_graph", "svils_batch_set_state", "svils_batch_get_state",
     "svils_batch_sweep", "svils_batch_pair_loglik", "svils_batch_get_stats", "svils_batch_get_timing", "svils_batch_variant",
     "svils_batch_step_node", "svils_batch_step_pairs", "svils_batch_step_star", "svils_batch_set_star_chain",
-    "svils_batch_get_expectations",
+    "svils_batch_get_expectations", "svils_batch_elbo", "svils_batch_set_elbo_tiles",
     "svils_orig_create", "svils_orig_destroy", "svils_orig_set_graph", "svils_orig_set_state", "svils_orig_get_state",
     "svils_orig_sweep", "svils_orig_pair_loglik", "svils_orig_get_stats", "svils_orig_get_timing", "svils_orig_variant",
     "svils_orig_set_launch_rows", "svils_orig_link_prob", "svils_orig_predict_links", "svils_orig_rank_links",
@@ -210,6 +210,8 @@ def load():
     L.svils_batch_step_star.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.svils_batch_set_star_chain.argtypes = [vp, C.c_uint32]
     L.svils_batch_get_expectations.argtypes = [vp, vp, vp]
+    L.svils_batch_elbo.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.svils_batch_set_elbo_tiles.argtypes = [vp, C.c_uint32]
     L.svils_orig_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(vp)]
     L.svils_orig_destroy.argtypes = [vp]
     L.svils_orig_set_graph.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
@@ -733,6 +735,16 @@ class Batch:
         ep, eb = np.empty((self.n, self.k)), np.empty((self.k, 2))
         _chk(load().svils_batch_get_expectations(self._h, ep.ctypes.data, eb.ctypes.data))
         return ep, eb
+
+    def elbo(self):
+        """svils_batch_elbo: (parts [4] = total, G, P, N; pairs of the pass; their fixed-point rounds)"""
+        parts, a, b = np.empty(4), C.c_uint64(), C.c_uint64()
+        _chk(load().svils_batch_elbo(self._h, parts.ctypes.data, C.byref(a), C.byref(b)))
+        return parts, a.value, b.value
+
+    def set_elbo_tiles(self, tiles_per_launch):
+        """svils_batch_set_elbo_tiles: tiles per launch of the pass (0: the default); results do not depend on it"""
+        _chk(load().svils_batch_set_elbo_tiles(self._h, tiles_per_launch))
 
     def pair_loglik(self, pairs, y):
         pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)

@@ -36,6 +36,13 @@
 // -infset: the informative-set steps of FastAMM::infer (src/fastamm.cc:549-672) on the same handle:
 //
 //   k_batch_star_chain<W,V> a chain of star steps in one workgroup of one launch, a barrier between steps
+//
+// -logl: approx_log_likelihood (src/mmsbinfer.cc:1948-2060) of the current state on the same handle:
+//
+//   k_batch_elbo<W,V>       the tiles of k_batch_pairs; a pair's term from the registers its group holds, one double per
+//                           (tile, wavefront)
+//   k_batch_elbo_nodes      one wavefront per node: the node's term
+//   k_batch_elbo_reduce     one block: the lambda terms, and the three sums in a fixed order
 #include "svils_devutil.h"
 #include "svils_tool.h"
 #include "svils_waveutil.h"
@@ -349,6 +356,152 @@ __global__ __launch_bounds__(256) void k_batch_pair_ll(uint64_t m, uint32_t K, d
   }
   s = wave_sum_f64(s);
   if (lane == 0) out[x] = log(s < 1e-30 ? 1e-30 : s);
+}
+
+// ---- the variational lower bound (svils_batch_elbo) -------------------------------------------
+// approx_log_likelihood (src/mmsbinfer.cc:1948-2060): s = G + P + N.  The pair part runs the tiles of a sweep and keeps a
+// scalar where the sweep keeps gamma and lambda partials.
+
+// phi log phi; an entry that has underflowed to exactly 0 adds 0 (the reference's log(phi) * phi is NaN there)
+__device__ __forceinline__ double xlogx(double p) { return p > 0.0 ? p * log(p) : 0.0; }
+
+struct ElboArgs {
+  uint32_t n, K, nw, t0;            // as PairArgs
+  const uint32_t *tiles;
+  const uint32_t *adj, *skip;
+  const double *elogpi, *elogbeta;
+  double logeps;
+  double *part;                     // [tile of the pass][4]: one double per (tile, wavefront), indexed by the pass's tile
+  unsigned long long *ctr;          // the pass's own five: pairs, rounds, most rounds, underflows (twice)
+};
+
+// The tile and group layout of k_batch_pairs<W,V>.  A group that has left the fixed point forms its pair's term from the
+// registers it holds; a lane adds its share of every step of its wavefront, one butterfly at the end.
+template <int W, int V>
+__global__ __launch_bounds__(256) void k_batch_elbo(ElboArgs x) {
+  constexpr int G = 64 / W, WV = W * V, A = rows_per_wave(WV);
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / W, lw = lane % W;
+  const uint32_t bt = blockIdx.x, K = x.K, n = x.n;
+  const uint32_t rb = x.tiles[2 * (size_t)(x.t0 + bt)], cb = x.tiles[2 * (size_t)(x.t0 + bt) + 1];
+  const uint32_t row0 = rb * (4 * A) + wave * A, col0 = cb * TILE_COLS;
+  bool kval[V];
+  double ef0[V], ef1[V];   // elogf for y = 0 / y = 1
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const uint32_t k = v * W + lw;
+    kval[v] = k < K;
+    ef1[v] = kval[v] ? x.elogbeta[2 * k] : 0.0;
+    ef0[v] = kval[v] ? x.elogbeta[2 * k + 1] : 0.0;
+  }
+  double acc = 0.0;
+  uint32_t npairs = 0, rtot = 0, rmax = 0, under = 0;
+
+  for (uint32_t c = 0; c < (uint32_t)W; ++c) {   // 64 / G chunks of G columns
+    const uint32_t b = col0 + c * G + g;
+    const bool bval = b < n;
+    double elq[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) elq[v] = bval && kval[v] ? x.elogpi[(size_t)b * K + v * W + lw] : 0.0;
+    for (uint32_t ai = 0; ai < (uint32_t)A; ++ai) {
+      const uint32_t a = row0 + ai;
+      if (a >= n) break;   // the same in every lane
+      bool valid = bval && a < b;
+      bool y = false;
+      if (valid) {
+        const size_t wd = (size_t)a * x.nw + (b >> 5);
+        const uint32_t bit = 1u << (b & 31);
+        valid = (x.skip[wd] & bit) == 0;
+        y = (x.adj[wd] & bit) != 0;
+      }
+      if (!__ballot(valid)) continue;   // the same in every lane
+      double elp[V], ef[V], p1[V], p2[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        elp[v] = kval[v] ? x.elogpi[(size_t)a * K + v * W + lw] : 0.0;
+        ef[v] = y ? ef1[v] : ef0[v];
+        p1[v] = p2[v] = phi_start(kval[v], K);
+      }
+      uint32_t rounds;
+      const double le = y ? x.logeps : 0.0;
+      pair_fixed_point<W, V>(elp, elq, ef, le, kval, K, valid, p1, p2, rounds, under);
+      if (valid && lw == 0) {
+        ++npairs;
+        rtot += rounds;
+        rmax = max(rmax, rounds);
+      }
+      // sum_k phi1 phi2 elogf + phi1 Elogpi_p + phi2 Elogpi_q - phi1 log phi1 - phi2 log phi2, this lane's k; the g != h sum
+      // of a link is S1 S2 - sum_k phi1 phi2 (lane 0 of the group carries S1 S2)
+      double t = 0.0, s1 = 0.0, s2 = 0.0, spp = 0.0;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        const double q1 = p1[v], q2 = p2[v], pp = q1 * q2;
+        t += pp * ef[v] + q1 * elp[v] + q2 * elq[v] - xlogx(q1) - xlogx(q2);
+        s1 += q1;
+        s2 += q2;
+        spp += pp;
+      }
+      s1 = group_sum<W>(s1);
+      s2 = group_sum<W>(s2);
+      t += le * ((lw == 0 ? s1 * s2 : 0.0) - spp);
+      acc += valid ? t : 0.0;
+    }
+  }
+  acc = wave_sum_f64(acc);
+  if (lane == 0) x.part[(size_t)(x.t0 + bt) * 4 + wave] = acc;
+  count_pairs(x.ctr, lane, npairs, rtot, rmax, lw == 0 ? under : 0);
+}
+
+// one wavefront per node, as k_batch_dir_exp: the node's term of N
+__global__ __launch_bounds__(256) void k_batch_elbo_nodes(uint32_t n, uint32_t K, double alpha, const double *__restrict__ gamma,
+                                                          const double *__restrict__ elogpi, double *__restrict__ out) {
+  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n) return;   // whole wavefronts leave together
+  const double *g = gamma + (size_t)i * K, *e = elogpi + (size_t)i * K;
+  double se = 0.0, sg = 0.0, sl = 0.0, sge = 0.0;
+  for (uint32_t k = lane; k < K; k += 64) {
+    se += e[k];
+    sg += g[k];
+    sl += lgamma(fmax(g[k], 1e-30));
+    sge += (g[k] - 1.0) * e[k];
+  }
+  se = wave_sum_f64(se);
+  sg = wave_sum_f64(sg);
+  sl = wave_sum_f64(sl);
+  sge = wave_sum_f64(sge);
+  if (lane == 0) out[i] = lgamma((double)K * alpha) - (double)K * lgamma(alpha) + (alpha - 1.0) * se - (lgamma(sg) - sl) - sge;
+}
+
+// One block.  P: the (tile, wavefront) partials of the whole pass; N: the node terms; G: the terms of the communities,
+// formed here.  Each sum: every thread its entries in ascending order, then a fixed tree over the threads -- the order
+// depends on the counts alone, never on how the tiles were cut into launches.  out: total, G, P, N
+__global__ __launch_bounds__(256) void k_batch_elbo_reduce(uint64_t nent, const double *__restrict__ part, uint32_t n,
+                                                           const double *__restrict__ node, uint32_t K, const double *__restrict__ lam,
+                                                           const double *__restrict__ elogbeta, double eta0, double eta1,
+                                                           double *__restrict__ out) {
+  __shared__ double red[3][256];
+  const uint32_t t = threadIdx.x;
+  double sp = 0.0, sn = 0.0, sg = 0.0;
+  for (uint64_t e = t; e < nent; e += 256) sp += part[e];
+  for (uint32_t i = t; i < n; i += 256) sn += node[i];
+  for (uint32_t k = t; k < K; k += 256) {
+    const double l0 = lam[2 * k], l1 = lam[2 * k + 1], e0 = elogbeta[2 * k], e1 = elogbeta[2 * k + 1];
+    sg += (lgamma(eta0 + eta1) - lgamma(eta0) - lgamma(eta1)) + ((eta0 - 1.0) * e0 + (eta1 - 1.0) * e1) -
+          (lgamma(l0 + l1) - lgamma(l0) - lgamma(l1)) - ((l0 - 1.0) * e0 + (l1 - 1.0) * e1);
+  }
+  red[0][t] = sg;
+  red[1][t] = sp;
+  red[2][t] = sn;
+  __syncthreads();
+  for (uint32_t o = 128; o > 0; o >>= 1) {
+    if (t < o) { red[0][t] += red[0][t + o]; red[1][t] += red[1][t + o]; red[2][t] += red[2][t + o]; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    out[0] = red[0][0] + red[1][0] + red[2][0];
+    out[1] = red[0][0];
+    out[2] = red[1][0];
+    out[3] = red[2][0];
+  }
 }
 
 // ---- sampled-pair steps (svils_batch_step_node / svils_batch_step_pairs) ----------------------
@@ -723,6 +876,13 @@ struct svils_batch : ToolHandle {
   size_t cap_pin = 0;
   hipEvent_t ev_copy = nullptr;
   bool copy_pending = false;
+  // the lower bound (svils_batch_elbo): buffers, counters and events of its own -- nothing a sweep or a step reads
+  uint32_t elbo_tiles = BATCH_TILES;                              // tiles per launch of k_batch_elbo
+  double *el_part = nullptr;                                      // GRAPH scope: [ntiles][4]
+  double *el_node = nullptr, *el_out = nullptr;                   // HANDLE scope: [n], [4]
+  unsigned long long *el_ctr = nullptr;                           // HANDLE scope: [5]
+  hipEvent_t ev_elbo[2] = {nullptr, nullptr};                     // the bracket of the last pass
+  bool timed_elbo = false;                                        // the last timed call was svils_batch_elbo
 };
 
 namespace {
@@ -798,7 +958,7 @@ int one_sweep(svils_batch *h) {
   std::swap(h->gamma, h->gnext);   // gamma = gamma_next (:883-886); later launches take the new pointers
   std::swap(h->lam, h->lnext);
   h->timed = true;
-  h->timed_steps = false;
+  h->timed_steps = h->timed_elbo = false;
   h->elog_fresh = false;
   return 0;
 }
@@ -834,6 +994,7 @@ int begin_steps(svils_batch *h) {
 int end_steps(svils_batch *h) {
   HIPCHK(hipEventRecord(h->ev[1], h->st));
   h->timed = h->timed_steps = true;
+  h->timed_elbo = false;
   return 0;
 }
 
@@ -934,6 +1095,8 @@ int svils_batch_destroy(svils_batch *h) {
     (void)hipStreamSynchronize(h->st);
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->ev_copy) (void)hipEventDestroy(h->ev_copy);
+    for (hipEvent_t e : h->ev_elbo)
+      if (e) (void)hipEventDestroy(e);
   }
   delete h;   // ~ToolHandle: waits for the stream, frees both scopes
   return 0;
@@ -997,7 +1160,7 @@ int svils_batch_set_graph(svils_batch *h, const uint32_t *links, uint64_t nlinks
   h->nrb = nrb;
   h->batch = batch;
   h->have_graph = true;
-  h->timed = false;
+  h->timed = h->timed_elbo = false;
   return 0;
 }
 
@@ -1286,6 +1449,60 @@ int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t
   return 0;
 }
 
+int svils_batch_set_elbo_tiles(svils_batch *h, uint32_t tiles_per_launch) {
+  if (int rc = check(h, "svils_batch_set_elbo_tiles")) return rc;
+  if (tiles_per_launch > BATCH_TILES)
+    return fail(SVILS_ERR_ARG, "svils_batch_set_elbo_tiles: %u tiles per launch exceed the most, %u", tiles_per_launch, BATCH_TILES);
+  h->elbo_tiles = tiles_per_launch ? tiles_per_launch : BATCH_TILES;
+  return 0;
+}
+
+int svils_batch_elbo(svils_batch *h, double parts[4], uint64_t *pairs_done, uint64_t *rounds_total) {
+  const char *name = "svils_batch_elbo";
+  if (int rc = check(h, name)) return rc;
+  if (!parts) return fail(SVILS_ERR_ARG, "%s: null argument", name);
+  if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "%s: set the graph and the state first", name);
+  if (int rc = settle(h, name)) return rc;
+  const uint32_t n = h->n, K = h->k;
+  if (int rc = h->reserve(ToolHandle::GRAPH, &h->el_part, 4 * (size_t)h->ntiles)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->el_node, (size_t)n)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->el_out, (size_t)4)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->el_ctr, (size_t)5)) return rc;
+  for (hipEvent_t &e : h->ev_elbo)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  if (int rc = renew_expectations(h)) return rc;   // those svils_batch_get_expectations would return
+  HIPCHK(hipMemsetAsync(h->el_ctr, 0, 5 * sizeof(unsigned long long), h->st));
+  HIPCHK(hipEventRecord(h->ev_elbo[0], h->st));
+  hipLaunchKernelGGL(k_batch_elbo_nodes, dim3(blocks(n, 4)), dim3(256), 0, h->st, n, K, h->alpha, h->gamma, h->elogpi, h->el_node);
+  HIPCHK(hipGetLastError());
+  for (uint32_t t0 = 0; t0 < h->ntiles; t0 += h->elbo_tiles) {
+    const uint32_t nt = std::min(h->ntiles - t0, h->elbo_tiles);
+    ElboArgs a{n, K, h->nw, t0, h->tiles, h->adj, h->skip, h->elogpi, h->elogbeta, std::log(h->epsilon), h->el_part, h->el_ctr};
+    if (int rc = launch_for_width(h, name, [&](auto w) {
+          hipLaunchKernelGGL((k_batch_elbo<decltype(w)::value, (int)VARIANT_V>), dim3(nt), dim3(256), 0, h->st, a);
+        }))
+      return rc;
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_batch_elbo_reduce, dim3(1), dim3(256), 0, h->st, (uint64_t)4 * h->ntiles, h->el_part, n, h->el_node, K, h->lam,
+                     h->elogbeta, h->eta0, h->eta1, h->el_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev_elbo[1], h->st));
+  h->timed_elbo = true;
+  unsigned long long c[5] = {};
+  double out[4] = {};
+  HIPCHK(hipMemcpyAsync(c, h->el_ctr, sizeof c, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(out, h->el_out, sizeof out, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  if (c[3])
+    return fail(SVILS_ERR_UNSUPPORTED, "%s: phi normaliser underflow in %llu pair(s) of the pass (the reference asserts s > 0 there)", name,
+                c[3]);
+  for (int i = 0; i < 4; ++i) parts[i] = out[i];
+  if (pairs_done) *pairs_done = c[0];
+  if (rounds_total) *rounds_total = c[1];
+  return 0;
+}
+
 int svils_batch_get_stats(svils_batch *h, uint64_t *pairs_done, uint64_t *rounds_total, uint32_t *rounds_max, uint64_t *underflow_pairs) {
   if (int rc = check(h, "svils_batch_get_stats")) return rc;
   unsigned long long c[5] = {};
@@ -1302,6 +1519,12 @@ int svils_batch_get_timing(svils_batch *h, double ms[3]) {
   if (int rc = check(h, "svils_batch_get_timing")) return rc;
   if (!ms) return fail(SVILS_ERR_ARG, "svils_batch_get_timing: null argument");
   HIPCHK(hipStreamSynchronize(h->st));
+  if (h->timed_elbo) {   // the last timed call was svils_batch_elbo: its own bracket, the sweep's events are as they were
+    float t = 0;
+    ms[0] = hipEventElapsedTime(&t, h->ev_elbo[0], h->ev_elbo[1]) == hipSuccess ? (double)t : -1.0;
+    ms[1] = ms[2] = -1.0;
+    return 0;
+  }
   ms[0] = h->elapsed_ms(0, 1, h->timed);
   const bool swept = h->timed && !h->timed_steps;
   ms[1] = h->launches_ms(1, h->nlaunch, swept);   // (the first launch's bracket includes the fill)

@@ -45,6 +45,7 @@ typedef struct {
   int32_t nodelay;         // ... with -nodelay
   double tau0, kappa, nodetau0, nodekappa;   // their step sizes (svih_options_default: 1024, 0.9, 1024, 0.5)
   double inf_epsilon;      // svih_infset_from_file: the chance of a non-informative step (svih_options_default: 1e-4)
+  int32_t logl;            // svih_batch_from_file / svih_infset_from_file: -logl, a row of the lower bound after the constructor and at every report
 } svih_options;
 
 struct svih_setup {
@@ -189,6 +190,7 @@ static svih_batch *make_batch(const char *path, const svih_options *o, const cha
     a.batch_gpu = o->batch_device != 0;
   }
   a.device = o->device;
+  a.logl = o->logl != 0;
   a.rand_seed = o->seed;
   a.hol_ratio = o->heldout_ratio;
   a.eta_type = eta_names[(o->eta_type >= 0 && o->eta_type < 4) ? o->eta_type : 0];
@@ -260,6 +262,10 @@ uint64_t svih_batch_nrows(const svih_batch *b) { return b->eng->heldout_rows().s
 const double *svih_batch_rows(const svih_batch *b) { return b->eng->heldout_rows().data(); }
 int svih_batch_sweep(svih_batch *b) { return svils_rc([&] { b->eng->sweep(); return 0; }); }   // < 0: a svils_error of the device backend
 int svih_batch_report(svih_batch *b) { return svils_rc([&] { return b->eng->report() ? 1 : 0; }); }
+// the variational lower bound of the current state: parts[4] = total, G, P, N (MMSBBatch::elbo); the rows -logl has written
+int svih_batch_elbo(svih_batch *b, double *parts) { return svils_rc([&] { b->eng->elbo(parts); return 0; }); }
+uint64_t svih_batch_nlogl(const svih_batch *b) { return b->eng->logl_rows().size() / 2; }
+const double *svih_batch_logl(const svih_batch *b) { return b->eng->logl_rows().data(); }
 double svih_batch_eta0(const svih_batch *b) { return b->env->eta0; }
 double svih_batch_eta1(const svih_batch *b) { return b->env->eta1; }
 double svih_batch_ones_prob(const svih_batch *b) { return b->env->ones_prob; }

@@ -199,6 +199,10 @@ static void usage() {
           "\t-no-stop\tdisable stopping criteria\n\n"
           "\t-seed\t\tset random generator seed\n\n"
           "\t-heldout-ratio, -link-thresh, -lt-min-deg, -eta-type, -accuracy\tas in the reference\n\n"
+          "\t-logl\t\twith -batch, -batch-gpu, -rnode, -rpair and -infset: the variational lower bound after the\n"
+          "\t\t\tinitialisation and at every report (a row of logl.txt; with -accuracy the convergence rule\n"
+          "\t\t\tthat writes done.txt); on the device unless -batch or -host-loops is given.  Accepted and\n"
+          "\t\t\twithout effect with every other mode\n\n"
           "\t-strid\t\tnode names are strings (writes str2id.txt)\n\n"
           "\t-nmi <file>\tground-truth communities (\"node<TAB>community ...\" per line): the normalised mutual\n"
           "\t\t\tinformation of every communities.txt against it is appended to mutual.txt\n\n"
@@ -280,6 +284,7 @@ int main(int argc, char **argv) {
     else if (is("-nmi")) { need(i); a.ground_truth_fname = argv[++i]; a.nmi = true; }
     else if (is("-rfreq")) { need(i); a.rfreq = atoi(argv[++i]); }
     else if (is("-accuracy")) { a.accuracy = true; }
+    else if (is("-logl")) { a.logl = true; }                 // src/main.cc:221-222: read by MMSBBatch alone (-batch, -rnode, -rpair, -infset)
     else if (is("-max-iterations")) { need(i); a.max_iterations = atoi(argv[++i]); }
     else if (is("-no-stop")) { a.use_validation_stop = false; }
     else if (is("-seed")) { need(i); a.rand_seed = atof(argv[++i]); }

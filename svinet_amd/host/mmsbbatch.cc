@@ -69,11 +69,13 @@ MMSBBatch::MMSBBatch(Env &env, Network &network)
       for (const char *f : {"/precision-pairs.txt", "/precision.txt"}) fclose(open_or_die(Env::file_str(f), f + 1));
     hf_ = open_or_die(Env::file_str("/heldout.txt"), "heldout");
     vf_ = open_or_die(Env::file_str("/validation.txt"), "validation");
+    if (env_.logl) lf_ = open_or_die(Env::file_str("/logl.txt"), "logl");   // without -logl it stays the empty file above
   }
   Env::plog("network ones", network_.ones());
   Env::plog("network singles", network_.singles());
   heldout_likelihood();
   validation_likelihood(nullptr);
+  if (env_.logl) approx_log_likelihood();                   // :174-175, src/fastamm.cc:289-290
   fprintf(stdout, "+ initialization end\n");
   fflush(stdout);
   start_time_ = time(0);
@@ -82,6 +84,7 @@ MMSBBatch::MMSBBatch(Env &env, Network &network)
 MMSBBatch::~MMSBBatch() {
   if (hf_) fclose(hf_);
   if (vf_) fclose(vf_);
+  if (lf_) fclose(lf_);
   if (dev_) svils_batch_destroy(dev_);
 }
 
@@ -686,9 +689,94 @@ void MMSBBatch::validation_likelihood(double *av) {         // src/mmsbinfer.cc:
 
 bool MMSBBatch::report() {                                  // src/mmsbinfer.cc:895-905
   if (!dev_) set_dir_exp();                                 // (the device forms Elogpi / Elogbeta at the head of its sweep)
-  if (heldout_likelihood()) return true;
+  if (heldout_likelihood()) return true;                    // (the reference exits there: no row of logl.txt)
   validation_likelihood(nullptr);
+  if (env_.logl) approx_log_likelihood();                   // :726-727, :914-915, src/fastamm.cc:668-669
   return false;
+}
+
+// ---------------------------------------------------------------------------
+// -logl: the variational lower bound (src/mmsbinfer.cc:1948-2083, src/fastamm.cc:1129-1258)
+// ---------------------------------------------------------------------------
+double MMSBBatch::elbo(double *parts) {
+  double out[4] = {0, 0, 0, 0};
+  if (dev_) {
+    if (int rc = svils_batch_elbo(dev_, out, nullptr, nullptr)) device_failed("svils_batch_elbo", rc);
+  } else {
+    set_dir_exp();
+    const uint32_t K = k_;
+    const double logeps = log(env_.epsilon);
+    double G = 0, P = 0, N = 0;
+    for (uint32_t k = 0; k < K; ++k) {                      // :1962-1982
+      const double *l = &lambda_[2 * k], *e = &elogbeta_[2 * k];
+      G += std::lgamma(env_.eta0 + env_.eta1) - (std::lgamma(env_.eta0) + std::lgamma(env_.eta1));
+      G += (env_.eta0 - 1) * e[0] + (env_.eta1 - 1) * e[1];
+      G -= std::lgamma(l[0] + l[1]) - (std::lgamma(l[0]) + std::lgamma(l[1]));
+      G -= (l[0] - 1) * e[0] + (l[1] - 1) * e[1];
+    }
+    std::vector<double> phi1(K), phi2(K);
+    for (uint32_t p = 0; p < n_; ++p)                       // :1984-2029
+      for (uint32_t q = p + 1; q < n_; ++q) {
+        const Edge e(p, q);
+        if (heldout_map_.count(e) || validation_map_.count(e)) continue;
+        const int y = network_.y(p, q) ? 1 : 0;
+        phis(p, q, y, phi1.data(), phi2.data());
+        const double *ep = &elogpi_[(size_t)p * K], *eq = &elogpi_[(size_t)q * K];
+        double t = 0, s1 = 0, s2 = 0, spp = 0;
+        for (uint32_t k = 0; k < K; ++k) {
+          const double pp = phi1[k] * phi2[k];
+          t += pp * (elogbeta_[2 * k] * y + elogbeta_[2 * k + 1] * (1 - y));
+          s1 += phi1[k];
+          s2 += phi2[k];
+          spp += pp;
+        }
+        if (y == 1) t += logeps * (s1 * s2 - spp);          // the g != h double loop
+        for (uint32_t k = 0; k < K; ++k) t += phi1[k] * ep[k] + phi2[k] * eq[k];
+        for (uint32_t k = 0; k < K; ++k) {                  // 0 log 0 = 0
+          if (phi1[k] > 0) t -= log(phi1[k]) * phi1[k];
+          if (phi2[k] > 0) t -= log(phi2[k]) * phi2[k];
+        }
+        P += t;
+      }
+    for (uint32_t p = 0; p < n_; ++p) {                     // :2031-2056
+      const double *g = &gamma_[(size_t)p * K], *ep = &elogpi_[(size_t)p * K];
+      double se = 0, sg = 0, sl = 0, sge = 0;
+      for (uint32_t k = 0; k < K; ++k) {
+        se += ep[k];
+        sg += g[k];
+        sl += std::lgamma(g[k] < 1e-30 ? 1e-30 : g[k]);
+        sge += (g[k] - 1) * ep[k];
+      }
+      N += std::lgamma(K * env_.alpha) - K * std::lgamma(env_.alpha) + (env_.alpha - 1) * se - (std::lgamma(sg) - sl) - sge;
+    }
+    out[0] = G + P + N;
+    out[1] = G;
+    out[2] = P;
+    out[3] = N;
+  }
+  if (parts) memcpy(parts, out, sizeof out);
+  return out[0];
+}
+
+double MMSBBatch::approx_log_likelihood() {
+  const double s = elbo(nullptr);
+  printf("approx. log likelihood = %f\n", s);
+  logl_rows_.push_back((double)iter_);
+  logl_rows_.push_back(s);
+  const uint32_t dur = duration();
+  if (lf_) {
+    fprintf(lf_, "%d\t%d\t%.5f\n", iter_, dur, s);
+    fflush(lf_);
+  }
+  const double w = s;                                       // :2062-2081
+  if (env_.accuracy && (iter_ > n_ || iter_ > 5000))
+    if (w > prev_w_ && prev_w_ != 0 && fabs((w - prev_w_) / prev_w_) < 0.00001 && env_.write_files) {
+      FILE *f = open_or_die(Env::file_str("/done.txt"), "done");
+      fprintf(f, "%d\t%d\t%.5f\n", iter_, dur, w);
+      fclose(f);
+    }
+  prev_w_ = w;
+  return s;
 }
 
 int MMSBBatch::batch_infer() {

@@ -61,6 +61,13 @@ class MMSBBatch {
   // the report step (:895-905); returns true when the stop rule fired
   bool report();
   void do_on_stop();                                      // :743-752
+  // -logl: the variational lower bound of the current state, s = G + P + N (approx_log_likelihood, :1948-2056; the same
+  // formula in src/fastamm.cc:1129-1232).  parts (may be null): s, G, P, N.  The device backend asks svils_batch_elbo; the
+  // host loops run the restated sums with std::lgamma.  An entry of phi that is exactly 0 adds 0 (the reference: NaN)
+  double elbo(double *parts);
+  // ... printed, a row of logl.txt, and with -accuracy the rule that writes done.txt (:2058-2081; no shell-out to `mutual`)
+  double approx_log_likelihood();
+  const std::vector<double> &logl_rows() const { return logl_rows_; }   // [rows][2]: iter, s
 
   // the sampled-pair engines.  infer(): as batch_infer(), a report every reportfreq iterations
   int infer();
@@ -141,6 +148,9 @@ class MMSBBatch {
   double spare_ = 0;
   time_t start_time_;
   FILE *hf_ = nullptr, *vf_ = nullptr;
+  FILE *lf_ = nullptr;               // logl.txt, open for rows under -logl alone
+  double prev_w_ = -2147483647.0;    // _prev_w (src/mmsbinfer.cc:35)
+  std::vector<double> logl_rows_;
   Drawn draw();                                           // get_subsample and the step sizes of iteration iter_ + drawn so far
   void step_host(const Drawn &d);
   int family_ = 0;                                        // _family, alternating under -stratified (:682-683)

@@ -23,7 +23,7 @@ class Options(C.Structure):
                 ("lt_min_deg", C.c_uint32), ("eta_type", C.c_int32), ("accuracy", C.c_int32), ("defer_gamma", C.c_int32),
                 ("batch_device", C.c_int32), ("device", C.c_int32), ("sampled", C.c_int32), ("nodelay", C.c_int32),
                 ("tau0", C.c_double), ("kappa", C.c_double), ("nodetau0", C.c_double), ("nodekappa", C.c_double),
-                ("inf_epsilon", C.c_double)]
+                ("inf_epsilon", C.c_double), ("logl", C.c_int32)]
 
 
 _lib = None
@@ -213,7 +213,7 @@ class BatchEngine:
         return L.svih_batch_from_file(os.fsencode(path), C.byref(o))
 
     def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, eta_type="uniform", on_device=False, device=0, nodelay=False,
-                 **step_sizes):
+                 logl=False, **step_sizes):
         L = load()
         vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
         if not hasattr(L, "_batch_ready"):
@@ -241,12 +241,19 @@ class BatchEngine:
                 f = getattr(L, "svih_batch_" + name)
                 f.argtypes = [vp]
                 f.restype = P(u32)
+            L.svih_batch_elbo.argtypes = [vp, vp]
+            L.svih_batch_elbo.restype = C.c_int
+            L.svih_batch_nlogl.argtypes = [vp]
+            L.svih_batch_nlogl.restype = u64
+            L.svih_batch_logl.argtypes = [vp]
+            L.svih_batch_logl.restype = P(dbl)
             L._batch_ready = True
         o = Options()
         L.svih_options_default(C.byref(o), n, k)
         o.seed, o.heldout_ratio, o.eta_type = seed, heldout_ratio, ETA_TYPES[eta_type]
         o.batch_device, o.device = int(bool(on_device)), device
         o.sampled, o.nodelay = self._SAMPLED, int(bool(nodelay))
+        o.logl = int(bool(logl))
         for key, value in step_sizes.items():
             if key not in self._STEP_SIZES:
                 raise TypeError("unexpected argument %r" % key)
@@ -292,6 +299,20 @@ class BatchEngine:
         if rc < 0:
             _svils._chk(rc)
         return bool(rc)
+
+    def elbo(self):
+        """the variational lower bound of the current state (approx_log_likelihood, src/mmsbinfer.cc:1948-2056):
+        (total, G, P, N).  on_device=True: svils_batch_elbo; else the host loops"""
+        parts = np.empty(4)
+        rc = load().svih_batch_elbo(self._h, parts.ctypes.data)
+        if rc < 0:
+            _svils._chk(rc)
+        return tuple(parts)
+
+    @property
+    def logl_rows(self):
+        """[rows][2] (iter, lower bound): with logl=True one row after the constructor and one per report"""
+        return _arr(load().svih_batch_logl(self._h), (load().svih_batch_nlogl(self._h), 2), np.float64)
 
     def close(self):
         if getattr(self, "_h", None):
