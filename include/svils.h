@@ -47,6 +47,7 @@ extern "C" {
                                     (additive, same version) svils_batch_elbo / svils_batch_set_elbo_tiles: -logl, the variational lower bound;
                                     (additive, same version) svils_orig_*: -orig, the full K x K blockmodel over all ordered pairs;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
+                                    (additive, same version) svils_ppc_*: -ppc / -gen, networks drawn from a model and their statistics;
                                     (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
                                     resource-allocation scores of pairs, the model-free baselines of svils_rank_links */
 
@@ -855,6 +856,58 @@ int svils_orig_get_query_timing(svils_orig *h, double *ms);
 /* host only: the instantiation of the pair kernel for k -- padded K, pairs per wavefront, 1 if the log tables live in LDS
  * (0: in registers).  SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_ORIG_MAX_K */
 int svils_orig_variant(uint32_t k, uint32_t *padded_k, uint32_t *pairs_per_wave, uint32_t *tables_in_lds);
+
+/* ---- -ppc / -gen: networks drawn from a model and their statistics (an ADDITION of ABI 8; a handle of its own) -----------
+ * The device side of the reference's MMSBGen::gen (src/mmsbgen.cc:43-71) and MMSBGen::ppc (draw_and_save, :662-697, with
+ * the statistics of :418-499 and :605-630).  GSL's random stream is not reproduced and cannot be: the draw is DEFINED here
+ * (DESIGN.md section 4l), and every decision is that definition's, bit for bit, on any grid:
+ *   random     Philox4x32-10, key (seed, r), counter (p, q, stream, block); the pair draw is stream 0, block 0, and
+ *              u = ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53 from the first two output words
+ *   link       for p < q: x_j = (pi_p[j] pi_q[j]) beta_j, s = sum of x_j in ascending j, y = (u < s).  No link is drawn
+ *              through epsilon (the reference's generator draws none when the indicators differ, src/mmsbgen.hh:180).
+ *              The tile kernel sums s on v_mfma_f64_16x16x4_f64; a pair whose tile sum lies within 2 K DBL_EPSILON s of
+ *              u is decided again with the ascending sum (the recheck of svils_lc)
+ *   colour     of a link: the first strict maximum x_max of x from 0; ratio = x_max / s; the link joins community
+ *              colour unless ratio < 0.5 (lc_current_draw_helper, :425-470; a NaN ratio joins) -- the same rule for a
+ *              drawn and for an observed list
+ *   statistics of the current list: links, deg [n], the largest degree and its smallest node, tri [n] (triangles through
+ *              a node), wedges = sum deg (deg - 1) / 2, transitivity = 3 T / wedges, the mean over nodes of
+ *              tri_i / C(deg_i, 2) (0 where deg < 2); per community size_k (joined links) and logpe_k = sum of
+ *              log x_max over them (the reference's edge_likelihood, :605-630), accumulated exactly in integer bins, so
+ *              it depends on no order
+ * n <= SVILS_PPC_MAX_N and 1 <= k <= SVILS_PPC_MAX_K, else SVILS_ERR_UNSUPPORTED before any device call.  Without a HIP
+ * device every other entry point answers SVILS_ERR_DEVICE ("no CPU path"); with one, a null handle SVILS_ERR_ARG. */
+#define SVILS_PPC_MAX_N 32768
+#define SVILS_PPC_MAX_K 2048
+typedef struct svils_ppc svils_ppc;
+/* device memory: two bit matrices n x ceil(n / 64) words (at most 128 MB each), pi twice (n x k doubles, padded), and
+ * max_links x 56 bytes of lists; max_links is the capacity of the link list */
+int svils_ppc_create(int device, uint32_t n, uint32_t k, uint64_t max_links, svils_ppc **out);
+int svils_ppc_destroy(svils_ppc *h);
+/* pi [n][k]: every entry >= 0 and finite, every row summing to 1 within 1e-9; beta [k] in [0, 1]: else SVILS_ERR_ARG */
+int svils_ppc_set_params(svils_ppc *h, const double *pi, const double *beta);
+/* replicate r of seed becomes the current list.  More links than max_links: SVILS_ERR_NOMEM, the count is what
+ * svils_ppc_get_draw_counts reports, and the current list and its statistics stay as they were */
+int svils_ppc_draw(svils_ppc *h, uint32_t seed, uint32_t r);
+/* the observed network becomes the current list: links [nlinks][2] with p < q < n, no repeats, any order */
+int svils_ppc_set_links(svils_ppc *h, const uint32_t *links, uint64_t nlinks);
+/* the statistics of the current list under the current parameters; synchronises */
+int svils_ppc_stats(svils_ppc *h);
+/* counts[2] = the links of the last svils_ppc_draw (also where it answered SVILS_ERR_NOMEM), the pairs it rechecked */
+int svils_ppc_get_draw_counts(svils_ppc *h, uint64_t counts[2]);
+/* the current list in (p, q) order: *count, and links [count][2]; after svils_ppc_stats colour [count] and joined [count] */
+int svils_ppc_get_links(svils_ppc *h, uint64_t *count, uint32_t *links, uint32_t *colour, uint8_t *joined);
+/* after svils_ppc_stats (any pointer may be null): deg [n], tri [n] */
+int svils_ppc_get_nodes(svils_ppc *h, uint32_t *deg, uint32_t *tri);
+/* after svils_ppc_stats: counts[5] = links, largest degree, its smallest node, triangles, wedges; values[2] = transitivity,
+ * mean local clustering (transitivity is NaN without a wedge) */
+int svils_ppc_get_summary(svils_ppc *h, uint64_t counts[5], double values[2]);
+/* after svils_ppc_stats: size [k], logpe [k] (0 for an empty community, -inf where a joined link has x_max = 0) */
+int svils_ppc_get_communities(svils_ppc *h, uint64_t *size, double *logpe);
+/* device milliseconds of the last draw, of the last list / CSR build and of the last statistics; -1: not run */
+int svils_ppc_get_timing(svils_ppc *h, double ms[3]);
+/* tiles per launch of the draw (0: all in one launch); no result depends on it */
+int svils_ppc_set_tile_batch(svils_ppc *h, uint32_t tiles_per_launch);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * Every tunable of the library is a row of ONE table: key, the SVILS_* environment variable that sets its default, the

@@ -48,7 +48,11 @@ EXPORTS = (
     "svils_orig_sweep", "svils_orig_pair_loglik", "svils_orig_get_stats", "svils_orig_get_timing", "svils_orig_variant",
     "svils_orig_set_launch_rows", "svils_orig_link_prob", "svils_orig_predict_links", "svils_orig_rank_links",
     "svils_orig_get_query_timing",
+    "svils_ppc_create", "svils_ppc_destroy", "svils_ppc_set_params", "svils_ppc_draw", "svils_ppc_set_links", "svils_ppc_stats",
+    "svils_ppc_get_draw_counts", "svils_ppc_get_links", "svils_ppc_get_nodes", "svils_ppc_get_summary", "svils_ppc_get_communities",
+    "svils_ppc_get_timing", "svils_ppc_set_tile_batch",
 )
+PPC_MAX_N, PPC_MAX_K = 32768, 2048      # SVILS_PPC_MAX_N, SVILS_PPC_MAX_K
 ORIG_MAX_K, ORIG_MAX_N = 64, 32768      # SVILS_ORIG_MAX_K, SVILS_ORIG_MAX_N
 BATCH_MAX_K, BATCH_MAX_N = 256, 32768   # SVILS_BATCH_MAX_K, SVILS_BATCH_MAX_N
 BATCH_STAR_CHAIN_MAX = 1024             # SVILS_BATCH_STAR_CHAIN_MAX
@@ -228,6 +232,19 @@ def load():
     L.svils_orig_rank_links.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
     L.svils_orig_get_query_timing.argtypes = [vp, vp]
     L.svils_orig_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.svils_ppc_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(vp)]
+    L.svils_ppc_destroy.argtypes = [vp]
+    L.svils_ppc_set_params.argtypes = [vp, vp, vp]
+    L.svils_ppc_draw.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.svils_ppc_set_links.argtypes = [vp, vp, C.c_uint64]
+    L.svils_ppc_stats.argtypes = [vp]
+    L.svils_ppc_get_draw_counts.argtypes = [vp, vp]
+    L.svils_ppc_get_links.argtypes = [vp, C.POINTER(C.c_uint64), vp, vp, vp]
+    L.svils_ppc_get_nodes.argtypes = [vp, vp, vp]
+    L.svils_ppc_get_summary.argtypes = [vp, vp, vp]
+    L.svils_ppc_get_communities.argtypes = [vp, vp, vp]
+    L.svils_ppc_get_timing.argtypes = [vp, vp]
+    L.svils_ppc_set_tile_batch.argtypes = [vp, C.c_uint32]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):

@@ -15,6 +15,7 @@
 #include "mmsbinferorig.hh"
 #include "network.hh"
 #include "nmi.hh"
+#include "ppc.hh"
 
 using namespace svinet;
 
@@ -152,6 +153,14 @@ int svih_mt_jump_check(unsigned long seed, uint64_t pos, uint32_t count, double 
     if (j.get() != b.get()) return 1;
   return j.position() == pos + count ? 0 : 1;
 }
+
+// the host random stream of -ppc / -gen (ppc.hh) for the tests: Philox4x32-10 of m counters ctr [m][4] under one key ->
+// out [m][4], and the parameter draws of replicate r of seed
+void svih_ppc_philox(const uint32_t *ctr, uint64_t m, const uint32_t *key, uint32_t *out) {
+  for (uint64_t i = 0; i < m; ++i) philox4x32_10(ctr + 4 * i, key, out + 4 * i);
+}
+void svih_ppc_dirichlet(const double *gam, uint32_t n, uint32_t k, uint32_t seed, uint32_t r, double *pi) { dirichlet_rows(gam, n, k, seed, r, pi); }
+void svih_ppc_beta(const double *lam, uint32_t k, uint32_t seed, uint32_t r, double *beta) { beta_draws(lam, k, seed, r, beta); }
 
 double svih_nmi(const char *communities_path, const char *ground_truth_path) {
   Cover x, y;

@@ -35,6 +35,10 @@ class Env {
     int itype = 0;
     bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
+    bool ppc = false, gen = false;      // -ppc / -gen: posterior predictive checks, a network from the prior (MMSBGen, src/main.cc:268-303)
+    int ppc_draws = 100;                // -ppc-draws (ppc_ndraws, src/env.hh:452)
+    int ppc_save = 0;                   // -ppc-save <m>: the networks of the first m replicates
+    bool ppc_mean = false;              // -ppc-mean: no parameter draws
     bool load = false;
     std::string location;
     bool val_load = false;

@@ -42,6 +42,9 @@ class LinkCommunities {
   uint64_t gml_edges() const { return counts_[1]; }
   uint64_t rechecked() const { return counts_[2]; }
   const double *timing_ms() const { return ms_; }
+  // the loaded model, until run() hands gamma to the device: gamma [n][k], lambda [k][2] (ppc.cc reads it with this loader)
+  const std::vector<double> &gamma() const { return gamma_; }
+  const std::vector<double> &lambda() const { return lambda_; }
 
  private:
   double avg(uint32_t k) const;

@@ -28,6 +28,7 @@
 #include "env.hh"
 #include "findk.hh"
 #include "lcstats.hh"
+#include "ppc.hh"
 #include "linksampling.hh"
 #include "mmsbbatch.hh"
 #include "mmsbinferorig.hh"
@@ -69,6 +70,10 @@ struct ToolMode {
 static const ToolMode kLinkCommunities = {   // -gml / -lcstats: one pass over a saved model
     F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %2$s is not available with %1$s (a single-GPU pass over gamma.txt / lambda.txt)\n"};
+static const ToolMode kPosterior = {         // -ppc / -gen: replicates of a saved model, or one network from the prior
+    F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
+        F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
+    "error: %2$s is not available with %1$s (a single-GPU tool: it fits nothing)\n"};
 static const ToolMode kFindK = {             // -findk: whole iterations
     F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %2$s is not available with %1$s (a single-GPU run)\n"};
@@ -191,6 +196,17 @@ static void usage() {
           "\t\t\tstatistics (community_stats.txt, node_bridgeness.txt, node_influence.txt, number_of_memberships.txt).\n"
           "\t\t\tSingle GPU\n\n"
           "\t-lcstats\tthe link-community statistics of -gml without network.gml, into the run's output directory\n\n"
+          "\t-ppc\t\tposterior predictive checks: reads gamma.txt and lambda.txt of the working directory, draws\n"
+          "\t\t\t-ppc-draws <R> (default 100) networks from the fitted model on the GPU and writes under ppc/ the observed\n"
+          "\t\t\tand replicated statistics (obs.txt, rep.txt: links, density, degrees, triangles, transitivity, clustering),\n"
+          "\t\t\tper-community sizes and log-likelihoods with z-scores (lc_size.txt, lc_logpe.txt) and summary.txt with\n"
+          "\t\t\tposterior predictive p-values.  Every replicate draws pi ~ Dirichlet(gamma), beta ~ Beta(lambda) afresh;\n"
+          "\t\t\t-ppc-mean uses the posterior means instead; -ppc-save <m> writes ppc/<r>/network.dat of the first m.\n"
+          "\t\t\tThe random stream is Philox4x32-10 keyed by -seed and the replicate, not the reference's GSL stream:\n"
+          "\t\t\tthat one is not reproduced.  -n <= 32768, -k <= 2048, single GPU, no host route\n\n"
+          "\t-gen\t\tgenerate a network from the model (-n, -k, -seed): pi ~ Dirichlet(0.05), beta ~ Beta(4700.59, 0.77);\n"
+          "\t\t\twrites gen/network_gen.dat, gen/pi-gen.txt, gen/beta-gen.txt.  The same stream and limits as -ppc;\n"
+          "\t\t\t-gen -orig, -disjoint and -gp are not implemented\n\n"
           "\t-load-validation <fname>\tuse the pairs in the file as the validation set for convergence\n\n"
           "\t-load <dir>\tresume from <dir>gamma.txt / <dir>lambda.txt\n\n"
           "\t-label\t\ttag output directory\n\n"
@@ -329,7 +345,12 @@ int main(int argc, char **argv) {
     else if (is("-infset")) { a.infset = true; }             // src/main.cc:189-190, :214-216: rfreq stays as it is
     else if (is("-preprocess")) { a.preprocess = true; }
     else if (is("-randzeros")) {}                            // ignored: the informative sets are the two-hop ones
-    else if (is("-gen") || is("-ppc") || is("-single") ||
+    else if (is("-ppc")) { a.ppc = true; }                   // src/main.cc:131-132, :139-140
+    else if (is("-gen")) { a.gen = true; }
+    else if (is("-ppc-draws")) { need(i); a.ppc_draws = atoi(argv[++i]); }
+    else if (is("-ppc-save")) { need(i); a.ppc_save = atoi(argv[++i]); }
+    else if (is("-ppc-mean")) { a.ppc_mean = true; }
+    else if (is("-single") ||
              is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
       unsupported = true;
@@ -339,6 +360,50 @@ int main(int argc, char **argv) {
   }
   const bool sampled = a.rnode || a.rpair;
   const bool infset = a.infset || a.preprocess;
+  if ((a.ppc || a.gen) && !unsupported) {                // -ppc / -gen (MMSBGen): refusals before anything is read or created
+    const char *flag = a.gen ? "-gen" : "-ppc";
+    if (a.ppc && a.gen) {
+      fprintf(stderr, "error: -gen is not available with -ppc (one draws from the prior, the other from a fitted model)\n");
+      return 2;
+    }
+    if (refused(a, kPosterior, flag)) return 2;
+    const struct { bool set; const char *name; } more[] = {
+        {a.orig, "-orig"}, {a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.batch_gpu, "-batch-gpu"}, {a.load, "-load"}};
+    for (const auto &m : more)
+      if (m.set) {
+        fprintf(stderr, kPosterior.fmt, flag, m.name);
+        return 2;
+      }
+    if (a.k < 1 || a.k > SVILS_PPC_MAX_K) {              // the limits of svils_ppc_create
+      fprintf(stderr, "error: %s holds 1 <= -k <= %d (SVILS_PPC_MAX_K); -k %u is refused\n", flag, SVILS_PPC_MAX_K, a.k);
+      return 2;
+    }
+    if (a.n < 2 || a.n > SVILS_PPC_MAX_N) {
+      fprintf(stderr, "error: %s holds 2 <= -n <= %d (SVILS_PPC_MAX_N); -n %u is refused\n", flag, SVILS_PPC_MAX_N, a.n);
+      return 2;
+    }
+    if (a.ppc && (a.ppc_draws < 1 || a.ppc_save < 0)) {
+      fprintf(stderr, "error: -ppc-draws wants a count >= 1 and -ppc-save a count >= 0\n");
+      return 2;
+    }
+    if (a.gen) {                                         // src/main.cc:268-280: no network is read
+      try {
+        return run_gen(a.n, a.k, (uint32_t)a.rand_seed, a.device) < 0 ? -1 : 0;
+      } catch (const SvilsError &e) {
+        fprintf(stderr, "error: %s\n", e.what());
+        return -1;
+      }
+    }
+    for (const char *m : {"gamma.txt", "lambda.txt"}) {
+      FILE *f = fopen(m, "r");
+      if (!f) {
+        fprintf(stderr, "error: -ppc needs %s in the working directory (the output directory of a fit): %s\n", m, strerror(errno));
+        return 2;
+      }
+      fclose(f);
+    }
+    a.write_files = false;                               // everything goes under ppc/ of the working directory; no run directory
+  }
   if (infset && !unsupported) {                          // -infset / -preprocess (FastAMM): an engine of its own
     const char *flag = a.preprocess ? "-preprocess" : "-infset";
     if (refused(a, kInfset, flag)) return 2;
@@ -387,7 +452,7 @@ int main(int argc, char **argv) {
     unsupported = true;
     unsupported_flag = "-stratified";
   }
-  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || sampled || infset || a.orig)) {
+  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || a.ppc || sampled || infset || a.orig)) {
     fprintf(stderr,
             "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk, -gml, -lcstats)%s%s.\n"
             "Use the reference build for the other engines.\n",
@@ -610,6 +675,16 @@ run:
         }
       }
       exit(0);
+    }
+    if (a.ppc) {                             // src/main.cc:298-304
+      printf("+ generating networks for posterior predictive checks\n");
+      fflush(stdout);
+      PpcOptions po;
+      po.draws = (uint32_t)a.ppc_draws;
+      po.seed = (uint32_t)a.rand_seed;
+      po.save = (uint32_t)a.ppc_save;
+      po.mean = a.ppc_mean;
+      exit(run_ppc(env, network, po) < 0 ? 255 : 0);
     }
     if (a.findk) {                           // src/main.cc:321-327, before the other engines (-batch / -link-sampling only name the directory)
       FindK(env, network).run();

@@ -78,6 +78,12 @@ def load():
     L.svih_findk_state.restype = None
     L.svih_findk_timing.argtypes = [vp, vp]
     L.svih_findk_timing.restype = C.c_int
+    L.svih_ppc_philox.argtypes = [vp, u64, vp, vp]
+    L.svih_ppc_philox.restype = None
+    L.svih_ppc_dirichlet.argtypes = [vp, u32, u32, u32, u32, vp]
+    L.svih_ppc_dirichlet.restype = None
+    L.svih_ppc_beta.argtypes = [vp, u32, u32, u32, vp]
+    L.svih_ppc_beta.restype = None
     _lib = L
     return L
 
@@ -688,3 +694,113 @@ def LinkCommunities(links, gamma, lam, device=0, with_pi=False):
     finally:
         L.svils_lc_destroy(h)
     return out
+
+
+class PPC:
+    """One svils_ppc handle: networks drawn from a model (pi [n][k], beta [k]) and the statistics of a link list, the device
+    side of the reference's MMSBGen::gen and MMSBGen::ppc (src/mmsbgen.cc:43-71, 662-697).  The draw is the library's own
+    definition (include/svils.h), not GSL's stream.  max_links: the room of the link list (default:
+    every pair).
+
+        ppc = PPC(n, k); links = ppc.draw(pi, beta, seed, r); rep = ppc.stats()
+        ppc.observe(observed_links); obs = ppc.stats()"""
+
+    def __init__(self, n, k, device=0, max_links=None):
+        self._h = C.c_void_p()
+        self.n, self.k = int(n), int(k)
+        if max_links is None:
+            max_links = self.n * (self.n - 1) // 2
+        _svils._chk(_svils.load().svils_ppc_create(device, self.n, self.k, int(max_links), C.byref(self._h)))
+
+    def set_params(self, pi, beta):
+        pi = np.ascontiguousarray(pi, dtype=np.float64)
+        beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        if pi.shape != (self.n, self.k) or beta.shape != (self.k,):
+            raise ValueError("pi must be [%d][%d] and beta [%d]" % (self.n, self.k, self.k))
+        _svils._chk(_svils.load().svils_ppc_set_params(self._h, pi.ctypes.data, beta.ctypes.data))
+
+    def set_tile_batch(self, tiles_per_launch):
+        """tiles per launch of the draw (0: one launch); no result depends on it"""
+        _svils._chk(_svils.load().svils_ppc_set_tile_batch(self._h, int(tiles_per_launch)))
+
+    def draw(self, pi=None, beta=None, seed=0, r=0):
+        """replicate r of seed under (pi, beta) (None: the parameters set last) becomes the current list -> links [E][2]"""
+        if pi is not None:
+            self.set_params(pi, beta)
+        _svils._chk(_svils.load().svils_ppc_draw(self._h, int(seed), int(r)))
+        return self.links()
+
+    def draw_counts(self):
+        """(links of the last draw -- also of one that did not fit the list --, pairs it rechecked)"""
+        c = np.zeros(2, np.uint64)
+        _svils._chk(_svils.load().svils_ppc_get_draw_counts(self._h, c.ctypes.data))
+        return int(c[0]), int(c[1])
+
+    def observe(self, links):
+        """the observed network (links [E][2], p < q, no repeats) becomes the current list"""
+        links = np.ascontiguousarray(links, dtype=np.uint32).reshape(-1, 2)
+        _svils._chk(_svils.load().svils_ppc_set_links(self._h, links.ctypes.data, links.shape[0]))
+
+    def links(self):
+        m = C.c_uint64()
+        L = _svils.load()
+        _svils._chk(L.svils_ppc_get_links(self._h, C.byref(m), None, None, None))
+        out = np.zeros((m.value, 2), np.uint32)
+        _svils._chk(L.svils_ppc_get_links(self._h, C.byref(m), out.ctypes.data, None, None))
+        return out
+
+    def stats(self):
+        """the statistics of the current list under the current parameters, as a dict: links [E][2] in (p, q) order with
+        colour and join per link; deg, tri [n]; ones, max_deg, argmax_deg, triangles, wedges, transitivity, clustering;
+        size, logpe [k]; rechecked (pairs of the last draw); timing_ms (draw, csr, stats)"""
+        L, ok = _svils.load(), _svils._chk
+        ok(L.svils_ppc_stats(self._h))
+        out = {"links": self.links()}
+        E = out["links"].shape[0]
+        colour, joined = np.zeros(E, np.uint32), np.zeros(E, np.uint8)
+        m = C.c_uint64()
+        ok(L.svils_ppc_get_links(self._h, C.byref(m), None, colour.ctypes.data, joined.ctypes.data))
+        out["colour"], out["join"] = colour, joined != 0
+        out["deg"], out["tri"] = np.zeros(self.n, np.uint32), np.zeros(self.n, np.uint32)
+        ok(L.svils_ppc_get_nodes(self._h, out["deg"].ctypes.data, out["tri"].ctypes.data))
+        counts, values = np.zeros(5, np.uint64), np.zeros(2, np.float64)
+        ok(L.svils_ppc_get_summary(self._h, counts.ctypes.data, values.ctypes.data))
+        for name, v in zip(("ones", "max_deg", "argmax_deg", "triangles", "wedges"), counts):
+            out[name] = int(v)
+        out["transitivity"], out["clustering"] = float(values[0]), float(values[1])
+        out["size"], out["logpe"] = np.zeros(self.k, np.uint64), np.zeros(self.k, np.float64)
+        ok(L.svils_ppc_get_communities(self._h, out["size"].ctypes.data, out["logpe"].ctypes.data))
+        out["rechecked"] = self.draw_counts()[1]
+        ms = np.zeros(3, np.float64)
+        ok(L.svils_ppc_get_timing(self._h, ms.ctypes.data))
+        out["timing_ms"] = {"draw": ms[0], "csr": ms[1], "stats": ms[2]}
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _svils.load().svils_ppc_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def ppc_philox(counters, key):
+    """the host side's Philox4x32-10 (host/ppc.cc) of counters [m][4] under key (k0, k1) -> uint32 [m][4]"""
+    c = np.ascontiguousarray(counters, dtype=np.uint32).reshape(-1, 4)
+    k = np.ascontiguousarray(key, dtype=np.uint32).reshape(2)
+    out = np.zeros_like(c)
+    load().svih_ppc_philox(c.ctypes.data, c.shape[0], k.ctypes.data, out.ctypes.data)
+    return out
+
+
+def ppc_params(gamma, lam, seed, r):
+    """the parameters of replicate r of seed as -ppc draws them on the host: pi_i ~ Dirichlet(gamma_i) [n][k],
+    beta_k ~ Beta(lam_k0, lam_k1) [k] (MMSBGen::draw_all, src/mmsbgen.cc:730-742, over this project's Philox streams)"""
+    gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+    lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1, 2)
+    n, k = gamma.shape
+    assert lam.shape[0] == k
+    pi, beta = np.zeros((n, k)), np.zeros(k)
+    load().svih_ppc_dirichlet(gamma.ctypes.data, n, k, int(seed), int(r), pi.ctypes.data)
+    load().svih_ppc_beta(lam.ctypes.data, k, int(seed), int(r), beta.ctypes.data)
+    return pi, beta
