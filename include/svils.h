@@ -45,6 +45,7 @@ extern "C" {
                                     (additive, same version) svils_batch_step_node / svils_batch_step_pairs: -rnode / -rpair, sampled-pair steps;
                                     (additive, same version) svils_batch_step_star / svils_batch_set_star_chain / svils_batch_get_expectations: -infset, informative-set steps;
                                     (additive, same version) svils_batch_elbo / svils_batch_set_elbo_tiles: -logl, the variational lower bound;
+                                    (additive, same version) svils_batch_step_strat / svils_batch_get_lag: -snode, stratified random node steps;
                                     (additive, same version) svils_orig_*: -orig, the full K x K blockmodel over all ordered pairs;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_ppc_*: -ppc / -gen, networks drawn from a model and their statistics;
@@ -674,7 +675,7 @@ int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t
 int svils_batch_get_stats(svils_batch *h, uint64_t *pairs_done, uint64_t *rounds_total, uint32_t *rounds_max,
                           uint64_t *underflow_pairs);
 /* device milliseconds of the last sweep: Elogpi / Elogbeta, the pair pass, the reductions (hipEvent brackets; -1: none yet).
- * After a call of svils_batch_step_node / svils_batch_step_pairs / svils_batch_step_star: ms[0] brackets all steps of that call, ms[1] = ms[2] = -1 */
+ * After a call of svils_batch_step_node / svils_batch_step_pairs / svils_batch_step_star / svils_batch_step_strat: ms[0] brackets all steps of that call, ms[1] = ms[2] = -1 */
 int svils_batch_get_timing(svils_batch *h, double ms[3]);
 /* the pair kernel's instantiation for k: a group of W lanes per pair, V values per lane, W * V >= k.  No device needed.
  * SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_BATCH_MAX_K */
@@ -739,6 +740,36 @@ int svils_batch_set_star_chain(svils_batch *h, uint32_t max_steps);
  * sweep or svils_batch_set_state came since the last step call (what the next step call would do), else the ones the steps
  * maintain row by row.  Waits for the stream.  Either pointer may be null.  SVILS_ERR_ARG: no state */
 int svils_batch_get_expectations(svils_batch *h, double *elogpi, double *elogbeta);
+
+/* ---- -snode: stratified random node steps on the svils_batch handle (an ADDITION of ABI 8) ------------------------------
+ * The reference's FastAMM2::infer (src/fastamm2.cc:535-702) with opt_process / opt_process_noninf (:933-1165), the engine
+ * behind `-stratified -rnode`.  Step s is a star as in svils_batch_step_star -- the start node a = start[s], the entries
+ * off[s] .. off[s + 1) with partner[e] = j and y[e] the pair's link bit -- but EVERY row of gamma moves, with one step
+ * size rho = rho_gamma[s]:
+ *   Elogpi / Elogbeta   those of the current gamma and lambda
+ *   pair pass           every listed pair (a, j): the fixed point of svils_batch_sweep
+ *   listed rows and a   gamma_i = (1 - rho) gamma_i + rho (alpha + scale[s] gammat_i), gammat_j = phi_j, gammat_a = sum phi_a
+ *   every other row     gamma_i = (1 - rho) gamma_i + rho alpha
+ *   lambda              as svils_batch_step_star: rho_lambda[s] < 0 leaves lambda and Elogbeta bit for bit
+ * The other rows are not written by the step.  gamma_i - alpha of such a row is multiplied by (1 - rho_s) at every step,
+ * so the handle keeps, on the host, the running c = sum_s log1p(-rho_s) (one addition per step, in step order, whatever
+ * the cut into calls) and per row the value c had when the row was last written; a row's true value is
+ * alpha + (gamma_i - alpha) exp(c - c_i), and the step applies that factor to the rows it names as it reads them (a
+ * factor of exactly 1 leaves the bits).  Every other entry point that reads or writes gamma (svils_batch_get_state,
+ * _get_expectations, _sweep, _step_node, _step_pairs, _step_star, _pair_loglik, _elbo) first brings every row that is
+ * behind to its true value in one elementwise launch; svils_batch_set_state starts the bookkeeping afresh.  No caller can
+ * observe a stale row.  Two launches per step with entries (grid-wide pair pass, fixed-order tail), one without; Elogpi is
+ * formed in registers and its buffer is not maintained (the next entry point that needs it renews it).  No floating-point
+ * atomics; the result does not depend on how the steps are cut into calls.  A call between two steps that catches the rows
+ * up (svils_batch_get_state, say) rounds them there: later results then agree with the uninterrupted run to rounding, not
+ * bit for bit.  svils_batch_get_stats / svils_batch_get_timing cover the call as for the other steps.
+ * SVILS_ERR_ARG, checked before anything is enqueued (the state and the bookkeeping are untouched): the cases of
+ * svils_batch_step_star (it has no rho_partner), a rho_gamma outside (0, 1) -- 1 is refused: log1p(-1) has no value --
+ * and a rho_lambda above 1 */
+int svils_batch_step_strat(svils_batch *h, uint32_t nsteps, const uint32_t *start, const uint64_t *off, const uint32_t *partner,
+                           const uint8_t *y, const double *rho_gamma, const double *scale, const double *rho_lambda);
+/* rows of gamma whose stored value is behind their true value (c_i != c).  No device work.  SVILS_ERR_ARG: a null pointer */
+int svils_batch_get_lag(svils_batch *h, uint64_t *rows_behind);
 
 /* ---- -logl: the variational lower bound on the svils_batch handle (an ADDITION of ABI 8) ---------------------------------
  * The reference's approx_log_likelihood (src/mmsbinfer.cc:1948-2060, src/fastamm.cc:1129-1258) of the current state:

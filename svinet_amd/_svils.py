@@ -44,6 +44,7 @@ EXPORTS = (
     "svils_batch_sweep", "svils_batch_pair_loglik", "svils_batch_get_stats", "svils_batch_get_timing", "svils_batch_variant",
     "svils_batch_step_node", "svils_batch_step_pairs", "svils_batch_step_star", "svils_batch_set_star_chain",
     "svils_batch_get_expectations", "svils_batch_elbo", "svils_batch_set_elbo_tiles",
+    "svils_batch_step_strat", "svils_batch_get_lag",
     "svils_orig_create", "svils_orig_destroy", "svils_orig_set_graph", "svils_orig_set_state", "svils_orig_get_state",
     "svils_orig_sweep", "svils_orig_pair_loglik", "svils_orig_get_stats", "svils_orig_get_timing", "svils_orig_variant",
     "svils_orig_set_launch_rows", "svils_orig_link_prob", "svils_orig_predict_links", "svils_orig_rank_links",
@@ -216,6 +217,8 @@ def load():
     L.svils_batch_get_expectations.argtypes = [vp, vp, vp]
     L.svils_batch_elbo.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.svils_batch_set_elbo_tiles.argtypes = [vp, C.c_uint32]
+    L.svils_batch_step_strat.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+    L.svils_batch_get_lag.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.svils_orig_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(vp)]
     L.svils_orig_destroy.argtypes = [vp]
     L.svils_orig_set_graph.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
@@ -742,6 +745,28 @@ class Batch:
         rs, sc, rl = (np.array([s[key] for s in steps], dtype=np.float64) for key in ("rho_start", "scale", "rho_lambda"))
         _chk(load().svils_batch_step_star(self._h, ns, start.ctypes.data, off.ctypes.data, partner.ctypes.data, y.ctypes.data,
                                           rp.ctypes.data, rs.ctypes.data, sc.ctypes.data, rl.ctypes.data))
+
+    def step_strat(self, steps):
+        """svils_batch_step_strat: one stratified random node step per entry of `steps`, enqueued.  A step is a dict: start,
+        partner [m], y [m], rho_gamma, scale, rho_lambda (< 0 leaves lambda alone).  Every row of gamma moves"""
+        ns = len(steps)
+        parts = [np.ascontiguousarray(s["partner"], dtype=np.uint32).reshape(-1) for s in steps]
+        ys = [np.ascontiguousarray(s["y"], dtype=np.uint8).reshape(-1) for s in steps]
+        assert all(a.shape == b.shape for a, b in zip(parts, ys))
+        off = np.zeros(ns + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([p.shape[0] for p in parts])
+        partner = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=np.uint32)
+        y = np.ascontiguousarray(np.concatenate(ys) if ys else np.zeros(0), dtype=np.uint8)
+        start = np.array([s["start"] for s in steps], dtype=np.uint32)
+        rg, sc, rl = (np.array([s[key] for s in steps], dtype=np.float64) for key in ("rho_gamma", "scale", "rho_lambda"))
+        _chk(load().svils_batch_step_strat(self._h, ns, start.ctypes.data, off.ctypes.data, partner.ctypes.data, y.ctypes.data,
+                                           rg.ctypes.data, sc.ctypes.data, rl.ctypes.data))
+
+    def lag(self):
+        """svils_batch_get_lag: rows of gamma whose stored value is behind (no device work)"""
+        c = C.c_uint64()
+        _chk(load().svils_batch_get_lag(self._h, C.byref(c)))
+        return c.value
 
     def set_star_chain(self, max_steps):
         """steps per launch of the star chain (0: the default, at most BATCH_STAR_CHAIN_MAX); results do not depend on it"""

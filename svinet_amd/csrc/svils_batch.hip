@@ -37,6 +37,15 @@
 //
 //   k_batch_star_chain<W,V> a chain of star steps in one workgroup of one launch, a barrier between steps
 //
+// -snode: the stratified random node steps of FastAMM2::infer (src/fastamm2.cc:535-702) on the same handle (DESIGN.md section
+// 4m).  Every row of gamma moves at every step; the rows a step does not name are not written -- their decay is one factor
+// per row, kept on the host and applied when the row is next read:
+//
+//   k_batch_strat_pairs<W,V> group e holds pair (a, j_e): catches both rows up, forms their Elogpi in registers, writes the
+//                            blended gamma_j and no Elogpi; phi_a and the lambda terms leave as per-wavefront partials
+//   k_batch_strat_tail       block k: the partials in a fixed order; gamma_a[k] caught up and blended, lambda[k], Elogbeta[k]
+//   k_batch_catch_up         every row at its true value, before any other entry point touches gamma
+//
 // -logl: approx_log_likelihood (src/mmsbinfer.cc:1948-2060) of the current state on the same handle:
 //
 //   k_batch_elbo<W,V>       the tiles of k_batch_pairs; a pair's term from the registers its group holds, one double per
@@ -715,6 +724,144 @@ __global__ __launch_bounds__(256) void k_batch_step_tail(uint32_t K, uint32_t nw
   }
 }
 
+// ---- stratified random node steps (svils_batch_step_strat) -------------------------------------
+// FastAMM2::infer (src/fastamm2.cc:565-640): a step is a star, but EVERY row of gamma moves -- the rows of the star towards
+// alpha + scale phi, all others a step rho towards alpha.  The others are not written: gamma_i - alpha of an untouched row
+// is multiplied by (1 - rho_s) at every step, so the host keeps the running c = sum log1p(-rho_s) and per row the c of its
+// last write, and a row is caught up with the one factor f = exp(c - c_i) when it is next read.
+
+// a stored row value at its true value; f == 1 exactly (a row that is not behind) keeps its bits
+__device__ __forceinline__ double caught_up(double g, double alpha, double f) { return f == 1.0 ? g : alpha + (g - alpha) * f; }
+
+// Elogpi of the row a group holds in registers (0 on the lanes past K): psi(g) - psi(row sum), the sum by group_sum
+template <int W, int V>
+__device__ __forceinline__ void row_elogpi(const double (&g)[V], const bool (&kval)[V], bool row_ok, const double2 *logtab,
+                                           double (&el)[V]) {
+  double s = 0.0;
+#pragma unroll
+  for (int v = 0; v < V; ++v) s += g[v];
+  s = group_sum<W>(s);
+  const double ps = digamma(row_ok ? s : 1.0, logtab);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const bool ok = row_ok && kval[v];
+    const double d = digamma(ok ? g[v] : 1.0, logtab) - ps;
+    el[v] = ok ? d : 0.0;
+  }
+}
+
+struct StratArgs {
+  uint32_t K, m, a;                 // entries of the step, its start node
+  double *gamma;                    // [n][K]: group e writes row partner[e]; row a is only read
+  const double *elogbeta;
+  const uint32_t *partner;          // [m]
+  const uint8_t *y;                 // [m]
+  const double *fj;                 // [m]: what catches row partner[e] up
+  double fa;                        // ... and row a
+  double logeps, alpha, scale, rho;
+  double *part_a, *pl;              // per-wavefront partials, as StepArgs
+  unsigned long long *ctr;
+  const double *gtab;
+};
+
+// First launch of a step: group e holds the pair (a, partner[e]).  Both rows are caught up and their Elogpi formed in
+// registers -- the Elogpi buffer is neither read nor written.  Row j belongs to its group (a partner is listed once),
+// which writes the blended row; row a is only read.  phi_a and the lambda terms leave per wavefront.
+template <int W, int V>
+__global__ __launch_bounds__(256) void k_batch_strat_pairs(StratArgs x) {
+  constexpr int G = 64 / W;
+  __shared__ double2 logtab[128];
+  load_logtab(logtab, x.gtab);
+  __syncthreads();
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / W, lw = lane % W;
+  const uint32_t K = x.K, a = x.a, wv = blockIdx.x * 4 + wave, e = wv * G + g;
+  const bool valid = e < x.m;
+  const uint32_t j = valid ? x.partner[e] : 0;
+  const bool y = valid && x.y[e] != 0;
+  const double f = valid ? x.fj[e] : 1.0;
+  bool kval[V];
+  double ga[V], gj[V], ef[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const uint32_t k = v * W + lw;
+    kval[v] = k < K;
+    ga[v] = kval[v] ? caught_up(x.gamma[(size_t)a * K + k], x.alpha, x.fa) : 0.0;
+    gj[v] = kval[v] && valid ? caught_up(x.gamma[(size_t)j * K + k], x.alpha, f) : 0.0;
+    ef[v] = kval[v] ? x.elogbeta[2 * k + (y ? 0 : 1)] : 0.0;
+  }
+  double ela[V], elj[V], pa[V], pj[V];
+  row_elogpi<W, V>(ga, kval, true, logtab, ela);
+  row_elogpi<W, V>(gj, kval, valid, logtab, elj);
+#pragma unroll
+  for (int v = 0; v < V; ++v) pa[v] = pj[v] = phi_start(kval[v], K);
+  uint32_t rounds, under = 0;
+  pair_fixed_point<W, V>(ela, elj, ef, y ? x.logeps : 0.0, kval, K, valid, pa, pj, rounds, under);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const uint32_t k = v * W + lw;
+    pa[v] = valid ? pa[v] : 0.0;
+    pj[v] = valid ? pj[v] : 0.0;
+    if (valid && kval[v]) x.gamma[(size_t)j * K + k] = (1.0 - x.rho) * gj[v] + x.rho * (x.alpha + x.scale * pj[v]);
+    const double pp = pa[v] * pj[v];
+    const double sa = cross_group_sum<W>(pa[v]);
+    const double t0 = cross_group_sum<W>(y ? pp : 0.0), t1 = cross_group_sum<W>(y ? 0.0 : pp);
+    if (g == 0 && kval[v]) {
+      x.part_a[(size_t)wv * K + k] = sa;
+      x.pl[((size_t)wv * K + k) * 2] = t0;
+      x.pl[((size_t)wv * K + k) * 2 + 1] = t1;
+    }
+  }
+  const bool cnt = valid && lw == 0;
+  count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt ? under : 0);
+}
+
+// Last launch of a step, block k: the fixed-order sums of k_batch_step_tail over the nwv wavefronts of the first launch
+// (nwv = 0, a step without entries: zero sums); gamma[a][k] caught up, then blended; lambda[k] and Elogbeta[k] as there.
+// A kernel of its own: k_batch_step_tail keeps its text, and with it the bits of the steps that run it
+__global__ __launch_bounds__(256) void k_batch_strat_tail(uint32_t K, uint32_t nwv, const double *__restrict__ part_a,
+                                                          const double *__restrict__ pl, double *__restrict__ gamma_a, double alpha,
+                                                          double fa, double eta0, double eta1, double scale, double rho_g,
+                                                          double rho_l, double *__restrict__ lam, double *__restrict__ elogbeta,
+                                                          const double *__restrict__ gtab) {
+  __shared__ double red[3][256];
+  const uint32_t k = blockIdx.x, t = threadIdx.x;
+  double sa = 0.0, s0 = 0.0, s1 = 0.0;
+  for (uint32_t w = t; w < nwv; w += 256) {
+    sa += part_a[(size_t)w * K + k];
+    s0 += pl[((size_t)w * K + k) * 2];
+    s1 += pl[((size_t)w * K + k) * 2 + 1];
+  }
+  red[0][t] = sa;
+  red[1][t] = s0;
+  red[2][t] = s1;
+  __syncthreads();
+  for (uint32_t o = 128; o > 0; o >>= 1) {
+    if (t < o) { red[0][t] += red[0][t + o]; red[1][t] += red[1][t + o]; red[2][t] += red[2][t + o]; }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  gamma_a[k] = (1.0 - rho_g) * caught_up(gamma_a[k], alpha, fa) + rho_g * (alpha + scale * red[0][0]);
+  if (rho_l >= 0.0) {
+    const double2 *tab = reinterpret_cast<const double2 *>(gtab);
+    const double l0 = (1.0 - rho_l) * lam[2 * k] + rho_l * (eta0 + scale * red[1][0]);
+    const double l1 = (1.0 - rho_l) * lam[2 * k + 1] + rho_l * (eta1 + scale * red[2][0]);
+    lam[2 * k] = l0;
+    lam[2 * k + 1] = l1;
+    const double ps = digamma(l0 + l1, tab);
+    elogbeta[2 * k] = digamma(l0, tab) - ps;
+    elogbeta[2 * k + 1] = digamma(l1, tab) - ps;
+  }
+}
+
+// every row at its true value: one thread per cell, one factor per row; a row with f == 1 exactly is not rewritten
+__global__ __launch_bounds__(256) void k_batch_catch_up(uint64_t nk, uint32_t K, double alpha, const double *__restrict__ fac,
+                                                        double *__restrict__ gamma) {
+  const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= nk) return;
+  const double f = fac[x / K];
+  if (f != 1.0) gamma[x] = alpha + (gamma[x] - alpha) * f;
+}
+
 // ---- informative-set steps (svils_batch_step_star) ---------------------------------------------
 // FastAMM::infer (src/fastamm.cc:565-616) with opt_process / opt_process_noninf (:915-1126): a step is a star -- a start
 // node a and the listed partners j -- and moves only the rows it names, each with its own step size.  A chain of steps
@@ -876,6 +1023,14 @@ struct svils_batch : ToolHandle {
   size_t cap_pin = 0;
   hipEvent_t ev_copy = nullptr;
   bool copy_pending = false;
+  // stratified random node steps (svils_batch_step_strat): the decay of the rows no step wrote, kept on the host.  A
+  // row's true value is alpha + (gamma_i - alpha) exp(lag_c - row_c[i])
+  double lag_c = 0.0;                                             // sum of log1p(-rho_s) over the strat steps, in step order
+  std::vector<double> row_c;                                      // [n] what lag_c was when the row was last written
+  bool behind = false;                                            // a strat step ran since every row was last at its true value
+  bool elogbeta_fresh = false;                                    // Elogbeta is that of lambda (the strat steps keep it, not Elogpi)
+  std::vector<double> h_fac;                                      // [n] the factors of a catch-up, alive until its copy is done
+  double *d_fac = nullptr;                                        // HANDLE scope
   // the lower bound (svils_batch_elbo): buffers, counters and events of its own -- nothing a sweep or a step reads
   uint32_t elbo_tiles = BATCH_TILES;                              // tiles per launch of k_batch_elbo
   double *el_part = nullptr;                                      // GRAPH scope: [ntiles][4]
@@ -926,6 +1081,25 @@ int settle(svils_batch *h, const char *name) {
   return 0;
 }
 
+// Every row of gamma at its true value: what every entry point other than svils_batch_step_strat runs before it reads
+// or writes gamma.  Nothing to do unless a strat step ran since the last one; the bookkeeping starts again from zero
+int catch_up(svils_batch *h) {
+  if (!h->behind) return 0;
+  const uint32_t n = h->n, K = h->k;
+  HIPCHK(hipStreamSynchronize(h->st));   // h_fac may still be on its way from the previous catch-up
+  h->h_fac.resize(n);
+  for (uint32_t i = 0; i < n; ++i) h->h_fac[i] = std::exp(h->lag_c - h->row_c[i]);   // exp(0) is 1 exactly
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->d_fac, (size_t)n)) return rc;
+  HIPCHK(hipMemcpyAsync(h->d_fac, h->h_fac.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->st));
+  const uint64_t nk = (uint64_t)n * K;
+  hipLaunchKernelGGL(k_batch_catch_up, dim3(blocks(nk, 256)), dim3(256), 0, h->st, nk, K, h->alpha, h->d_fac, h->gamma);
+  HIPCHK(hipGetLastError());
+  h->lag_c = 0.0;
+  std::fill(h->row_c.begin(), h->row_c.end(), 0.0);
+  h->behind = false;
+  return 0;
+}
+
 int one_sweep(svils_batch *h) {
   const uint32_t n = h->n, K = h->k;
   const uint64_t nk = (uint64_t)n * K;
@@ -959,7 +1133,7 @@ int one_sweep(svils_batch *h) {
   std::swap(h->lam, h->lnext);
   h->timed = true;
   h->timed_steps = h->timed_elbo = false;
-  h->elog_fresh = false;
+  h->elog_fresh = h->elogbeta_fresh = false;
   return 0;
 }
 
@@ -980,7 +1154,7 @@ int renew_expectations(svils_batch *h) {
   hipLaunchKernelGGL(k_batch_dir_exp, dim3(blocks(h->n, 4)), dim3(256), 0, h->st, h->n, h->k, h->gamma, h->gtab, h->elogpi);
   hipLaunchKernelGGL(k_batch_beta, dim3(blocks(h->k, 256)), dim3(256), 0, h->st, h->k, h->lam, h->gtab, h->elogbeta);
   HIPCHK(hipGetLastError());
-  h->elog_fresh = true;
+  h->elog_fresh = h->elogbeta_fresh = true;
   return 0;
 }
 
@@ -1068,6 +1242,7 @@ int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double 
   h->eta0 = eta0;
   h->eta1 = eta1;
   h->epsilon = epsilon;
+  h->row_c.assign(n, 0.0);
   const auto scope = ToolHandle::HANDLE;
   const size_t nk = (size_t)n * k;
   int rc = h->open(device, 2);
@@ -1177,13 +1352,17 @@ int svils_batch_set_state(svils_batch *h, const double *gamma, const double *lam
   HIPCHK(hipMemcpy(h->lam, lambda, 2 * (size_t)h->k * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemset(h->ctr, 0, 5 * sizeof(unsigned long long)));
   h->have_state = true;
-  h->elog_fresh = false;
+  h->elog_fresh = h->elogbeta_fresh = false;
+  h->lag_c = 0.0;   // the rows are as given: nothing is behind
+  std::fill(h->row_c.begin(), h->row_c.end(), 0.0);
+  h->behind = false;
   return 0;
 }
 
 int svils_batch_get_state(svils_batch *h, double *gamma, double *lambda) {
   if (int rc = check(h, "svils_batch_get_state")) return rc;
   if (!h->have_state) return fail(SVILS_ERR_ARG, "svils_batch_get_state: no state");
+  if (int rc = catch_up(h)) return rc;
   if (int rc = settle(h, "svils_batch_get_state")) return rc;
   if (gamma) HIPCHK(hipMemcpy(gamma, h->gamma, (size_t)h->n * h->k * sizeof(double), hipMemcpyDeviceToHost));
   if (lambda) HIPCHK(hipMemcpy(lambda, h->lam, 2 * (size_t)h->k * sizeof(double), hipMemcpyDeviceToHost));
@@ -1193,6 +1372,7 @@ int svils_batch_get_state(svils_batch *h, double *gamma, double *lambda) {
 int svils_batch_sweep(svils_batch *h, uint32_t nsweeps) {
   if (int rc = check(h, "svils_batch_sweep")) return rc;
   if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "svils_batch_sweep: set the graph and the state first");
+  if (int rc = catch_up(h)) return rc;
   for (uint32_t s = 0; s < nsweeps; ++s)
     if (int rc = one_sweep(h)) return rc;
   return 0;
@@ -1208,6 +1388,7 @@ int svils_batch_step_node(svils_batch *h, uint32_t nsteps, const uint32_t *nodes
   for (uint32_t s = 0; s < nsteps; ++s)
     if (nodes[s] >= h->n) return fail(SVILS_ERR_ARG, "%s: nodes[%u] = %u is not < n = %u", name, s, nodes[s], h->n);
   if (!nsteps) return 0;
+  if (int rc = catch_up(h)) return rc;
   const uint32_t n = h->n, K = h->k, G = 64 / h->w, nb = blocks(n, 4 * G), nwv = 4 * nb;
   if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_part, (size_t)nwv * K)) return rc;
   if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_pl, (size_t)nwv * K * 2)) return rc;
@@ -1255,6 +1436,7 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
       if (h->h_skip[(size_t)p * h->nw + (q >> 5)] & (1u << (q & 31)))
         return fail(SVILS_ERR_ARG, "%s: pair %llu of step %u (%u, %u) is in the skip set", name, (unsigned long long)(e - off[s]), s, p, q);
     }
+  if (int rc = catch_up(h)) return rc;
   // the call's lists go through pinned memory in one copy, so that the call need not wait for it; the staging area is
   // free again once the previous call's copy has left it
   const size_t nlists = 4 * (size_t)total + (size_t)nsteps * (n + 1);
@@ -1323,6 +1505,7 @@ int svils_batch_get_expectations(svils_batch *h, double *elogpi, double *elogbet
   const char *name = "svils_batch_get_expectations";
   if (int rc = check(h, name)) return rc;
   if (!h->have_state) return fail(SVILS_ERR_ARG, "%s: no state", name);
+  if (int rc = catch_up(h)) return rc;
   if (int rc = renew_expectations(h)) return rc;   // what the next step call would do first
   if (int rc = settle(h, name)) return rc;
   if (elogpi) HIPCHK(hipMemcpy(elogpi, h->elogpi, (size_t)h->n * h->k * sizeof(double), hipMemcpyDeviceToHost));
@@ -1371,6 +1554,7 @@ int svils_batch_step_star(svils_batch *h, uint32_t nsteps, const uint32_t *start
       if (!(rho_partner[e] > 0.0 && rho_partner[e] <= 1.0))
         return fail(SVILS_ERR_ARG, "%s: rho_partner of entry %llu of step %u is not in (0, 1]", name, x, s);
     }
+  if (int rc = catch_up(h)) return rc;
   // the call's lists in one copy through the pinned staging area, doubles first: rho_partner [total], rho_start, scale,
   // rho_lambda [nsteps] each; then off [nsteps + 1] (as uint32), start [nsteps], partner [total]; then y [total] bytes
   const size_t ndbl = (size_t)total + 3 * (size_t)nsteps;
@@ -1426,6 +1610,129 @@ int svils_batch_step_star(svils_batch *h, uint32_t nsteps, const uint32_t *start
   return end_steps(h);
 }
 
+int svils_batch_step_strat(svils_batch *h, uint32_t nsteps, const uint32_t *start, const uint64_t *off, const uint32_t *partner,
+                           const uint8_t *y, const double *rho_gamma, const double *scale, const double *rho_lambda) {
+  const char *name = "svils_batch_step_strat";
+  if (int rc = check(h, name)) return rc;
+  if (nsteps && (!start || !off || !rho_gamma || !scale || !rho_lambda)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
+  if (!nsteps) return 0;
+  if (int rc = check_steps(h, name, nsteps, rho_gamma, rho_lambda)) return rc;
+  if (off[0] != 0) return fail(SVILS_ERR_ARG, "%s: off[0] is not 0", name);
+  uint64_t most = 0;
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    if (!(rho_gamma[s] < 1.0)) return fail(SVILS_ERR_ARG, "%s: rho_gamma[%u] is not in (0, 1) (log1p(-1) has no value)", name, s);
+    if (off[s + 1] < off[s]) return fail(SVILS_ERR_ARG, "%s: off[%u] decreases", name, s + 1);
+    if (!(scale[s] > 0.0) || !std::isfinite(scale[s])) return fail(SVILS_ERR_ARG, "%s: scale[%u] is not a positive number", name, s);
+    if (start[s] >= h->n) return fail(SVILS_ERR_ARG, "%s: start[%u] = %u is not < n = %u", name, s, start[s], h->n);
+    most = std::max(most, off[s + 1] - off[s]);
+  }
+  const uint64_t total = off[nsteps];
+  if (total && (!partner || !y)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
+  if (total >= ((uint64_t)1 << 30)) return fail(SVILS_ERR_UNSUPPORTED, "%s: more than 2^30 entries in one call", name);
+  const uint32_t n = h->n, K = h->k, G = 64 / h->w;
+  if (total && h->h_adj.empty()) {   // as svils_batch_step_star: the link bits come back once per graph
+    std::vector<uint32_t> bits((size_t)n * h->nw);
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipMemcpy(bits.data(), h->adj, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    h->h_adj.swap(bits);
+  }
+  // Checked before anything is enqueued, and in the same pass the factor of every row the call reads: the decay runs on
+  // copies, which replace the handle's once the whole call has passed.  c takes one addition per step, in step order
+  std::vector<uint32_t> seen(n, 0);
+  std::vector<double> row_c(h->row_c), fj((size_t)total), fa(nsteps);
+  double c = h->lag_c;
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    const uint32_t a = start[s];
+    fa[s] = std::exp(c - row_c[a]);
+    for (uint64_t e = off[s]; e < off[s + 1]; ++e) {
+      const uint32_t j = partner[e];
+      const unsigned long long x = e - off[s];
+      if (j >= n || j == a) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u pairs node %u with %u (n = %u)", name, x, s, a, j, n);
+      if (seen[j] == s + 1) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u lists partner %u twice", name, x, s, j);
+      seen[j] = s + 1;
+      const uint32_t p = std::min(a, j), q = std::max(a, j), bit = 1u << (q & 31);
+      const size_t wd = (size_t)p * h->nw + (q >> 5);
+      if (h->h_skip[wd] & bit) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) is in the skip set", name, x, s, p, q);
+      if (((h->h_adj[wd] & bit) != 0) != (y[e] != 0))
+        return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) has y = %u, the graph says otherwise", name, x, s, p, q, (unsigned)y[e]);
+      fj[e] = std::exp(c - row_c[j]);
+    }
+    c += std::log1p(-rho_gamma[s]);
+    row_c[a] = c;
+    for (uint64_t e = off[s]; e < off[s + 1]; ++e) row_c[partner[e]] = c;
+  }
+  // the call's lists in one copy through the pinned staging area: fj [total] doubles, partner [total], y [total] bytes
+  const size_t nwords = 2 * (size_t)total + (size_t)total + ((size_t)total + 3) / 4;
+  const uint32_t nwv_most = 4 * blocks(most, 4 * G);
+  if (int rc = reserve_pin(h, nwords)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_part, (size_t)nwv_most * K)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_pl, (size_t)nwv_most * K * 2)) return rc;
+  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_lists, nwords)) return rc;
+  if (total) {
+    std::memcpy(h->pin, fj.data(), total * sizeof(double));
+    std::memcpy(h->pin + 2 * total, partner, total * sizeof(uint32_t));
+    std::memcpy(h->pin + 3 * total, y, total);
+    HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nwords * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipEventRecord(h->ev_copy, h->st));
+    h->copy_pending = true;
+  }
+  if (!h->elogbeta_fresh) {   // Elogbeta of the current lambda; Elogpi is formed per row in the step's registers
+    hipLaunchKernelGGL(k_batch_beta, dim3(blocks(K, 256)), dim3(256), 0, h->st, K, h->lam, h->gtab, h->elogbeta);
+    HIPCHK(hipGetLastError());
+    h->elogbeta_fresh = true;
+  }
+  HIPCHK(hipMemsetAsync(h->ctr, 0, 4 * sizeof(unsigned long long), h->st));
+  HIPCHK(hipEventRecord(h->ev[0], h->st));
+  // from here on rows are written with the call's factors: the bookkeeping is the call's
+  h->row_c.swap(row_c);
+  h->lag_c = c;
+  h->behind = true;
+  h->elog_fresh = false;      // nothing here maintains Elogpi
+  StratArgs x{};
+  x.K = K;
+  x.gamma = h->gamma;
+  x.elogbeta = h->elogbeta;
+  x.logeps = std::log(h->epsilon);
+  x.alpha = h->alpha;
+  x.part_a = h->st_part;
+  x.pl = h->st_pl;
+  x.ctr = h->ctr;
+  x.gtab = h->gtab;
+  const double *dfj = reinterpret_cast<const double *>(h->st_lists);
+  const uint32_t *dpartner = h->st_lists + 2 * total;
+  const uint8_t *dy = reinterpret_cast<const uint8_t *>(h->st_lists + 3 * total);
+  for (uint32_t s = 0; s < nsteps; ++s) {
+    const uint32_t m = (uint32_t)(off[s + 1] - off[s]), nb = blocks(m, 4 * G);
+    x.m = m;
+    x.a = start[s];
+    x.partner = dpartner + off[s];
+    x.y = dy + off[s];
+    x.fj = dfj + off[s];
+    x.fa = fa[s];
+    x.scale = scale[s];
+    x.rho = rho_gamma[s];
+    if (m)
+      if (int rc = launch_for_width(h, name, [&](auto w) {
+            hipLaunchKernelGGL((k_batch_strat_pairs<decltype(w)::value, (int)VARIANT_V>), dim3(nb), dim3(256), 0, h->st, x);
+          }))
+        return rc;
+    hipLaunchKernelGGL(k_batch_strat_tail, dim3(K), dim3(256), 0, h->st, K, 4 * nb, h->st_part, h->st_pl,
+                       h->gamma + (size_t)x.a * K, h->alpha, x.fa, h->eta0, h->eta1, x.scale, x.rho, rho_lambda[s], h->lam, h->elogbeta,
+                       h->gtab);
+    HIPCHK(hipGetLastError());
+  }
+  return end_steps(h);
+}
+
+int svils_batch_get_lag(svils_batch *h, uint64_t *rows_behind) {
+  if (int rc = check(h, "svils_batch_get_lag")) return rc;
+  if (!rows_behind) return fail(SVILS_ERR_ARG, "svils_batch_get_lag: null argument");
+  uint64_t c = 0;
+  for (double rc : h->row_c) c += rc != h->lag_c;
+  *rows_behind = c;
+  return 0;
+}
+
 int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t *y, uint64_t m, double *out) {
   if (int rc = check(h, "svils_batch_pair_loglik")) return rc;
   if (m && (!pairs || !y || !out)) return fail(SVILS_ERR_ARG, "svils_batch_pair_loglik: null argument");
@@ -1433,6 +1740,7 @@ int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t
   for (uint64_t x = 0; x < m; ++x)
     if (pairs[2 * x] >= h->n || pairs[2 * x + 1] >= h->n)
       return fail(SVILS_ERR_ARG, "svils_batch_pair_loglik: pair %llu names a node >= n = %u", (unsigned long long)x, h->n);
+  if (int rc = catch_up(h)) return rc;
   if (int rc = settle(h, "svils_batch_pair_loglik")) return rc;
   if (!m) return 0;
   const auto scope = ToolHandle::GRAPH;   // the lists are the held-out sets of a graph
@@ -1462,6 +1770,7 @@ int svils_batch_elbo(svils_batch *h, double parts[4], uint64_t *pairs_done, uint
   if (int rc = check(h, name)) return rc;
   if (!parts) return fail(SVILS_ERR_ARG, "%s: null argument", name);
   if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "%s: set the graph and the state first", name);
+  if (int rc = catch_up(h)) return rc;
   if (int rc = settle(h, name)) return rc;
   const uint32_t n = h->n, K = h->k;
   if (int rc = h->reserve(ToolHandle::GRAPH, &h->el_part, 4 * (size_t)h->ntiles)) return rc;

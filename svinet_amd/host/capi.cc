@@ -175,14 +175,16 @@ struct svih_batch {
   std::unique_ptr<MMSBBatch> eng;
 };
 
-// neighbors non-null: the -infset engine with the informative sets of that file
-static svih_batch *make_batch(const char *path, const svih_options *o, const char *neighbors) {
+// neighbors non-null: the -infset engine with the informative sets of that file; snode: the -snode engine
+static svih_batch *make_batch(const char *path, const svih_options *o, const char *neighbors, bool snode = false) {
   static const char *eta_names[] = {"uniform", "fromdata", "sparse", "dense"};
   Env::Args a;
   a.n = o->n;
   a.k = o->k;
-  if (neighbors) {
-    a.infset = true;
+  if (neighbors || snode) {
+    a.infset = !snode;
+    a.snode = snode;
+    if (snode) a.rfreq = 100;
     a.host_loops = o->batch_device == 0;
     a.inf_epsilon = o->inf_epsilon;
     a.tau0 = o->tau0; a.kappa = o->kappa; a.nodetau0 = o->nodetau0; a.nodekappa = o->nodekappa;
@@ -214,12 +216,14 @@ static svih_batch *make_batch(const char *path, const svih_options *o, const cha
     delete b;
     return nullptr;
   }
-  b->eng->keep_schedule(o->sampled != 0 || neighbors);
+  b->eng->keep_schedule(o->sampled != 0 || neighbors || snode);
   return b;
 }
 svih_batch *svih_batch_from_file(const char *path, const svih_options *o) { return make_batch(path, o, nullptr); }
 // the -infset engine (svih_batch_step steps it; its schedule: svih_batch_nstars / svih_batch_star)
 svih_batch *svih_infset_from_file(const char *path, const char *neighbors, const svih_options *o) { return make_batch(path, o, neighbors); }
+// the -snode engine (svih_batch_step steps it; its schedule is read as -infset's; o->inf_epsilon: the chance of a non-link step)
+svih_batch *svih_snode_from_file(const char *path, const svih_options *o) { return make_batch(path, o, nullptr, true); }
 // -preprocess: the informative sets of the graph of `path` (declared n nodes) into `out` in the reference's format; 0, or -1
 int svih_preprocess(const char *path, uint32_t n, const char *out) {
   Env::Args a;

@@ -66,8 +66,8 @@ Env::Env(const Args &a)
       use_init_communities(a.init_comm), init_communities_fname(a.init_comm_fname),
       nmi(a.nmi), ground_truth_fname(a.ground_truth_fname),
       datfname(a.datfname), label(a.label), gpus(a.gpus), rank(a.rank), kshard(a.kshard), sharded((a.sharded || a.gpus > 1) && !a.kshard), comm_rfd(a.comm_rfd), comm_wfds(a.comm_wfds),
-      batch_mode(a.batch), link_sampling(a.link_sampling), findk(a.findk), batch_device((a.batch && a.batch_gpu) || ((a.rnode || a.rpair || a.infset) && !a.host_loops)),
-      randomnode(a.rnode), randompair(a.rpair), stratified(a.stratified), delaylearn((a.rnode || a.rpair) && !a.nodelay), infset(a.infset || a.preprocess), preprocess(a.preprocess), inf_epsilon(a.inf_epsilon), orig(a.orig), orig_device(a.orig && !a.host_loops), itype(a.itype), clean_holdout(a.clean_holdout), s(a.n / 2), gml(a.gml), lcstats(a.lcstats), strid(a.strid),
+      batch_mode(a.batch), link_sampling(a.link_sampling), findk(a.findk), batch_device((a.batch && a.batch_gpu) || ((a.rnode || a.rpair || a.infset || a.snode) && !a.host_loops)),
+      randomnode(a.rnode), randompair(a.rpair), stratified(a.stratified), delaylearn((a.rnode || a.rpair) && !a.nodelay), infset(a.infset || a.preprocess), preprocess(a.preprocess), inf_epsilon(a.inf_epsilon), snode(a.snode), orig(a.orig), orig_device(a.orig && !a.host_loops), itype(a.itype), clean_holdout(a.clean_holdout), s(a.n / 2), gml(a.gml), lcstats(a.lcstats), strid(a.strid),
       terminate(0), total_pairs(0), ones_prob(0), zeros_prob(1),
       device(a.device), sweep_batch(a.sweep_batch), write_files(a.write_files),
       minibatch(a.minibatch), tau0(a.tau0), kappa(a.kappa), nodetau0(a.nodetau0), nodekappa(a.nodekappa),
@@ -91,6 +91,7 @@ Env::Env(const Args &a)
   if (seed) sa << "-seed" << seed;
   if (batch_mode) { sa << "-batch"; if (!gml) reportfreq = 1; }   // the reference names no directory for -gml (the block is skipped)
   else if (infset) sa << "-infset";                               // src/env.hh:523
+  else if (snode) sa << (a.nodelay ? "-Srnode" : "-SUrnode");     // what the reference names a -stratified -rnode run (:529-546)
   else if (link_sampling) sa << "-linksampling";
   else if (findk) sa << "-findk";
   else if (sampled()) {   // src/env.hh:529-546 (undirected is always set there: the dash is always written)
@@ -162,7 +163,7 @@ Env::Env(const Args &a)
   plog("test_file_location", load_test_fname);
   plog("reportfreq", reportfreq);
   plog("eta_type", eta_type);
-  if (minibatch || sampled() || infset) {   // keys of this build (mini-batch mode, the sampled-pair engines), after the reference's
+  if (minibatch || sampled() || fastamm()) {   // keys of this build (mini-batch mode, the sampled-pair engines), after the reference's
     if (minibatch) plog("link_sampling_minibatch_nodes", minibatch);
     plog("tau0", tau0);
     plog("kappa", kappa);

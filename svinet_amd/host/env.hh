@@ -27,6 +27,9 @@ class Env {
     // neighbors.bin (Network::set_neighborhood_sets, src/network.cc:558-686).  Both name the directory -infset (src/env.hh:523)
     bool infset = false, preprocess = false;
     double inf_epsilon = 0.0001;        // _inf_epsilon (src/fastamm.cc:18): library callers only
+    // -snode: stratified random node SVI (FastAMM2::infer, src/fastamm2.cc:535-702; the reference starts it with
+    // -stratified -rnode).  The constructor is -infset's; the chance of a non-link step is inf_epsilon, 0.5 there (:15)
+    bool snode = false;
     // -orig: the full K x K blockmodel (MMSBInferOrig::batch_infer, src/mmsbinferorig.cc:212-294); -itype: its beta start
     // (0: init_beta1, > 0: init_beta2).  On the device unless -host-loops is given
     bool orig = false;
@@ -127,11 +130,13 @@ class Env {
   int comm_rfd;
   std::vector<int> comm_wfds;
   bool batch_mode, link_sampling, findk;
-  bool batch_device;                 // -batch-gpu, and -rnode / -rpair / -infset without -host-loops: MMSBBatch drives a svils_batch handle
+  bool batch_device;                 // -batch-gpu, and -rnode / -rpair / -infset / -snode without -host-loops: MMSBBatch drives a svils_batch handle
   bool randomnode, randompair, stratified, delaylearn;   // the sampled-pair engines (src/env.hh:485-501)
   bool sampled() const { return randomnode || randompair; }
   bool infset, preprocess;           // -infset / -preprocess (src/env.hh:325, :436)
-  double inf_epsilon;                // the chance of a non-informative step
+  double inf_epsilon;                // the chance of a non-informative step (-snode: of a non-link step)
+  bool snode;                        // -snode (FastAMM2)
+  bool fastamm() const { return infset || snode; }   // the constructor both engines share (src/fastamm.cc:64-97)
   bool orig, orig_device;            // -orig; without -host-loops MMSBInferOrig drives a svils_orig handle
   int itype;                         // -itype (src/main.cc:193-194), read by -orig alone
   bool clean_holdout;                // -clean-holdout: -orig trains on no orientation of a held-out or validation pair

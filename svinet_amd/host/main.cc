@@ -6,7 +6,7 @@
 // estimate of the number of communities, also on the device), -gml / -lcstats (the
 // link communities of a fitted model's gamma.txt / lambda.txt, on the device) and the
 // reference's small all-pairs CPU engine -batch (plumbing only), with
-// -batch-gpu, -rnode, -rpair, -rpair -stratified and -infset (with its -preprocess pass) the same model on the device, and
+// -batch-gpu, -rnode, -rpair, -rpair -stratified, -infset (with its -preprocess pass) and -snode the same model on the device, and
 // -orig, the blockmodel with a full K x K matrix of block rates (MMSBInferOrig), on the device as well (with -clean-holdout
 // it answers the link-prediction flags too); the
 // flags that select the reference's other engines are recognised and rejected
@@ -94,6 +94,11 @@ static const ToolMode kInfset = {            // -infset / -preprocess: an engine
         F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
 
+static const ToolMode kSnode = {             // -snode: an engine of its own on one GPU
+    F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
+        F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
+    "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
+
 // -orig: an engine of its own on one GPU.  The link-prediction flags are not in this table: -orig answers them from its final
 // state (svils_orig_link_prob / _predict_links / _rank_links), under the conditions of orig_queries_refused below.
 // -adamic-adar stays refused: the neighbourhood baselines need the training CSR of a -link-sampling handle
@@ -173,7 +178,11 @@ static void usage() {
           "\t-stratified\twith -rpair: mini-batches alternate between non-links and links (with -rnode or alone: refused)\n\n"
           "\t-nodelay\twith -rnode / -rpair: learn lambda from the first iteration (default: once iterations x n / 2 exceed the\n"
           "\t\t\tnumber of pairs)\n\n"
-          "\t-host-loops\twith -rnode / -rpair / -infset: the host CPU loops instead of the GPU (small graphs)\n\n"
+          "\t-host-loops\twith -rnode / -rpair / -infset / -snode: the host CPU loops instead of the GPU (small graphs)\n\n"
+          "\t-snode\t\tinference using stratified random node sampling (the reference's -stratified -rnode): an iteration\n"
+          "\t\t\ttakes a random node with its links or, as often, with n / 10 of its non-links, and moves every row.\n"
+          "\t\t\tOn the GPU (-k <= 256, -n <= 32768; without one the run fails); a report every 100 iterations unless\n"
+          "\t\t\t-rfreq came before it; step sizes -tau0 -kappa -nodetau0 -nodekappa\n\n"
           "\t-infset\t\tinference using informative set sampling: an iteration takes a random node, its links and the\n"
           "\t\t\tnon-links -preprocess chose for it (rarely: 200 other non-links) and moves only their rows.  Reads neighbors.bin\n"
           "\t\t\tof the working directory.  On the GPU, a report interval per launch chain (-k <= 256, -n <= 32768; without\n"
@@ -215,7 +224,7 @@ static void usage() {
           "\t-no-stop\tdisable stopping criteria\n\n"
           "\t-seed\t\tset random generator seed\n\n"
           "\t-heldout-ratio, -link-thresh, -lt-min-deg, -eta-type, -accuracy\tas in the reference\n\n"
-          "\t-logl\t\twith -batch, -batch-gpu, -rnode, -rpair and -infset: the variational lower bound after the\n"
+          "\t-logl\t\twith -batch, -batch-gpu, -rnode, -rpair, -infset and -snode: the variational lower bound after the\n"
           "\t\t\tinitialisation and at every report (a row of logl.txt; with -accuracy the convergence rule\n"
           "\t\t\tthat writes done.txt); on the device unless -batch or -host-loops is given.  Accepted and\n"
           "\t\t\twithout effect with every other mode\n\n"
@@ -342,6 +351,7 @@ int main(int argc, char **argv) {
     else if (is("-stopthresh") || is("-inf") || is("-groups-file")) {
       need(i); ++i;   // value flags of other engines: consumed, no effect on this path
     }
+    else if (is("-snode")) { a.snode = true; if (a.rfreq == 1) a.rfreq = 100; }   // as -rnode (src/main.cc:141-163)
     else if (is("-infset")) { a.infset = true; }             // src/main.cc:189-190, :214-216: rfreq stays as it is
     else if (is("-preprocess")) { a.preprocess = true; }
     else if (is("-randzeros")) {}                            // ignored: the informative sets are the two-hop ones
@@ -368,7 +378,8 @@ int main(int argc, char **argv) {
     }
     if (refused(a, kPosterior, flag)) return 2;
     const struct { bool set; const char *name; } more[] = {
-        {a.orig, "-orig"}, {a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.batch_gpu, "-batch-gpu"}, {a.load, "-load"}};
+        {a.orig, "-orig"}, {a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.batch_gpu, "-batch-gpu"}, {a.load, "-load"},
+        {a.snode, "-snode"}};
     for (const auto &m : more)
       if (m.set) {
         fprintf(stderr, kPosterior.fmt, flag, m.name);
@@ -403,6 +414,28 @@ int main(int argc, char **argv) {
       fclose(f);
     }
     a.write_files = false;                               // everything goes under ppc/ of the working directory; no run directory
+  }
+  if (a.snode && !unsupported) {                         // -snode (FastAMM2): an engine of its own; refusals before anything is read
+    if (refused(a, kSnode, "-snode")) return 2;
+    const struct { bool set; const char *name; } more[] = {{a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.orig, "-orig"}};
+    for (const auto &m : more)
+      if (m.set) {
+        fprintf(stderr, kSnode.fmt, "-snode", m.name);
+        return 2;
+      }
+    if (a.scale != 1) {
+      fprintf(stderr, "error: -snode is not available with -scale other than 1 (subsampling of the non-links is not implemented)\n");
+      return 2;
+    }
+    if (!a.host_loops && a.k > SVILS_BATCH_MAX_K) {      // the limits of svils_batch_create, before anything is read
+      fprintf(stderr, "error: -snode holds -k <= %d (SVILS_BATCH_MAX_K); -k %u is refused\n", SVILS_BATCH_MAX_K, a.k);
+      return 2;
+    }
+    if (!a.host_loops && a.n > SVILS_BATCH_MAX_N) {
+      fprintf(stderr, "error: -snode holds -n <= %d (SVILS_BATCH_MAX_N); -n %u is refused\n", SVILS_BATCH_MAX_N, a.n);
+      return 2;
+    }
+    a.inf_epsilon = 0.5;                                 // _inf_epsilon of FastAMM2 (src/fastamm2.cc:15)
   }
   if (infset && !unsupported) {                          // -infset / -preprocess (FastAMM): an engine of its own
     const char *flag = a.preprocess ? "-preprocess" : "-infset";
@@ -452,7 +485,7 @@ int main(int argc, char **argv) {
     unsupported = true;
     unsupported_flag = "-stratified";
   }
-  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || a.ppc || sampled || infset || a.orig)) {
+  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || a.ppc || sampled || infset || a.orig || a.snode)) {
     fprintf(stderr,
             "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk, -gml, -lcstats)%s%s.\n"
             "Use the reference build for the other engines.\n",
@@ -462,7 +495,7 @@ int main(int argc, char **argv) {
   if (sampled) {                                         // -rnode / -rpair / -rpair -stratified (MMSBInfer::infer)
     const char *flag = a.rnode ? "-rnode" : "-rpair";
     if (a.rnode && a.stratified) {
-      fprintf(stderr, "error: -stratified -rnode is a different engine of the reference (FastAMM2) and is not implemented here\n");
+      fprintf(stderr, "error: -stratified -rnode is a different engine of the reference (FastAMM2) and is not implemented here under these flags: use -snode\n");
       return 2;
     }
     if (a.rnode && a.rpair) {
@@ -725,11 +758,11 @@ run:
     }
     exit(0);
   }
-  if (a.batch || sampled || infset) {        // src/main.cc:354-358; -rnode / -rpair: :373-377; -infset: :361-366
-    printf(infset ? "+ running mmsb inference (with infset network option)\n" : sampled ? "+ running mmsb inference\n" : "+ running mmsb batch inference\n");
+  if (a.batch || sampled || infset || a.snode) {   // src/main.cc:354-358; -rnode / -rpair: :373-377; -infset: :361-366; -snode: :368-372
+    printf(a.snode ? "+ running mmsb inference (with stratified random node option)\n" : infset ? "+ running mmsb inference (with infset network option)\n" : sampled ? "+ running mmsb inference\n" : "+ running mmsb batch inference\n");
     try {                                    // the device backends: a failed svils_batch_* call ends the run (no host fall-back)
       MMSBBatch mmsb(env, network);
-      if (sampled || infset) mmsb.infer(); else mmsb.batch_infer();
+      if (sampled || infset || a.snode) mmsb.infer(); else mmsb.batch_infer();
     } catch (const SvilsError &e) {
       fprintf(stderr, "error: %s\n", e.what());
       return -1;

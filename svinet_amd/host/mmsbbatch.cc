@@ -18,6 +18,7 @@ const double kNegInit = -2147483647.0;     // _max_t/_max_h/_max_v/_prev_h, src/
 const uint32_t kOnlineIterations = 50;     // src/env.hh:415
 const double kMeanChangeThresh = 0.00001;  // src/env.hh:337
 const uint32_t kNoninfSetsize = 200;       // _noninf_setsize, src/fastamm.cc:18
+const uint32_t kStratSets = 10;            // _m, src/fastamm2.cc:16: a non-link step takes n / 10 nodes
 
 // psi(x), x > 0: recurrence up to x >= 6, then the asymptotic series (double accurate)
 double digamma(double x) {
@@ -41,15 +42,15 @@ MMSBBatch::MMSBBatch(Env &env, Network &network)
       start_time_(time(0)) {
   fprintf(stdout, "+ initialization begin\n+ running inference on %d nodes\n", n_);
   Env::plog("inference n", n_);
-  if (env_.infset) {                                        // src/fastamm.cc:64-66, :85: the shuffle draws before the sampler
+  if (env_.fastamm()) {                                     // src/fastamm.cc:64-66, :85: the shuffle draws before the sampler
     Env::plog("inf_epsilon", env_.inf_epsilon);
-    Env::plog("noninf_setsize", kNoninfSetsize);
+    Env::plog("noninf_setsize", env_.snode ? n_ / kStratSets : kNoninfSetsize);
     shuffle_nodes();
     nodec_.assign(n_, 0);
   }
   init_heldout();
   printf("+ heldout sets created\n");
-  if (env_.infset) {
+  if (env_.fastamm()) {
     init_gamma_lambda_infset();
   } else {
     init_gamma();
@@ -65,7 +66,7 @@ MMSBBatch::MMSBBatch(Env &env, Network &network)
     for (const char *f : {"/stats.txt", "/time.txt", "/convergence.txt", "/cmap.txt", "/training.txt",
                           "/training-edges.txt", "/logl.txt", "/modularity.txt"})
       fclose(open_or_die(Env::file_str(f), f + 1));
-    if (env_.infset)                                        // src/fastamm.cc:99, :241 (PRECISION_SAMPLE is off: both stay empty)
+    if (env_.fastamm())                                     // src/fastamm.cc:99, :241 (PRECISION_SAMPLE is off: both stay empty)
       for (const char *f : {"/precision-pairs.txt", "/precision.txt"}) fclose(open_or_die(Env::file_str(f), f + 1));
     hf_ = open_or_die(Env::file_str("/heldout.txt"), "heldout");
     vf_ = open_or_die(Env::file_str("/validation.txt"), "validation");
@@ -170,7 +171,7 @@ void MMSBBatch::set_sample(int s, bool heldout) {
   while (c0 < p || c1 < p) {
     Edge e;
     if (c0 == p) get_random_edge(false, true, 1, e);        // enough non-links: draw links only
-    else get_random_edge(heldout && !env_.infset, false, 0, e);   // FastAMM's edge_ok always looks at both maps (src/fastamm.hh:592-613)
+    else get_random_edge(heldout && !env_.fastamm(), false, 0, e);   // FastAMM's edge_ok always looks at both maps (src/fastamm.hh:592-613)
     const bool y = network_.y(e.first, e.second);
     if ((!y && c0 < p) || (y && c1 < p)) {
       (y ? c1 : c0)++;
@@ -196,10 +197,10 @@ void MMSBBatch::init_heldout() {
   Env::plog("heldout edges (1s and 0s)", (uint32_t)heldout_map_.size());
   if (!env_.write_files) return;
   // (FastAMM names them -pairs, src/fastamm.cc:87-97)
-  FILE *f = open_or_die(Env::file_str(env_.infset ? "/heldout-pairs.txt" : "/heldout-edges.txt"), "heldout edges");
+  FILE *f = open_or_die(Env::file_str(env_.fastamm() ? "/heldout-pairs.txt" : "/heldout-edges.txt"), "heldout edges");
   fprintf(f, "%s\n", edgelist_s(heldout_edges_).c_str());
   fclose(f);
-  f = open_or_die(Env::file_str(env_.infset ? "/validation-pairs.txt" : "/validation-edges.txt"), "validation edges");
+  f = open_or_die(Env::file_str(env_.fastamm() ? "/validation-pairs.txt" : "/validation-edges.txt"), "validation edges");
   fprintf(f, "%s\n", edgelist_s(validation_edges_).c_str());
   fclose(f);
 }
@@ -531,8 +532,107 @@ void MMSBBatch::step_stars(uint32_t nsteps) {
     for (Star &d : chunk) stars_.push_back(std::move(d));
 }
 
+// ---------------------------------------------------------------------------
+// -snode: FastAMM2 (src/fastamm2.cc).  _iter and _lambda_start_iter are never initialised there: both are 0 here
+// ---------------------------------------------------------------------------
+MMSBBatch::Star MMSBBatch::draw_strat() {
+  Star d;
+  const uint32_t it = drawn_++;
+  const double eps = env_.inf_epsilon;                      // 0.5 (:15)
+  d.kind = rng_.uniform() < eps ? 1 : 0;                    // gsl_ran_bernoulli (:574)
+  const uint32_t a = d.start = rng_.uniform_int(n_);        // :936, :1078
+  auto ok = [&](uint32_t j) { return edge_ok(a < j ? Edge(a, j) : Edge(j, a), false, false, 0); };
+  if (d.kind == 0) {                                        // opt_process: the links (:944-1000); no informative set (:1009)
+    for (uint32_t j : network_.get_edges(a))
+      if (ok(j)) {
+        d.partner.push_back(j);
+        d.y.push_back(1);
+      }
+    d.scale = (double)n_ / (2 * (1 - eps));                 // :591-592
+  } else {                                                  // opt_process_noninf (:1101-1125)
+    // The reference walks on until it has setsize nodes -- for ever when fewer qualify; here the walk ends after one
+    // lap of the shuffled order, as -infset's does
+    const uint32_t setsize = n_ / kStratSets;
+    if (setsize) {
+      uint32_t q = (uint32_t)((int)((double)rng_.uniform_int(n_) / setsize)) * setsize;
+      for (uint32_t seen = 0; seen < n_ && d.partner.size() < setsize; ++seen, q = (q + 1) % n_) {
+        const uint32_t node = shuffled_[q];
+        if (node == a || network_.y(a, node) || !ok(node)) continue;
+        d.partner.push_back(node);
+        d.y.push_back(0);
+      }
+    }
+    d.scale = ((double)n_ * kStratSets) / (2 * eps);
+  }
+  // one step size for all n rows: _nodec[i] is incremented for every i at every iteration (:606, :622)
+  d.rho_start = pow(env_.nodetau0 + 1 + it, -1 * env_.nodekappa);
+  d.rho_partner.assign(d.partner.size(), d.rho_start);
+  d.rho_lambda = pow(env_.tau0 + 1 + (it - lambda_start_iter_ + 1), -1 * env_.kappa);   // :627 (nolambda is never set here)
+  return d;
+}
+
+void MMSBBatch::strat_host(const Star &d) {
+  const uint32_t a = d.start, K = k_;
+  set_dir_exp();                                            // every row from the gamma the iteration began with
+  std::vector<double> gammat((size_t)n_ * K, 0.0), lambdat(2 * (size_t)K, 0.0), phi1(K), phi2(K);
+  std::vector<char> named(n_, 0);
+  named[a] = 1;
+  for (size_t e = 0; e < d.partner.size(); ++e) {
+    const uint32_t j = d.partner[e], p = std::min(a, j), q = std::max(a, j);
+    const int y = d.y[e];
+    named[j] = 1;
+    phis(p, q, y, phi1.data(), phi2.data());
+    for (uint32_t k = 0; k < K; ++k) {
+      gammat[(size_t)p * K + k] += phi1[k];
+      gammat[(size_t)q * K + k] += phi2[k];
+      lambdat[2 * k + (y ? 0 : 1)] += phi1[k] * phi2[k];
+    }
+  }
+  const double rho = d.rho_start;
+  for (uint32_t i = 0; i < n_; ++i)                         // :605-624: every row moves
+    for (uint32_t k = 0; k < K; ++k) {
+      double &g = gamma_[(size_t)i * K + k];
+      g = named[i] ? (1 - rho) * g + rho * (env_.alpha + d.scale * gammat[(size_t)i * K + k]) : (1 - rho) * g + rho * env_.alpha;
+    }
+  if (d.rho_lambda >= 0)                                    // :626-638
+    for (uint32_t k = 0; k < K; ++k) {
+      lambda_[2 * k] = (1 - d.rho_lambda) * lambda_[2 * k] + d.rho_lambda * (env_.eta0 + d.scale * lambdat[2 * k]);
+      lambda_[2 * k + 1] = (1 - d.rho_lambda) * lambda_[2 * k + 1] + d.rho_lambda * (env_.eta1 + d.scale * lambdat[2 * k + 1]);
+    }
+}
+
+void MMSBBatch::step_strats(uint32_t nsteps) {
+  std::vector<Star> chunk(nsteps);
+  for (Star &d : chunk) d = draw_strat();
+  if (!dev_) {
+    for (const Star &d : chunk) strat_host(d);
+  } else if (nsteps) {
+    std::vector<uint32_t> start(nsteps), partner;
+    std::vector<uint64_t> off(nsteps + 1, 0);
+    std::vector<uint8_t> y;
+    std::vector<double> rg(nsteps), sc(nsteps), rl(nsteps);
+    for (uint32_t s = 0; s < nsteps; ++s) {
+      const Star &d = chunk[s];
+      start[s] = d.start;
+      partner.insert(partner.end(), d.partner.begin(), d.partner.end());
+      y.insert(y.end(), d.y.begin(), d.y.end());
+      off[s + 1] = partner.size();
+      rg[s] = d.rho_start;
+      sc[s] = d.scale;
+      rl[s] = d.rho_lambda;
+    }
+    if (int rc = svils_batch_step_strat(dev_, nsteps, start.data(), off.data(), partner.data(), y.data(), rg.data(), sc.data(), rl.data()))
+      device_failed("svils_batch_step_strat", rc);
+    host_stale_ = true;
+  }
+  iter_ += nsteps;
+  if (keep_schedule_)
+    for (Star &d : chunk) stars_.push_back(std::move(d));
+}
+
 void MMSBBatch::step(uint32_t nsteps) {
   if (env_.infset) return step_stars(nsteps);
+  if (env_.snode) return step_strats(nsteps);
   std::vector<Drawn> chunk(nsteps);
   for (Drawn &d : chunk) d = draw();
   if (!dev_) {

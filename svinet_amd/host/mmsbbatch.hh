@@ -27,6 +27,13 @@
 // fixed point, the likelihoods, the stop rule and the writers are the ones above.  A whole report interval is drawn
 // first, counters and step sizes included, and handed to the device in one svils_batch_step_star call.
 //
+// -snode (Env::snode) runs FastAMM2::infer() (src/fastamm2.cc:535-702) on the same object: the stratified random node
+// sampler.  The constructor is -infset's (the shuffle, the samplers, init_gamma / init_lambda, the -pairs files).  An
+// iteration is a star again -- with chance 1/2 a random node and its links, else a random node and n / 10 of its
+// non-links, a block of the shuffled order -- but EVERY row of gamma moves, with one step size: the rows of the star
+// towards alpha + scale phi, all others towards alpha.  A report interval is drawn first and handed to the device in one
+// svils_batch_step_strat call, which keeps the decay of the untouched rows as one factor per row.
+//
 // Seam mirrored:   MMSBInfer mmsb(env, network);  mmsb.batch_infer();
 //
 // Where the reference reads members it never initialises (`_iter`, `_ones_prob`,
@@ -163,6 +170,11 @@ class MMSBBatch {
   void shuffle_nodes();                                   // :506-511
   void init_gamma_lambda_infset();                        // :514-546
   Star draw_star();                                       // :574-605 with the lists of opt_process / opt_process_noninf
+  // -snode (FastAMM2, src/fastamm2.cc).  A drawn iteration is a Star whose rho_start and every rho_partner are the one
+  // step size of the iteration; kind 0: the links of the start node, 1: a block of its non-links
+  Star draw_strat();                                      // :573-592 with the lists of opt_process / opt_process_noninf (:933-1165)
+  void strat_host(const Star &d);                         // :565-640, the restated eager loops: all n rows move
+  void step_strats(uint32_t nsteps);
   void star_host(const Star &d);                          // :565-616, the restated loops
   void step_stars(uint32_t nsteps);
   std::vector<uint32_t> shuffled_, nodec_;

@@ -549,6 +549,42 @@ class InfsetEngine(BatchEngine):
         return _arr(load().svih_batch_shuffled(self._h), (self.n,), np.uint32)
 
 
+class StratNodeEngine(InfsetEngine):
+    """The -snode engine of the host library: the reference's FastAMM2::infer (src/fastamm2.cc:535-702), the stratified
+    random node sampler behind `-stratified -rnode`.  on_device=False: its host loops (-host-loops), which move all n rows
+    at every iteration; on_device=True: the steps run through svils_batch_step_strat on `device`, one call per sweep() or
+    step(nsteps).  sweep() runs one report interval (rfreq iterations, 100 as the CLI's default).  schedule() lists, per
+    executed iteration, what was drawn: dict(start, kind (0 links, 1 a block of non-links), partner [m], y [m], rho_gamma,
+    scale, rho_lambda); shuffled() is the node order the non-link steps walk.  inf_epsilon: the chance of kind 1 (0.5)."""
+
+    def __init__(self, path, n, k, on_device=False, rfreq=100, inf_epsilon=0.5, **kw):
+        self.rfreq = rfreq
+        BatchEngine.__init__(self, path, n, k, on_device=on_device, inf_epsilon=inf_epsilon, **kw)
+
+    def _open(self, L, path, o):
+        L.svih_snode_from_file.argtypes = [C.c_char_p, C.POINTER(Options)]
+        L.svih_snode_from_file.restype = C.c_void_p
+        return L.svih_snode_from_file(os.fsencode(path), C.byref(o))
+
+    def sweep(self):
+        """one report interval: rfreq iterations drawn, then run (on the device: one svils_batch_step_strat call)"""
+        self.step(self.rfreq)
+
+    def schedule(self):
+        out = []
+        for d in InfsetEngine.schedule.fget(self):
+            rho = d.pop("rho_start")
+            assert np.all(d.pop("rho_partner") == rho)
+            d["rho_gamma"] = rho
+            out.append(d)
+        return out
+
+    def shuffled(self):
+        return InfsetEngine.shuffled.fget(self)
+
+    node_counts = None   # FastAMM2 counts every node at every iteration: the count is iter
+
+
 class FindK:
     """-findk on the device (svils_findk_*), driven by the product's host side (host/findk.cc: init_gamma, the held-out
     sample, the padding draws) with nothing written to disk.  step() runs one pass of the reference's batch_infer loop
