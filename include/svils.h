@@ -843,6 +843,35 @@ int svils_orig_get_stats(svils_orig *h, uint64_t *pairs_done, uint64_t *rounds_t
                          uint64_t *bad_normalisers, uint64_t *bad_betas);
 /* device ms of the last sweep: Elogpi and the log tables, the pair pass, the reductions (-1 before the first sweep) */
 int svils_orig_get_timing(svils_orig *h, double ms[3]);
+/* ---- -orig -logl: the variational lower bound on the svils_orig handle (an ADDITION of ABI 8) ----------------------------
+ * The reference's MMSBInferOrig::approx_log_likelihood (src/mmsbinferorig.cc:624-726, under GLOBALPHIS) of the CURRENT
+ * state: s = P + N (beta is a point estimate, so it has no term), with Elogpi of the current gamma,
+ * T1 = log(beta + 1e-10), T0 = log((1 - beta) + 1e-10),
+ *   P   sum over every ordered pair (p, q), p != q, outside the skip list -- the pairs a sweep visits -- phi1 / phi2 the
+ *       fixed point of svils_orig_sweep from 1 / k (the same kernel: the same rounds, the same exit rule), of
+ *       sum_g sum_h phi1[g] phi2[h] T_y[g][h] + sum_k phi1[k] Elogpi_p[k] + sum_k phi2[k] Elogpi_q[k]
+ *       - sum_k phi1[k] log phi1[k] - sum_k phi2[k] log phi2[k]; an entry of phi that is exactly 0 adds 0 (the reference: NaN)
+ *   N   sum over p of lnGamma(k alpha) - k lnGamma(alpha) + (alpha - 1) sum_k Elogpi_pk
+ *       - [lnGamma(sum_k gamma_pk) - sum_k lnGamma(max(gamma_pk, 1e-30))] - sum_k (gamma_pk - 1) Elogpi_pk
+ * out: total, P, N.  The reference reads the phi vectors the last sweep stored (fixed points of the state before it) and
+ * adds the held-out pairs no sweep visits with whatever their slots hold; here the fixed point is taken from the current
+ * state over the visited pairs only, so the bound of a fresh state is defined.
+ * The pass runs the sweep's pair kernel over the sweep's row cuts with a counter block, Elogpi and tables of its own, and
+ * writes only that scratch and the phi buffers every sweep overwrites: gamma, beta, svils_orig_get_stats, the caches of
+ * the link queries and every later sweep are bit for bit as without it.  No floating-point atomics; a partial sum belongs
+ * to a piece of a row that depends on n alone and the partials are added in a fixed order: the three outputs are bitwise
+ * equal from run to run, on two handles, and for every svils_orig_set_launch_rows value.  Waits for the device.
+ * SVILS_ERR_ARG: a null handle or a null out, no graph or no state; SVILS_ERR_UNSUPPORTED: the degenerate flag is up (the
+ * message of svils_orig_get_state), or "normaliser not > 0": a pair of the pass whose normaliser is not > 0 (out and the
+ * state untouched); SVILS_ERR_DEVICE: no HIP device, as for the siblings. */
+int svils_orig_elbo(svils_orig *h, double out[3]);
+/* of the last svils_orig_elbo pass: pairs visited, rounds over all pairs, most rounds of one pair, pairs whose normaliser
+ * was not > 0 (all 0 before the first pass).  Any pointer may be null; waits */
+int svils_orig_get_elbo_stats(svils_orig *h, uint64_t *pairs_done, uint64_t *rounds_total, uint32_t *rounds_max,
+                              uint64_t *bad_normalisers);
+/* device ms of the last svils_orig_elbo pass: the whole pass, its pair launches (the first one's bracket includes Elogpi,
+ * the tables and the node terms), its term launches (-1 before the first pass).  The sweep's events are as they were */
+int svils_orig_get_elbo_timing(svils_orig *h, double ms[3]);
 /* ---- link prediction from a fitted -orig state (an ADDITION of ABI 8; nothing a sweep reads is written) ------------------
  * score(p, c) = sum_g sum_h pi_p[g] beta[g][h] pi_c[h], pi_x = gamma_x / sum_k gamma_xk: the argument of the reference's
  * edge_likelihood(p, c, 1) (src/mmsbinferorig.cc:563-587).  beta is not symmetric in general, so score(p, c) != score(c, p):

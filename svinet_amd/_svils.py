@@ -48,7 +48,7 @@ EXPORTS = (
     "svils_orig_create", "svils_orig_destroy", "svils_orig_set_graph", "svils_orig_set_state", "svils_orig_get_state",
     "svils_orig_sweep", "svils_orig_pair_loglik", "svils_orig_get_stats", "svils_orig_get_timing", "svils_orig_variant",
     "svils_orig_set_launch_rows", "svils_orig_link_prob", "svils_orig_predict_links", "svils_orig_rank_links",
-    "svils_orig_get_query_timing",
+    "svils_orig_get_query_timing", "svils_orig_elbo", "svils_orig_get_elbo_stats", "svils_orig_get_elbo_timing",
     "svils_ppc_create", "svils_ppc_destroy", "svils_ppc_set_params", "svils_ppc_draw", "svils_ppc_set_links", "svils_ppc_stats",
     "svils_ppc_get_draw_counts", "svils_ppc_get_links", "svils_ppc_get_nodes", "svils_ppc_get_summary", "svils_ppc_get_communities",
     "svils_ppc_get_timing", "svils_ppc_set_tile_batch",
@@ -234,6 +234,9 @@ def load():
     L.svils_orig_predict_links.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.svils_orig_rank_links.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
     L.svils_orig_get_query_timing.argtypes = [vp, vp]
+    L.svils_orig_elbo.argtypes = [vp, vp]
+    L.svils_orig_get_elbo_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.svils_orig_get_elbo_timing.argtypes = [vp, vp]
     L.svils_orig_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.svils_ppc_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(vp)]
     L.svils_ppc_destroy.argtypes = [vp]
@@ -876,6 +879,24 @@ class Orig:
         """device ms of the last sweep: Elogpi and log tables, pair pass, reductions"""
         ms = np.zeros(3)
         _chk(load().svils_orig_get_timing(self._h, ms.ctypes.data))
+        return ms
+
+    def elbo(self):
+        """the variational lower bound of the current state (svils_orig_elbo): (total, P, N); elbo_stats() has the pass's counters"""
+        out = np.empty(3)
+        _chk(load().svils_orig_elbo(self._h, out.ctypes.data))
+        return tuple(out)
+
+    def elbo_stats(self):
+        """(pairs visited, rounds over all pairs, most rounds of a pair, normalisers not > 0) of the last elbo() pass"""
+        a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+        _chk(load().svils_orig_get_elbo_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
+
+    def elbo_timing(self):
+        """device ms of the last elbo() pass: the whole pass, its pair launches, its term launches"""
+        ms = np.zeros(3)
+        _chk(load().svils_orig_get_elbo_timing(self._h, ms.ctypes.data))
         return ms
 
     def link_prob(self, pairs):

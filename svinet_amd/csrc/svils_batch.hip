@@ -53,6 +53,7 @@
 //   k_batch_elbo_nodes      one wavefront per node: the node's term
 //   k_batch_elbo_reduce     one block: the lambda terms, and the three sums in a fixed order
 #include "svils_devutil.h"
+#include "svils_elbo.h"
 #include "svils_tool.h"
 #include "svils_waveutil.h"
 
@@ -371,8 +372,7 @@ __global__ __launch_bounds__(256) void k_batch_pair_ll(uint64_t m, uint32_t K, d
 // approx_log_likelihood (src/mmsbinfer.cc:1948-2060): s = G + P + N.  The pair part runs the tiles of a sweep and keeps a
 // scalar where the sweep keeps gamma and lambda partials.
 
-// phi log phi; an entry that has underflowed to exactly 0 adds 0 (the reference's log(phi) * phi is NaN there)
-__device__ __forceinline__ double xlogx(double p) { return p > 0.0 ? p * log(p) : 0.0; }
+// (xlogx and the node term: svils_elbo.h, shared with svils_orig_elbo)
 
 struct ElboArgs {
   uint32_t n, K, nw, t0;            // as PairArgs
@@ -465,19 +465,8 @@ __global__ __launch_bounds__(256) void k_batch_elbo_nodes(uint32_t n, uint32_t K
                                                           const double *__restrict__ elogpi, double *__restrict__ out) {
   const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= n) return;   // whole wavefronts leave together
-  const double *g = gamma + (size_t)i * K, *e = elogpi + (size_t)i * K;
-  double se = 0.0, sg = 0.0, sl = 0.0, sge = 0.0;
-  for (uint32_t k = lane; k < K; k += 64) {
-    se += e[k];
-    sg += g[k];
-    sl += lgamma(fmax(g[k], 1e-30));
-    sge += (g[k] - 1.0) * e[k];
-  }
-  se = wave_sum_f64(se);
-  sg = wave_sum_f64(sg);
-  sl = wave_sum_f64(sl);
-  sge = wave_sum_f64(sge);
-  if (lane == 0) out[i] = lgamma((double)K * alpha) - (double)K * lgamma(alpha) + (alpha - 1.0) * se - (lgamma(sg) - sl) - sge;
+  const double t = elbo_node_term(gamma + (size_t)i * K, elogpi + (size_t)i * K, K, alpha, lane);
+  if (lane == 0) out[i] = t;
 }
 
 // One block.  P: the (tile, wavefront) partials of the whole pass; N: the node terms; G: the terms of the communities,
@@ -724,7 +713,7 @@ __global__ __launch_bounds__(256) void k_batch_step_tail(uint32_t K, uint32_t nw
   }
 }
 
-// ---- stratified random node steps (svils_batch_step_strat, DESIGN.md section 4m) -------------------------------------
+// ---- stratified random node steps (svils_batch_step_strat, DESIGN.md section 4n) -------------------------------------
 // FastAMM2::infer (src/fastamm2.cc:565-640): a step is a star, but EVERY row of gamma moves -- the rows of the star towards
 // alpha + scale phi, all others a step rho towards alpha.  The others are not written: gamma_i - alpha of an untouched row
 // is multiplied by (1 - rho_s) at every step, so the host keeps the running c = sum log1p(-rho_s) and per row the c of its

@@ -36,14 +36,11 @@ namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t TILE_PAIRS = 16;                 // pairs per wavefront: the columns of one MFMA
 constexpr uint32_t TILES_PER_BLOCK = 16;            // four per wavefront
 constexpr size_t PHI_BYTES = (size_t)256 << 20;     // phi1 and phi2 of one launch
 constexpr uint32_t ACC_WAVES = 256;                 // wavefronts (and partial sums) of k_orig_acc
 
 inline uint32_t padded_k(uint32_t k) { return (k + 15) / 16 * 16; }
-// row stride of the transposed log tables: 16 (mod 32) doubles, so the four lane groups of an A operand read take two LDS passes
-constexpr int tab_ld(int kp) { return kp % 32 == 0 ? kp + 16 : kp; }
 
 // the sum over the four lane groups of a pair (lanes c, c + 16, c + 32, c + 48): the same bits in all four
 __device__ inline double groups_sum(double v) {
@@ -67,16 +64,17 @@ __global__ __launch_bounds__(256) void k_orig_dir_exp(uint32_t n, uint32_t K, co
 }
 
 // tabs[which][h][ld]: entry (h, g) = log f[g][h], f = 1 - beta (which 0) or beta (which 1); zero past K
+// (eps: 0 for the sweep's L tables; 1e-10 for the T tables of the lower bound, svils_orig_elbo.hip)
 __global__ __launch_bounds__(256) void k_orig_tables(uint32_t K, uint32_t KP, uint32_t ld, const double *__restrict__ beta,
-                                                     double *__restrict__ tabs) {
+                                                     double eps, double *__restrict__ tabs) {
   const uint32_t e = blockIdx.x * 256 + threadIdx.x;
   if (e >= KP * ld) return;
   const uint32_t h = e / ld, g = e % ld;
   double l0 = 0.0, l1 = 0.0;
   if (h < K && g < K) {
     const double b = beta[(size_t)g * K + h];
-    l0 = log(1.0 - b);
-    l1 = log(b);
+    l0 = log((1.0 - b) + eps);
+    l1 = log(b + eps);
   }
   tabs[e] = l0;
   tabs[(size_t)KP * ld + e] = l1;
@@ -89,16 +87,6 @@ __global__ __launch_bounds__(256) void k_orig_fill(uint64_t nk, uint32_t nnt, do
   if (x < nnt) nt[x] = 0.0;
   if (x == 0) ctr[CTR_FLAG] = ctr[CTR_PENDING];   // no launch reads the flag between k_orig_final and here
 }
-
-struct PairArgs {
-  uint32_t n, K, nw, p0, rows, tpr;   // nw: words per row of the bit matrices; rows p0 .. p0 + rows; tpr = ceil(n / 16)
-  const uint32_t *adj, *skip;         // [n][nw] bit q of row p: y(p, q) / the ordered pair (p, q) is left out
-  const double *elogpi;               // [n][K]
-  const double *tabs;                 // [2][KP][ld]
-  double *phi1, *phi2;                // [rows n][KP]
-  uint8_t *yv;                        // [rows n]
-  u64 *ctr;
-};
 
 template <int KP, bool LREG>
 __global__ __launch_bounds__(256) void k_orig_pairs(PairArgs x) {
@@ -391,25 +379,15 @@ int one_sweep(svils_orig *h) {
   const uint64_t nk = (uint64_t)n * K;
   const uint32_t nnt = 2 * KP * KP;
   HIPCHK(hipEventRecord(h->ev[0], h->st));
-  hipLaunchKernelGGL(k_orig_dir_exp, dim3(blocks(n, 4)), dim3(256), 0, h->st, n, K, h->gamma, h->gtab, h->elogpi);
-  hipLaunchKernelGGL(k_orig_tables, dim3(blocks((uint64_t)KP * h->ld, 256)), dim3(256), 0, h->st, K, KP, h->ld, h->beta, h->tabs);
-  HIPCHK(hipGetLastError());
+  if (int rc = orig_launch_prologue(h, h->elogpi, h->tabs, 0.0)) return rc;
   HIPCHK(hipEventRecord(h->ev[1], h->st));
   hipLaunchKernelGGL(k_orig_fill, dim3(blocks(std::max<uint64_t>(nk, nnt), 256)), dim3(256), 0, h->st, nk, nnt, h->alpha, h->gnext,
                      h->nt, h->ctr);
   uint32_t b = 0;
   for (uint32_t p0 = 0; p0 < n; p0 += h->rows, ++b) {
     const uint32_t rows = std::min(h->rows, n - p0), tpr = (n + TILE_PAIRS - 1) / TILE_PAIRS;
-    const uint32_t nblocks = blocks((uint64_t)rows * tpr, TILES_PER_BLOCK);
     PairArgs a{n, K, h->nw, p0, rows, tpr, h->adj, h->skip, h->elogpi, h->tabs, h->phi1, h->phi2, h->yv, h->ctr};
-    switch (KP) {
-      case 16: launch_pairs<16, true>(h, nblocks, a); break;
-      case 32: launch_pairs<32, true>(h, nblocks, a); break;
-      case 48: launch_pairs<48, false>(h, nblocks, a); break;
-      case 64: launch_pairs<64, false>(h, nblocks, a); break;
-      default: return fail(SVILS_ERR_UNSUPPORTED, "svils_orig_sweep: no pair kernel for padded K = %u", KP);   // a missing kernel is an error
-    }
-    HIPCHK(hipGetLastError());
+    if (int rc = orig_launch_pairs(h, "svils_orig_sweep", a)) return rc;
     HIPCHK(hipEventRecord(h->ev[2 + 2 * b], h->st));
     hipLaunchKernelGGL(k_orig_gamma_rows, dim3(rows), dim3(256), 0, h->st, n, K, KP, p0, h->phi1, h->gnext, h->ctr);
     hipLaunchKernelGGL(k_orig_gamma_cols, dim3(blocks(nk, 256)), dim3(256), 0, h->st, n, K, KP, rows, h->phi2, h->gnext, h->ctr);
@@ -433,6 +411,31 @@ int one_sweep(svils_orig *h) {
 }
 
 }  // namespace
+
+namespace svils_impl {
+
+int orig_launch_prologue(svils_orig *h, double *elogpi, double *tabs, double eps) {
+  const uint32_t n = h->n, K = h->k, KP = h->kp;
+  if (elogpi) hipLaunchKernelGGL(k_orig_dir_exp, dim3(blocks(n, 4)), dim3(256), 0, h->st, n, K, h->gamma, h->gtab, elogpi);
+  hipLaunchKernelGGL(k_orig_tables, dim3(blocks((uint64_t)KP * h->ld, 256)), dim3(256), 0, h->st, K, KP, h->ld, h->beta, eps, tabs);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int orig_launch_pairs(svils_orig *h, const char *name, const PairArgs &a) {
+  const uint32_t nblocks = blocks((uint64_t)a.rows * a.tpr, TILES_PER_BLOCK);
+  switch (h->kp) {
+    case 16: launch_pairs<16, true>(h, nblocks, a); break;
+    case 32: launch_pairs<32, true>(h, nblocks, a); break;
+    case 48: launch_pairs<48, false>(h, nblocks, a); break;
+    case 64: launch_pairs<64, false>(h, nblocks, a); break;
+    default: return fail(SVILS_ERR_UNSUPPORTED, "%s: no pair kernel for padded K = %u", name, h->kp);   // a missing kernel is an error
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace svils_impl
 
 extern "C" {
 
@@ -488,6 +491,7 @@ int svils_orig_destroy(svils_orig *h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->st);
     free_queries(h);
+    free_elbo(h);
   }
   delete h;   // ~ToolHandle: waits for the stream, frees both scopes
   return 0;

@@ -292,8 +292,8 @@ struct svih_orig {
   std::unique_ptr<MMSBInferOrig> eng;
 };
 // clean_holdout: -clean-holdout (both orientations of every held-out and validation pair are left out of training)
-svih_orig *svih_orig_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t itype,
-                               int32_t on_device, int32_t device, int32_t clean_holdout) {
+static svih_orig *orig_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t itype,
+                                 int32_t on_device, int32_t device, int32_t clean_holdout, int32_t logl) {
   Env::Args a;
   a.n = n;
   a.k = k;
@@ -305,6 +305,7 @@ svih_orig *svih_orig_from_file(const char *path, uint32_t n, uint32_t k, double 
   a.rand_seed = seed;
   a.hol_ratio = heldout_ratio;
   a.write_files = false;
+  a.logl = logl != 0;
   svih_orig *b = new svih_orig();
   b->env.reset(new Env(a));
   b->net.reset(new Network(*b->env));
@@ -316,7 +317,36 @@ svih_orig *svih_orig_from_file(const char *path, uint32_t n, uint32_t k, double 
   }
   return b;
 }
+svih_orig *svih_orig_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t itype,
+                               int32_t on_device, int32_t device, int32_t clean_holdout) {
+  return orig_from_file(path, n, k, seed, heldout_ratio, itype, on_device, device, clean_holdout, 0);
+}
+// logl: -logl (a row of the lower bound after the constructor's rows and at every report: svih_orig_logl_rows)
+svih_orig *svih_orig_from_file_logl(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t itype,
+                                    int32_t on_device, int32_t device, int32_t clean_holdout, int32_t logl) {
+  return orig_from_file(path, n, k, seed, heldout_ratio, itype, on_device, device, clean_holdout, logl);
+}
 void svih_orig_free(svih_orig *b) { delete b; }
+// the variational lower bound of the current state: out = total, P, N; stats = pairs visited, fixed-point rounds
+int svih_orig_elbo(svih_orig *b, double *out, uint64_t *stats) {
+  return svils_rc([&] { b->eng->elbo(out, stats, stats ? stats + 1 : nullptr); return 0; });
+}
+uint64_t svih_orig_nlogl_rows(const svih_orig *b) { return b->eng->logl_rows().size() / 2; }
+const double *svih_orig_logl_rows(const svih_orig *b) { return b->eng->logl_rows().data(); }   // [rows][2]: iter, s
+// tests: the stop rule of -orig -logl on its own.  state [4]: max, prev, nh, enabled (in and out); returns the verdict
+// (0 go on, 1 the drop rule, 2 the gain rule)
+int32_t svih_orig_stop_rule(double *state, uint32_t iter, double s) {
+  OrigStopRule r;
+  r.max = state[0];
+  r.prev = state[1];
+  r.nh = (uint32_t)state[2];
+  r.enabled = state[3] != 0;
+  const int32_t v = (int32_t)r.update(iter, s);
+  state[0] = r.max;
+  state[1] = r.prev;
+  state[2] = (double)r.nh;
+  return v;
+}
 uint32_t svih_orig_n(const svih_orig *b) { return b->eng->n(); }
 uint32_t svih_orig_iter(const svih_orig *b) { return b->eng->iter(); }
 int svih_orig_gamma(svih_orig *b, double *out) {

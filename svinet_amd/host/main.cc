@@ -226,8 +226,14 @@ static void usage() {
           "\t-heldout-ratio, -link-thresh, -lt-min-deg, -eta-type, -accuracy\tas in the reference\n\n"
           "\t-logl\t\twith -batch, -batch-gpu, -rnode, -rpair, -infset and -snode: the variational lower bound after the\n"
           "\t\t\tinitialisation and at every report (a row of logl.txt; with -accuracy the convergence rule\n"
-          "\t\t\tthat writes done.txt); on the device unless -batch or -host-loops is given.  Accepted and\n"
-          "\t\t\twithout effect with every other mode\n\n"
+          "\t\t\tthat writes done.txt); on the device unless -batch or -host-loops is given.\n"
+          "\t\t\tWith -orig: the bound of the K x K blockmodel, P + N of the current state over the pairs a sweep\n"
+          "\t\t\tvisits (the reference reads the vectors of the sweep before and adds the held-out pairs), a row\n"
+          "\t\t\tof logl.txt after the initialisation and at every report, and two stop rules on it: the bound\n"
+          "\t\t\tbelow its maximum at more than 3 reports past iteration 10 (writes max.txt), or a relative gain\n"
+          "\t\t\tbelow 1e-5 (writes done.txt).  Either ends the run with the model saved, so -orig -logl needs no\n"
+          "\t\t\t-max-iterations (if given it still caps the run); -no-stop turns both rules off.  About one\n"
+          "\t\t\tsweep's pair pass per row.  Accepted and without effect with every other mode\n\n"
           "\t-strid\t\tnode names are strings (writes str2id.txt)\n\n"
           "\t-nmi <file>\tground-truth communities (\"node<TAB>community ...\" per line): the normalised mutual\n"
           "\t\t\tinformation of every communities.txt against it is appended to mutual.txt\n\n"
@@ -309,7 +315,7 @@ int main(int argc, char **argv) {
     else if (is("-nmi")) { need(i); a.ground_truth_fname = argv[++i]; a.nmi = true; }
     else if (is("-rfreq")) { need(i); a.rfreq = atoi(argv[++i]); }
     else if (is("-accuracy")) { a.accuracy = true; }
-    else if (is("-logl")) { a.logl = true; }                 // src/main.cc:221-222: read by MMSBBatch alone (-batch, -rnode, -rpair, -infset)
+    else if (is("-logl")) { a.logl = true; }                 // src/main.cc:221-222: read by MMSBBatch (-batch, -rnode, -rpair, -infset) and MMSBInferOrig (-orig)
     else if (is("-max-iterations")) { need(i); a.max_iterations = atoi(argv[++i]); }
     else if (is("-no-stop")) { a.use_validation_stop = false; }
     else if (is("-seed")) { need(i); a.rand_seed = atof(argv[++i]); }
@@ -464,7 +470,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, kOrig.fmt, "-orig", m.name);
         return 2;
       }
-    if (a.max_iterations == 0) {
+    if (a.max_iterations == 0 && !(a.logl && a.use_validation_stop)) {   // -orig -logl: the stop rules of the bound end the run
       fprintf(stderr, "error: -orig needs -max-iterations N: the reference's loop never ends and its stop rule is compiled out\n");
       return 2;
     }

@@ -52,6 +52,7 @@ MMSBInferOrig::MMSBInferOrig(Env &env, Network &network, int itype)
     // files the reference's constructor opens (:86-128); the ones this path never writes stay empty
     for (const char *f : {"/stats.txt", "/time.txt", "/convergence.txt", "/logl.txt", "/modularity.txt"})
       fclose(open_or_die(Env::file_str(f), f + 1));
+    if (env_.logl) lf_ = open_or_die(Env::file_str("/logl.txt"), "logl");
     hf_ = open_or_die(Env::file_str("/heldout.txt"), "heldout");
     vf_ = open_or_die(Env::file_str("/validation.txt"), "validation");
   }
@@ -59,6 +60,8 @@ MMSBInferOrig::MMSBInferOrig(Env &env, Network &network, int itype)
   Env::plog("network singles", network_.singles());
   likelihood_row(heldout_map_, hf_, 0);      // :129-133
   likelihood_row(validation_map_, vf_, 1);
+  rule_.enabled = env_.use_validation_stop;
+  if (env_.logl) approx_log_likelihood();   // :135-137: the bound of the initial state (no rule can fire at the first row)
   fprintf(stdout, "+ mmsb initialization end\n");
   fflush(stdout);
   start_time_ = time(0);
@@ -67,6 +70,7 @@ MMSBInferOrig::MMSBInferOrig(Env &env, Network &network, int itype)
 MMSBInferOrig::~MMSBInferOrig() {
   if (hf_) fclose(hf_);
   if (vf_) fclose(vf_);
+  if (lf_) fclose(lf_);
   if (dev_) svils_orig_destroy(dev_);
 }
 
@@ -214,6 +218,47 @@ void MMSBInferOrig::init_beta2() {
 // ---------------------------------------------------------------------------
 // one sweep (:217-271)
 // ---------------------------------------------------------------------------
+// update_phis_until_conv (src/mmsbinferorig.hh:186-220) from 1 / K; returns the rounds run
+uint32_t MMSBInferOrig::fixed_point(const double *ep, const double *eq, const double *lf, double *phi1, double *phi2, uint32_t p,
+                                    uint32_t q) const {
+  const uint32_t K = k_;
+  std::vector<double> n1(K), n2(K), o1(K, 0.0), o2(K, 0.0);
+  for (uint32_t g = 0; g < K; ++g) phi1[g] = phi2[g] = 1.0 / K;
+  uint32_t rounds = 0;
+  for (uint32_t i = 0; i < kOnlineIterations; ++i) {
+    if (i % 2 == 0) { o1.assign(phi1, phi1 + K); o2.assign(phi2, phi2 + K); }
+    double s1 = 0, s2 = 0;
+    for (uint32_t g = 0; g < K; ++g) {                        // both from the old vectors, both with lf[g][h]
+      double u1 = ep[g], u2 = eq[g];
+      for (uint32_t h = 0; h < K; ++h) {
+        u1 += lf[(size_t)g * K + h] * phi2[h];
+        u2 += lf[(size_t)g * K + h] * phi1[h];
+      }
+      n1[g] = exp(u1);
+      n2[g] = exp(u2);
+      s1 += n1[g];
+      s2 += n2[g];
+    }
+    if (!(s1 > 0) || !(s2 > 0)) {                             // the reference asserts here (:146)
+      fprintf(stderr, "error: -orig: the normaliser of pair (%u, %u) is not > 0\n", p, q);
+      exit(-1);
+    }
+    double v1 = 0, v2 = 0;
+    for (uint32_t g = 0; g < K; ++g) {
+      n1[g] /= s1;
+      n2[g] /= s2;
+      v1 += fabs(n1[g] - o1[g]);
+      v2 += fabs(n2[g] - o2[g]);
+    }
+    std::copy(n1.begin(), n1.end(), phi1);
+    std::copy(n2.begin(), n2.end(), phi2);
+    rounds = i + 1;
+    if (i % 2 == 0) continue;
+    if (v1 / K < kMeanChangeThresh && v2 / K < kMeanChangeThresh) break;
+  }
+  return rounds;
+}
+
 void MMSBInferOrig::sweep_host() {
   const uint32_t K = k_;
   std::vector<double> elogpi((size_t)n_ * K), l0((size_t)K * K), l1((size_t)K * K);
@@ -229,7 +274,7 @@ void MMSBInferOrig::sweep_host() {
     l1[e] = log(beta_[e]);
   }
   std::vector<double> gnext((size_t)n_ * K, env_.alpha), num((size_t)K * K, 0.0), tot((size_t)K * K, 0.0);
-  std::vector<double> phi1(K), phi2(K), n1(K), n2(K), o1(K), o2(K);
+  std::vector<double> phi1(K), phi2(K);
   rounds_total_ = 0;
   for (uint32_t p = 0; p < n_; ++p)
     for (uint32_t q = 0; q < n_; ++q) {
@@ -238,39 +283,7 @@ void MMSBInferOrig::sweep_host() {
       if (skip_.count(e) || extra_skip_.count(e)) continue;   // an ordered pair: init_skip
       const bool y = network_.y(p, q);
       const double *lf = y ? l1.data() : l0.data();
-      for (uint32_t g = 0; g < K; ++g) { phi1[g] = phi2[g] = 1.0 / K; o1[g] = o2[g] = 0; }
-      uint32_t rounds = 0;
-      for (uint32_t i = 0; i < kOnlineIterations; ++i) {      // update_phis_until_conv (src/mmsbinferorig.hh:186-220)
-        if (i % 2 == 0) { o1 = phi1; o2 = phi2; }
-        double s1 = 0, s2 = 0;
-        for (uint32_t g = 0; g < K; ++g) {                    // both from the old vectors, both with lf[g][h]
-          double u1 = elogpi[(size_t)p * K + g], u2 = elogpi[(size_t)q * K + g];
-          for (uint32_t h = 0; h < K; ++h) {
-            u1 += lf[(size_t)g * K + h] * phi2[h];
-            u2 += lf[(size_t)g * K + h] * phi1[h];
-          }
-          n1[g] = exp(u1);
-          n2[g] = exp(u2);
-          s1 += n1[g];
-          s2 += n2[g];
-        }
-        if (!(s1 > 0) || !(s2 > 0)) {                         // the reference asserts here (:146)
-          fprintf(stderr, "error: -orig: the normaliser of pair (%u, %u) is not > 0\n", p, q);
-          exit(-1);
-        }
-        double v1 = 0, v2 = 0;
-        for (uint32_t g = 0; g < K; ++g) {
-          n1[g] /= s1;
-          n2[g] /= s2;
-          v1 += fabs(n1[g] - o1[g]);
-          v2 += fabs(n2[g] - o2[g]);
-        }
-        phi1 = n1;
-        phi2 = n2;
-        rounds = i + 1;
-        if (i % 2 == 0) continue;
-        if (v1 / K < kMeanChangeThresh && v2 / K < kMeanChangeThresh) break;
-      }
+      const uint32_t rounds = fixed_point(&elogpi[(size_t)p * K], &elogpi[(size_t)q * K], lf, phi1.data(), phi2.data(), p, q);
       rounds_total_ += rounds;
       for (uint32_t g = 0; g < K; ++g) {
         gnext[(size_t)p * K + g] += phi1[g];
@@ -354,11 +367,113 @@ void MMSBInferOrig::report() {
   if (env_.write_files) compute_and_log_groups();
   likelihood_row(heldout_map_, hf_, 0);
   likelihood_row(validation_map_, vf_, 1);
+  if (env_.logl && approx_log_likelihood()) stopped_ = true;   // :287-289
+}
+
+// ---------------------------------------------------------------------------
+// the variational lower bound (:624-726 under GLOBALPHIS)
+// ---------------------------------------------------------------------------
+void MMSBInferOrig::elbo_host(double out[3], uint64_t *pairs, uint64_t *rounds) {
+  const uint32_t K = k_;
+  std::vector<double> elogpi((size_t)n_ * K), l0((size_t)K * K), l1((size_t)K * K), t0((size_t)K * K), t1((size_t)K * K);
+  for (uint32_t i = 0; i < n_; ++i) {
+    const double *g = &gamma_[(size_t)i * K];
+    double s = 0;
+    for (uint32_t k = 0; k < K; ++k) s += g[k];
+    const double ps = digamma(s);
+    for (uint32_t k = 0; k < K; ++k) elogpi[(size_t)i * K + k] = digamma(g[k] < 1e-30 ? 1e-30 : g[k]) - ps;
+  }
+  for (size_t e = 0; e < l0.size(); ++e) {
+    l0[e] = log(1 - beta_[e]);
+    l1[e] = log(beta_[e]);
+    t0[e] = log((1 - beta_[e]) + 1e-10);                      // the reference's log(fd[g][h] + 1e-10) (:654)
+    t1[e] = log(beta_[e] + 1e-10);
+  }
+  auto xlogx = [](double v) { return v > 0 ? v * log(v) : 0.0; };   // (log(phi) * phi there: NaN at an exact 0)
+  std::vector<double> phi1(K), phi2(K);
+  uint64_t np = 0, nr = 0;
+  double P = 0;
+  for (uint32_t p = 0; p < n_; ++p)
+    for (uint32_t q = 0; q < n_; ++q) {
+      if (p == q) continue;
+      const Edge e(p, q);
+      if (skip_.count(e) || extra_skip_.count(e)) continue;   // the pairs a sweep visits
+      const bool y = network_.y(p, q);
+      const double *ep = &elogpi[(size_t)p * K], *eq = &elogpi[(size_t)q * K], *tf = y ? t1.data() : t0.data();
+      nr += fixed_point(ep, eq, y ? l1.data() : l0.data(), phi1.data(), phi2.data(), p, q);
+      np++;
+      double t = 0;
+      for (uint32_t g = 0; g < K; ++g)
+        for (uint32_t h = 0; h < K; ++h) t += phi1[g] * phi2[h] * tf[(size_t)g * K + h];
+      for (uint32_t k = 0; k < K; ++k) t += phi1[k] * ep[k] + phi2[k] * eq[k];
+      for (uint32_t k = 0; k < K; ++k) t -= xlogx(phi1[k]) + xlogx(phi2[k]);
+      P += t;
+    }
+  double N = 0;
+  const double a = env_.alpha;
+  for (uint32_t p = 0; p < n_; ++p) {                         // :668-688
+    const double *g = &gamma_[(size_t)p * K], *e = &elogpi[(size_t)p * K];
+    double se = 0, sg = 0, sl = 0, sge = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+      se += e[k];
+      sg += g[k];
+      sl += std::lgamma(g[k] < 1e-30 ? 1e-30 : g[k]);
+      sge += (g[k] - 1) * e[k];
+    }
+    N += std::lgamma(K * a) - K * std::lgamma(a) + (a - 1) * se - (std::lgamma(sg) - sl) - sge;
+  }
+  out[0] = P + N;
+  out[1] = P;
+  out[2] = N;
+  if (pairs) *pairs = np;
+  if (rounds) *rounds = nr;
+}
+
+void MMSBInferOrig::elbo(double out[3], uint64_t *pairs, uint64_t *rounds) {
+  if (dev_) {
+    if (int rc = svils_orig_elbo(dev_, out)) throw_svils("svils_orig_elbo", rc);
+    if (int rc = svils_orig_get_elbo_stats(dev_, pairs, rounds, nullptr, nullptr)) throw_svils("svils_orig_get_elbo_stats", rc);
+  } else {
+    elbo_host(out, pairs, rounds);
+  }
+}
+
+bool MMSBInferOrig::approx_log_likelihood() {
+  double o[3];
+  elbo(o);
+  const double s = o[0];
+  printf("approx. log likelihood = %f\n", s);
+  if (lf_) {
+    fprintf(lf_, "%d\t%d\t%.5f\n", iter_, duration(), s);
+    fflush(lf_);
+  }
+  logl_rows_.push_back((double)iter_);
+  logl_rows_.push_back(s);
+  const OrigStopRule::Verdict v = rule_.update(iter_, s);
+  if (rule_.new_max && rows_.size() >= 16) {                  // the report's own rows (the reference recomputes and re-logs them)
+    const double *h = &rows_[rows_.size() - 16], *vr = h + 8;
+    for (int i = 0; i < 3; ++i) { max_h_[i] = h[2 + 2 * i]; max_v_[i] = vr[2 + 2 * i]; }
+  }
+  if (v == OrigStopRule::GO_ON) return false;
+  if (env_.write_files) {
+    if (v == OrigStopRule::STOP_DROP) {                       // :717-722
+      FILE *f = open_or_die(Env::file_str("/max.txt"), "max");
+      fprintf(f, "%d\t%d\t%f\t%f\t%f\t%f\t%f\t%f\t%f\n", iter_, duration(), rule_.max, max_h_[0], max_h_[1], max_h_[2], max_v_[0],
+              max_v_[1], max_v_[2]);
+      fclose(f);
+    } else {                                                  // src/mmsbinfer.cc:2062-2081
+      FILE *f = open_or_die(Env::file_str("/done.txt"), "done");
+      fprintf(f, "%d\t%d\t%.5f\n", iter_, duration(), s);
+      fclose(f);
+    }
+  }
+  return true;
 }
 
 int MMSBInferOrig::batch_infer() {
   printf("+ Running MMSB Orig batch inference\n");
-  while (iter_ < env_.max_iterations && !env_.terminate) {
+  const bool open_end = env_.max_iterations == 0 && env_.logl && rule_.enabled;   // a stop rule ends the run
+  while ((open_end || iter_ < env_.max_iterations) && !env_.terminate && !stopped_) {
     sweep();
     printf("iteration = %d took %d secs\n", iter_, duration());
     fflush(stdout);

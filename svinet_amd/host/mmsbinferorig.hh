@@ -25,13 +25,18 @@
 //   - the held-out and validation pairs are kept in the order drawn (no p < q), and the files list sequence ids.
 // Departures, all forced:
 //   - the reference's loop never ends and its stop rule is compiled out (:499-522): here -orig requires
-//     -max-iterations N, runs N sweeps, then writes gamma.txt (this project's format) and beta.txt (K lines of K values);
+//     -max-iterations N, runs N sweeps, then writes gamma.txt (this project's format) and beta.txt (K lines of K values) --
+//     unless -logl is given: then the variational lower bound (elbo(), DESIGN.md section 4n: approx_log_likelihood,
+//     :624-726 under GLOBALPHIS, of the CURRENT state over the visited pairs, with x log x for log(phi) phi) is written to
+//     logl.txt after the constructor's rows and at every report, and OrigStopRule ends the run (the model is saved and the
+//     queries run, as at the -max-iterations exit; the reference exits without saving);
 //   - `_iter` is never initialised there; it starts at 0 here;
 //   - the reference never seeds this engine; -seed is honoured here when given;
 //   - the reference's printf of every beta entry is dropped;
 //   - gsl_ran_gamma: the same Marsaglia-Tsang recipe as mmsbbatch.cc over the same MT19937 stream with a polar Box-Muller
 //     Gaussian, so the distribution matches and the stream does not.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <ctime>
@@ -47,13 +52,45 @@
 
 namespace svinet {
 
+// The stop rules of -orig -logl as a function of (iter, s), s the lower bound of a report.
+//   drop  the reference's (:694-723): s > max remembers s (and the caller this report's rows) and clears nh; s < max with
+//         iter > 10 counts nh up; nh > 3 ends the run (max.txt)
+//   gain  the sibling's threshold (src/mmsbinfer.cc:2062-2081): s > prev, prev != 0 and |(s - prev) / prev| < 1e-5 ends the
+//         run (done.txt) -- a loop on a shared machine must end
+// enabled false (-no-stop): update() still tracks max and prev but never answers a stop.
+struct OrigStopRule {
+  enum Verdict { GO_ON = 0, STOP_DROP = 1, STOP_GAIN = 2 };
+  bool enabled = true;
+  double max = -1.7976931348623157e308, prev = 0;
+  uint32_t nh = 0;
+  bool new_max = false;   // the last update() raised max: the caller remembers the report's held-out and validation rows
+  Verdict update(uint32_t iter, double s) {
+    new_max = false;
+    if (s > max) { max = s; nh = 0; new_max = true; }
+    else if (s < max && iter > 10) nh++;
+    const bool gain = s > prev && prev != 0 && fabs((s - prev) / prev) < 1e-5;
+    prev = s;
+    if (!enabled) return GO_ON;
+    if (nh > 3) return STOP_DROP;
+    return gain ? STOP_GAIN : GO_ON;
+  }
+};
+
 class MMSBInferOrig {
  public:
   MMSBInferOrig(Env &env, Network &network, int itype);
   ~MMSBInferOrig();
 
-  // env.max_iterations sweeps, a report every env.reportfreq of them, then gamma.txt and beta.txt; returns 0
+  // env.max_iterations sweeps (0 with -logl: until a stop rule fires), a report every env.reportfreq of them, then gamma.txt
+  // and beta.txt; returns 0
   int batch_infer();
+  // The variational lower bound of the current state: total, P, N.  Device backend: svils_orig_elbo;
+  // -host-loops: the loops restated.  pairs / rounds (either may be null): the visited pairs and their fixed-point rounds
+  void elbo(double out[3], uint64_t *pairs = nullptr, uint64_t *rounds = nullptr);
+  // approx_log_likelihood (:690-723): prints the bound, appends a row of logl.txt, drives the stop rule; true: end the run
+  bool approx_log_likelihood();
+  const std::vector<double> &logl_rows() const { return logl_rows_; }   // [rows][2]: iter, s
+  OrigStopRule &stop_rule() { return rule_; }
   void sweep();    // one pass of :217-271 (iter() advances)
   // after the last sweep, device backend only: link-prob.txt, recommendations.txt, link-ranks.txt / heldout-ranks.txt and
   // link-ranks-summary.txt for the flags given, in the formats of pairfiles.hh, from the final state.  A score is
@@ -89,6 +126,8 @@ class MMSBInferOrig {
   double ran_gamma(double a, double b);
   double ran_gaussian();
   void sweep_host();
+  void elbo_host(double out[3], uint64_t *pairs, uint64_t *rounds);
+  uint32_t fixed_point(const double *ep, const double *eq, const double *lf, double *phi1, double *phi2, uint32_t p, uint32_t q) const;
   void likelihood_row(const std::map<Edge, bool> &pairs, FILE *f, int which);
   void compute_and_log_groups();
   void save_model();
@@ -111,7 +150,11 @@ class MMSBInferOrig {
   bool have_spare_ = false;
   double spare_ = 0;
   time_t start_time_;
-  FILE *hf_ = nullptr, *vf_ = nullptr;
+  FILE *hf_ = nullptr, *vf_ = nullptr, *lf_ = nullptr;
+  std::vector<double> logl_rows_;
+  OrigStopRule rule_;
+  double max_h_[3] = {0, 0, 0}, max_v_[3] = {0, 0, 0};   // the held-out / validation triples of the report at the maximum
+  bool stopped_ = false;
   svils_orig *dev_ = nullptr;   // the device backend (null: host loops)
   bool host_stale_ = false;     // the device has swept since gamma_ / beta_ were fetched
 };

@@ -328,6 +328,21 @@ class BatchEngine:
     __del__ = close
 
 
+def orig_stop_rule(seq, enabled=True):
+    """The stop rules of -orig -logl (OrigStopRule, svinet_amd/host/mmsbinferorig.hh) driven over seq = [(iter, s), ...]:
+    the verdict of every row -- 0 go on, 1 the drop rule (max.txt), 2 the gain rule (done.txt) -- stopping at the first stop"""
+    L = load()
+    L.svih_orig_stop_rule.argtypes = [C.c_void_p, C.c_uint32, C.c_double]
+    L.svih_orig_stop_rule.restype = C.c_int32
+    state = np.array([-np.finfo(np.float64).max, 0.0, 0.0, 1.0 if enabled else 0.0])
+    out = []
+    for it, s in seq:
+        out.append(int(L.svih_orig_stop_rule(state.ctypes.data, int(it), float(s))))
+        if out[-1]:
+            break
+    return out
+
+
 class OrigEngine:
     """The `-orig` engine of the host library (svinet_amd/host/mmsbinferorig.cc): the reference's MMSBInferOrig::batch_infer
     (src/mmsbinferorig.cc:212-294), the blockmodel with a full K x K matrix of block rates.  on_device=True: the sweeps and
@@ -337,7 +352,8 @@ class OrigEngine:
     link_prob / predict_links / rank_links query the current state on the device (svils_orig_link_prob / _predict_links /
     _rank_links) and return what the _svils.Engine methods of the same names return."""
 
-    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, itype=0, on_device=True, device=0, clean_holdout=False):
+    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, itype=0, on_device=True, device=0, clean_holdout=False,
+                 logl=False):
         L = load()
         vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
         if not hasattr(L, "_orig_ready"):
@@ -359,9 +375,19 @@ class OrigEngine:
             L.svih_orig_set_state.restype = C.c_int
             L.svih_orig_skip_also.argtypes = [vp, vp, u64]
             L.svih_orig_skip_also.restype = None
+            L.svih_orig_from_file_logl.argtypes = L.svih_orig_from_file.argtypes + [C.c_int32]
+            L.svih_orig_from_file_logl.restype = vp
+            L.svih_orig_elbo.argtypes = [vp, vp, vp]
+            L.svih_orig_elbo.restype = C.c_int
+            L.svih_orig_nlogl_rows.argtypes = [vp]
+            L.svih_orig_nlogl_rows.restype = u64
+            L.svih_orig_logl_rows.argtypes = [vp]
+            L.svih_orig_logl_rows.restype = P(dbl)
+            L.svih_orig_stop_rule.argtypes = [vp, u32, dbl]
+            L.svih_orig_stop_rule.restype = C.c_int32
             L._orig_ready = True
-        self._h = L.svih_orig_from_file(os.fsencode(path), n, k, seed, heldout_ratio, itype, int(bool(on_device)), device,
-                                        int(bool(clean_holdout)))
+        self._h = L.svih_orig_from_file_logl(os.fsencode(path), n, k, seed, heldout_ratio, itype, int(bool(on_device)), device,
+                                             int(bool(clean_holdout)), int(bool(logl)))
         if not self._h:
             if on_device:
                 err = _svils.load().svils_last_error().decode("utf-8", "replace")
@@ -438,6 +464,22 @@ class OrigEngine:
         rc = load().svih_orig_report(self._h)
         if rc < 0:
             _svils._chk(rc)
+
+    def elbo(self):
+        """the variational lower bound of the current state (approx_log_likelihood, src/mmsbinferorig.cc:624-726, over the
+        pairs a sweep visits): (total, P, N).  on_device=True: svils_orig_elbo; else the host loops.  elbo_stats: (pairs,
+        fixed-point rounds) of this pass"""
+        out, st = np.empty(3), np.zeros(2, dtype=np.uint64)
+        rc = load().svih_orig_elbo(self._h, out.ctypes.data, st.ctypes.data)
+        if rc < 0:
+            _svils._chk(rc)
+        self.elbo_stats = (int(st[0]), int(st[1]))
+        return tuple(out)
+
+    @property
+    def logl_rows(self):
+        """[rows][2] (iter, lower bound): with logl=True one row after the constructor and one per report"""
+        return _arr(load().svih_orig_logl_rows(self._h), (load().svih_orig_nlogl_rows(self._h), 2), np.float64)
 
     def close(self):
         if getattr(self, "_h", None):
