@@ -730,39 +730,34 @@ class Batch:
         _chk(load().svils_batch_step_pairs(self._h, len(lists), off.ctypes.data, pairs.ctypes.data, sc.ctypes.data, rg.ctypes.data,
                                            rl.ctypes.data))
 
+    @staticmethod
+    def _star_lists(steps, entry_keys, step_keys):
+        """what step_star and step_strat hand over: start [ns], off [ns + 1], one concatenated array per (key, dtype) of
+        `entry_keys` (the first is partner; each step's as long as its partner list) and one double per step per `step_keys`"""
+        per_step = [[np.ascontiguousarray(s[key], dtype=dtype).reshape(-1) for s in steps] for key, dtype in entry_keys]
+        parts = per_step[0]
+        assert all(x.shape == p.shape for a in per_step[1:] for x, p in zip(a, parts))
+        off = np.zeros(len(steps) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([p.shape[0] for p in parts])
+        entries = [np.ascontiguousarray(np.concatenate(a) if a else np.zeros(0), dtype=dtype)
+                   for a, (_, dtype) in zip(per_step, entry_keys)]
+        start = np.array([s["start"] for s in steps], dtype=np.uint32)
+        return start, off, entries, [np.array([s[key] for s in steps], dtype=np.float64) for key in step_keys]
+
     def step_star(self, steps):
         """svils_batch_step_star: one informative-set step per entry of `steps`, enqueued as one chain.  A step is a dict:
         start, partner [m], y [m], rho_partner [m], rho_start, scale, rho_lambda (< 0 leaves lambda alone)"""
-        ns = len(steps)
-        parts = [np.ascontiguousarray(s["partner"], dtype=np.uint32).reshape(-1) for s in steps]
-        off = np.zeros(ns + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([p.shape[0] for p in parts])
-
-        def cat(key, dtype):
-            a = [np.ascontiguousarray(s[key], dtype=dtype).reshape(-1) for s in steps]
-            assert all(x.shape == p.shape for x, p in zip(a, parts))
-            return np.ascontiguousarray(np.concatenate(a) if a else np.zeros(0), dtype=dtype)
-
-        partner, y, rp = cat("partner", np.uint32), cat("y", np.uint8), cat("rho_partner", np.float64)
-        start = np.array([s["start"] for s in steps], dtype=np.uint32)
-        rs, sc, rl = (np.array([s[key] for s in steps], dtype=np.float64) for key in ("rho_start", "scale", "rho_lambda"))
-        _chk(load().svils_batch_step_star(self._h, ns, start.ctypes.data, off.ctypes.data, partner.ctypes.data, y.ctypes.data,
+        start, off, (partner, y, rp), (rs, sc, rl) = self._star_lists(
+            steps, (("partner", np.uint32), ("y", np.uint8), ("rho_partner", np.float64)), ("rho_start", "scale", "rho_lambda"))
+        _chk(load().svils_batch_step_star(self._h, len(steps), start.ctypes.data, off.ctypes.data, partner.ctypes.data, y.ctypes.data,
                                           rp.ctypes.data, rs.ctypes.data, sc.ctypes.data, rl.ctypes.data))
 
     def step_strat(self, steps):
         """svils_batch_step_strat: one stratified random node step per entry of `steps`, enqueued.  A step is a dict: start,
         partner [m], y [m], rho_gamma, scale, rho_lambda (< 0 leaves lambda alone).  Every row of gamma moves"""
-        ns = len(steps)
-        parts = [np.ascontiguousarray(s["partner"], dtype=np.uint32).reshape(-1) for s in steps]
-        ys = [np.ascontiguousarray(s["y"], dtype=np.uint8).reshape(-1) for s in steps]
-        assert all(a.shape == b.shape for a, b in zip(parts, ys))
-        off = np.zeros(ns + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([p.shape[0] for p in parts])
-        partner = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=np.uint32)
-        y = np.ascontiguousarray(np.concatenate(ys) if ys else np.zeros(0), dtype=np.uint8)
-        start = np.array([s["start"] for s in steps], dtype=np.uint32)
-        rg, sc, rl = (np.array([s[key] for s in steps], dtype=np.float64) for key in ("rho_gamma", "scale", "rho_lambda"))
-        _chk(load().svils_batch_step_strat(self._h, ns, start.ctypes.data, off.ctypes.data, partner.ctypes.data, y.ctypes.data,
+        start, off, (partner, y), (rg, sc, rl) = self._star_lists(
+            steps, (("partner", np.uint32), ("y", np.uint8)), ("rho_gamma", "scale", "rho_lambda"))
+        _chk(load().svils_batch_step_strat(self._h, len(steps), start.ctypes.data, off.ctypes.data, partner.ctypes.data, y.ctypes.data,
                                            rg.ctypes.data, sc.ctypes.data, rl.ctypes.data))
 
     def lag(self):

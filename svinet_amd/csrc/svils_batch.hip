@@ -52,8 +52,11 @@
 //                           (tile, wavefront)
 //   k_batch_elbo_nodes      one wavefront per node: the node's term
 //   k_batch_elbo_reduce     one block: the lambda terms, and the three sums in a fixed order
+#include <cassert>
+
 #include "svils_devutil.h"
 #include "svils_elbo.h"
+#include "svils_steplists.h"
 #include "svils_tool.h"
 #include "svils_waveutil.h"
 
@@ -504,7 +507,26 @@ __global__ __launch_bounds__(256) void k_batch_elbo_reduce(uint64_t nent, const 
 
 // ---- sampled-pair steps (svils_batch_step_node / svils_batch_step_pairs) ----------------------
 
+// Elogpi of the row a group holds in registers (0 on the lanes past K): psi(g) - psi(row sum), the sum by group_sum
+template <int W, int V>
+__device__ __forceinline__ void row_elogpi(const double (&g)[V], const bool (&kval)[V], bool row_ok, const double2 *logtab,
+                                           double (&el)[V]) {
+  double s = 0.0;
+#pragma unroll
+  for (int v = 0; v < V; ++v) s += g[v];
+  s = group_sum<W>(s);
+  const double ps = digamma(row_ok ? s : 1.0, logtab);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const bool ok = row_ok && kval[v];
+    const double d = digamma(ok ? g[v] : 1.0, logtab) - ps;
+    el[v] = ok ? d : 0.0;
+  }
+}
+
 // a group's new row: gamma = (1 - rho) gamma + rho (alpha + scale t), then Elogpi of it.  Only groups with row < n store.
+// The arithmetic of row_elogpi, written out: each Elogpi is stored as it is formed.  Through row_elogpi the four stay live
+// together, and k_batch_step_rows goes from 50 to 74 VGPRs, a step down in occupancy (profiles/r25a_batch_steps.md)
 template <int W, int V>
 __device__ __forceinline__ void blend_row(bool row_ok, size_t row, uint32_t K, uint32_t lw, const bool (&kval)[V], const double (&t)[V],
                                           double rho, double alpha, double scale, double *__restrict__ gamma, double *__restrict__ elogpi,
@@ -529,6 +551,28 @@ __device__ __forceinline__ void blend_row(bool row_ok, size_t row, uint32_t K, u
     }
   }
 }
+
+// What wavefront wv hands to the tail for community k, from inside the caller's loop over its V values: its groups'
+// phi_a (WITH_A: to part_a [wavefront][K]) and lambda terms (to pl [wavefront][K][2], y = 1 first), each summed over the
+// groups in cross_group_sum's fixed order.  A group without a pair comes with zeros.  One value at a time, so that the
+// caller's other stores of that value stay in the same loop: as a loop of its own behind them it cost k_batch_step_phi 1 %
+// and k_batch_strat_pairs 1.5-3 % (profiles/r25a_batch_steps.md)
+template <int W, bool WITH_A>
+__device__ __forceinline__ void wave_partial(double pa, double pj, bool y, bool kval, uint32_t g, uint32_t k, uint32_t wv, uint32_t K,
+                                             double *part_a, double *pl) {
+  const double pp = pa * pj;
+  double sa = 0.0;
+  if constexpr (WITH_A) sa = cross_group_sum<W>(pa);
+  const double t0 = cross_group_sum<W>(y ? pp : 0.0), t1 = cross_group_sum<W>(y ? 0.0 : pp);
+  if (g == 0 && kval) {
+    if constexpr (WITH_A) part_a[(size_t)wv * K + k] = sa;
+    pl[((size_t)wv * K + k) * 2] = t0;
+    pl[((size_t)wv * K + k) * 2 + 1] = t1;
+  }
+}
+
+// a stored row value at its true value (strat steps, below): f == 1 exactly (a row that is not behind) keeps its bits
+__device__ __forceinline__ double caught_up(double g, double alpha, double f) { return f == 1.0 ? g : alpha + (g - alpha) * f; }
 
 struct StepArgs {
   uint32_t n, K, nw;
@@ -588,17 +632,7 @@ __global__ __launch_bounds__(256) void k_batch_step_node(StepArgs x) {
   }
   blend_row<W, V>(row_ok, j, K, lw, kval, pj, x.rho, x.alpha, x.scale, x.gamma, x.elogpi, logtab);
 #pragma unroll
-  for (int v = 0; v < V; ++v) {
-    const double pp = pa[v] * pj[v];
-    const double sa = cross_group_sum<W>(pa[v]);
-    const double t0 = cross_group_sum<W>(y ? pp : 0.0), t1 = cross_group_sum<W>(y ? 0.0 : pp);
-    if (g == 0 && kval[v]) {
-      const uint32_t k = v * W + lw;
-      x.part_a[(size_t)wv * K + k] = sa;
-      x.pl[((size_t)wv * K + k) * 2] = t0;
-      x.pl[((size_t)wv * K + k) * 2 + 1] = t1;
-    }
-  }
+  for (int v = 0; v < V; ++v) wave_partial<W, true>(pa[v], pj[v], y, kval[v], g, v * W + lw, wv, K, x.part_a, x.pl);
   const bool cnt = valid && lw == 0;
   count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt ? under : 0);
 }
@@ -638,12 +672,7 @@ __global__ __launch_bounds__(256) void k_batch_step_phi(StepArgs x) {
       x.phi[(2 * (size_t)e) * K + k] = q1;
       x.phi[(2 * (size_t)e + 1) * K + k] = q2;
     }
-    const double pp = q1 * q2;
-    const double t0 = cross_group_sum<W>(y ? pp : 0.0), t1 = cross_group_sum<W>(y ? 0.0 : pp);
-    if (g == 0 && kval[v]) {
-      x.pl[((size_t)wv * K + k) * 2] = t0;
-      x.pl[((size_t)wv * K + k) * 2 + 1] = t1;
-    }
+    wave_partial<W, false>(q1, q2, y, kval[v], g, k, wv, K, nullptr, x.pl);
   }
   const bool cnt = valid && lw == 0;
   count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt ? under : 0);
@@ -717,27 +746,7 @@ __global__ __launch_bounds__(256) void k_batch_step_tail(uint32_t K, uint32_t nw
 // FastAMM2::infer (src/fastamm2.cc:565-640): a step is a star, but EVERY row of gamma moves -- the rows of the star towards
 // alpha + scale phi, all others a step rho towards alpha.  The others are not written: gamma_i - alpha of an untouched row
 // is multiplied by (1 - rho_s) at every step, so the host keeps the running c = sum log1p(-rho_s) and per row the c of its
-// last write, and a row is caught up with the one factor f = exp(c - c_i) when it is next read.
-
-// a stored row value at its true value; f == 1 exactly (a row that is not behind) keeps its bits
-__device__ __forceinline__ double caught_up(double g, double alpha, double f) { return f == 1.0 ? g : alpha + (g - alpha) * f; }
-
-// Elogpi of the row a group holds in registers (0 on the lanes past K): psi(g) - psi(row sum), the sum by group_sum
-template <int W, int V>
-__device__ __forceinline__ void row_elogpi(const double (&g)[V], const bool (&kval)[V], bool row_ok, const double2 *logtab,
-                                           double (&el)[V]) {
-  double s = 0.0;
-#pragma unroll
-  for (int v = 0; v < V; ++v) s += g[v];
-  s = group_sum<W>(s);
-  const double ps = digamma(row_ok ? s : 1.0, logtab);
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    const bool ok = row_ok && kval[v];
-    const double d = digamma(ok ? g[v] : 1.0, logtab) - ps;
-    el[v] = ok ? d : 0.0;
-  }
-}
+// last write, and a row is caught up (caught_up, above) with the one factor f = exp(c - c_i) when it is next read.
 
 struct StratArgs {
   uint32_t K, m, a;                 // entries of the step, its start node
@@ -791,14 +800,7 @@ __global__ __launch_bounds__(256) void k_batch_strat_pairs(StratArgs x) {
     pa[v] = valid ? pa[v] : 0.0;
     pj[v] = valid ? pj[v] : 0.0;
     if (valid && kval[v]) x.gamma[(size_t)j * K + k] = (1.0 - x.rho) * gj[v] + x.rho * (x.alpha + x.scale * pj[v]);
-    const double pp = pa[v] * pj[v];
-    const double sa = cross_group_sum<W>(pa[v]);
-    const double t0 = cross_group_sum<W>(y ? pp : 0.0), t1 = cross_group_sum<W>(y ? 0.0 : pp);
-    if (g == 0 && kval[v]) {
-      x.part_a[(size_t)wv * K + k] = sa;
-      x.pl[((size_t)wv * K + k) * 2] = t0;
-      x.pl[((size_t)wv * K + k) * 2 + 1] = t1;
-    }
+    wave_partial<W, true>(pa[v], pj[v], y, kval[v], g, k, wv, K, x.part_a, x.pl);
   }
   const bool cnt = valid && lw == 0;
   count_pairs(x.ctr, lane, cnt, cnt ? rounds : 0, cnt ? rounds : 0, cnt ? under : 0);
@@ -998,10 +1000,12 @@ struct svils_batch : ToolHandle {
   double *ll_out = nullptr;
   uint32_t ntiles = 0, nrb = 0, batch = 0;                        // batch: tiles per launch
   std::vector<uint32_t> h_tiles;
-  bool have_graph = false, have_state = false, timed = false;
+  bool have_graph = false, have_state = false;
+  // the last timed call: a sweep (ev[0] .. and the launches' events), a step call (ev[0] .. ev[1] bracket it), svils_batch_elbo
+  // (ev_elbo; the sweep's events are as they were)
+  enum class Timed { NONE, SWEEP, STEPS, ELBO } timed = Timed::NONE;
   uint32_t nlaunch = 0;                                           // launches of the last sweep
   // sampled-pair steps.  HANDLE scope, grown on demand: the per-wavefront partials, one step's phi, a call's lists
-  bool timed_steps = false;                                       // the last timed call was a step call: ev[0] .. ev[1] bracket it
   bool elog_fresh = false;                                        // Elogpi / Elogbeta are those of gamma / lambda
   std::vector<uint32_t> h_skip;                                   // the skip bits, to refuse a listed skipped pair
   std::vector<uint32_t> h_adj;                                    // the link bits, to refuse a star entry whose y disagrees: fetched by the first star call
@@ -1026,7 +1030,6 @@ struct svils_batch : ToolHandle {
   double *el_node = nullptr, *el_out = nullptr;                   // HANDLE scope: [n], [4]
   unsigned long long *el_ctr = nullptr;                           // HANDLE scope: [5]
   hipEvent_t ev_elbo[2] = {nullptr, nullptr};                     // the bracket of the last pass
-  bool timed_elbo = false;                                        // the last timed call was svils_batch_elbo
 };
 
 namespace {
@@ -1120,8 +1123,7 @@ int one_sweep(svils_batch *h) {
   h->nlaunch = b;
   std::swap(h->gamma, h->gnext);   // gamma = gamma_next (:883-886); later launches take the new pointers
   std::swap(h->lam, h->lnext);
-  h->timed = true;
-  h->timed_steps = h->timed_elbo = false;
+  h->timed = svils_batch::Timed::SWEEP;
   h->elog_fresh = h->elogbeta_fresh = false;
   return 0;
 }
@@ -1156,27 +1158,107 @@ int begin_steps(svils_batch *h) {
 
 int end_steps(svils_batch *h) {
   HIPCHK(hipEventRecord(h->ev[1], h->st));
-  h->timed = h->timed_steps = true;
-  h->timed_elbo = false;
+  h->timed = svils_batch::Timed::STEPS;
   return 0;
 }
 
-// the pinned staging area for a call's lists, nwords uint32 wide: free again once the previous call's copy has left it
-int reserve_pin(svils_batch *h, size_t nwords) {
-  if (h->copy_pending) {
-    HIPCHK(hipEventSynchronize(h->ev_copy));
-    h->copy_pending = false;
+// What the star entry points (svils_batch_step_star, _step_strat) check of their entries: the partner a node other than
+// the start, listed once in its step (seen[j] = s + 1: one owner per row), the pair outside the skip set, y the graph's
+// link bit, and rho_partner, where the steps have one per entry, in (0, 1].  The link bits come back from the device once
+// per graph, for handles that take such steps
+int check_star_entries(svils_batch *h, const char *name, uint32_t nsteps, const uint32_t *start, const uint64_t *off,
+                       const uint32_t *partner, const uint8_t *y, const double *rho_partner) {
+  const uint32_t n = h->n;
+  if (off[nsteps] && h->h_adj.empty()) {
+    std::vector<uint32_t> bits((size_t)n * h->nw);
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipMemcpy(bits.data(), h->adj, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    h->h_adj.swap(bits);
   }
-  if (!h->ev_copy) HIPCHK(hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
-  if (nwords > h->cap_pin) {
-    if (h->pin) (void)hipHostFree(h->pin);
-    h->pin = nullptr;
-    h->cap_pin = 0;
-    HIPCHK(hipHostMalloc((void **)&h->pin, nwords * sizeof(uint32_t), hipHostMallocDefault));
-    h->cap_pin = nwords;
-  }
+  std::vector<uint32_t> seen(n, 0);
+  for (uint32_t s = 0; s < nsteps; ++s)
+    for (uint64_t e = off[s]; e < off[s + 1]; ++e) {
+      const uint32_t a = start[s], j = partner[e];
+      const unsigned long long x = e - off[s];
+      if (j >= n || j == a) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u pairs node %u with %u (n = %u)", name, x, s, a, j, n);
+      if (seen[j] == s + 1) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u lists partner %u twice", name, x, s, j);
+      seen[j] = s + 1;
+      const uint32_t p = std::min(a, j), q = std::max(a, j), bit = 1u << (q & 31);
+      const size_t wd = (size_t)p * h->nw + (q >> 5);
+      if (h->h_skip[wd] & bit) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) is in the skip set", name, x, s, p, q);
+      if (((h->h_adj[wd] & bit) != 0) != (y[e] != 0))
+        return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) has y = %u, the graph says otherwise", name, x, s, p, q, (unsigned)y[e]);
+      if (rho_partner && !(rho_partner[e] > 0.0 && rho_partner[e] <= 1.0))
+        return fail(SVILS_ERR_ARG, "%s: rho_partner of entry %llu of step %u is not in (0, 1]", name, x, s);
+    }
   return 0;
 }
+
+// A call's lists on their way to the device: typed segments, back to back in the pinned staging area and, after ONE async
+// copy, at the same offsets in st_lists, so that the call need not wait for it.  A call declares its segments with add(),
+// open()s the pinned area (its host arrays are copied in; a segment without one is the caller's to fill through pinned()),
+// send()s it and takes the device pointers.
+// THE ALIGNMENT RULE: doubles are declared first, then 32-bit words, then bytes.  Both areas start aligned for a double
+// and offsets are kept in 32-bit words, so every segment then starts at a multiple of its element size; bytes, which come
+// last, are rounded up to whole words.  add() asserts the order; the library is built without NDEBUG (build.py), so the
+// assert is there in the product build too.
+class Staging {
+ public:
+  template <class T>
+  struct Seg {
+    size_t at;   // in 32-bit words
+  };
+  explicit Staging(svils_batch *h) : h_(h) {}
+  template <class T>
+  Seg<T> add(const T *src, size_t count) {
+    assert(sizeof(T) <= elem_);
+    elem_ = sizeof(T);
+    segs_.push_back({src, count * sizeof(T), nwords_});
+    nwords_ += (count * sizeof(T) + 3) / 4;
+    return {segs_.back().at};
+  }
+  // the pinned area: free again once the previous call's copy has left it
+  int open() {
+    svils_batch *h = h_;
+    if (h->copy_pending) {
+      HIPCHK(hipEventSynchronize(h->ev_copy));
+      h->copy_pending = false;
+    }
+    if (!h->ev_copy) HIPCHK(hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
+    if (nwords_ > h->cap_pin) {
+      if (h->pin) (void)hipHostFree(h->pin);
+      h->pin = nullptr;
+      h->cap_pin = 0;
+      HIPCHK(hipHostMalloc((void **)&h->pin, nwords_ * sizeof(uint32_t), hipHostMallocDefault));
+      h->cap_pin = nwords_;
+    }
+    for (const Segment &s : segs_)
+      if (s.src && s.bytes) std::memcpy(h->pin + s.at, s.src, s.bytes);
+    return 0;
+  }
+  // ordered behind the steps of earlier calls, which read the device copy, by the stream
+  int send() {
+    svils_batch *h = h_;
+    if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_lists, nwords_)) return rc;
+    HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nwords_ * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipEventRecord(h->ev_copy, h->st));
+    h->copy_pending = true;
+    return 0;
+  }
+  template <class T>
+  T *pinned(Seg<T> s) const { return reinterpret_cast<T *>(h_->pin + s.at); }
+  template <class T>
+  const T *device(Seg<T> s) const { return reinterpret_cast<const T *>(h_->st_lists + s.at); }
+
+ private:
+  struct Segment {
+    const void *src;
+    size_t bytes, at;
+  };
+  svils_batch *h_;
+  std::vector<Segment> segs_;
+  size_t nwords_ = 0, elem_ = sizeof(double);
+};
 
 StepArgs step_args(svils_batch *h, double scale, double rho) {
   StepArgs x{};
@@ -1324,7 +1406,7 @@ int svils_batch_set_graph(svils_batch *h, const uint32_t *links, uint64_t nlinks
   h->nrb = nrb;
   h->batch = batch;
   h->have_graph = true;
-  h->timed = h->timed_elbo = false;
+  h->timed = svils_batch::Timed::NONE;
   return 0;
 }
 
@@ -1405,16 +1487,8 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
   if (nsteps && (!off || !scale || !rho_gamma || !rho_lambda)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
   if (!nsteps) return 0;
   if (int rc = check_steps(h, name, nsteps, rho_gamma, rho_lambda)) return rc;
-  if (off[0] != 0) return fail(SVILS_ERR_ARG, "%s: off[0] is not 0", name);
-  uint64_t most = 0;
-  for (uint32_t s = 0; s < nsteps; ++s) {
-    if (off[s + 1] < off[s]) return fail(SVILS_ERR_ARG, "%s: off[%u] decreases", name, s + 1);
-    if (!(scale[s] > 0.0) || !std::isfinite(scale[s])) return fail(SVILS_ERR_ARG, "%s: scale[%u] is not a positive number", name, s);
-    most = std::max(most, off[s + 1] - off[s]);
-  }
-  const uint64_t total = off[nsteps];
-  if (total && !pairs) return fail(SVILS_ERR_ARG, "%s: null argument", name);
-  if (total >= ((uint64_t)1 << 30)) return fail(SVILS_ERR_UNSUPPORTED, "%s: more than 2^30 pairs in one call", name);
+  uint64_t total, most;
+  if (int rc = check_step_lists(name, "pairs", h->n, nsteps, off, scale, nullptr, nullptr, pairs != nullptr, &total, &most)) return rc;
   const uint32_t n = h->n, K = h->k, G = 64 / h->w;
   // checked before anything is enqueued
   for (uint32_t s = 0; s < nsteps; ++s)
@@ -1426,12 +1500,12 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
         return fail(SVILS_ERR_ARG, "%s: pair %llu of step %u (%u, %u) is in the skip set", name, (unsigned long long)(e - off[s]), s, p, q);
     }
   if (int rc = catch_up(h)) return rc;
-  // the call's lists go through pinned memory in one copy, so that the call need not wait for it; the staging area is
-  // free again once the previous call's copy has left it
-  const size_t nlists = 4 * (size_t)total + (size_t)nsteps * (n + 1);
-  if (int rc = reserve_pin(h, nlists)) return rc;
-  uint32_t *const pin_pairs = h->pin, *const pin_ent = h->pin + 2 * total, *const pin_noff = h->pin + 4 * total;
-  if (total) std::memcpy(pin_pairs, pairs, 2 * total * sizeof(uint32_t));
+  // the call's lists: pairs [total][2], entries [2 total], offsets [nsteps][n + 1] -- the last two written where they are staged
+  Staging lists(h);
+  const auto s_pairs = lists.add(pairs, 2 * (size_t)total);
+  const auto s_ent = lists.add<uint32_t>(nullptr, 2 * (size_t)total), s_noff = lists.add<uint32_t>(nullptr, (size_t)nsteps * (n + 1));
+  if (int rc = lists.open()) return rc;
+  uint32_t *const pin_ent = lists.pinned(s_ent), *const pin_noff = lists.pinned(s_noff);
   std::memset(pin_noff, 0, (size_t)nsteps * (n + 1) * sizeof(uint32_t));
   // every node's (pair, side) entries of a step in list order: a counting sort per step
   for (uint32_t s = 0; s < nsteps; ++s) {
@@ -1453,19 +1527,15 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
   const uint32_t nwv_most = 4 * blocks(std::max<uint64_t>(most, 1), 4 * G);
   if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_pl, (size_t)nwv_most * K * 2)) return rc;
   if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_phi, 2 * (size_t)most * K)) return rc;
-  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_lists, nlists)) return rc;
-  // ordered behind the steps of earlier calls, which read the device copy, by the stream
-  HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nlists * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
-  HIPCHK(hipEventRecord(h->ev_copy, h->st));
-  h->copy_pending = true;
+  if (int rc = lists.send()) return rc;
   if (int rc = begin_steps(h)) return rc;
   for (uint32_t s = 0; s < nsteps; ++s) {
     const uint32_t m = (uint32_t)(off[s + 1] - off[s]);
     StepArgs x = step_args(h, scale[s], rho_gamma[s]);
     x.m = m;
-    x.pairs = h->st_lists + 2 * off[s];
-    x.ent = h->st_lists + 2 * total + 2 * off[s];
-    x.noff = h->st_lists + 4 * total + (size_t)s * (n + 1);
+    x.pairs = lists.device(s_pairs) + 2 * off[s];
+    x.ent = lists.device(s_ent) + 2 * off[s];
+    x.noff = lists.device(s_noff) + (size_t)s * (n + 1);
     x.phi = h->st_phi;
     const uint32_t nb = blocks(m, 4 * G);
     if (int rc = launch_for_width(h, name, [&](auto w) {
@@ -1510,62 +1580,22 @@ int svils_batch_step_star(svils_batch *h, uint32_t nsteps, const uint32_t *start
   if (nsteps && (!start || !off || !rho_start || !scale || !rho_lambda)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
   if (!nsteps) return 0;
   if (int rc = check_steps(h, name, nsteps, rho_start, rho_lambda)) return rc;
-  if (off[0] != 0) return fail(SVILS_ERR_ARG, "%s: off[0] is not 0", name);
-  for (uint32_t s = 0; s < nsteps; ++s) {
-    if (off[s + 1] < off[s]) return fail(SVILS_ERR_ARG, "%s: off[%u] decreases", name, s + 1);
-    if (!(scale[s] > 0.0) || !std::isfinite(scale[s])) return fail(SVILS_ERR_ARG, "%s: scale[%u] is not a positive number", name, s);
-    if (start[s] >= h->n) return fail(SVILS_ERR_ARG, "%s: start[%u] = %u is not < n = %u", name, s, start[s], h->n);
-  }
-  const uint64_t total = off[nsteps];
-  if (total && (!partner || !y || !rho_partner)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
-  if (total >= ((uint64_t)1 << 30)) return fail(SVILS_ERR_UNSUPPORTED, "%s: more than 2^30 entries in one call", name);
-  const uint32_t n = h->n, K = h->k;
-  if (total && h->h_adj.empty()) {   // the link bits come back once per graph, for handles that take star steps
-    std::vector<uint32_t> bits((size_t)n * h->nw);
-    HIPCHK(hipStreamSynchronize(h->st));
-    HIPCHK(hipMemcpy(bits.data(), h->adj, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    h->h_adj.swap(bits);
-  }
-  // checked before anything is enqueued; seen[j] = s + 1: j is a partner of step s already (one owner per row)
-  std::vector<uint32_t> seen(n, 0);
-  for (uint32_t s = 0; s < nsteps; ++s)
-    for (uint64_t e = off[s]; e < off[s + 1]; ++e) {
-      const uint32_t a = start[s], j = partner[e];
-      const unsigned long long x = e - off[s];
-      if (j >= n || j == a) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u pairs node %u with %u (n = %u)", name, x, s, a, j, n);
-      if (seen[j] == s + 1) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u lists partner %u twice", name, x, s, j);
-      seen[j] = s + 1;
-      const uint32_t p = std::min(a, j), q = std::max(a, j), bit = 1u << (q & 31);
-      const size_t wd = (size_t)p * h->nw + (q >> 5);
-      if (h->h_skip[wd] & bit) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) is in the skip set", name, x, s, p, q);
-      if (((h->h_adj[wd] & bit) != 0) != (y[e] != 0))
-        return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) has y = %u, the graph says otherwise", name, x, s, p, q, (unsigned)y[e]);
-      if (!(rho_partner[e] > 0.0 && rho_partner[e] <= 1.0))
-        return fail(SVILS_ERR_ARG, "%s: rho_partner of entry %llu of step %u is not in (0, 1]", name, x, s);
-    }
+  uint64_t total, most;
+  if (int rc = check_step_lists(name, "entries", h->n, nsteps, off, scale, start, nullptr, partner && y && rho_partner, &total, &most)) return rc;
+  if (int rc = check_star_entries(h, name, nsteps, start, off, partner, y, rho_partner)) return rc;
   if (int rc = catch_up(h)) return rc;
-  // the call's lists in one copy through the pinned staging area, doubles first: rho_partner [total], rho_start, scale,
-  // rho_lambda [nsteps] each; then off [nsteps + 1] (as uint32), start [nsteps], partner [total]; then y [total] bytes
-  const size_t ndbl = (size_t)total + 3 * (size_t)nsteps;
-  const size_t nwords = 2 * ndbl + (size_t)nsteps + 1 + nsteps + (size_t)total + ((size_t)total + 3) / 4;
-  if (int rc = reserve_pin(h, nwords)) return rc;
-  double *const pd = reinterpret_cast<double *>(h->pin);
-  uint32_t *const pu = h->pin + 2 * ndbl;
-  if (total) std::memcpy(pd, rho_partner, total * sizeof(double));
-  std::memcpy(pd + total, rho_start, nsteps * sizeof(double));
-  std::memcpy(pd + total + nsteps, scale, nsteps * sizeof(double));
-  std::memcpy(pd + total + 2 * (size_t)nsteps, rho_lambda, nsteps * sizeof(double));
-  for (uint32_t s = 0; s <= nsteps; ++s) pu[s] = (uint32_t)off[s];
-  std::memcpy(pu + nsteps + 1, start, nsteps * sizeof(uint32_t));
-  if (total) std::memcpy(pu + 2 * (size_t)nsteps + 1, partner, total * sizeof(uint32_t));
-  if (total) std::memcpy(pu + 2 * (size_t)nsteps + 1 + total, y, total);
-  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_lists, nwords)) return rc;
-  HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nwords * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
-  HIPCHK(hipEventRecord(h->ev_copy, h->st));
-  h->copy_pending = true;
+  // the call's lists; off travels as uint32
+  Staging lists(h);
+  const auto s_rp = lists.add(rho_partner, total), s_rs = lists.add(rho_start, nsteps), s_sc = lists.add(scale, nsteps),
+             s_rl = lists.add(rho_lambda, nsteps);
+  const auto s_off = lists.add<uint32_t>(nullptr, (size_t)nsteps + 1), s_start = lists.add(start, nsteps), s_partner = lists.add(partner, total);
+  const auto s_y = lists.add(y, total);
+  if (int rc = lists.open()) return rc;
+  for (uint32_t s = 0; s <= nsteps; ++s) lists.pinned(s_off)[s] = (uint32_t)off[s];
+  if (int rc = lists.send()) return rc;
   if (int rc = begin_steps(h)) return rc;
   StarArgs x{};
-  x.K = K;
+  x.K = h->k;
   x.gamma = h->gamma;
   x.elogpi = h->elogpi;
   x.lam = h->lam;
@@ -1575,16 +1605,14 @@ int svils_batch_step_star(svils_batch *h, uint32_t nsteps, const uint32_t *start
   x.alpha = h->alpha;
   x.eta0 = h->eta0;
   x.eta1 = h->eta1;
-  const double *dd = reinterpret_cast<const double *>(h->st_lists);
-  const uint32_t *du = h->st_lists + 2 * ndbl;
-  x.rho_partner = dd;
-  x.rho_start = dd + total;
-  x.scale = dd + total + nsteps;
-  x.rho_lambda = dd + total + 2 * (size_t)nsteps;
-  x.off = du;
-  x.start = du + nsteps + 1;
-  x.partner = du + 2 * (size_t)nsteps + 1;
-  x.y = reinterpret_cast<const uint8_t *>(du + 2 * (size_t)nsteps + 1 + total);
+  x.rho_partner = lists.device(s_rp);
+  x.rho_start = lists.device(s_rs);
+  x.scale = lists.device(s_sc);
+  x.rho_lambda = lists.device(s_rl);
+  x.off = lists.device(s_off);
+  x.start = lists.device(s_start);
+  x.partner = lists.device(s_partner);
+  x.y = lists.device(s_y);
   x.ctr = h->ctr;
   // a chain is cut into launches of at most star_chain steps: no kernel runs long, and a step does the same wherever the cut falls
   for (uint32_t s0 = 0; s0 < nsteps; s0 += h->star_chain) {
@@ -1606,65 +1634,32 @@ int svils_batch_step_strat(svils_batch *h, uint32_t nsteps, const uint32_t *star
   if (nsteps && (!start || !off || !rho_gamma || !scale || !rho_lambda)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
   if (!nsteps) return 0;
   if (int rc = check_steps(h, name, nsteps, rho_gamma, rho_lambda)) return rc;
-  if (off[0] != 0) return fail(SVILS_ERR_ARG, "%s: off[0] is not 0", name);
-  uint64_t most = 0;
-  for (uint32_t s = 0; s < nsteps; ++s) {
-    if (!(rho_gamma[s] < 1.0)) return fail(SVILS_ERR_ARG, "%s: rho_gamma[%u] is not in (0, 1) (log1p(-1) has no value)", name, s);
-    if (off[s + 1] < off[s]) return fail(SVILS_ERR_ARG, "%s: off[%u] decreases", name, s + 1);
-    if (!(scale[s] > 0.0) || !std::isfinite(scale[s])) return fail(SVILS_ERR_ARG, "%s: scale[%u] is not a positive number", name, s);
-    if (start[s] >= h->n) return fail(SVILS_ERR_ARG, "%s: start[%u] = %u is not < n = %u", name, s, start[s], h->n);
-    most = std::max(most, off[s + 1] - off[s]);
-  }
-  const uint64_t total = off[nsteps];
-  if (total && (!partner || !y)) return fail(SVILS_ERR_ARG, "%s: null argument", name);
-  if (total >= ((uint64_t)1 << 30)) return fail(SVILS_ERR_UNSUPPORTED, "%s: more than 2^30 entries in one call", name);
-  const uint32_t n = h->n, K = h->k, G = 64 / h->w;
-  if (total && h->h_adj.empty()) {   // as svils_batch_step_star: the link bits come back once per graph
-    std::vector<uint32_t> bits((size_t)n * h->nw);
-    HIPCHK(hipStreamSynchronize(h->st));
-    HIPCHK(hipMemcpy(bits.data(), h->adj, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    h->h_adj.swap(bits);
-  }
-  // Checked before anything is enqueued, and in the same pass the factor of every row the call reads: the decay runs on
-  // copies, which replace the handle's once the whole call has passed.  c takes one addition per step, in step order
-  std::vector<uint32_t> seen(n, 0);
+  uint64_t total, most;
+  if (int rc = check_step_lists(name, "entries", h->n, nsteps, off, scale, start, rho_gamma, partner && y, &total, &most)) return rc;
+  if (int rc = check_star_entries(h, name, nsteps, start, off, partner, y, nullptr)) return rc;
+  // The call is accepted.  What catches up every row it reads, on COPIES of the handle's bookkeeping, which replace it
+  // below: c takes one log1p(-rho) per step, in step order, and a step's factors come from row_c as it stood before the step
+  const uint32_t K = h->k, G = 64 / h->w;
   std::vector<double> row_c(h->row_c), fj((size_t)total), fa(nsteps);
   double c = h->lag_c;
   for (uint32_t s = 0; s < nsteps; ++s) {
-    const uint32_t a = start[s];
-    fa[s] = std::exp(c - row_c[a]);
-    for (uint64_t e = off[s]; e < off[s + 1]; ++e) {
-      const uint32_t j = partner[e];
-      const unsigned long long x = e - off[s];
-      if (j >= n || j == a) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u pairs node %u with %u (n = %u)", name, x, s, a, j, n);
-      if (seen[j] == s + 1) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u lists partner %u twice", name, x, s, j);
-      seen[j] = s + 1;
-      const uint32_t p = std::min(a, j), q = std::max(a, j), bit = 1u << (q & 31);
-      const size_t wd = (size_t)p * h->nw + (q >> 5);
-      if (h->h_skip[wd] & bit) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) is in the skip set", name, x, s, p, q);
-      if (((h->h_adj[wd] & bit) != 0) != (y[e] != 0))
-        return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) has y = %u, the graph says otherwise", name, x, s, p, q, (unsigned)y[e]);
-      fj[e] = std::exp(c - row_c[j]);
-    }
+    fa[s] = std::exp(c - row_c[start[s]]);
+    for (uint64_t e = off[s]; e < off[s + 1]; ++e) fj[e] = std::exp(c - row_c[partner[e]]);
     c += std::log1p(-rho_gamma[s]);
-    row_c[a] = c;
+    row_c[start[s]] = c;
     for (uint64_t e = off[s]; e < off[s + 1]; ++e) row_c[partner[e]] = c;
   }
-  // the call's lists in one copy through the pinned staging area: fj [total] doubles, partner [total], y [total] bytes
-  const size_t nwords = 2 * (size_t)total + (size_t)total + ((size_t)total + 3) / 4;
+  // the call's lists; a call without entries sends nothing
+  Staging lists(h);
+  const auto s_fj = lists.add(fj.data(), total);
+  const auto s_partner = lists.add(partner, total);
+  const auto s_y = lists.add(y, total);
   const uint32_t nwv_most = 4 * blocks(most, 4 * G);
-  if (int rc = reserve_pin(h, nwords)) return rc;
+  if (int rc = lists.open()) return rc;
   if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_part, (size_t)nwv_most * K)) return rc;
   if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_pl, (size_t)nwv_most * K * 2)) return rc;
-  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_lists, nwords)) return rc;
-  if (total) {
-    std::memcpy(h->pin, fj.data(), total * sizeof(double));
-    std::memcpy(h->pin + 2 * total, partner, total * sizeof(uint32_t));
-    std::memcpy(h->pin + 3 * total, y, total);
-    HIPCHK(hipMemcpyAsync(h->st_lists, h->pin, nwords * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
-    HIPCHK(hipEventRecord(h->ev_copy, h->st));
-    h->copy_pending = true;
-  }
+  if (total)
+    if (int rc = lists.send()) return rc;
   if (!h->elogbeta_fresh) {   // Elogbeta of the current lambda; Elogpi is formed per row in the step's registers
     hipLaunchKernelGGL(k_batch_beta, dim3(blocks(K, 256)), dim3(256), 0, h->st, K, h->lam, h->gtab, h->elogbeta);
     HIPCHK(hipGetLastError());
@@ -1687,16 +1682,13 @@ int svils_batch_step_strat(svils_batch *h, uint32_t nsteps, const uint32_t *star
   x.pl = h->st_pl;
   x.ctr = h->ctr;
   x.gtab = h->gtab;
-  const double *dfj = reinterpret_cast<const double *>(h->st_lists);
-  const uint32_t *dpartner = h->st_lists + 2 * total;
-  const uint8_t *dy = reinterpret_cast<const uint8_t *>(h->st_lists + 3 * total);
   for (uint32_t s = 0; s < nsteps; ++s) {
     const uint32_t m = (uint32_t)(off[s + 1] - off[s]), nb = blocks(m, 4 * G);
     x.m = m;
     x.a = start[s];
-    x.partner = dpartner + off[s];
-    x.y = dy + off[s];
-    x.fj = dfj + off[s];
+    x.partner = lists.device(s_partner) + off[s];
+    x.y = lists.device(s_y) + off[s];
+    x.fj = lists.device(s_fj) + off[s];
     x.fa = fa[s];
     x.scale = scale[s];
     x.rho = rho_gamma[s];
@@ -1786,7 +1778,7 @@ int svils_batch_elbo(svils_batch *h, double parts[4], uint64_t *pairs_done, uint
                      h->elogbeta, h->eta0, h->eta1, h->el_out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(h->ev_elbo[1], h->st));
-  h->timed_elbo = true;
+  h->timed = svils_batch::Timed::ELBO;
   unsigned long long c[5] = {};
   double out[4] = {};
   HIPCHK(hipMemcpyAsync(c, h->el_ctr, sizeof c, hipMemcpyDeviceToHost, h->st));
@@ -1817,14 +1809,15 @@ int svils_batch_get_timing(svils_batch *h, double ms[3]) {
   if (int rc = check(h, "svils_batch_get_timing")) return rc;
   if (!ms) return fail(SVILS_ERR_ARG, "svils_batch_get_timing: null argument");
   HIPCHK(hipStreamSynchronize(h->st));
-  if (h->timed_elbo) {   // the last timed call was svils_batch_elbo: its own bracket, the sweep's events are as they were
+  using Timed = svils_batch::Timed;
+  if (h->timed == Timed::ELBO) {   // its own bracket
     float t = 0;
     ms[0] = hipEventElapsedTime(&t, h->ev_elbo[0], h->ev_elbo[1]) == hipSuccess ? (double)t : -1.0;
     ms[1] = ms[2] = -1.0;
     return 0;
   }
-  ms[0] = h->elapsed_ms(0, 1, h->timed);
-  const bool swept = h->timed && !h->timed_steps;
+  ms[0] = h->elapsed_ms(0, 1, h->timed != Timed::NONE);
+  const bool swept = h->timed == Timed::SWEEP;
   ms[1] = h->launches_ms(1, h->nlaunch, swept);   // (the first launch's bracket includes the fill)
   ms[2] = h->launches_ms(2, h->nlaunch, swept);
   return 0;

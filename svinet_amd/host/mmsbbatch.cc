@@ -20,21 +20,12 @@ const double kMeanChangeThresh = 0.00001;  // src/env.hh:337
 const uint32_t kNoninfSetsize = 200;       // _noninf_setsize, src/fastamm.cc:18
 const uint32_t kStratSets = 10;            // _m, src/fastamm2.cc:16: a non-link step takes n / 10 nodes
 
-// psi(x), x > 0: recurrence up to x >= 6, then the asymptotic series (double accurate)
-double digamma(double x) {
-  double r = 0;
-  while (x < 6) { r -= 1 / x; x += 1; }
-  const double f = 1 / (x * x);
-  return r + log(x) - 0.5 / x -
-         f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132)))));
-}
-
 }  // namespace
 
 MMSBBatch::MMSBBatch(Env &env, Network &network)
     : env_(env), network_(network), n_(env.n), k_(env.k),
       ones_prob_(env.ones_prob), zeros_prob_(env.zeros_prob),
-      rng_((unsigned long)env.seed),
+      rng_((unsigned long)env.seed), gamma_rng_(rng_),
       gamma_((size_t)n_ * k_), gammanext_((size_t)n_ * k_, env.alpha),
       lambda_(2 * (size_t)k_), lambdanext_(2 * (size_t)k_),
       elogpi_((size_t)n_ * k_), elogbeta_(2 * (size_t)k_),
@@ -212,35 +203,8 @@ void MMSBBatch::init_heldout() {
 // Box-Muller Gaussian, so the distribution matches and the stream does not (parity unpinned,
 // SURVEY 8c).
 // ---------------------------------------------------------------------------
-double MMSBBatch::ran_gaussian() {
-  if (have_spare_) { have_spare_ = false; return spare_; }
-  double u, v, s;
-  do {
-    u = 2 * rng_.uniform() - 1;
-    v = 2 * rng_.uniform() - 1;
-    s = u * u + v * v;
-  } while (s >= 1 || s == 0);
-  const double m = sqrt(-2 * log(s) / s);
-  spare_ = v * m;
-  have_spare_ = true;
-  return u * m;
-}
-
-double MMSBBatch::ran_gamma(double a, double b) {           // a >= 1
-  const double d = a - 1.0 / 3.0, c = (1.0 / 3.0) / sqrt(d);
-  for (;;) {
-    double x, v;
-    do { x = ran_gaussian(); v = 1.0 + c * x; } while (v <= 0);
-    v = v * v * v;
-    double u;
-    do u = rng_.uniform(); while (u == 0);
-    if (u < 1 - 0.0331 * x * x * x * x) return b * d * v;
-    if (log(u) < 0.5 * x * x + d * (1 - v + log(v))) return b * d * v;
-  }
-}
-
 void MMSBBatch::init_gamma() {
-  for (size_t i = 0; i < gamma_.size(); ++i) gamma_[i] = ran_gamma(100, 1. / 100);
+  for (size_t i = 0; i < gamma_.size(); ++i) gamma_[i] = gamma_rng_.gamma(100, 1. / 100);
 }
 
 void MMSBBatch::set_dir_exp() {                             // src/mmsbinfer.hh:563-580 (same as A5)
@@ -251,10 +215,23 @@ void MMSBBatch::set_dir_exp() {                             // src/mmsbinfer.hh:
     const double ps = digamma(s);
     for (uint32_t k = 0; k < k_; ++k) elogpi_[(size_t)i * k_ + k] = digamma(g[k]) - ps;
   }
+  set_elogbeta();
+}
+
+void MMSBBatch::set_elogbeta() {                            // set_dir_exp(_lambda, _Elogbeta)
   for (uint32_t k = 0; k < k_; ++k) {
     const double ps = digamma(lambda_[2 * k] + lambda_[2 * k + 1]);
     elogbeta_[2 * k] = digamma(lambda_[2 * k]) - ps;
     elogbeta_[2 * k + 1] = digamma(lambda_[2 * k + 1]) - ps;
+  }
+}
+
+// lambda a step rho towards eta + scale lambdat (:613-631, src/fastamm.cc:604-616, src/fastamm2.cc:626-638); rho < 0: lambda waits
+void MMSBBatch::blend_lambda(double rho, double scale, const std::vector<double> &lambdat) {
+  if (!(rho >= 0)) return;
+  for (uint32_t k = 0; k < k_; ++k) {
+    lambda_[2 * k] = (1 - rho) * lambda_[2 * k] + rho * (env_.eta0 + scale * lambdat[2 * k]);
+    lambda_[2 * k + 1] = (1 - rho) * lambda_[2 * k + 1] + rho * (env_.eta1 + scale * lambdat[2 * k + 1]);
   }
 }
 
@@ -394,11 +371,7 @@ void MMSBBatch::step_host(const Drawn &d) {                  // :513-642, proces
   }
   for (size_t x = 0; x < gamma_.size(); ++x)
     gamma_[x] = (1 - d.rho_gamma) * gamma_[x] + d.rho_gamma * (env_.alpha + d.scale * gammat[x]);
-  if (d.rho_lambda >= 0)
-    for (uint32_t k = 0; k < k_; ++k) {
-      lambda_[2 * k] = (1 - d.rho_lambda) * lambda_[2 * k] + d.rho_lambda * (env_.eta0 + d.scale * lambdat[2 * k]);
-      lambda_[2 * k + 1] = (1 - d.rho_lambda) * lambda_[2 * k + 1] + d.rho_lambda * (env_.eta1 + d.scale * lambdat[2 * k + 1]);
-    }
+  blend_lambda(d.rho_lambda, d.scale, lambdat);
 }
 
 // ---------------------------------------------------------------------------
@@ -412,9 +385,9 @@ void MMSBBatch::shuffle_nodes() {                           // :506-511; gsl_ran
 
 void MMSBBatch::init_gamma_lambda_infset() {                // :514-546 (k < 100 for gamma, k <= 100 for lambda)
   const double vg = k_ < 100 ? 1.0 : 100.0 / k_, vl = k_ <= 100 ? 1.0 : 100.0 / k_;
-  for (size_t i = 0; i < gamma_.size(); ++i) gamma_[i] = ran_gamma(100 * vg, 0.01);
+  for (size_t i = 0; i < gamma_.size(); ++i) gamma_[i] = gamma_rng_.gamma(100 * vg, 0.01);
   for (uint32_t k = 0; k < k_; ++k)
-    for (uint32_t t = 0; t < 2; ++t) lambda_[2 * k + t] = lambdanext_[2 * k + t] = (t ? env_.eta1 : env_.eta0) + ran_gamma(100 * vl, 0.01);
+    for (uint32_t t = 0; t < 2; ++t) lambda_[2 * k + t] = lambdanext_[2 * k + t] = (t ? env_.eta1 : env_.eta0) + gamma_rng_.gamma(100 * vl, 0.01);
 }
 
 MMSBBatch::Star MMSBBatch::draw_star() {
@@ -469,11 +442,7 @@ void MMSBBatch::star_host(const Star &d) {
     const double ps = digamma(s);
     for (uint32_t k = 0; k < K; ++k) elogpi_[(size_t)i * K + k] = digamma(g[k]) - ps;
   };
-  for (uint32_t k = 0; k < K; ++k) {                        // set_dir_exp(_lambda, _Elogbeta), :566
-    const double ps = digamma(lambda_[2 * k] + lambda_[2 * k + 1]);
-    elogbeta_[2 * k] = digamma(lambda_[2 * k]) - ps;
-    elogbeta_[2 * k + 1] = digamma(lambda_[2 * k + 1]) - ps;
-  }
+  set_elogbeta();                                           // :566
   row_exp(a);
   std::vector<double> ta(K, 0.0), tj(K), lambdat(2 * (size_t)K, 0.0), phi1(K), phi2(K);
   auto blend = [&](uint32_t i, double rho, const std::vector<double> &t) {   // :594-598
@@ -494,42 +463,7 @@ void MMSBBatch::star_host(const Star &d) {
     blend(j, d.rho_partner[e], tj);                         // a partner is listed once: its gammat is this pair's phi
   }
   blend(a, d.rho_start, ta);
-  if (d.rho_lambda >= 0)                                    // :604-616
-    for (uint32_t k = 0; k < K; ++k) {
-      lambda_[2 * k] = (1 - d.rho_lambda) * lambda_[2 * k] + d.rho_lambda * (env_.eta0 + d.scale * lambdat[2 * k]);
-      lambda_[2 * k + 1] = (1 - d.rho_lambda) * lambda_[2 * k + 1] + d.rho_lambda * (env_.eta1 + d.scale * lambdat[2 * k + 1]);
-    }
-}
-
-void MMSBBatch::step_stars(uint32_t nsteps) {
-  std::vector<Star> chunk(nsteps);
-  for (Star &d : chunk) d = draw_star();
-  if (!dev_) {
-    for (const Star &d : chunk) star_host(d);
-  } else if (nsteps) {
-    std::vector<uint32_t> start(nsteps), partner;
-    std::vector<uint64_t> off(nsteps + 1, 0);
-    std::vector<uint8_t> y;
-    std::vector<double> rp, rs(nsteps), sc(nsteps), rl(nsteps);
-    for (uint32_t s = 0; s < nsteps; ++s) {
-      const Star &d = chunk[s];
-      start[s] = d.start;
-      partner.insert(partner.end(), d.partner.begin(), d.partner.end());
-      y.insert(y.end(), d.y.begin(), d.y.end());
-      rp.insert(rp.end(), d.rho_partner.begin(), d.rho_partner.end());
-      off[s + 1] = partner.size();
-      rs[s] = d.rho_start;
-      sc[s] = d.scale;
-      rl[s] = d.rho_lambda;
-    }
-    if (int rc = svils_batch_step_star(dev_, nsteps, start.data(), off.data(), partner.data(), y.data(), rp.data(), rs.data(), sc.data(),
-                                       rl.data()))
-      device_failed("svils_batch_step_star", rc);
-    host_stale_ = true;
-  }
-  iter_ += nsteps;
-  if (keep_schedule_)
-    for (Star &d : chunk) stars_.push_back(std::move(d));
+  blend_lambda(d.rho_lambda, d.scale, lambdat);
 }
 
 // ---------------------------------------------------------------------------
@@ -594,35 +528,38 @@ void MMSBBatch::strat_host(const Star &d) {
       double &g = gamma_[(size_t)i * K + k];
       g = named[i] ? (1 - rho) * g + rho * (env_.alpha + d.scale * gammat[(size_t)i * K + k]) : (1 - rho) * g + rho * env_.alpha;
     }
-  if (d.rho_lambda >= 0)                                    // :626-638
-    for (uint32_t k = 0; k < K; ++k) {
-      lambda_[2 * k] = (1 - d.rho_lambda) * lambda_[2 * k] + d.rho_lambda * (env_.eta0 + d.scale * lambdat[2 * k]);
-      lambda_[2 * k + 1] = (1 - d.rho_lambda) * lambda_[2 * k + 1] + d.rho_lambda * (env_.eta1 + d.scale * lambdat[2 * k + 1]);
-    }
+  blend_lambda(d.rho_lambda, d.scale, lambdat);
 }
 
-void MMSBBatch::step_strats(uint32_t nsteps) {
+// -infset / -snode: a chunk of stars -- drawn, then run by the host loops or flattened once into the lists of one device call
+void MMSBBatch::step_stars(uint32_t nsteps) {
+  const bool strat = env_.snode;
   std::vector<Star> chunk(nsteps);
-  for (Star &d : chunk) d = draw_strat();
+  for (Star &d : chunk) d = strat ? draw_strat() : draw_star();
   if (!dev_) {
-    for (const Star &d : chunk) strat_host(d);
+    for (const Star &d : chunk) strat ? strat_host(d) : star_host(d);
   } else if (nsteps) {
     std::vector<uint32_t> start(nsteps), partner;
     std::vector<uint64_t> off(nsteps + 1, 0);
     std::vector<uint8_t> y;
-    std::vector<double> rg(nsteps), sc(nsteps), rl(nsteps);
+    std::vector<double> rp, rs(nsteps), sc(nsteps), rl(nsteps);
     for (uint32_t s = 0; s < nsteps; ++s) {
       const Star &d = chunk[s];
       start[s] = d.start;
       partner.insert(partner.end(), d.partner.begin(), d.partner.end());
       y.insert(y.end(), d.y.begin(), d.y.end());
+      rp.insert(rp.end(), d.rho_partner.begin(), d.rho_partner.end());
       off[s + 1] = partner.size();
-      rg[s] = d.rho_start;
+      rs[s] = d.rho_start;
       sc[s] = d.scale;
       rl[s] = d.rho_lambda;
     }
-    if (int rc = svils_batch_step_strat(dev_, nsteps, start.data(), off.data(), partner.data(), y.data(), rg.data(), sc.data(), rl.data()))
-      device_failed("svils_batch_step_strat", rc);
+    // -snode: rho_start carries the step's one rho_gamma, and rp is not handed over
+    const char *call = strat ? "svils_batch_step_strat" : "svils_batch_step_star";
+    if (int rc = strat ? svils_batch_step_strat(dev_, nsteps, start.data(), off.data(), partner.data(), y.data(), rs.data(), sc.data(), rl.data())
+                       : svils_batch_step_star(dev_, nsteps, start.data(), off.data(), partner.data(), y.data(), rp.data(), rs.data(), sc.data(),
+                                               rl.data()))
+      device_failed(call, rc);
     host_stale_ = true;
   }
   iter_ += nsteps;
@@ -631,8 +568,7 @@ void MMSBBatch::step_strats(uint32_t nsteps) {
 }
 
 void MMSBBatch::step(uint32_t nsteps) {
-  if (env_.infset) return step_stars(nsteps);
-  if (env_.snode) return step_strats(nsteps);
+  if (env_.infset || env_.snode) return step_stars(nsteps);
   std::vector<Drawn> chunk(nsteps);
   for (Drawn &d : chunk) d = draw();
   if (!dev_) {

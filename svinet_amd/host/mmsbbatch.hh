@@ -129,9 +129,9 @@ class MMSBBatch {
   void get_random_edge(bool heldout_flag, bool stratified, int family, Edge &e);
   bool edge_ok(const Edge &e, bool heldout_flag, bool stratified, int family) const;
   void init_gamma();
-  double ran_gamma(double a, double b);
-  double ran_gaussian();
   void set_dir_exp();
+  void set_elogbeta();                                    // Elogbeta of lambda_
+  void blend_lambda(double rho, double scale, const std::vector<double> &lambdat);
   bool heldout_likelihood();
   void validation_likelihood(double *av);
   void save_model();
@@ -145,14 +145,13 @@ class MMSBBatch {
   uint32_t iter_ = 0;
   double ones_prob_, zeros_prob_;
   GslMt19937 rng_;
+  GammaSampler gamma_rng_;           // init_gamma's draws, over rng_
   std::map<Edge, bool> heldout_map_, validation_map_;
   std::vector<uint32_t> heldout_edges_, validation_edges_;
   std::vector<double> gamma_, gammanext_, lambda_, lambdanext_, elogpi_, elogbeta_;
   std::vector<double> rows_;
   double max_t_, max_h_, max_v_, prev_h_;
   uint32_t nh_ = 0;
-  bool have_spare_ = false;
-  double spare_ = 0;
   time_t start_time_;
   FILE *hf_ = nullptr, *vf_ = nullptr;
   FILE *lf_ = nullptr;               // logl.txt, open for rows under -logl alone
@@ -174,9 +173,8 @@ class MMSBBatch {
   // step size of the iteration; kind 0: the links of the start node, 1: a block of its non-links
   Star draw_strat();                                      // :573-592 with the lists of opt_process / opt_process_noninf (:933-1165)
   void strat_host(const Star &d);                         // :565-640, the restated eager loops: all n rows move
-  void step_strats(uint32_t nsteps);
   void star_host(const Star &d);                          // :565-616, the restated loops
-  void step_stars(uint32_t nsteps);
+  void step_stars(uint32_t nsteps);                       // -infset and -snode: draw a chunk, run it
   std::vector<uint32_t> shuffled_, nodec_;
   std::vector<Star> stars_;
   svils_batch *dev_ = nullptr;       // the device backend (null: host loops)

@@ -15,22 +15,13 @@ namespace {
 const uint32_t kOnlineIterations = 50;     // src/env.hh: online_iterations
 const double kMeanChangeThresh = 0.00001;  // src/env.hh: meanchangethresh
 
-// psi(x), x > 0: recurrence up to x >= 6, then the asymptotic series (double accurate)
-double digamma(double x) {
-  double r = 0;
-  while (x < 6) { r -= 1 / x; x += 1; }
-  const double f = 1 / (x * x);
-  return r + log(x) - 0.5 / x -
-         f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132)))));
-}
-
 }  // namespace
 
 MMSBInferOrig::MMSBInferOrig(Env &env, Network &network, int itype)
     : env_(env), network_(network), n_(env.n), k_(env.k), itype_(itype),
       total_pairs_((double)env.n * (env.n - 1) / 2),          // undirected (:34-35)
       ones_prob_((double)network.ones() / ((double)env.n * (env.n - 1) / 2)),
-      rng_((unsigned long)env.seed),
+      rng_((unsigned long)env.seed), gamma_rng_(rng_),
       gamma_((size_t)n_ * k_), beta_((size_t)k_ * k_),
       start_time_(time(0)) {
   fprintf(stdout, "+ mmsb orig initialization begin\n+ running inference on %d nodes\n", n_);
@@ -167,35 +158,8 @@ void MMSBInferOrig::init_heldout() {
 // ---------------------------------------------------------------------------
 // starts (:157-209)
 // ---------------------------------------------------------------------------
-double MMSBInferOrig::ran_gaussian() {
-  if (have_spare_) { have_spare_ = false; return spare_; }
-  double u, v, s;
-  do {
-    u = 2 * rng_.uniform() - 1;
-    v = 2 * rng_.uniform() - 1;
-    s = u * u + v * v;
-  } while (s >= 1 || s == 0);
-  const double m = sqrt(-2 * log(s) / s);
-  spare_ = v * m;
-  have_spare_ = true;
-  return u * m;
-}
-
-double MMSBInferOrig::ran_gamma(double a, double b) {       // a >= 1 (Marsaglia-Tsang, as mmsbbatch.cc)
-  const double d = a - 1.0 / 3.0, c = (1.0 / 3.0) / sqrt(d);
-  for (;;) {
-    double x, v;
-    do { x = ran_gaussian(); v = 1.0 + c * x; } while (v <= 0);
-    v = v * v * v;
-    double u;
-    do u = rng_.uniform(); while (u == 0);
-    if (u < 1 - 0.0331 * x * x * x * x) return b * d * v;
-    if (log(u) < 0.5 * x * x + d * (1 - v + log(v))) return b * d * v;
-  }
-}
-
 void MMSBInferOrig::init_gamma() {
-  for (size_t i = 0; i < gamma_.size(); ++i) gamma_[i] = ran_gamma(100, 1. / 100);
+  for (size_t i = 0; i < gamma_.size(); ++i) gamma_[i] = gamma_rng_.gamma(100, 1. / 100);
 }
 
 void MMSBInferOrig::init_beta1() {
@@ -259,16 +223,24 @@ uint32_t MMSBInferOrig::fixed_point(const double *ep, const double *eq, const do
   return rounds;
 }
 
-void MMSBInferOrig::sweep_host() {
+// Elogpi of all rows: set_dir_exp (:601-622), psi of a cell clamped at 1e-30
+std::vector<double> MMSBInferOrig::elogpi_rows() const {
   const uint32_t K = k_;
-  std::vector<double> elogpi((size_t)n_ * K), l0((size_t)K * K), l1((size_t)K * K);
-  for (uint32_t i = 0; i < n_; ++i) {                         // set_dir_exp (:601-622)
+  std::vector<double> elogpi((size_t)n_ * K);
+  for (uint32_t i = 0; i < n_; ++i) {
     const double *g = &gamma_[(size_t)i * K];
     double s = 0;
     for (uint32_t k = 0; k < K; ++k) s += g[k];
     const double ps = digamma(s);
     for (uint32_t k = 0; k < K; ++k) elogpi[(size_t)i * K + k] = digamma(g[k] < 1e-30 ? 1e-30 : g[k]) - ps;
   }
+  return elogpi;
+}
+
+void MMSBInferOrig::sweep_host() {
+  const uint32_t K = k_;
+  const std::vector<double> elogpi = elogpi_rows();
+  std::vector<double> l0((size_t)K * K), l1((size_t)K * K);
   for (size_t e = 0; e < l0.size(); ++e) {                    // compute_f gives exactly beta or 1 - beta (:159-172)
     l0[e] = log(1 - beta_[e]);
     l1[e] = log(beta_[e]);
@@ -375,14 +347,8 @@ void MMSBInferOrig::report() {
 // ---------------------------------------------------------------------------
 void MMSBInferOrig::elbo_host(double out[3], uint64_t *pairs, uint64_t *rounds) {
   const uint32_t K = k_;
-  std::vector<double> elogpi((size_t)n_ * K), l0((size_t)K * K), l1((size_t)K * K), t0((size_t)K * K), t1((size_t)K * K);
-  for (uint32_t i = 0; i < n_; ++i) {
-    const double *g = &gamma_[(size_t)i * K];
-    double s = 0;
-    for (uint32_t k = 0; k < K; ++k) s += g[k];
-    const double ps = digamma(s);
-    for (uint32_t k = 0; k < K; ++k) elogpi[(size_t)i * K + k] = digamma(g[k] < 1e-30 ? 1e-30 : g[k]) - ps;
-  }
+  const std::vector<double> elogpi = elogpi_rows();
+  std::vector<double> l0((size_t)K * K), l1((size_t)K * K), t0((size_t)K * K), t1((size_t)K * K);
   for (size_t e = 0; e < l0.size(); ++e) {
     l0[e] = log(1 - beta_[e]);
     l1[e] = log(beta_[e]);

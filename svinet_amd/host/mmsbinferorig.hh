@@ -123,8 +123,7 @@ class MMSBInferOrig {
   void init_gamma();
   void init_beta1();
   void init_beta2();
-  double ran_gamma(double a, double b);
-  double ran_gaussian();
+  std::vector<double> elogpi_rows() const;                // Elogpi [n][k] of gamma_ (sweep_host, elbo_host)
   void sweep_host();
   void elbo_host(double out[3], uint64_t *pairs, uint64_t *rounds);
   uint32_t fixed_point(const double *ep, const double *eq, const double *lf, double *phi1, double *phi2, uint32_t p, uint32_t q) const;
@@ -140,6 +139,7 @@ class MMSBInferOrig {
   uint32_t iter_ = 0;
   double total_pairs_, ones_prob_;
   GslMt19937 rng_;
+  GammaSampler gamma_rng_;           // init_gamma's draws, over rng_
   std::map<Edge, bool> heldout_map_, validation_map_, extra_skip_;
   std::set<Edge> skip_;         // the ordered pairs a sweep leaves out (init_skip)
   std::vector<int> pp_ext_, rp_ext_;        // -predict-pairs / -rank-pairs: the ids as given, and as sequence ids
@@ -147,8 +147,6 @@ class MMSBInferOrig {
   std::vector<uint32_t> heldout_edges_, validation_edges_;
   std::vector<double> gamma_, beta_, rows_;
   uint64_t rounds_total_ = 0;
-  bool have_spare_ = false;
-  double spare_ = 0;
   time_t start_time_;
   FILE *hf_ = nullptr, *vf_ = nullptr, *lf_ = nullptr;
   std::vector<double> logl_rows_;

@@ -9,6 +9,7 @@
 // produced by three dependency-free loops the compiler can vectorise: the
 // initialisation of gamma draws E*K uniforms from this one sequential stream.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -112,6 +113,44 @@ class GslMt19937 {
   int idx_;
   uint64_t blocks_ = 0;    // refills since construction
   uint64_t base_ = 0;      // position of the state this object was built from
+};
+
+// gsl_ran_gamma(r, a, b), a >= 1, over one GslMt19937 stream.  GSL's sampler is Marsaglia-Tsang driven by its ziggurat
+// Gaussian, whose tables are internal to GSL; this is the same Marsaglia-Tsang recipe with a polar Box-Muller Gaussian, so
+// the distribution matches and the stream does not (parity unpinned).  The Gaussian's spare value lives here
+class GammaSampler {
+ public:
+  explicit GammaSampler(GslMt19937 &rng) : rng_(rng) {}
+  double gamma(double a, double b) {
+    const double d = a - 1.0 / 3.0, c = (1.0 / 3.0) / sqrt(d);
+    for (;;) {
+      double x, v;
+      do { x = gaussian(); v = 1.0 + c * x; } while (v <= 0);
+      v = v * v * v;
+      double u;
+      do u = rng_.uniform(); while (u == 0);
+      if (u < 1 - 0.0331 * x * x * x * x) return b * d * v;
+      if (log(u) < 0.5 * x * x + d * (1 - v + log(v))) return b * d * v;
+    }
+  }
+
+ private:
+  double gaussian() {
+    if (have_spare_) { have_spare_ = false; return spare_; }
+    double u, v, s;
+    do {
+      u = 2 * rng_.uniform() - 1;
+      v = 2 * rng_.uniform() - 1;
+      s = u * u + v * v;
+    } while (s >= 1 || s == 0);
+    const double m = sqrt(-2 * log(s) / s);
+    spare_ = v * m;
+    have_spare_ = true;
+    return u * m;
+  }
+  GslMt19937 &rng_;
+  bool have_spare_ = false;
+  double spare_ = 0;
 };
 
 }  // namespace svinet

@@ -1,5 +1,6 @@
 // util.hh -- what the host drivers share: the error of a failed svils_* call, output files, usable CPUs, a clock.
 #pragma once
+#include <cmath>
 #include <cstdio>
 #include <stdexcept>
 #include <string>
@@ -23,5 +24,14 @@ FILE *open_or_die(const std::string &path, const char *what, const char *mode = 
 unsigned usable_cpus();
 
 double now_s();   // CLOCK_MONOTONIC in seconds
+
+// psi(x), x > 0, of the host loops: recurrence up to x >= 6, then the asymptotic series (double accurate)
+inline double digamma(double x) {
+  double r = 0;
+  while (x < 6) { r -= 1 / x; x += 1; }
+  const double f = 1 / (x * x);
+  return r + std::log(x) - 0.5 / x -
+         f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132)))));
+}
 
 }  // namespace svinet

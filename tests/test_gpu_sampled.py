@@ -346,6 +346,38 @@ def test_cli_runs_on_the_device(graph_files, tmp_path, flags, name):
         assert (d / f).read_bytes() == (tmp_path / "host" / "n75-k4-mmsb-batch" / f).read_bytes(), f
 
 
+def test_timing_and_stats_name_the_last_timed_call(tmp_path):
+    """sweep, step call, elbo(), step call, sweep on one handle: timing() is (all three >= 0) after a sweep and
+    (>= 0, -1, -1) after a step call and after elbo(); stats() are those of the last sweep or step call, which elbo()
+    leaves alone.  A step call and elbo() both read (>= 0, -1, -1): what this pins is that neither is taken for a sweep, and,
+    by the last sweep, that neither state sticks"""
+    n, k = 70, 5
+    s = Start(BC.write_graph(tmp_path / "g.txt", BC.planted_links(n, 2, 0.3, 0.03, seed=70)), n, k)
+    assert s.n == n
+
+    def stepped(pairs_done):
+        ms = s.dev.timing()
+        assert ms[0] >= 0 and ms[1] == ms[2] == -1
+        assert s.dev.stats()[0] == pairs_done
+
+    def swept():
+        assert np.all(s.dev.timing() >= 0)
+        assert s.dev.stats()[0] == s.trained
+
+    s.dev.sweep()
+    swept()
+    s.dev.step_node([7], n / 2.0, [SC.rho_gamma(0)], [SC.rho_lambda(0, 0)])
+    in_node_step = len(SC.node_pairs(n, 7, s.skip)[0])
+    stepped(in_node_step)
+    parts, pairs_done, _ = s.dev.elbo()
+    assert pairs_done == s.trained and math.isfinite(parts[0])
+    stepped(in_node_step)
+    s.dev.step_pairs([_draw_pairs(s, 37, 70)], [n * (n - 1) / 2.0 / 37], [SC.rho_gamma(1)], [SC.rho_lambda(1, 0)])
+    stepped(37)
+    s.dev.sweep()
+    swept()
+
+
 def test_cli_refuses_k_above_the_limit(graph_files, tmp_path):
     r = _cli(["-file", graph_files["assort"], "-n", "75", "-k", "300", "-rnode"], tmp_path, timeout=60)
     assert r.returncode == 2 and "256" in r.stderr
