@@ -49,6 +49,7 @@ extern "C" {
                                     (additive, same version) svils_orig_*: -orig, the full K x K blockmodel over all ordered pairs;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_ppc_*: -ppc / -gen, networks drawn from a model and their statistics;
+                                    (additive, same version) svils_ppc_hops / svils_ppc_get_hop*: -ppc-hops, the exact hop plot and components;
                                     (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
                                     resource-allocation scores of pairs, the model-free baselines of svils_rank_links */
 
@@ -968,6 +969,34 @@ int svils_ppc_get_communities(svils_ppc *h, uint64_t *size, double *logpe);
 int svils_ppc_get_timing(svils_ppc *h, double ms[3]);
 /* tiles per launch of the draw (0: all in one launch); no result depends on it */
 int svils_ppc_set_tile_batch(svils_ppc *h, uint32_t tiles_per_launch);
+
+/* -ppc-hops: the exact hop plot and the components of the current list, an undirected simple graph
+ * on n nodes.  d(s, v) is the BFS distance (infinite across components, d(s, s) = 0).
+ *   D[h]       ordered pairs (s, v) with d(s, v) = h: D[0] = n, D[1] = 2 links (SNAP's hop plot counts the self pairs);
+ *              levels = the largest finite distance + 1; C[h] = D[0] + .. + D[h]
+ *   ecc [n]    the largest finite d(s, .), 0 for an isolated node;  comp [n]: the smallest node id of v's component
+ *   counts[6]  reachable = C[levels - 1] - n, diameter = levels - 1, components, the size of the largest one, isolated
+ *              (nodes of degree 0), levels
+ *   values[2]  effdiam: the 90th percentile of the hop plot, linearly interpolated as SNAP's CalcEffDiam -- t = 0.9 C[levels - 1],
+ *              h* the smallest h with C[h] >= t, 0 if h* = 0, else (h* - 1) + (t - C[h* - 1]) / (C[h*] - C[h* - 1]) in fp64, in this
+ *              order, nothing contracted;  meandist = (sum of h D[h]) / reachable, NaN when nothing is reachable
+ * All-sources BFS, bit-parallel over sources in passes of 64 x words sources, one launch per level, integer atomics alone:
+ * every integer is exact and the same for any batch.  ceil(n / (64 words)) x levels launches: a long-diameter graph is slow.
+ * The results belong to the list they were computed for: a successful svils_ppc_draw / svils_ppc_set_links invalidates them
+ * (the getters answer SVILS_ERR_ARG until svils_ppc_hops runs again); a draw that answers SVILS_ERR_NOMEM keeps them.
+ * svils_ppc_hops needs neither parameters nor svils_ppc_stats and changes nothing of theirs; it synchronises.  The first call
+ * allocates three tables of n x words 64-bit words (6 MiB at n = 32768, words = 8). */
+int svils_ppc_hops(svils_ppc *h);
+/* *levels, and D[0 .. min(levels, cap)) */
+int svils_ppc_get_hops(svils_ppc *h, uint32_t *levels, uint64_t *D, uint32_t cap);
+/* ecc [n], comp [n]; either may be null */
+int svils_ppc_get_hop_nodes(svils_ppc *h, uint32_t *ecc, uint32_t *comp);
+int svils_ppc_get_hop_summary(svils_ppc *h, uint64_t counts[6], double values[2]);
+/* words per node of a pass (1 .. 8, else SVILS_ERR_ARG) and levels queued between two reads of the level counter (>= 1);
+ * 0 restores that default (8 and 8).  No result depends on it */
+int svils_ppc_set_hop_batch(svils_ppc *h, uint32_t words, uint32_t levels_per_chunk);
+/* ms[0]: device milliseconds of the last svils_ppc_hops, ms[1]: the kernel launches it queued; both -1 before the first run */
+int svils_ppc_get_hop_timing(svils_ppc *h, double ms[2]);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * Every tunable of the library is a row of ONE table: key, the SVILS_* environment variable that sets its default, the

@@ -52,6 +52,8 @@ EXPORTS = (
     "svils_ppc_create", "svils_ppc_destroy", "svils_ppc_set_params", "svils_ppc_draw", "svils_ppc_set_links", "svils_ppc_stats",
     "svils_ppc_get_draw_counts", "svils_ppc_get_links", "svils_ppc_get_nodes", "svils_ppc_get_summary", "svils_ppc_get_communities",
     "svils_ppc_get_timing", "svils_ppc_set_tile_batch",
+    "svils_ppc_hops", "svils_ppc_get_hops", "svils_ppc_get_hop_nodes", "svils_ppc_get_hop_summary", "svils_ppc_set_hop_batch",
+    "svils_ppc_get_hop_timing",
 )
 PPC_MAX_N, PPC_MAX_K = 32768, 2048      # SVILS_PPC_MAX_N, SVILS_PPC_MAX_K
 ORIG_MAX_K, ORIG_MAX_N = 64, 32768      # SVILS_ORIG_MAX_K, SVILS_ORIG_MAX_N
@@ -251,6 +253,12 @@ def load():
     L.svils_ppc_get_communities.argtypes = [vp, vp, vp]
     L.svils_ppc_get_timing.argtypes = [vp, vp]
     L.svils_ppc_set_tile_batch.argtypes = [vp, C.c_uint32]
+    L.svils_ppc_hops.argtypes = [vp]
+    L.svils_ppc_get_hops.argtypes = [vp, C.POINTER(C.c_uint32), vp, C.c_uint32]
+    L.svils_ppc_get_hop_nodes.argtypes = [vp, vp, vp]
+    L.svils_ppc_get_hop_summary.argtypes = [vp, vp, vp]
+    L.svils_ppc_set_hop_batch.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.svils_ppc_get_hop_timing.argtypes = [vp, vp]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):

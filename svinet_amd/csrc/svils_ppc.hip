@@ -21,6 +21,19 @@
 //                 bins per community (three adds per link), which hold the sum exactly in any order
 // The O(n) and O(K) closings -- wedges, the largest degree, the mean local clustering, the bins to a double -- run on
 // the host in index order.
+//
+// The hop plot and the components of the current list (svils_ppc_hops): all-sources BFS, bit-parallel
+// over sources.  Sources go in passes of 64 W consecutive ids (W words of 64 bits per node); a pass holds visited and two
+// frontier tables [n][W].
+//   k_hop_seed    a pass's tables: bit s - s0 of row s for the sources s of the pass, nothing else
+//   k_hop_level   one launch, one level, pull form over the sorted CSR: 16 lanes own a node and split its neighbours, each
+//                 reads whole rows of the frontier table (16-byte loads) and ORs them; fresh = acc & ~visited goes to the
+//                 next frontier.  A node that every source of the pass has reached already gathers nothing.  popcount(fresh) is reduced over the wavefront into one integer atomicAdd on the level's
+//                 counter; the OR of fresh over the block goes by integer atomicOr into the level's source mask, which
+//                 the NEXT launch reads (block 0: ecc[s] = the last level whose mask holds s).  A launch whose
+//                 predecessor counted nothing returns at once
+//   k_hop_close   a pass's counters into D, and comp[v] = the first source of the first pass that reached v
+// The host queues the levels in chunks and reads one counter per chunk; the summary (integers, and two doubles) is the host's.
 #include "svils_tool.h"
 #include "svils_pairtiles.h"
 
@@ -291,9 +304,131 @@ __global__ __launch_bounds__(256) void k_link_stats(uint64_t E, uint32_t K, uint
   if (p2) atomicAdd(row + 2, p2);
 }
 
+// ---- hop plot and components (section 4o) ----
+
+constexpr uint32_t HOP_WORDS = 8, HOP_CHUNK = 8;   // the defaults of svils_ppc_set_hop_batch
+
+// the tables of the pass of sources s0 .. s0 + nsrc: row s holds bit s - s0; cnt[0] = the pairs at distance 0
+__global__ __launch_bounds__(256) void k_hop_seed(uint32_t n, uint32_t W, uint32_t s0, uint32_t nsrc, unsigned long long *__restrict__ vis,
+                                                  unsigned long long *__restrict__ front, unsigned long long *__restrict__ cnt) {
+  const uint32_t x = blockIdx.x * 256 + threadIdx.x;
+  if (x == 0) cnt[0] = nsrc;
+  if (x >= n * W) return;
+  const uint32_t v = x / W, w = x - v * W, b = v - s0;   // b wraps below s0: then it is >= nsrc
+  const unsigned long long word = (v >= s0 && b < nsrc && (b >> 6) == w) ? 1ull << (b & 63) : 0ull;
+  vis[x] = word;
+  front[x] = word;
+}
+
+// level `level` >= 1 of a pass: 16 lanes per node, 16 nodes per block.  cnt [n + 2]: pairs found per level; mask [2][8]: the
+// sources that found a node at level l, in slot l & 1 -- written here for `level`, read (and cleared for level + 1) for level - 1
+template <int W>
+__global__ __launch_bounds__(256) void k_hop_level(uint32_t n, uint32_t level, uint32_t s0, uint32_t nsrc, const uint64_t *__restrict__ rowptr,
+                                                   const uint32_t *__restrict__ scol, const unsigned long long *__restrict__ front,
+                                                   unsigned long long *__restrict__ next, unsigned long long *__restrict__ vis,
+                                                   unsigned long long *__restrict__ cnt, unsigned long long *__restrict__ mask,
+                                                   uint32_t *__restrict__ ecc) {
+  if (cnt[level - 1] == 0) return;   // written by the launch before: the pass has ended
+  __shared__ unsigned long long sm[HOP_WORDS];
+  const uint32_t t = threadIdx.x, lane = t & 63, j = t & 15, v = blockIdx.x * 16 + (t >> 4);
+  unsigned long long *mprev = mask + HOP_WORDS * ((level - 1) & 1), *mcur = mask + HOP_WORDS * (level & 1);
+  if (t < HOP_WORDS) sm[t] = 0;
+  if (blockIdx.x == 0) {
+    for (uint32_t b = t; b < 64 * W; b += 256)
+      if (((mprev[b >> 6] >> (b & 63)) & 1ull) && s0 + b < n) ecc[s0 + b] = level - 1;
+    __syncthreads();
+    if (t < W) mprev[t] = 0;   // the slot of level + 1; nobody else touches it in this launch
+  }
+  __syncthreads();
+  // lane j of the group owns word j of the node: a node every source of the pass has reached gathers nothing
+  const bool owner = v < n && j < (uint32_t)W;
+  const size_t slot = (size_t)v * W + j;
+  const unsigned long long old = owner ? vis[slot] : ~0ull;
+  const uint32_t real = nsrc > 64 * j ? min(64u, nsrc - 64 * j) : 0u;   // the sources of the pass in word j
+  const bool open = owner && real && (~old & (~0ull >> (64 - real)));
+  const bool gather = ((__ballot(open) >> (lane & 48)) & 0xffffull) != 0;
+  unsigned long long acc[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) acc[w] = 0;
+  if (gather) {
+    const uint64_t e = rowptr[v + 1];
+    for (uint64_t x = rowptr[v] + j; x < e; x += 16) {
+      const unsigned long long *row = front + (size_t)scol[x] * W;
+      if constexpr (W % 2 == 0) {   // rows are 16-byte aligned
+#pragma unroll
+        for (int w = 0; w < W; w += 2) {
+          const ulonglong2 p = *reinterpret_cast<const ulonglong2 *>(row + w);
+          acc[w] |= p.x;
+          acc[w + 1] |= p.y;
+        }
+      } else {
+#pragma unroll
+        for (int w = 0; w < W; ++w) acc[w] |= row[w];
+      }
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < W; ++w)
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) acc[w] |= __shfl_xor(acc[w], o, 64);
+  unsigned long long fresh = 0;
+  if (owner) {
+    unsigned long long a = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+      if (j == (uint32_t)w) a = acc[w];
+    fresh = a & ~old;
+    if (fresh) vis[slot] = old | fresh;
+    next[slot] = fresh;
+  }
+  uint32_t c = (uint32_t)__popcll(fresh);
+  for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
+  if (lane == 0 && c) atomicAdd(&cnt[level], (unsigned long long)c);
+  unsigned long long m = fresh;   // word j of the wavefront's four nodes
+  m |= __shfl_xor(m, 16, 64);
+  m |= __shfl_xor(m, 32, 64);
+  if (lane < (uint32_t)W && m) atomicOr(&sm[lane], m);
+  __syncthreads();
+  if (t < (uint32_t)W && sm[t]) atomicOr(&mcur[t], sm[t]);
+}
+
+// the end of a pass: its counters into D [n + 1], and the label of every node this pass reached first
+__global__ __launch_bounds__(256) void k_hop_close(uint32_t n, uint32_t W, uint32_t s0, const unsigned long long *__restrict__ vis,
+                                                   const unsigned long long *__restrict__ cnt, unsigned long long *__restrict__ D,
+                                                   uint32_t *__restrict__ comp) {
+  const uint32_t x = blockIdx.x * 256 + threadIdx.x;
+  if (x > n) return;
+  D[x] += cnt[x];
+  if (x == n || comp[x] != NONE) return;
+  for (uint32_t w = 0; w < W; ++w) {
+    const unsigned long long word = vis[(size_t)x * W + w];
+    if (word) {
+      comp[x] = s0 + 64 * w + (uint32_t)__builtin_ctzll(word);
+      return;
+    }
+  }
+}
+
+using HopLevel = void (*)(uint32_t, uint32_t, uint32_t, uint32_t, const uint64_t *, const uint32_t *, const unsigned long long *, unsigned long long *,
+                          unsigned long long *, unsigned long long *, unsigned long long *, uint32_t *);
+constexpr HopLevel kHopLevel[HOP_WORDS] = {k_hop_level<1>, k_hop_level<2>, k_hop_level<3>, k_hop_level<4>,
+                                           k_hop_level<5>, k_hop_level<6>, k_hop_level<7>, k_hop_level<8>};
+
+// the 90th percentile of the hop plot, linearly interpolated (SNAP's CalcEffDiam) over the cumulative counts C: these
+// operations in this order, nothing contracted (the pragma above)
+__attribute__((noinline)) double effective_diameter(const std::vector<uint64_t> &C) {
+  const double t = 0.9 * (double)C.back();
+  size_t hs = 0;
+  while ((double)C[hs] < t) ++hs;
+  if (hs == 0) return 0.0;
+  const double below = (double)C[hs - 1], step = (double)(C[hs] - C[hs - 1]);
+  const double part = (t - below) / step;
+  return (double)(hs - 1) + part;
+}
+
 }  // namespace
 
-// events ev[6]: draw, list / CSR build, statistics (a bracket each)
+// events ev[6]: draw, list / CSR build, statistics (a bracket each); ev[6], ev[7] (made by the first svils_ppc_hops): the hop passes
 struct svils_ppc : ToolHandle {
   uint32_t n = 0, k = 0, ld = 0, k16 = 0, nt = 0, tile_batch = 0;
   uint64_t cap = 0, E = 0;
@@ -309,6 +444,15 @@ struct svils_ppc : ToolHandle {
   std::vector<uint32_t> hdeg, htri;
   uint64_t maxdeg = 0, argmax = 0, triangles = 0, wedges = 0;
   double transitivity = 0, clustering = 0;
+  // the hop plot (svils_ppc_hops): tables [n][W], cnt [n + 2] and mask [2][8] in hopc, D [n + 1]; made by the first call
+  uint32_t hop_words = HOP_WORDS, hop_chunk = HOP_CHUNK;
+  unsigned long long *hvis = nullptr, *hfa = nullptr, *hfb = nullptr, *hopc = nullptr, *hopd = nullptr;
+  uint32_t *hecc = nullptr, *hcomp = nullptr;
+  bool hops_done = false, hops_timed = false;
+  uint64_t hop_launches = 0, hop_counts[6] = {0, 0, 0, 0, 0, 0};
+  double hop_values[2] = {0, 0};
+  std::vector<uint64_t> hopD;
+  std::vector<uint32_t> ecc, comp;
 };
 
 namespace {
@@ -327,13 +471,19 @@ int build_lists(svils_ppc *h, uint64_t E) {
   HIPCHK(hipStreamSynchronize(st));
   h->E = E;
   h->have_list = h->timed[1] = true;
-  h->done = false;
+  h->done = h->hops_done = false;
   return 0;
 }
 
 int check_done(svils_ppc *h, const char *name) {
   if (int rc = check(h, name)) return rc;
   if (!h->done) return fail(SVILS_ERR_ARG, "%s: svils_ppc_stats has not run on the current list and parameters", name);
+  return 0;
+}
+
+int check_hops(svils_ppc *h, const char *name) {
+  if (int rc = check(h, name)) return rc;
+  if (!h->hops_done) return fail(SVILS_ERR_ARG, "%s: svils_ppc_hops has not run on the current list", name);
   return 0;
 }
 
@@ -477,7 +627,7 @@ int svils_ppc_set_links(svils_ppc *h, const uint32_t *links, uint64_t nlinks) {
     return fail(SVILS_ERR_NOMEM, "svils_ppc_set_links: %llu links, the list has room for %llu", (unsigned long long)nlinks, (unsigned long long)h->cap);
   hipStream_t st = h->st;
   HIPCHK(hipStreamSynchronize(st));
-  h->have_list = h->done = false;
+  h->have_list = h->done = h->hops_done = false;
   HIPCHK(hipMemsetAsync(h->bits, 0, (size_t)n * h->nt * sizeof(unsigned long long), st));
   if (nlinks) {   // the caller's list waits in scol until k_fill overwrites it with the CSR (2 cap words: room for it)
     HIPCHK(hipMemcpyAsync(h->scol, links, 2 * nlinks * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -596,6 +746,135 @@ int svils_ppc_get_timing(svils_ppc *h, double ms[3]) {
   if (!ms) return fail(SVILS_ERR_ARG, "svils_ppc_get_timing: null argument");
   HIPCHK(hipStreamSynchronize(h->st));
   for (int p = 0; p < 3; ++p) ms[p] = h->elapsed_ms(2 * p, 2 * p + 1, h->timed[p]);
+  return 0;
+}
+
+int svils_ppc_set_hop_batch(svils_ppc *h, uint32_t words, uint32_t levels_per_chunk) {
+  if (int rc = check(h, "svils_ppc_set_hop_batch")) return rc;
+  if (words > HOP_WORDS) return fail(SVILS_ERR_ARG, "svils_ppc_set_hop_batch: words = %u is not in 1 .. %u (0: the default)", words, HOP_WORDS);
+  h->hop_words = words ? words : HOP_WORDS;
+  h->hop_chunk = levels_per_chunk ? levels_per_chunk : HOP_CHUNK;
+  return 0;
+}
+
+int svils_ppc_hops(svils_ppc *h) {
+  if (int rc = check(h, "svils_ppc_hops")) return rc;
+  if (!h->have_list) return fail(SVILS_ERR_ARG, "svils_ppc_hops: no list yet (svils_ppc_draw / svils_ppc_set_links)");
+  const uint32_t n = h->n, W = h->hop_words, per = 64 * W;
+  const size_t table = (size_t)n * W, ncnt = (size_t)n + 2;
+  const auto scope = ToolHandle::HANDLE;
+  hipStream_t st = h->st;
+  if (int rc = h->need_events(8)) return rc;
+  if (int rc = h->reserve(scope, &h->hvis, table)) return rc;
+  if (int rc = h->reserve(scope, &h->hfa, table)) return rc;
+  if (int rc = h->reserve(scope, &h->hfb, table)) return rc;
+  if (int rc = h->reserve(scope, &h->hopc, ncnt + 2 * HOP_WORDS)) return rc;
+  if (int rc = h->reserve(scope, &h->hopd, (size_t)n + 1)) return rc;
+  if (int rc = h->reserve(scope, &h->hecc, (size_t)n)) return rc;
+  if (int rc = h->reserve(scope, &h->hcomp, (size_t)n)) return rc;
+  h->hops_done = false;
+  unsigned long long *cnt = h->hopc, *mask = h->hopc + ncnt;
+  uint64_t launches = 0;
+  HIPCHK(hipEventRecord(h->ev[6], st));
+  HIPCHK(hipMemsetAsync(h->hopd, 0, ((size_t)n + 1) * sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(h->hecc, 0, (size_t)n * sizeof(uint32_t), st));
+  HIPCHK(hipMemsetAsync(h->hcomp, 0xff, (size_t)n * sizeof(uint32_t), st));   // NONE
+  for (uint32_t s0 = 0; s0 < n; s0 += per) {   // passes in ascending source order: the labels depend on it
+    const uint32_t nsrc = std::min(per, n - s0);
+    HIPCHK(hipMemsetAsync(h->hopc, 0, (ncnt + 2 * HOP_WORDS) * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_hop_seed, dim3(blocks(table, 256)), dim3(256), 0, st, n, W, s0, nsrc, h->hvis, h->hfa, cnt);
+    ++launches;
+    unsigned long long *cur = h->hfa, *nxt = h->hfb;
+    // levels 1 .. n: no distance exceeds n - 1, so level n is empty whatever the graph
+    for (uint32_t level = 1; level <= n;) {
+      const uint32_t m = std::min(h->hop_chunk, n - level + 1);
+      for (uint32_t i = 0; i < m; ++i, ++level) {
+        hipLaunchKernelGGL(kHopLevel[W - 1], dim3(blocks(n, 16)), dim3(256), 0, st, n, level, s0, nsrc, h->rowptr, h->scol, cur, nxt, h->hvis, cnt, mask,
+                           h->hecc);
+        std::swap(cur, nxt);
+      }
+      launches += m;
+      HIPCHK(hipGetLastError());
+      unsigned long long last = 0;   // the chunk's last level: empty, and so is every later one
+      HIPCHK(hipMemcpyAsync(&last, cnt + (level - 1), sizeof last, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (!last) break;
+    }
+    hipLaunchKernelGGL(k_hop_close, dim3(blocks((uint64_t)n + 1, 256)), dim3(256), 0, st, n, W, s0, h->hvis, cnt, h->hopd, h->hcomp);
+    ++launches;
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev[7], st));
+  std::vector<uint64_t> D((size_t)n + 1);
+  std::vector<uint32_t> deg(n);
+  h->ecc.assign(n, 0);
+  h->comp.assign(n, 0);
+  HIPCHK(hipMemcpyAsync(D.data(), h->hopd, D.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h->ecc.data(), h->hecc, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h->comp.data(), h->hcomp, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(deg.data(), h->deg, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  h->hop_launches = launches;
+  h->hops_timed = true;
+  // the summary, in index order
+  uint32_t levels = 1;
+  for (uint32_t l = 1; l < n; ++l)
+    if (D[l]) levels = l + 1;
+  D.resize(levels);
+  std::vector<uint64_t> cum(levels), size(n, 0);
+  uint64_t run = 0, far = 0, components = 0, largest = 0, isolated = 0;
+  for (uint32_t l = 0; l < levels; ++l) {
+    run += D[l];
+    cum[l] = run;
+    far += (uint64_t)l * D[l];
+  }
+  for (uint32_t v = 0; v < n; ++v) {
+    if (h->comp[v] >= n) return fail(SVILS_ERR_DEVICE, "svils_ppc_hops: node %u has no component", v);
+    components += h->comp[v] == v;
+    largest = std::max(largest, ++size[h->comp[v]]);
+    isolated += deg[v] == 0;
+  }
+  const uint64_t reachable = run - n;
+  h->hop_counts[0] = reachable;
+  h->hop_counts[1] = levels - 1;
+  h->hop_counts[2] = components;
+  h->hop_counts[3] = largest;
+  h->hop_counts[4] = isolated;
+  h->hop_counts[5] = levels;
+  h->hop_values[0] = effective_diameter(cum);
+  h->hop_values[1] = reachable ? (double)far / (double)reachable : (double)NAN;
+  h->hopD.swap(D);
+  h->hops_done = true;
+  return 0;
+}
+
+int svils_ppc_get_hops(svils_ppc *h, uint32_t *levels, uint64_t *D, uint32_t cap) {
+  if (int rc = check_hops(h, "svils_ppc_get_hops")) return rc;
+  if (levels) *levels = (uint32_t)h->hopD.size();
+  if (D) memcpy(D, h->hopD.data(), std::min<size_t>(h->hopD.size(), cap) * sizeof(uint64_t));
+  return 0;
+}
+
+int svils_ppc_get_hop_nodes(svils_ppc *h, uint32_t *ecc, uint32_t *comp) {
+  if (int rc = check_hops(h, "svils_ppc_get_hop_nodes")) return rc;
+  if (ecc) memcpy(ecc, h->ecc.data(), (size_t)h->n * sizeof(uint32_t));
+  if (comp) memcpy(comp, h->comp.data(), (size_t)h->n * sizeof(uint32_t));
+  return 0;
+}
+
+int svils_ppc_get_hop_summary(svils_ppc *h, uint64_t counts[6], double values[2]) {
+  if (int rc = check_hops(h, "svils_ppc_get_hop_summary")) return rc;
+  if (counts) memcpy(counts, h->hop_counts, sizeof h->hop_counts);
+  if (values) memcpy(values, h->hop_values, sizeof h->hop_values);
+  return 0;
+}
+
+int svils_ppc_get_hop_timing(svils_ppc *h, double ms[2]) {
+  if (int rc = check(h, "svils_ppc_get_hop_timing")) return rc;
+  if (!ms) return fail(SVILS_ERR_ARG, "svils_ppc_get_hop_timing: null argument");
+  HIPCHK(hipStreamSynchronize(h->st));
+  ms[0] = h->hops_timed ? h->elapsed_ms(6, 7, true) : -1.0;
+  ms[1] = h->hops_timed ? (double)h->hop_launches : -1.0;
   return 0;
 }
 

@@ -42,6 +42,7 @@ class Env {
     int ppc_draws = 100;                // -ppc-draws (ppc_ndraws, src/env.hh:452)
     int ppc_save = 0;                   // -ppc-save <m>: the networks of the first m replicates
     bool ppc_mean = false;              // -ppc-mean: no parameter draws
+    bool ppc_hops = false;              // -ppc-hops: the hop plot and the components of every list (svils_ppc_hops)
     bool load = false;
     std::string location;
     bool val_load = false;

@@ -74,6 +74,10 @@ static const ToolMode kPosterior = {         // -ppc / -gen: replicates of a sav
     F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
         F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %2$s is not available with %1$s (a single-GPU tool: it fits nothing)\n"};
+static const ToolMode kHops = {              // -ppc-hops: one more call per list of a -ppc run, and nothing else
+    F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
+        F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
+    "error: %1$s is not available with %2$s (it adds the hop plot and the components to a -ppc run: it fits nothing)\n"};
 static const ToolMode kFindK = {             // -findk: whole iterations
     F_GPUS | F_KSHARD | F_SHARDED | F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
     "error: %2$s is not available with %1$s (a single-GPU run)\n"};
@@ -213,6 +217,12 @@ static void usage() {
           "\t\t\t-ppc-mean uses the posterior means instead; -ppc-save <m> writes ppc/<r>/network.dat of the first m.\n"
           "\t\t\tThe random stream is Philox4x32-10 keyed by -seed and the replicate, not the reference's GSL stream:\n"
           "\t\t\tthat one is not reproduced.  -n <= 32768, -k <= 2048, single GPU, no host route\n\n"
+          "\t-ppc-hops\twith -ppc: the exact hop plot and the components of the observed network and of every replicate\n"
+          "\t\t\t(all-sources BFS on the GPU): obs-hop.txt and ppc/ppc-hop.txt (effective diameters, the reference's\n"
+          "\t\t\tnames), ppc/obs-hops.txt (h, pairs at distance h, cumulative), ppc/rep-hops.txt (r, effective diameter,\n"
+          "\t\t\tdiameter, mean distance, components, largest component, isolated nodes) and ppc/hops-summary.txt in the\n"
+          "\t\t\tcolumns of ppc/summary.txt.  One launch per BFS level: a long-diameter network is slow.  Refused\n"
+          "\t\t\twithout -ppc, with -gen and with every fitting flag\n\n"
           "\t-gen\t\tgenerate a network from the model (-n, -k, -seed): pi ~ Dirichlet(0.05), beta ~ Beta(4700.59, 0.77);\n"
           "\t\t\twrites gen/network_gen.dat, gen/pi-gen.txt, gen/beta-gen.txt.  The same stream and limits as -ppc;\n"
           "\t\t\t-gen -orig, -disjoint and -gp are not implemented\n\n"
@@ -366,6 +376,7 @@ int main(int argc, char **argv) {
     else if (is("-ppc-draws")) { need(i); a.ppc_draws = atoi(argv[++i]); }
     else if (is("-ppc-save")) { need(i); a.ppc_save = atoi(argv[++i]); }
     else if (is("-ppc-mean")) { a.ppc_mean = true; }
+    else if (is("-ppc-hops")) { a.ppc_hops = true; }
     else if (is("-single") ||
              is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
@@ -376,6 +387,21 @@ int main(int argc, char **argv) {
   }
   const bool sampled = a.rnode || a.rpair;
   const bool infset = a.infset || a.preprocess;
+  if (a.ppc_hops && !unsupported) {                      // -ppc-hops: beside -ppc alone; refusals before anything is read or created
+    if (refused(a, kHops, "-ppc-hops")) return 2;
+    const struct { bool set; const char *name; } more[] = {
+        {a.gen, "-gen"}, {a.orig, "-orig"}, {a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.batch_gpu, "-batch-gpu"},
+        {a.load, "-load"}, {a.snode, "-snode"}};
+    for (const auto &m : more)
+      if (m.set) {
+        fprintf(stderr, kHops.fmt, "-ppc-hops", m.name);
+        return 2;
+      }
+    if (!a.ppc) {
+      fprintf(stderr, "error: -ppc-hops belongs to -ppc runs (the hop plot and the components of the observed network and of every replicate)\n");
+      return 2;
+    }
+  }
   if ((a.ppc || a.gen) && !unsupported) {                // -ppc / -gen (MMSBGen): refusals before anything is read or created
     const char *flag = a.gen ? "-gen" : "-ppc";
     if (a.ppc && a.gen) {
@@ -723,6 +749,7 @@ run:
       po.seed = (uint32_t)a.rand_seed;
       po.save = (uint32_t)a.ppc_save;
       po.mean = a.ppc_mean;
+      po.hops = a.ppc_hops;
       exit(run_ppc(env, network, po) < 0 ? 255 : 0);
     }
     if (a.findk) {                           // src/main.cc:321-327, before the other engines (-batch / -link-sampling only name the directory)

@@ -132,6 +132,19 @@ struct Moments {
   }
 };
 
+// -ppc-hops: what svils_ppc_hops says of one list
+struct Hops {
+  double effdiam, meandist;
+  uint64_t diameter, components, largest, isolated;
+  std::vector<uint64_t> D;
+};
+
+// a row of summary.txt / hops-summary.txt: statistic, observed, replicate mean, deviation, two-sided posterior predictive p-value
+std::string summary_row(const char *name, double obs, const std::vector<double> &x, int digits) {
+  const Moments m(x, obs);
+  return std::string(name) + "\t" + fx(obs, digits) + "\t" + fx(m.mean, digits) + "\t" + fx(m.sd, digits) + "\t" + fx(m.p) + "\n";
+}
+
 struct Handle {
   svils_ppc *h = nullptr;
   uint32_t n, k;
@@ -158,6 +171,16 @@ struct Handle {
     s.avgdeg = (double)(2 * c[0]) / (double)n;
     s.transitivity = v[0];
     s.clustering = v[1];
+    return s;
+  }
+  Hops hops() {
+    if (int rc = svils_ppc_hops(h)) throw_svils("svils_ppc_hops", rc);
+    uint64_t c[6];
+    double v[2];
+    if (int rc = svils_ppc_get_hop_summary(h, c, v)) throw_svils("svils_ppc_get_hop_summary", rc);
+    Hops s{v[0], v[1], c[1], c[2], c[3], c[4], std::vector<uint64_t>(c[5])};
+    uint32_t levels = 0;
+    if (int rc = svils_ppc_get_hops(h, &levels, s.D.data(), (uint32_t)s.D.size())) throw_svils("svils_ppc_get_hops", rc);
     return s;
   }
   std::vector<uint32_t> links() {
@@ -222,6 +245,19 @@ int run_ppc(Env &env, Network &network, const PpcOptions &opt) {
   write_file("obs-ones.txt", fx(obs.density) + "\n");            // obs_ones, obs_avg_deg (:640-660)
   write_file("obs-avg-deg.txt", fx(obs.avgdeg) + "\n");
   write_file("obs-max-deg.txt", std::to_string(obs.maxdeg) + "\n");
+  Hops obs_hops{};
+  std::vector<Hops> rep_hops;
+  if (opt.hops) {                                               // ppc_avg_deg's hop.ppc.tab (:340-380): exact here, nstat's is an estimate
+    obs_hops = h.hops();
+    std::string t;
+    uint64_t c = 0;
+    for (size_t l = 0; l < obs_hops.D.size(); ++l) {
+      c += obs_hops.D[l];
+      t += std::to_string(l) + "\t" + std::to_string(obs_hops.D[l]) + "\t" + std::to_string(c) + "\n";
+    }
+    write_file("ppc/obs-hops.txt", t);
+    write_file("obs-hop.txt", fx(obs_hops.effdiam) + "\n");
+  }
   std::vector<Scalars> rep;
   std::string rows, ones, avg, mx;
   if (!opt.mean) {
@@ -243,6 +279,7 @@ int run_ppc(Env &env, Network &network, const PpcOptions &opt) {
     ones += fx(s.density) + "\n";                               // ppc_ones, ppc_avg_deg (:339-362, :632-638)
     avg += fx(s.avgdeg) + "\n";
     mx += std::to_string(s.maxdeg) + "\n";
+    if (opt.hops) rep_hops.push_back(h.hops());
     if (r < opt.save) {
       make_dir("ppc/" + std::to_string(r));
       write_links("ppc/" + std::to_string(r) + "/network.dat", h.links());
@@ -279,10 +316,29 @@ int run_ppc(Env &env, Network &network, const PpcOptions &opt) {
   for (const auto &c : cols) {
     auto val = [&](const Scalars &s) { return c.d ? s.*(c.d) : (double)(s.*(c.u)); };
     for (uint32_t r = 0; r < R; ++r) x[r] = val(rep[r]);
-    const Moments m(x, val(obs));
-    sm += std::string(c.name) + "\t" + fx(val(obs), c.digits) + "\t" + fx(m.mean, c.digits) + "\t" + fx(m.sd, c.digits) + "\t" + fx(m.p) + "\n";
+    sm += summary_row(c.name, val(obs), x, c.digits);
   }
   write_file("ppc/summary.txt", sm);
+  if (opt.hops) {
+    std::string eff, rh, hs;
+    for (uint32_t r = 0; r < R; ++r) {
+      const Hops &s = rep_hops[r];
+      eff += fx(s.effdiam) + "\n";
+      rh += std::to_string(r) + "\t" + fx(s.effdiam) + "\t" + std::to_string(s.diameter) + "\t" + fx(s.meandist) + "\t" +
+            std::to_string(s.components) + "\t" + std::to_string(s.largest) + "\t" + std::to_string(s.isolated) + "\n";
+    }
+    write_file("ppc/ppc-hop.txt", eff);
+    write_file("ppc/rep-hops.txt", rh);
+    const struct { const char *name; double Hops::*d; uint64_t Hops::*u; } hcols[] = {
+        {"effdiam", &Hops::effdiam, nullptr},       {"diameter", nullptr, &Hops::diameter}, {"meandist", &Hops::meandist, nullptr},
+        {"components", nullptr, &Hops::components}, {"largest", nullptr, &Hops::largest},   {"isolated", nullptr, &Hops::isolated}};
+    for (const auto &c : hcols) {
+      auto val = [&](const Hops &s) { return c.d ? s.*(c.d) : (double)(s.*(c.u)); };
+      for (uint32_t r = 0; r < R; ++r) x[r] = val(rep_hops[r]);
+      hs += summary_row(c.name, val(obs_hops), x, 5);
+    }
+    write_file("ppc/hops-summary.txt", hs);
+  }
   printf("+ wrote ppc/summary.txt (%u replicates)\n", R);
   return 0;
 }

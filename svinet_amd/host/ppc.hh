@@ -34,6 +34,7 @@ struct PpcOptions {
   uint32_t seed = 0;      // -seed
   uint32_t save = 0;      // -ppc-save <m>: ppc/<r>/network.dat of the first m replicates
   bool mean = false;      // -ppc-mean: every replicate from pi = gamma / sum, beta = l0 / (l0 + l1)
+  bool hops = false;      // -ppc-hops: obs-hop.txt, ppc/ppc-hop.txt, ppc/obs-hops.txt, ppc/rep-hops.txt, ppc/hops-summary.txt
 };
 
 // -ppc in the output directory of a fit: gamma.txt / lambda.txt, files under ppc/ and the reference's obs-*.txt.

@@ -854,6 +854,33 @@ class PPC:
         out["timing_ms"] = {"draw": ms[0], "csr": ms[1], "stats": ms[2]}
         return out
 
+    def set_hop_batch(self, words=0, levels_per_chunk=0):
+        """64-bit words per node of a BFS pass (1 .. 8; a pass runs 64 x words sources) and the levels queued between two
+        reads of the level counter; 0: the default.  No result depends on it"""
+        _svils._chk(_svils.load().svils_ppc_set_hop_batch(self._h, int(words), int(levels_per_chunk)))
+
+    def hops(self):
+        """the exact hop plot and the components of the current list, as a dict: D [levels] (ordered
+        pairs at distance h, D[0] = n), ecc, comp [n]; effdiam, meandist; reachable, diameter, components, largest, isolated"""
+        L, ok = _svils.load(), _svils._chk
+        ok(L.svils_ppc_hops(self._h))
+        counts, values = np.zeros(6, np.uint64), np.zeros(2, np.float64)
+        ok(L.svils_ppc_get_hop_summary(self._h, counts.ctypes.data, values.ctypes.data))
+        out = {"D": np.zeros(int(counts[5]), np.uint64), "ecc": np.zeros(self.n, np.uint32), "comp": np.zeros(self.n, np.uint32)}
+        levels = C.c_uint32()
+        ok(L.svils_ppc_get_hops(self._h, C.byref(levels), out["D"].ctypes.data, out["D"].shape[0]))
+        ok(L.svils_ppc_get_hop_nodes(self._h, out["ecc"].ctypes.data, out["comp"].ctypes.data))
+        out["effdiam"], out["meandist"] = float(values[0]), float(values[1])
+        for name, v in zip(("reachable", "diameter", "components", "largest", "isolated"), counts):
+            out[name] = int(v)
+        return out
+
+    def hop_timing(self):
+        """(device ms of the last hops(), kernel launches it queued); (-1, -1) before the first"""
+        ms = np.zeros(2, np.float64)
+        _svils._chk(_svils.load().svils_ppc_get_hop_timing(self._h, ms.ctypes.data))
+        return float(ms[0]), int(ms[1])
+
     def close(self):
         if getattr(self, "_h", None):
             _svils.load().svils_ppc_destroy(self._h)
