@@ -50,6 +50,7 @@ extern "C" {
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_ppc_*: -ppc / -gen, networks drawn from a model and their statistics;
                                     (additive, same version) svils_ppc_hops / svils_ppc_get_hop*: -ppc-hops, the exact hop plot and components;
+                                    (additive, same version) svils_ppc_set_params_orig / svils_ppc_get_blocks: -ppc-orig, the same checks of a K x K blockmodel;
                                     (additive, same version) svils_nbr_score / svils_nbr_rank: common-neighbour, Adamic-Adar and
                                     resource-allocation scores of pairs, the model-free baselines of svils_rank_links */
 
@@ -969,6 +970,29 @@ int svils_ppc_get_communities(svils_ppc *h, uint64_t *size, double *logpe);
 int svils_ppc_get_timing(svils_ppc *h, double ms[3]);
 /* tiles per launch of the draw (0: all in one launch); no result depends on it */
 int svils_ppc_set_tile_batch(svils_ppc *h, uint32_t tiles_per_launch);
+
+/* -ppc-orig: the same handle under the K x K blockmodel of svils_orig, the device side of the
+ * reference's MMSBOrig::gen / draw_and_save (src/mmsborig.cc:25-116) taken marginally over its two indicators.  The random
+ * numbers, the statistics that name no community and every other entry point (svils_ppc_draw, _set_links, _stats, _get_links,
+ * _get_nodes, _get_summary, _get_draw_counts, _get_timing, _set_tile_batch, svils_ppc_hop*) are the ones above; what changes:
+ *   link       for p < q: x_gh = (pi_p[g] pi_q[h]) B[g][h], s = ONE running fp64 sum of x_gh over g ascending and, within
+ *              g, h ascending, nothing contracted; y = (u < s).  The smaller id indexes the rows of B (draw_and_save visits
+ *              i < j with rate beta[z_i][z_j]).  For a diagonal B every off-diagonal term adds an exact zero: s, and with it
+ *              the whole draw, is the assortative one's bit for bit.  The tile kernel sums sum_h aq_p[h] pi_q[h] with
+ *              aq_p[h] = sum_g pi_p[g] B[g][h] (fma, g ascending); a pair whose tile sum lies within
+ *              (K^2 + 2 K + 18) DBL_EPSILON s of u is decided again with the definition's sum, and counted
+ *   block      of a link: the first strict maximum x_max of x in row-major (g, h) order from (0, 0); colour = g K + h;
+ *              ratio = x_max / s, joined unless ratio < 0.5 (a NaN ratio joins)
+ *   statistics in place of size_k / logpe_k: bsize[g][h] = the joined links of block (g, h), blogpe[g][h] = the sum of
+ *              log x_max over them in the same exact bins (0 for an empty block, -inf where a joined link has x_max = 0)
+ * pi as svils_ppc_set_params; B [k][k] row-major, every entry finite and in [0, 1] (else SVILS_ERR_ARG), not necessarily
+ * symmetric.  A handle of k < 2 or k > SVILS_ORIG_MAX_K: SVILS_ERR_UNSUPPORTED before any device call.  The first call
+ * allocates B and 38 x k^2 counters.  A handle may change kinds at will: the last svils_ppc_set_params* decides, and it
+ * invalidates the statistics, not the list.  svils_ppc_get_communities answers SVILS_ERR_ARG while the K x K kind is
+ * current, svils_ppc_get_blocks while the assortative one is. */
+int svils_ppc_set_params_orig(svils_ppc *h, const double *pi, const double *B);
+/* after svils_ppc_stats under the K x K kind: bsize [k][k], blogpe [k][k] (either may be null) */
+int svils_ppc_get_blocks(svils_ppc *h, uint64_t *bsize, double *blogpe);
 
 /* -ppc-hops: the exact hop plot and the components of the current list, an undirected simple graph
  * on n nodes.  d(s, v) is the BFS distance (infinite across components, d(s, s) = 0).

@@ -54,6 +54,7 @@ EXPORTS = (
     "svils_ppc_get_timing", "svils_ppc_set_tile_batch",
     "svils_ppc_hops", "svils_ppc_get_hops", "svils_ppc_get_hop_nodes", "svils_ppc_get_hop_summary", "svils_ppc_set_hop_batch",
     "svils_ppc_get_hop_timing",
+    "svils_ppc_set_params_orig", "svils_ppc_get_blocks",
 )
 PPC_MAX_N, PPC_MAX_K = 32768, 2048      # SVILS_PPC_MAX_N, SVILS_PPC_MAX_K
 ORIG_MAX_K, ORIG_MAX_N = 64, 32768      # SVILS_ORIG_MAX_K, SVILS_ORIG_MAX_N
@@ -259,6 +260,8 @@ def load():
     L.svils_ppc_get_hop_summary.argtypes = [vp, vp, vp]
     L.svils_ppc_set_hop_batch.argtypes = [vp, C.c_uint32, C.c_uint32]
     L.svils_ppc_get_hop_timing.argtypes = [vp, vp]
+    L.svils_ppc_set_params_orig.argtypes = [vp, vp, vp]
+    L.svils_ppc_get_blocks.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         f = getattr(L, name)
         if name not in ("svils_last_error", "svils_kernel_name", "svils_abi_version", "svils_stochastic_default", "svils_option_table"):

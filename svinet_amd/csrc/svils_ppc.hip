@@ -19,6 +19,9 @@
 //                 common neighbours of p and q by the search of svils_nbr.hip (the shorter sorted row against the
 //                 longer).  size_k and the triangle counts are integer atomics; -log x_max goes into 32-bit-wide integer
 //                 bins per community (three adds per link), which hold the sum exactly in any order
+// The same handle serves the K x K blockmodel of svils_orig (svils_ppc_set_params_orig): a model kind
+// is a policy struct (Assortative, Blockmodel) that k_draw_tiles and k_link_stats are instantiated with -- the terms of a
+// pair, the definition's sequential sum and the band of the recheck; k_ppc_aq makes the query operand pi B.
 // The O(n) and O(K) closings -- wedges, the largest degree, the mean local clustering, the bins to a double -- run on
 // the host in index order.
 //
@@ -68,11 +71,57 @@ __device__ __forceinline__ double pair_uniform(uint32_t seed, uint32_t r, uint32
   return (double)(((uint64_t)(w0 >> 5) << 26) | (uint64_t)(w1 >> 6)) * 0x1p-53;
 }
 
-// the definition's s: (pi_p[j] pi_q[j]) beta_j summed in ascending j
-__device__ inline double seq_sum(const double *__restrict__ a, const double *__restrict__ b, const double *__restrict__ beta, uint32_t K) {
-  double s = 0;
-  for (uint32_t j = 0; j < K; ++j) s += (a[j] * b[j]) * beta[j];
-  return s;
+// A model kind is a policy passed by value to the draw and to the statistics: the terms x_t of a pair (a = pi_p, b = pi_q,
+// p < q) and the definition's s, ONE running sum over them in ascending t.  The tile sum and the fixed trees are held to
+// it within band(K) relative: a pair or a ratio that close to its threshold is decided again with sum().
+//
+// Assortative (section 4l): x_j = (pi_p[j] pi_q[j]) beta_j, K terms
+struct Assortative {
+  const double *__restrict__ beta;
+  static double band(uint32_t K) { return 2.0 * (double)K * DBL_EPS; }
+  __device__ __forceinline__ uint32_t terms(uint32_t K) const { return K; }
+  __device__ __forceinline__ double term(const double *__restrict__ a, const double *__restrict__ b, uint32_t, uint32_t t) const {
+    return (a[t] * b[t]) * beta[t];
+  }
+  __device__ inline double sum(const double *__restrict__ a, const double *__restrict__ b, uint32_t K) const {
+    double s = 0;
+    for (uint32_t j = 0; j < K; ++j) s += (a[j] * b[j]) * beta[j];
+    return s;
+  }
+};
+
+// K x K (section 4p): x_gh = (pi_p[g] pi_q[h]) B[g][h], K^2 terms in row-major t = g K + h; the smaller id indexes the rows
+// of B.  The definition's sum has at most K^2 + 1 roundings per term, the tile sum K + k16 + 1 (k_ppc_aq, then the MFMA
+// chain), k16 <= K + 15: they differ by less than (K^2 + 2 K + 18) DBL_EPSILON / 2 of s, half the band
+struct Blockmodel {
+  const double *__restrict__ B;
+  static double band(uint32_t K) { return ((double)K * (double)K + 2.0 * (double)K + 18.0) * DBL_EPS; }
+  __device__ __forceinline__ uint32_t terms(uint32_t K) const { return K * K; }
+  __device__ __forceinline__ double term(const double *__restrict__ a, const double *__restrict__ b, uint32_t K, uint32_t t) const {
+    const uint32_t g = t / K;
+    return (a[g] * b[t - g * K]) * B[t];
+  }
+  __device__ inline double sum(const double *__restrict__ a, const double *__restrict__ b, uint32_t K) const {
+    double s = 0;
+    for (uint32_t g = 0; g < K; ++g)
+      for (uint32_t h = 0; h < K; ++h) s += (a[g] * b[h]) * B[g * K + h];
+    return s;
+  }
+};
+
+// the query operand of the K x K kind: aq[i][h] = sum_g pi_i[g] B[g][h], g ascending by fma (as k_orig_aq), zero past
+// column K and past row n.  For a diagonal B row i is pi_i[h] B[h][h] rounded once: the assortative operand, bit for bit
+__global__ __launch_bounds__(256) void k_ppc_aq(uint32_t rows, uint32_t n, uint32_t K, uint32_t ld, uint32_t k16, const double *__restrict__ pi,
+                                                const double *__restrict__ B, double *__restrict__ aq) {
+  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (uint64_t)rows * k16) return;
+  const uint32_t i = (uint32_t)(e / k16), h = (uint32_t)(e % k16);
+  double s = 0.0;
+  if (i < n && h < K) {
+    const double *row = pi + (size_t)i * ld;
+    for (uint32_t g = 0; g < K; ++g) s = fma(row[g], B[(size_t)g * K + h], s);
+  }
+  aq[e] = s;
 }
 
 // tile t of the upper triangle of nt x nt tiles, row by row: (tp, tq) with tp <= tq
@@ -87,9 +136,10 @@ __device__ inline void tile_of(uint32_t t, uint32_t nt, uint32_t *tp, uint32_t *
   *tq = (uint32_t)(r + ((int64_t)t - off(r)));
 }
 
+template <class M>
 __global__ __launch_bounds__(256) void k_draw_tiles(uint32_t t0, uint32_t t1, uint32_t n, uint32_t K, uint32_t ld, uint32_t k16,
                                                     uint32_t nt, const double *__restrict__ pi, const double *__restrict__ aq,
-                                                    const double *__restrict__ beta, uint32_t seed, uint32_t rep, double band,
+                                                    const M model, uint32_t seed, uint32_t rep, double band,
                                                     unsigned long long *__restrict__ bits, unsigned long long *__restrict__ nrecheck) {
   __shared__ double S[PQ][PC + 1];
   __shared__ unsigned long long RM[64];
@@ -112,7 +162,7 @@ __global__ __launch_bounds__(256) void k_draw_tiles(uint32_t t0, uint32_t t1, ui
       double s = S[row][c];
       const double u = pair_uniform(seed, rep, p, q);
       if (fabs(s - u) <= band * s) {
-        s = seq_sum(pi + (size_t)p * ld, pi + (size_t)q * ld, beta, K);
+        s = model.sum(pi + (size_t)p * ld, pi + (size_t)q * ld, K);
         atomicAdd(nrecheck, 1ull);
       }
       if (u < s) mask |= 1ull << c;
@@ -234,18 +284,10 @@ __global__ __launch_bounds__(256) void k_fill(uint32_t n, uint32_t nw, const uns
   }
 }
 
-// one link per wavefront, four per block
-__global__ __launch_bounds__(256) void k_link_stats(uint64_t E, uint32_t K, uint32_t ld, const uint32_t *__restrict__ links,
-                                                    const double *__restrict__ pi, const double *__restrict__ beta,
-                                                    const uint64_t *__restrict__ rowptr, const uint32_t *__restrict__ scol, double band,
-                                                    uint32_t *__restrict__ colour, uint8_t *__restrict__ joined, uint32_t *__restrict__ t2,
-                                                    unsigned long long *__restrict__ tri3, unsigned long long *__restrict__ size,
-                                                    unsigned long long *__restrict__ bins, uint32_t *__restrict__ ninf) {
-  const uint64_t x = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63;
-  if (x >= E) return;   // whole wavefronts leave together
-  const uint32_t p = links[2 * x], q = links[2 * x + 1];
-  // the common neighbours of p and q: the shorter sorted row, 64 entries at a time, searched for in the longer one
+// the common neighbours of p and q, by a whole wavefront: the shorter sorted row, 64 entries at a time, searched for in the
+// longer one.  Every lane returns the count
+__device__ __forceinline__ uint32_t common_neighbours(const uint64_t *__restrict__ rowptr, const uint32_t *__restrict__ scol, uint32_t p,
+                                                      uint32_t q, uint32_t lane) {
   uint64_t ab = rowptr[p], ae = rowptr[p + 1], bb = rowptr[q], be = rowptr[q + 1];
   if (ae - ab > be - bb) {
     uint64_t s = ab; ab = bb; bb = s;
@@ -256,13 +298,49 @@ __global__ __launch_bounds__(256) void k_link_stats(uint64_t E, uint32_t K, uint
     const bool hit = base + lane < ae && in_row(scol, bb, be, scol[base + lane]);
     common += (uint32_t)__popcll(__ballot(hit));
   }
+  return common;
+}
+
+// -log m = mant 2^e >= 0 (0 < m <= 1) into the NBIN bins of `row`: bin b holds units of 2^(32 b - BIN_BIAS)
+__device__ __forceinline__ void add_neg_log(unsigned long long *__restrict__ row, double m) {
+  const double v = -log(m);
+  if (!(v > 0)) return;
+  int ex;
+  const double fr = frexp(v, &ex);                              // v = fr 2^ex, fr in [0.5, 1)
+  const unsigned long long mant = (unsigned long long)ldexp(fr, 53);   // 53 bits, exact
+  const int e = ex - 53 + BIN_BIAS;                             // v = mant 2^(ex - 53); v >= 2^-54, so e > 0
+  if (e < 0 || ((uint32_t)e >> 5) + 2 >= NBIN) return;         // no -log of a double in (0, 1) lies out there
+  const uint32_t bin = (uint32_t)e >> 5, sh = (uint32_t)e & 31;
+  row += bin;
+  const unsigned long long rest = mant >> (32 - sh);            // (mant << sh) >> 32, mant << sh being up to 84 bits wide
+  const unsigned long long p0 = (mant << sh) & 0xffffffffull, p1 = rest & 0xffffffffull, p2 = rest >> 32;
+  if (p0) atomicAdd(row, p0);
+  if (p1) atomicAdd(row + 1, p1);
+  if (p2) atomicAdd(row + 2, p2);
+}
+
+// one link per wavefront, four per block.  The terms of the link go over the lanes in ascending t (lane, lane + 64, ...),
+// so a lane's first strict maximum is the first in t among its own; size, bins and ninf have one entry (row) per term
+// index: K communities (Assortative) or K^2 blocks (Blockmodel, section 4p)
+template <class M>
+__global__ __launch_bounds__(256) void k_link_stats(uint64_t E, uint32_t K, uint32_t ld, const uint32_t *__restrict__ links,
+                                                    const double *__restrict__ pi, const M model,
+                                                    const uint64_t *__restrict__ rowptr, const uint32_t *__restrict__ scol, double band,
+                                                    uint32_t *__restrict__ colour, uint8_t *__restrict__ joined, uint32_t *__restrict__ t2,
+                                                    unsigned long long *__restrict__ tri3, unsigned long long *__restrict__ size,
+                                                    unsigned long long *__restrict__ bins, uint32_t *__restrict__ ninf) {
+  const uint64_t x = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (x >= E) return;   // whole wavefronts leave together
+  const uint32_t p = links[2 * x], q = links[2 * x + 1];
+  const uint32_t common = common_neighbours(rowptr, scol, p, q, lane);
   const double *a = pi + (size_t)p * ld, *b = pi + (size_t)q * ld;
   double s = 0, u = 0;
   uint32_t idx = NONE;
-  for (uint32_t k = lane; k < K; k += 64) {
-    const double v = (a[k] * b[k]) * beta[k];
+  for (uint32_t t = lane, T = model.terms(K); t < T; t += 64) {
+    const double v = model.term(a, b, K, t);
     s += v;
-    if (v > u) { u = v; idx = k; }
+    if (v > u) { u = v; idx = t; }
   }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   double m = u;
@@ -272,7 +350,7 @@ __global__ __launch_bounds__(256) void k_link_stats(uint64_t E, uint32_t K, uint
   if (lane != 0) return;
   if (wi == NONE) wi = 0;   // all terms 0: idx stays 0, the ratio is 0 / 0
   double ratio = m / s;
-  if (fabs(ratio - 0.5) <= band * ratio) ratio = m / seq_sum(a, b, beta, K);
+  if (fabs(ratio - 0.5) <= band * ratio) ratio = m / model.sum(a, b, K);
   const bool join = !(ratio < 0.5);
   colour[x] = wi;
   joined[x] = join ? 1 : 0;
@@ -287,21 +365,7 @@ __global__ __launch_bounds__(256) void k_link_stats(uint64_t E, uint32_t K, uint
     atomicAdd(&ninf[wi], 1u);
     return;
   }
-  // -log x_max = mant 2^e >= 0 into the bins: bin b holds units of 2^(32 b - BIN_BIAS)
-  const double v = -log(m);
-  if (!(v > 0)) return;
-  int ex;
-  const double fr = frexp(v, &ex);                              // v = fr 2^ex, fr in [0.5, 1)
-  const unsigned long long mant = (unsigned long long)ldexp(fr, 53);   // 53 bits, exact
-  const int e = ex - 53 + BIN_BIAS;                             // v = mant 2^(ex - 53); v >= 2^-54, so e > 0
-  if (e < 0 || ((uint32_t)e >> 5) + 2 >= NBIN) return;         // no -log of a double in (0, 1) lies out there
-  const uint32_t bin = (uint32_t)e >> 5, sh = (uint32_t)e & 31;
-  unsigned long long *row = bins + (size_t)wi * NBIN + bin;
-  const unsigned long long rest = mant >> (32 - sh);            // (mant << sh) >> 32, mant << sh being up to 84 bits wide
-  const unsigned long long p0 = (mant << sh) & 0xffffffffull, p1 = rest & 0xffffffffull, p2 = rest >> 32;
-  if (p0) atomicAdd(row, p0);
-  if (p1) atomicAdd(row + 1, p1);
-  if (p2) atomicAdd(row + 2, p2);
+  add_neg_log(bins + (size_t)wi * NBIN, m);
 }
 
 // ---- hop plot and components (section 4o) ----
@@ -438,7 +502,13 @@ struct svils_ppc : ToolHandle {
   uint8_t *joined = nullptr;
   uint64_t *rowptr = nullptr, *uoff = nullptr;
   unsigned long long *size = nullptr, *bins = nullptr;
-  bool have_params = false, have_list = false, done = false, timed[3] = {false, false, false};
+  // the K x K kind (svils_ppc_set_params_orig; made by its first call): B [k][k], and one counter, one row of bins and one
+  // count of zero maxima per block
+  enum Kind { NO_MODEL, ASSORTATIVE, BLOCKMODEL } kind = NO_MODEL;
+  double *B = nullptr;
+  unsigned long long *bsize = nullptr, *bbins = nullptr;
+  uint32_t *bninf = nullptr;
+  bool have_list = false, done = false, timed[3] = {false, false, false};
   uint64_t last_count = 0, last_recheck = 0;
   // the statistics' closings (host)
   std::vector<uint32_t> hdeg, htri;
@@ -478,6 +548,42 @@ int build_lists(svils_ppc *h, uint64_t E) {
 int check_done(svils_ppc *h, const char *name) {
   if (int rc = check(h, name)) return rc;
   if (!h->done) return fail(SVILS_ERR_ARG, "%s: svils_ppc_stats has not run on the current list and parameters", name);
+  return 0;
+}
+
+// the conditions on pi [n][k] of both kinds, and hp = pi padded to the handle's even leading dimension (16-byte rows)
+int padded_pi(const svils_ppc *h, const char *name, const double *pi, std::vector<double> &hp) {
+  const uint32_t n = h->n, K = h->k, ld = h->ld;
+  hp.assign((size_t)n * ld, 0.0);
+  for (uint32_t i = 0; i < n; ++i) {
+    double s = 0;
+    for (uint32_t j = 0; j < K; ++j) {
+      const double v = pi[(size_t)i * K + j];
+      if (!(v >= 0.0) || !std::isfinite(v)) return fail(SVILS_ERR_ARG, "%s: pi[%u][%u] = %g is not a finite number >= 0", name, i, j, v);
+      s += v;
+      hp[(size_t)i * ld + j] = v;
+    }
+    if (!(std::fabs(s - 1.0) <= 1e-9)) return fail(SVILS_ERR_ARG, "%s: row %u of pi sums to %.17g, not 1 within 1e-9", name, i, s);
+  }
+  return 0;
+}
+
+// the joined links and the sum of log x_max of `cells` communities or blocks (either pointer may be null)
+int read_cells(size_t cells, const unsigned long long *dsize, const unsigned long long *dbins, const uint32_t *dninf, uint64_t *size,
+               double *logpe) {
+  if (size) HIPCHK(hipMemcpy(size, dsize, cells * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (!logpe) return 0;
+  std::vector<unsigned long long> bins(cells * NBIN);
+  std::vector<uint32_t> ninf(cells);
+  HIPCHK(hipMemcpy(bins.data(), dbins, bins.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ninf.data(), dninf, cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < cells; ++k) {
+    // the bins hold the sum exactly; from the top down, every term is a 64-bit integer times a power of two
+    long double s = 0;
+    for (int b = (int)NBIN - 1; b >= 0; --b)
+      if (bins[k * NBIN + b]) s += std::ldexp((long double)bins[k * NBIN + b], 32 * b - BIN_BIAS);
+    logpe[k] = ninf[k] ? -HUGE_VAL : (s > 0 ? -(double)s : 0.0);
+  }
   return 0;
 }
 
@@ -549,48 +655,74 @@ int svils_ppc_set_tile_batch(svils_ppc *h, uint32_t tiles_per_launch) {
 int svils_ppc_set_params(svils_ppc *h, const double *pi, const double *beta) {
   if (int rc = check(h, "svils_ppc_set_params")) return rc;
   if (!pi || !beta) return fail(SVILS_ERR_ARG, "svils_ppc_set_params: null argument");
-  const uint32_t n = h->n, K = h->k, ld = h->ld, k16 = h->k16;
+  const uint32_t n = h->n, K = h->k, k16 = h->k16;
   for (uint32_t j = 0; j < K; ++j)
     if (!(beta[j] >= 0.0 && beta[j] <= 1.0)) return fail(SVILS_ERR_ARG, "svils_ppc_set_params: beta[%u] = %g is not in [0, 1]", j, beta[j]);
-  for (uint32_t i = 0; i < n; ++i) {
-    double s = 0;
-    for (uint32_t j = 0; j < K; ++j) {
-      const double v = pi[(size_t)i * K + j];
-      if (!(v >= 0.0) || !std::isfinite(v)) return fail(SVILS_ERR_ARG, "svils_ppc_set_params: pi[%u][%u] = %g is not a finite number >= 0", i, j, v);
-      s += v;
-    }
-    if (!(std::fabs(s - 1.0) <= 1e-9)) return fail(SVILS_ERR_ARG, "svils_ppc_set_params: row %u of pi sums to %.17g, not 1 within 1e-9", i, s);
-  }
   // pi padded to an even leading dimension (16-byte rows), and the query operand pi beta padded to whole tiles
-  std::vector<double> hp((size_t)n * ld, 0.0), ha((size_t)h->nt * 64 * k16, 0.0);
+  std::vector<double> hp, ha((size_t)h->nt * 64 * k16, 0.0);
+  if (int rc = padded_pi(h, "svils_ppc_set_params", pi, hp)) return rc;
   for (uint32_t i = 0; i < n; ++i)
-    for (uint32_t j = 0; j < K; ++j) {
-      const double v = pi[(size_t)i * K + j];
-      hp[(size_t)i * ld + j] = v;
-      ha[(size_t)i * k16 + j] = v * beta[j];
-    }
+    for (uint32_t j = 0; j < K; ++j) ha[(size_t)i * k16 + j] = pi[(size_t)i * K + j] * beta[j];
   HIPCHK(hipStreamSynchronize(h->st));
   HIPCHK(hipMemcpy(h->pi, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->aq, ha.data(), ha.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->beta, beta, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
-  h->have_params = true;
+  h->kind = svils_ppc::ASSORTATIVE;
   h->done = false;
+  return 0;
+}
+
+int svils_ppc_set_params_orig(svils_ppc *h, const double *pi, const double *B) {
+  if (!h) return no_device_or_null("svils_ppc_set_params_orig");
+  if (h->k < 2 || h->k > SVILS_ORIG_MAX_K)
+    return fail(SVILS_ERR_UNSUPPORTED, "svils_ppc_set_params_orig: k = %u (the K x K kind holds 2 <= k <= SVILS_ORIG_MAX_K = %d)", h->k,
+                SVILS_ORIG_MAX_K);
+  if (int rc = check(h, "svils_ppc_set_params_orig")) return rc;
+  if (!pi || !B) return fail(SVILS_ERR_ARG, "svils_ppc_set_params_orig: null argument");
+  const uint32_t n = h->n, K = h->k;
+  const size_t KK = (size_t)K * K;
+  for (size_t t = 0; t < KK; ++t)
+    if (!(B[t] >= 0.0 && B[t] <= 1.0))
+      return fail(SVILS_ERR_ARG, "svils_ppc_set_params_orig: B[%u][%u] = %g is not in [0, 1]", (uint32_t)(t / K), (uint32_t)(t % K), B[t]);
+  std::vector<double> hp;
+  if (int rc = padded_pi(h, "svils_ppc_set_params_orig", pi, hp)) return rc;
+  const auto scope = ToolHandle::HANDLE;
+  if (int rc = h->reserve(scope, &h->B, KK)) return rc;
+  if (int rc = h->reserve(scope, &h->bsize, KK)) return rc;
+  if (int rc = h->reserve(scope, &h->bbins, KK * NBIN)) return rc;
+  if (int rc = h->reserve(scope, &h->bninf, KK)) return rc;
+  hipStream_t st = h->st;
+  HIPCHK(hipStreamSynchronize(st));
+  h->kind = svils_ppc::NO_MODEL;   // until the operand is whole
+  h->done = false;
+  HIPCHK(hipMemcpy(h->pi, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->B, B, KK * sizeof(double), hipMemcpyHostToDevice));
+  const uint32_t rows = h->nt * 64;
+  hipLaunchKernelGGL(k_ppc_aq, dim3(blocks((uint64_t)rows * h->k16, 256)), dim3(256), 0, st, rows, n, K, h->ld, h->k16, h->pi, h->B, h->aq);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  h->kind = svils_ppc::BLOCKMODEL;
   return 0;
 }
 
 int svils_ppc_draw(svils_ppc *h, uint32_t seed, uint32_t r) {
   if (int rc = check(h, "svils_ppc_draw")) return rc;
-  if (!h->have_params) return fail(SVILS_ERR_ARG, "svils_ppc_draw: set the parameters first");
+  if (h->kind == svils_ppc::NO_MODEL) return fail(SVILS_ERR_ARG, "svils_ppc_draw: set the parameters first");
   const uint32_t n = h->n, K = h->k, nt = h->nt;
   hipStream_t st = h->st;
   const uint32_t tiles = (uint32_t)((uint64_t)nt * (nt + 1) / 2), per = h->tile_batch ? h->tile_batch : tiles;
-  const double band = 2.0 * (double)K * DBL_EPS;
+  const bool block = h->kind == svils_ppc::BLOCKMODEL;
+  const double band = block ? Blockmodel::band(K) : Assortative::band(K);
   HIPCHK(hipEventRecord(h->ev[0], st));
   HIPCHK(hipMemsetAsync(h->counters, 0, 2 * sizeof(unsigned long long), st));
   for (uint32_t t0 = 0; t0 < tiles; t0 += per) {
     const uint32_t t1 = std::min<uint64_t>(tiles, (uint64_t)t0 + per);
-    hipLaunchKernelGGL(k_draw_tiles, dim3(t1 - t0), dim3(256), 0, st, t0, t1, n, K, h->ld, h->k16, nt, h->pi, h->aq, h->beta, seed, r, band,
-                       h->bits_new, h->counters + 1);
+    if (block)
+      hipLaunchKernelGGL(k_draw_tiles<Blockmodel>, dim3(t1 - t0), dim3(256), 0, st, t0, t1, n, K, h->ld, h->k16, nt, h->pi, h->aq, Blockmodel{h->B},
+                         seed, r, band, h->bits_new, h->counters + 1);
+    else
+      hipLaunchKernelGGL(k_draw_tiles<Assortative>, dim3(t1 - t0), dim3(256), 0, st, t0, t1, n, K, h->ld, h->k16, nt, h->pi, h->aq,
+                         Assortative{h->beta}, seed, r, band, h->bits_new, h->counters + 1);
     if (t1 == tiles) break;
   }
   hipLaunchKernelGGL(k_row_count, dim3(blocks(n, 4)), dim3(256), 0, st, n, nt, h->bits_new, (uint32_t *)nullptr, (uint32_t *)nullptr, h->counters);
@@ -639,19 +771,27 @@ int svils_ppc_set_links(svils_ppc *h, const uint32_t *links, uint64_t nlinks) {
 
 int svils_ppc_stats(svils_ppc *h) {
   if (int rc = check(h, "svils_ppc_stats")) return rc;
-  if (!h->have_params || !h->have_list) return fail(SVILS_ERR_ARG, "svils_ppc_stats: set the parameters and a list (draw / set_links) first");
+  if (h->kind == svils_ppc::NO_MODEL || !h->have_list) return fail(SVILS_ERR_ARG, "svils_ppc_stats: set the parameters and a list (draw / set_links) first");
   const uint32_t n = h->n, K = h->k;
   const uint64_t E = h->E;
   hipStream_t st = h->st;
   HIPCHK(hipEventRecord(h->ev[4], st));
   HIPCHK(hipMemsetAsync(h->t2, 0, (size_t)n * sizeof(uint32_t), st));
-  HIPCHK(hipMemsetAsync(h->ninf, 0, (size_t)K * sizeof(uint32_t), st));
-  HIPCHK(hipMemsetAsync(h->size, 0, (size_t)K * sizeof(unsigned long long), st));
-  HIPCHK(hipMemsetAsync(h->bins, 0, (size_t)K * NBIN * sizeof(unsigned long long), st));
+  const bool block = h->kind == svils_ppc::BLOCKMODEL;
+  const size_t cells = block ? (size_t)K * K : (size_t)K;   // blocks, or communities
+  unsigned long long *size = block ? h->bsize : h->size, *bins = block ? h->bbins : h->bins;
+  uint32_t *ninf = block ? h->bninf : h->ninf;
+  HIPCHK(hipMemsetAsync(ninf, 0, cells * sizeof(uint32_t), st));
+  HIPCHK(hipMemsetAsync(size, 0, cells * sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(bins, 0, cells * NBIN * sizeof(unsigned long long), st));
   HIPCHK(hipMemsetAsync(h->counters + 2, 0, sizeof(unsigned long long), st));
   if (E) {
-    hipLaunchKernelGGL(k_link_stats, dim3(blocks(E, 4)), dim3(256), 0, st, E, K, h->ld, h->links, h->pi, h->beta, h->rowptr, h->scol,
-                       2.0 * (double)K * DBL_EPS, h->colour, h->joined, h->t2, h->counters + 2, h->size, h->bins, h->ninf);
+    if (block)
+      hipLaunchKernelGGL(k_link_stats<Blockmodel>, dim3(blocks(E, 4)), dim3(256), 0, st, E, K, h->ld, h->links, h->pi, Blockmodel{h->B}, h->rowptr,
+                         h->scol, Blockmodel::band(K), h->colour, h->joined, h->t2, h->counters + 2, size, bins, ninf);
+    else
+      hipLaunchKernelGGL(k_link_stats<Assortative>, dim3(blocks(E, 4)), dim3(256), 0, st, E, K, h->ld, h->links, h->pi, Assortative{h->beta},
+                         h->rowptr, h->scol, Assortative::band(K), h->colour, h->joined, h->t2, h->counters + 2, size, bins, ninf);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipEventRecord(h->ev[5], st));
@@ -724,21 +864,16 @@ int svils_ppc_get_summary(svils_ppc *h, uint64_t counts[5], double values[2]) {
 
 int svils_ppc_get_communities(svils_ppc *h, uint64_t *size, double *logpe) {
   if (int rc = check_done(h, "svils_ppc_get_communities")) return rc;
-  const size_t K = h->k;
-  if (size) HIPCHK(hipMemcpy(size, h->size, K * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  if (!logpe) return 0;
-  std::vector<unsigned long long> bins(K * NBIN);
-  std::vector<uint32_t> ninf(K);
-  HIPCHK(hipMemcpy(bins.data(), h->bins, bins.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(ninf.data(), h->ninf, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (size_t k = 0; k < K; ++k) {
-    // the bins hold the sum exactly; from the top down, every term is a 64-bit integer times a power of two
-    long double s = 0;
-    for (int b = (int)NBIN - 1; b >= 0; --b)
-      if (bins[k * NBIN + b]) s += std::ldexp((long double)bins[k * NBIN + b], 32 * b - BIN_BIAS);
-    logpe[k] = ninf[k] ? -HUGE_VAL : (s > 0 ? -(double)s : 0.0);
-  }
-  return 0;
+  if (h->kind != svils_ppc::ASSORTATIVE)
+    return fail(SVILS_ERR_ARG, "svils_ppc_get_communities: the current parameters are K x K (svils_ppc_get_blocks answers for them)");
+  return read_cells(h->k, h->size, h->bins, h->ninf, size, logpe);
+}
+
+int svils_ppc_get_blocks(svils_ppc *h, uint64_t *bsize, double *blogpe) {
+  if (int rc = check_done(h, "svils_ppc_get_blocks")) return rc;
+  if (h->kind != svils_ppc::BLOCKMODEL)
+    return fail(SVILS_ERR_ARG, "svils_ppc_get_blocks: the current parameters are not K x K (svils_ppc_get_communities answers for them)");
+  return read_cells((size_t)h->k * h->k, h->bsize, h->bbins, h->bninf, bsize, blogpe);
 }
 
 int svils_ppc_get_timing(svils_ppc *h, double ms[3]) {

@@ -43,6 +43,7 @@ class Env {
     int ppc_save = 0;                   // -ppc-save <m>: the networks of the first m replicates
     bool ppc_mean = false;              // -ppc-mean: no parameter draws
     bool ppc_hops = false;              // -ppc-hops: the hop plot and the components of every list (svils_ppc_hops)
+    bool ppc_orig = false;              // -ppc-orig: the -ppc mode for the K x K blockmodel of an -orig fit (gamma.txt, beta.txt)
     bool load = false;
     std::string location;
     bool val_load = false;

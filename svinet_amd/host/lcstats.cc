@@ -114,9 +114,14 @@ LinkCommunities::~LinkCommunities() {
 
 // MMSBGen::load_model (:74-150): "seq id g0 .. gK-1" rows, "k l0 l1" rows
 int LinkCommunities::load_model(const std::string &dir) {
+  if (load_gamma(dir) < 0) return -1;
+  lambda_.assign(2 * (size_t)k_, 0.0);
+  return read_text_rows(dir + "lambda.txt", 1, 2, k_, lambda_.data(), nullptr) < 0 ? -1 : 0;
+}
+
+int LinkCommunities::load_gamma(const std::string &dir) {
   fprintf(stderr, "+ Loading model\n");
   gamma_.assign((size_t)n_ * k_, 0.0);
-  lambda_.assign(2 * (size_t)k_, 0.0);
   std::vector<double> lead(2 * (size_t)n_);
   if (read_text_rows(dir + "gamma.txt", 2, k_, n_, gamma_.data(), lead.data()) < 0) return -1;
   // the reference does not check the id column; a gamma.txt of another numbering would give wrong rows silently
@@ -127,7 +132,6 @@ int LinkCommunities::load_model(const std::string &dir) {
               dir.c_str(), i + 1, lead[2 * (size_t)i + 1], s2i[i]);
       return -1;
     }
-  if (read_text_rows(dir + "lambda.txt", 1, 2, k_, lambda_.data(), nullptr) < 0) return -1;
   return 0;
 }
 

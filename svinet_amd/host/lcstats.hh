@@ -31,6 +31,7 @@ class LinkCommunities {
   // gamma.txt and lambda.txt of `dir` ("" = the working directory): n rows whose id column matches the reader's
   // numbering, k rows.  0, or -1 with a message on stderr.
   int load_model(const std::string &dir = "");
+  int load_gamma(const std::string &dir = "");   // gamma.txt alone, with the same check (-ppc-orig: an -orig fit has no lambda.txt)
   void run();                 // the three device passes (throws SvilsError)
   // community_stats.txt, node_bridgeness.txt, node_influence.txt, number_of_memberships.txt into Env's directory
   void write_stats() const;

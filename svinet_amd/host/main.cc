@@ -217,6 +217,13 @@ static void usage() {
           "\t\t\t-ppc-mean uses the posterior means instead; -ppc-save <m> writes ppc/<r>/network.dat of the first m.\n"
           "\t\t\tThe random stream is Philox4x32-10 keyed by -seed and the replicate, not the reference's GSL stream:\n"
           "\t\t\tthat one is not reproduced.  -n <= 32768, -k <= 2048, single GPU, no host route\n\n"
+          "\t-ppc-orig\t-ppc for the K x K blockmodel of an -orig fit: reads gamma.txt and beta.txt (K lines of K rates) of the\n"
+          "\t\t\tworking directory; every replicate draws pi_i ~ Dirichlet(gamma_i), the block rates are the fit's point\n"
+          "\t\t\testimate; pair p < q is a link with probability pi_p' B pi_q.  The files of -ppc, with ppc/block_size.txt\n"
+          "\t\t\tand ppc/block_logpe.txt (g, h, observed, mean, deviation, z for all K x K blocks) in place of the lc_*\n"
+          "\t\t\tfiles, and one more row of ppc/summary.txt: offdiag_share, the joined links in blocks g != h over the\n"
+          "\t\t\tjoined links.  2 <= -k <= 64.  Takes -ppc-draws, -ppc-mean, -ppc-save, -ppc-hops and -seed; refused beside\n"
+          "\t\t\t-ppc, -gen, -orig and every flag -ppc refuses\n\n"
           "\t-ppc-hops\twith -ppc: the exact hop plot and the components of the observed network and of every replicate\n"
           "\t\t\t(all-sources BFS on the GPU): obs-hop.txt and ppc/ppc-hop.txt (effective diameters, the reference's\n"
           "\t\t\tnames), ppc/obs-hops.txt (h, pairs at distance h, cumulative), ppc/rep-hops.txt (r, effective diameter,\n"
@@ -377,6 +384,7 @@ int main(int argc, char **argv) {
     else if (is("-ppc-save")) { need(i); a.ppc_save = atoi(argv[++i]); }
     else if (is("-ppc-mean")) { a.ppc_mean = true; }
     else if (is("-ppc-hops")) { a.ppc_hops = true; }
+    else if (is("-ppc-orig")) { a.ppc_orig = true; }
     else if (is("-single") ||
              is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
@@ -387,6 +395,8 @@ int main(int argc, char **argv) {
   }
   const bool sampled = a.rnode || a.rpair;
   const bool infset = a.infset || a.preprocess;
+  const bool ppc_plain = a.ppc;
+  if (a.ppc_orig) a.ppc = true;                          // -ppc-orig: the -ppc mode plus the K x K kind (it does not set -orig)
   if (a.ppc_hops && !unsupported) {                      // -ppc-hops: beside -ppc alone; refusals before anything is read or created
     if (refused(a, kHops, "-ppc-hops")) return 2;
     const struct { bool set; const char *name; } more[] = {
@@ -403,7 +413,12 @@ int main(int argc, char **argv) {
     }
   }
   if ((a.ppc || a.gen) && !unsupported) {                // -ppc / -gen (MMSBGen): refusals before anything is read or created
-    const char *flag = a.gen ? "-gen" : "-ppc";
+    const char *flag = a.ppc_orig ? "-ppc-orig" : a.gen ? "-gen" : "-ppc";
+    if (a.ppc_orig && (a.gen || ppc_plain)) {
+      fprintf(stderr, "error: -ppc-orig is not available with %s (it is the -ppc of a K x K blockmodel: gamma.txt and beta.txt of an -orig fit)\n",
+              a.gen ? "-gen" : "-ppc");
+      return 2;
+    }
     if (a.ppc && a.gen) {
       fprintf(stderr, "error: -gen is not available with -ppc (one draws from the prior, the other from a fitted model)\n");
       return 2;
@@ -417,6 +432,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, kPosterior.fmt, flag, m.name);
         return 2;
       }
+    if (a.ppc_orig && (a.k < 2 || a.k > SVILS_ORIG_MAX_K)) {   // the limits of svils_ppc_set_params_orig
+      fprintf(stderr, "error: -ppc-orig holds 2 <= -k <= %d (SVILS_ORIG_MAX_K); -k %u is refused\n", SVILS_ORIG_MAX_K, a.k);
+      return 2;
+    }
     if (a.k < 1 || a.k > SVILS_PPC_MAX_K) {              // the limits of svils_ppc_create
       fprintf(stderr, "error: %s holds 1 <= -k <= %d (SVILS_PPC_MAX_K); -k %u is refused\n", flag, SVILS_PPC_MAX_K, a.k);
       return 2;
@@ -437,10 +456,10 @@ int main(int argc, char **argv) {
         return -1;
       }
     }
-    for (const char *m : {"gamma.txt", "lambda.txt"}) {
+    for (const char *m : {"gamma.txt", a.ppc_orig ? "beta.txt" : "lambda.txt"}) {
       FILE *f = fopen(m, "r");
       if (!f) {
-        fprintf(stderr, "error: -ppc needs %s in the working directory (the output directory of a fit): %s\n", m, strerror(errno));
+        fprintf(stderr, "error: %s needs %s in the working directory (the output directory of a fit): %s\n", flag, m, strerror(errno));
         return 2;
       }
       fclose(f);
@@ -750,6 +769,7 @@ run:
       po.save = (uint32_t)a.ppc_save;
       po.mean = a.ppc_mean;
       po.hops = a.ppc_hops;
+      po.orig = a.ppc_orig;
       exit(run_ppc(env, network, po) < 0 ? 255 : 0);
     }
     if (a.findk) {                           // src/main.cc:321-327, before the other engines (-batch / -link-sampling only name the directory)

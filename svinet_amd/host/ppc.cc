@@ -5,6 +5,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -105,7 +106,8 @@ std::string fx(double x, int digits = 5) {
 struct Scalars {
   uint64_t ones, maxdeg, triangles;
   double density, avgdeg, transitivity, clustering;
-  std::vector<uint64_t> size;
+  double offdiag = NAN;   // -ppc-orig: joined links in blocks g != h / joined links
+  std::vector<uint64_t> size;   // per community, or per block [k][k] (-ppc-orig)
   std::vector<double> logpe;
 };
 
@@ -148,22 +150,38 @@ std::string summary_row(const char *name, double obs, const std::vector<double> 
 struct Handle {
   svils_ppc *h = nullptr;
   uint32_t n, k;
+  bool blocks = false;   // the K x K kind is current
   Handle(int device, uint32_t n_, uint32_t k_, uint64_t cap) : n(n_), k(k_) {
     if (int rc = svils_ppc_create(device, n, k, cap, &h)) throw_svils("svils_ppc_create", rc);
   }
   ~Handle() { svils_ppc_destroy(h); }
   void params(const double *pi, const double *beta) {
     if (int rc = svils_ppc_set_params(h, pi, beta)) throw_svils("svils_ppc_set_params", rc);
+    blocks = false;
+  }
+  void params_orig(const double *pi, const double *B) {
+    if (int rc = svils_ppc_set_params_orig(h, pi, B)) throw_svils("svils_ppc_set_params_orig", rc);
+    blocks = true;
   }
   Scalars stats() {
     if (int rc = svils_ppc_stats(h)) throw_svils("svils_ppc_stats", rc);
     uint64_t c[5];
     double v[2];
     Scalars s;
-    s.size.resize(k);
-    s.logpe.resize(k);
+    s.size.resize(blocks ? (size_t)k * k : k);
+    s.logpe.resize(s.size.size());
     if (int rc = svils_ppc_get_summary(h, c, v)) throw_svils("svils_ppc_get_summary", rc);
-    if (int rc = svils_ppc_get_communities(h, s.size.data(), s.logpe.data())) throw_svils("svils_ppc_get_communities", rc);
+    if (blocks) {
+      if (int rc = svils_ppc_get_blocks(h, s.size.data(), s.logpe.data())) throw_svils("svils_ppc_get_blocks", rc);
+      uint64_t joined = 0, diag = 0;
+      for (size_t t = 0; t < s.size.size(); ++t) {
+        joined += s.size[t];
+        if (t / k == t % k) diag += s.size[t];
+      }
+      if (joined) s.offdiag = (double)(joined - diag) / (double)joined;
+    } else if (int rc = svils_ppc_get_communities(h, s.size.data(), s.logpe.data())) {
+      throw_svils("svils_ppc_get_communities", rc);
+    }
     s.ones = c[0];
     s.maxdeg = c[1];
     s.triangles = c[3];
@@ -216,10 +234,62 @@ uint64_t list_room(uint64_t observed) { return std::max<uint64_t>(8 * observed, 
 
 }  // namespace
 
+int read_block_rates(const std::string &path, uint32_t k, double *B) {
+  FILE *f = fopen(path.c_str(), "r");
+  if (!f) {
+    fprintf(stderr, "error: cannot open %s: %s\n", path.c_str(), strerror(errno));
+    return -1;
+  }
+  std::string text;
+  char buf[1 << 16];
+  for (size_t m; (m = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, m);
+  fclose(f);
+  uint32_t line = 0;
+  for (size_t b = 0; b < text.size(); ++line) {
+    size_t e = text.find('\n', b);
+    if (e == std::string::npos) e = text.size();
+    const std::string row = text.substr(b, e - b);
+    b = e + 1;
+    const char *c = row.c_str();
+    uint32_t got = 0;
+    for (;; ++got) {
+      while (*c == ' ' || *c == '\t' || *c == '\r') ++c;
+      if (!*c) break;
+      char *end = nullptr;
+      const double v = strtod(c, &end);
+      if (end == c) {
+        fprintf(stderr, "error: %s line %u: \"%.20s\" is not a number\n", path.c_str(), line + 1, c);
+        return -1;
+      }
+      if (!(v >= 0.0 && v <= 1.0)) {
+        fprintf(stderr, "error: %s line %u: the rate %g is not in [0, 1]\n", path.c_str(), line + 1, v);
+        return -1;
+      }
+      if (line < k && got < k) B[(size_t)line * k + got] = v;
+      c = end;
+    }
+    if (line >= k || got != k) {
+      fprintf(stderr, "error: %s line %u holds %u values; -k %u wants %u lines of %u\n", path.c_str(), line + 1, got, k, k, k);
+      return -1;
+    }
+  }
+  if (line != k) {
+    fprintf(stderr, "error: %s line %u is missing: %u lines, -k %u wants %u lines of %u\n", path.c_str(), line + 1, line, k, k, k);
+    return -1;
+  }
+  return 0;
+}
+
 int run_ppc(Env &env, Network &network, const PpcOptions &opt) {
   const uint32_t n = env.n, K = env.k, R = opt.draws;
   LinkCommunities model(env, network);   // -gml's loader and checks
-  if (model.load_model() < 0) return -1;
+  std::vector<double> B;                 // -ppc-orig: the point estimate, the same for every replicate
+  if (opt.orig) {
+    B.resize((size_t)K * K);
+    if (model.load_gamma() < 0 || read_block_rates("beta.txt", K, B.data()) < 0) return -1;
+  } else if (model.load_model() < 0) {
+    return -1;
+  }
   const std::vector<double> &gam = model.gamma(), &lam = model.lambda();
   // estimate_all (:700-729): pi = gamma / sum in k order, beta = l0 / (l0 + l1)
   std::vector<double> pim((size_t)n * K), betam(K), pi, beta;
@@ -228,7 +298,8 @@ int run_ppc(Env &env, Network &network, const PpcOptions &opt) {
     for (uint32_t j = 0; j < K; ++j) s += gam[(size_t)i * K + j];
     for (uint32_t j = 0; j < K; ++j) pim[(size_t)i * K + j] = gam[(size_t)i * K + j] / s;
   }
-  for (uint32_t j = 0; j < K; ++j) betam[j] = lam[2 * j] / (lam[2 * j] + lam[2 * j + 1]);
+  if (!opt.orig)
+    for (uint32_t j = 0; j < K; ++j) betam[j] = lam[2 * j] / (lam[2 * j] + lam[2 * j + 1]);
   const std::vector<Edge> &ed = network.edges();
   std::vector<uint32_t> links(2 * ed.size());
   for (size_t x = 0; x < ed.size(); ++x) {
@@ -237,7 +308,7 @@ int run_ppc(Env &env, Network &network, const PpcOptions &opt) {
   }
   Handle h(env.device, n, K, list_room(ed.size()));
   // the observed network under the mean parameters
-  h.params(pim.data(), betam.data());
+  if (opt.orig) h.params_orig(pim.data(), B.data()); else h.params(pim.data(), betam.data());
   if (int rc = svils_ppc_set_links(h.h, links.data(), ed.size())) throw_svils("svils_ppc_set_links", rc);
   const Scalars obs = h.stats();
   make_dir("ppc");
@@ -269,8 +340,12 @@ int run_ppc(Env &env, Network &network, const PpcOptions &opt) {
     fflush(stdout);
     if (!opt.mean) {                                            // draw_all (:730-742), afresh for every replicate
       dirichlet_rows(gam.data(), n, K, opt.seed, r, pi.data());
-      beta_draws(lam.data(), K, opt.seed, r, beta.data());
-      h.params(pi.data(), beta.data());
+      if (opt.orig) {
+        h.params_orig(pi.data(), B.data());
+      } else {
+        beta_draws(lam.data(), K, opt.seed, r, beta.data());
+        h.params(pi.data(), beta.data());
+      }
     }
     if (int rc = svils_ppc_draw(h.h, opt.seed, r)) throw_svils("svils_ppc_draw", rc);
     rep.push_back(h.stats());
@@ -289,31 +364,49 @@ int run_ppc(Env &env, Network &network, const PpcOptions &opt) {
   write_file("ppc/ppc-ones.txt", ones);
   write_file("ppc/ppc-avg-deg.txt", avg);
   write_file("ppc/ppc-max-deg.txt", mx);
-  // per community: k, observed, replicate mean, deviation, z (compute_lc_zscores, :286-320)
-  std::string lsz, lpe, zsz, zpe;
   std::vector<double> x(R);
-  for (uint32_t k = 0; k < K; ++k) {
-    for (uint32_t r = 0; r < R; ++r) x[r] = (double)rep[r].size[k];
-    const Moments ms(x, (double)obs.size[k]);
-    lsz += std::to_string(k) + "\t" + std::to_string(obs.size[k]) + "\t" + fx(ms.mean) + "\t" + fx(ms.sd) + "\t" + fx(ms.z) + "\n";
-    zsz += std::to_string(k) + "\t" + fx(ms.z) + "\n";
-    for (uint32_t r = 0; r < R; ++r) x[r] = rep[r].logpe[k];
-    const Moments mp(x, obs.logpe[k]);
-    lpe += std::to_string(k) + "\t" + fx(obs.logpe[k]) + "\t" + fx(mp.mean) + "\t" + fx(mp.sd) + "\t" + fx(mp.z) + "\n";
-    zpe += std::to_string(k) + "\t" + fx(mp.z) + "\n";
+  if (opt.orig) {
+    // per block, row-major: g, h, observed, replicate mean, deviation, z
+    std::string bsz, bpe;
+    for (uint32_t t = 0; t < K * K; ++t) {
+      const std::string gh = std::to_string(t / K) + "\t" + std::to_string(t % K) + "\t";
+      for (uint32_t r = 0; r < R; ++r) x[r] = (double)rep[r].size[t];
+      const Moments ms(x, (double)obs.size[t]);
+      bsz += gh + std::to_string(obs.size[t]) + "\t" + fx(ms.mean) + "\t" + fx(ms.sd) + "\t" + fx(ms.z) + "\n";
+      for (uint32_t r = 0; r < R; ++r) x[r] = rep[r].logpe[t];
+      const Moments mp(x, obs.logpe[t]);
+      bpe += gh + fx(obs.logpe[t]) + "\t" + fx(mp.mean) + "\t" + fx(mp.sd) + "\t" + fx(mp.z) + "\n";
+    }
+    write_file("ppc/block_size.txt", bsz);
+    write_file("ppc/block_logpe.txt", bpe);
+  } else {
+    // per community: k, observed, replicate mean, deviation, z (compute_lc_zscores, :286-320)
+    std::string lsz, lpe, zsz, zpe;
+    for (uint32_t k = 0; k < K; ++k) {
+      for (uint32_t r = 0; r < R; ++r) x[r] = (double)rep[r].size[k];
+      const Moments ms(x, (double)obs.size[k]);
+      lsz += std::to_string(k) + "\t" + std::to_string(obs.size[k]) + "\t" + fx(ms.mean) + "\t" + fx(ms.sd) + "\t" + fx(ms.z) + "\n";
+      zsz += std::to_string(k) + "\t" + fx(ms.z) + "\n";
+      for (uint32_t r = 0; r < R; ++r) x[r] = rep[r].logpe[k];
+      const Moments mp(x, obs.logpe[k]);
+      lpe += std::to_string(k) + "\t" + fx(obs.logpe[k]) + "\t" + fx(mp.mean) + "\t" + fx(mp.sd) + "\t" + fx(mp.z) + "\n";
+      zpe += std::to_string(k) + "\t" + fx(mp.z) + "\n";
+    }
+    write_file("ppc/lc_size.txt", lsz);
+    write_file("ppc/lc_logpe.txt", lpe);
+    write_file("ppc/lc_zscores_size.txt", zsz);
+    write_file("ppc/lc_zscores_pe.txt", zpe);
   }
-  write_file("ppc/lc_size.txt", lsz);
-  write_file("ppc/lc_logpe.txt", lpe);
-  write_file("ppc/lc_zscores_size.txt", zsz);
-  write_file("ppc/lc_zscores_pe.txt", zpe);
   // summary.txt: statistic, observed, replicate mean, deviation, two-sided posterior predictive p-value
   const struct { const char *name; double Scalars::*d; uint64_t Scalars::*u; int digits; } cols[] = {
       {"ones", nullptr, &Scalars::ones, 5},           {"density", &Scalars::density, nullptr, 8},
       {"avg_deg", &Scalars::avgdeg, nullptr, 5},      {"max_deg", nullptr, &Scalars::maxdeg, 5},
       {"triangles", nullptr, &Scalars::triangles, 5}, {"transitivity", &Scalars::transitivity, nullptr, 5},
-      {"clustering", &Scalars::clustering, nullptr, 5}};
+      {"clustering", &Scalars::clustering, nullptr, 5},
+      {"offdiag_share", &Scalars::offdiag, nullptr, 5}};   // -ppc-orig alone
   std::string sm;
   for (const auto &c : cols) {
+    if (c.d == &Scalars::offdiag && !opt.orig) continue;
     auto val = [&](const Scalars &s) { return c.d ? s.*(c.d) : (double)(s.*(c.u)); };
     for (uint32_t r = 0; r < R; ++r) x[r] = val(rep[r]);
     sm += summary_row(c.name, val(obs), x, c.digits);

@@ -10,6 +10,7 @@
 // of pi and beta.
 #pragma once
 #include <cstdint>
+#include <string>
 
 #include "env.hh"
 #include "network.hh"
@@ -34,10 +35,16 @@ struct PpcOptions {
   uint32_t seed = 0;      // -seed
   uint32_t save = 0;      // -ppc-save <m>: ppc/<r>/network.dat of the first m replicates
   bool mean = false;      // -ppc-mean: every replicate from pi = gamma / sum, beta = l0 / (l0 + l1)
+  bool orig = false;      // -ppc-orig: the K x K blockmodel, gamma.txt and beta.txt; block_size.txt / block_logpe.txt for the lc_* files
   bool hops = false;      // -ppc-hops: obs-hop.txt, ppc/ppc-hop.txt, ppc/obs-hops.txt, ppc/rep-hops.txt, ppc/hops-summary.txt
 };
 
+// beta.txt of an -orig fit (MMSBInferOrig::save_model): exactly k lines of exactly k rates in [0, 1] -> B [k][k].  0, or -1
+// with a message on stderr that names the file and the line
+int read_block_rates(const std::string &path, uint32_t k, double *B);
 // -ppc in the output directory of a fit: gamma.txt / lambda.txt, files under ppc/ and the reference's obs-*.txt.
+// -ppc-orig (opt.orig) in that of an -orig fit: gamma.txt / beta.txt; pi is drawn per replicate, B is the fit's point
+// estimate.
 // 0, or -1 with a message on stderr; throws SvilsError where a svils_ppc_* call fails
 int run_ppc(Env &env, Network &network, const PpcOptions &opt);
 // -gen: gen/network_gen.dat, gen/pi-gen.txt, gen/beta-gen.txt (MMSBGen::gen, save_model)

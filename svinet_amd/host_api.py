@@ -781,13 +781,17 @@ class PPC:
     every pair).
 
         ppc = PPC(n, k); links = ppc.draw(pi, beta, seed, r); rep = ppc.stats()
-        ppc.observe(observed_links); obs = ppc.stats()"""
+        ppc.observe(observed_links); obs = ppc.stats()
+
+    The same handle serves the K x K blockmodel of -orig: set_params_orig(pi, B) or draw(pi, B=B, ...)
+    makes that kind current, set_params(pi, beta) the assortative one; the last call decides."""
 
     def __init__(self, n, k, device=0, max_links=None):
         self._h = C.c_void_p()
         self.n, self.k = int(n), int(k)
         if max_links is None:
             max_links = self.n * (self.n - 1) // 2
+        self.blocks = False          # the K x K kind is current
         _svils._chk(_svils.load().svils_ppc_create(device, self.n, self.k, int(max_links), C.byref(self._h)))
 
     def set_params(self, pi, beta):
@@ -796,14 +800,27 @@ class PPC:
         if pi.shape != (self.n, self.k) or beta.shape != (self.k,):
             raise ValueError("pi must be [%d][%d] and beta [%d]" % (self.n, self.k, self.k))
         _svils._chk(_svils.load().svils_ppc_set_params(self._h, pi.ctypes.data, beta.ctypes.data))
+        self.blocks = False
+
+    def set_params_orig(self, pi, B):
+        """the K x K kind: pi [n][k] and the block rates B [k][k] in [0, 1] (row g: the smaller node id's block)"""
+        pi = np.ascontiguousarray(pi, dtype=np.float64)
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if pi.shape != (self.n, self.k) or B.shape != (self.k, self.k):
+            raise ValueError("pi must be [%d][%d] and B [%d][%d]" % (self.n, self.k, self.k, self.k))
+        _svils._chk(_svils.load().svils_ppc_set_params_orig(self._h, pi.ctypes.data, B.ctypes.data))
+        self.blocks = True
 
     def set_tile_batch(self, tiles_per_launch):
         """tiles per launch of the draw (0: one launch); no result depends on it"""
         _svils._chk(_svils.load().svils_ppc_set_tile_batch(self._h, int(tiles_per_launch)))
 
-    def draw(self, pi=None, beta=None, seed=0, r=0):
-        """replicate r of seed under (pi, beta) (None: the parameters set last) becomes the current list -> links [E][2]"""
-        if pi is not None:
+    def draw(self, pi=None, beta=None, seed=0, r=0, B=None):
+        """replicate r of seed under (pi, beta), or under (pi, B) of the K x K kind (None: the parameters set last), becomes
+        the current list -> links [E][2]"""
+        if pi is not None and B is not None:
+            self.set_params_orig(pi, B)
+        elif pi is not None:
             self.set_params(pi, beta)
         _svils._chk(_svils.load().svils_ppc_draw(self._h, int(seed), int(r)))
         return self.links()
@@ -830,7 +847,9 @@ class PPC:
     def stats(self):
         """the statistics of the current list under the current parameters, as a dict: links [E][2] in (p, q) order with
         colour and join per link; deg, tri [n]; ones, max_deg, argmax_deg, triangles, wedges, transitivity, clustering;
-        size, logpe [k]; rechecked (pairs of the last draw); timing_ms (draw, csr, stats)"""
+        size, logpe [k]; rechecked (pairs of the last draw); timing_ms (draw, csr, stats).  Under the K x K kind colour is
+        g k + h and block_size, block_logpe [k][k] and offdiag_share (joined links in blocks g != h / joined links, NaN
+        without one) stand in place of size and logpe"""
         L, ok = _svils.load(), _svils._chk
         ok(L.svils_ppc_stats(self._h))
         out = {"links": self.links()}
@@ -846,8 +865,15 @@ class PPC:
         for name, v in zip(("ones", "max_deg", "argmax_deg", "triangles", "wedges"), counts):
             out[name] = int(v)
         out["transitivity"], out["clustering"] = float(values[0]), float(values[1])
-        out["size"], out["logpe"] = np.zeros(self.k, np.uint64), np.zeros(self.k, np.float64)
-        ok(L.svils_ppc_get_communities(self._h, out["size"].ctypes.data, out["logpe"].ctypes.data))
+        if self.blocks:
+            bs, bl = np.zeros((self.k, self.k), np.uint64), np.zeros((self.k, self.k), np.float64)
+            ok(L.svils_ppc_get_blocks(self._h, bs.ctypes.data, bl.ctypes.data))
+            joined = int(bs.sum())
+            out["block_size"], out["block_logpe"] = bs, bl
+            out["offdiag_share"] = float(joined - int(np.trace(bs))) / float(joined) if joined else float("nan")
+        else:
+            out["size"], out["logpe"] = np.zeros(self.k, np.uint64), np.zeros(self.k, np.float64)
+            ok(L.svils_ppc_get_communities(self._h, out["size"].ctypes.data, out["logpe"].ctypes.data))
         out["rechecked"] = self.draw_counts()[1]
         ms = np.zeros(3, np.float64)
         ok(L.svils_ppc_get_timing(self._h, ms.ctypes.data))

@@ -6,6 +6,12 @@ model: n (n - 1) / 2 pairs x 2 K flop on the fp64 MFMA.  One JSON line per model
 
     python tools/ppc_bench.py                                  # the three shapes of DESIGN.md section 4l
     python tools/ppc_bench.py --model 1000:28 --restate        # also time tools/restate_ppc.py's loops and compare
+    python tools/ppc_bench.py --orig                           # the K x K kind beside the assortative one
+
+--orig: after the assortative replicates, the same handle draws as many under svils_ppc_set_params_orig with
+B = diag(beta) / 2 + one off-diagonal rate that carries the other half of the links, so both kinds see lists of about
+the same length; the orig_* keys stand beside the assortative ones of the same run.  k_ppc_aq runs inside
+svils_ppc_set_params_orig, outside the draw's bracket: orig_set_params_wall_ms is its wall time, upload included.
 """
 import argparse
 import json
@@ -19,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+ORIG_SHAPES = ("32768:64", "18772:20")           # the K x K kind's largest shape, and ca-AstroPh's
 SHAPES = ("1000:28", "18772:20", "32768:256")    # LFR, ca-AstroPh (its node count and the K of the headline run), the handle's largest n
 MFMA_F64_TFLOPS = 49.5                           # measured, DESIGN.md section 4a
 
@@ -63,12 +70,33 @@ def run(shape, a):
     o = ppc.stats()
     out.update(observed_links=int(len(links)), observed_csr_ms=o["timing_ms"]["csr"], observed_stats_ms=o["timing_ms"]["stats"],
                observed_triangles=o["triangles"])
+    if a.orig:
+        mass = pi.sum(0)
+        cross = (mass.sum() ** 2 - float((mass * mass).sum())) / 2.0          # sum over g != h of mass_g mass_h / 2
+        B = np.full((k, k), min(1.0, (out["ones_mean"] / 2.0) / cross))
+        B[np.arange(k), np.arange(k)] = beta / 2.0
+        t = time.perf_counter()
+        ppc.set_params_orig(pi, B)
+        out["orig_set_params_wall_ms"] = 1e3 * (time.perf_counter() - t)
+        rows = []
+        for r in range(a.warmup + a.reps):
+            ppc.draw(seed=a.seed, r=r)
+            s = ppc.stats()
+            if r >= a.warmup:
+                rows.append(dict(s["timing_ms"], ones=s["ones"], rechecked=s["rechecked"], offdiag=s["offdiag_share"]))
+        for key in ("draw", "csr", "stats"):
+            out["orig_" + key + "_ms"] = float(np.median([x[key] for x in rows]))
+        out["orig_ones_mean"] = float(np.mean([x["ones"] for x in rows]))
+        out["orig_rechecked_total"] = int(sum(x["rechecked"] for x in rows))
+        out["orig_offdiag_share_mean"] = float(np.mean([x["offdiag"] for x in rows]))
+        out["orig_stats_us_per_link"] = 1e3 * out["orig_stats_ms"] / out["orig_ones_mean"]
+        out["stats_us_per_link"] = 1e3 * out["stats_ms"] / out["ones_mean"]
     if a.restate:
         import restate_ppc as R
         t = time.perf_counter()
         want = R.draw_loops(pi, beta, a.seed, 0)
         out["restate_loops_s"] = time.perf_counter() - t
-        out["restate_equal"] = bool(np.array_equal(ppc.draw(seed=a.seed, r=0).astype(np.int64), want))
+        out["restate_equal"] = bool(np.array_equal(ppc.draw(pi, beta, seed=a.seed, r=0).astype(np.int64), want))
     ppc.close()
     return out
 
@@ -81,9 +109,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--restate", action="store_true", help="also run the restatement's double loop once and compare the links")
+    ap.add_argument("--orig", action="store_true", help="also the K x K kind at the same n and K (default shapes: %s)" % " ".join(ORIG_SHAPES))
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     a = ap.parse_args()
-    for shape in a.model or SHAPES:
+    for shape in a.model or (ORIG_SHAPES if a.orig else SHAPES):
         line = json.dumps(run(shape, a))
         print(line, flush=True)
         if a.out:
