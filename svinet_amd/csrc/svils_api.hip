@@ -80,6 +80,117 @@ int elogpi_rows(svils_handle *h, double **rows) {
   return 0;
 }
 
+// ---- product mode of the lane-per-link layout (K <= 32; svils_lpl.hip: k_phi_lpl<.., PROD>) -------------------------------
+// The phi pass forms t_k = (e_p[k] e_q[k]) b[k] with e_x[k] = exp(psi(gamma_xk) - psi(sum_j gamma_xj)) stored by the finalise
+// pass and b[k] = exp(Elogbeta[k][0]), and divides by s = sum_k t_k.  It carries NO log-domain fall-back, so the mode is on
+// only where no t_k can come near the underflow threshold.  With  psi(x) >= -1/x - C  (x > 0; C = 0.5772..., from psi(x) =
+// psi(x + 1) - 1/x and psi(1) = -C) and  psi(x) <= ln x:
+//   * gamma_xk >= g_min := alpha min(1, ones / 2L): the finalise pass stores (alpha + acc (n - 1) / tl) scale with acc >= 0 and
+//     scale = ones / sum[k] (annealing; 1 otherwise), sum[k] <= 2L -- every directed entry adds phi_k <= 1 or a shortcut's 1;
+//     a mini-batch step scales its window's sum to at most 2L as well and blends convexly with the old row;
+//   * sum_j gamma_xj <= S_max := 1e30, a cap, not a theorem: a row sum is (K alpha + deg + n / 2) scale at most, i.e. it
+//     passes the cap only where some sum[k] has fallen below ~1e-24 of the link count, where the reference's own scale
+//     diverges.  Together:  ln e_x[k] >= -1/g_min - C - ln S_max;
+//   * lambda_k0 = eta0 + sum[k] in [eta0, eta0 + 2L] and lambda_k1 = eta1 + s1^2 - s2 - s3 in (0, eta1 + n^2] (s1 <= n), so
+//     ln b[k] = psi(lambda_k0) - psi(lambda_k0 + lambda_k1) >= -1/eta0 - C - ln(eta0 + eta1 + 2L + n^2).
+// The mode is on iff
+//     2 (1/g_min + C + ln S_max) + 1/eta0 + C + ln(eta0 + eta1 + 2L + n^2)  <=  250 ln 10,
+// i.e. every t_k >= 1e-250.  At K = 32, alpha = 1/K, ones >= L (g_min = 1/64) on ca-AstroPh that is eta0 >= 3.5e-3.
+// The two premises on gamma hold for every row a sweep or a mini-batch step WRITES.  A state that ARRIVES (svils_set_state,
+// svils_init_gamma) obeys neither -- the reference's own initialisation has entries of 1e-5 and below, whose factor is an
+// exact 0 -- so it is measured on the device instead (lpl_product_update): over the training links, the smallest
+// M = max_k (Elogpi[p][k] + Elogpi[q][k]) and the smallest row maximum X = max_k Elogpi[x][k] of an endpoint; over the
+// columns, the smallest Elogbeta[k][0] (B = the smaller of it and the bound above).  With ln e_min the bound of a written row:
+//     M + B >= -250 ln 10          a link between two arrived rows keeps its largest term, hence its sum, above 1e-250
+//     X + ln e_min + B >= -250 ln 10   ... and so does a link between an arrived row and a written one (mini-batch steps)
+// (a term below the largest may flush to 0: so does its exponential in the exp kernels).  A state that fails turns the handle
+// over to the exp kernels.
+namespace {
+constexpr double kProdSmax = 1e30;
+constexpr double kEulerC = 0.57721566490153286;
+constexpr double kProdFloor = -575.64627324851142;   // -250 ln 10
+double ln_e_min(double gmin) { return -1.0 / gmin - kEulerC - std::log(kProdSmax); }
+double ln_b_min(const svils_handle *h) {
+  const svils_config &c = h->cfg;
+  const double n = (double)h->geo.n;
+  return -1.0 / c.eta0 - kEulerC - std::log(c.eta0 + c.eta1 + 2.0 * (double)h->d.nlinks + n * n);
+}
+bool lpl_product_gate(const svils_handle *h, uint64_t nlinks, double *gmin) {
+  const svils_config &c = h->cfg;
+  const Geometry &g = h->geo;
+  *gmin = 0.0;
+  if (!h->d.lpl || g.K > 32u || g.node_begin != 0 || g.node_end != g.n) return false;   // (K-shards and column tiles are never lane-per-link)
+  if (!(c.link_thresh >= 0.5) || nlinks == 0 || !(c.alpha > 0.0) || !(c.eta0 > 0.0) || !(c.eta1 >= 0.0)) return false;
+  *gmin = c.alpha * std::min(1.0, (double)c.ones / (2.0 * (double)nlinks));
+  if (!(*gmin > 0.0)) return false;
+  return 2.0 * ln_e_min(*gmin) + ln_b_min(h) >= kProdFloor;
+}
+
+// out[0..2]: bit patterns of the largest -M, -X, -Elogbeta[k][0] (non-negative doubles order like their bit patterns);
+// out[3]: links / columns whose value is no number
+__global__ __launch_bounds__(256) void k_state_links(uint64_t nl, uint32_t K, uint32_t ld, const uint32_t *__restrict__ links,
+                                                     const double *__restrict__ el, const double *__restrict__ elogbeta,
+                                                     unsigned long long *out) {
+  if (blockIdx.x == 0 && threadIdx.x < K) {
+    const double b = elogbeta[2 * threadIdx.x];
+    if (!(b == b) || b == -__builtin_huge_val()) atomicAdd(&out[3], 1ull);
+    else atomicMax(&out[2], (unsigned long long)__double_as_longlong(fmax(-b, 0.0)));
+  }
+  for (uint64_t l = (uint64_t)blockIdx.x * 256u + threadIdx.x; l < nl; l += (uint64_t)gridDim.x * 256u) {
+    const uint32_t p = links[2 * l], q = links[2 * l + 1];
+    double m = -__builtin_huge_val(), xp = m, xq = m;
+    bool nan = false;
+    for (uint32_t k = 0; k < K; ++k) {
+      const double a = el[(size_t)p * ld + k], b = el[(size_t)q * ld + k];
+      nan |= !(a + b == a + b);   // (fmax drops a NaN operand)
+      m = fmax(m, a + b);
+      xp = fmax(xp, a);
+      xq = fmax(xq, b);
+    }
+    const double x = fmin(xp, xq);
+    if (nan || m == -__builtin_huge_val()) { atomicAdd(&out[3], 1ull); continue; }
+    atomicMax(&out[0], (unsigned long long)__double_as_longlong(fmax(-m, 0.0)));
+    atomicMax(&out[1], (unsigned long long)__double_as_longlong(fmax(-x, 0.0)));
+  }
+}
+}  // namespace
+
+// Brings d.epi / d.skip_elogpi in line with the gate and, once graph and state are both there, with the state on the device
+// (gamma and lambda are there or on their way on the handle's stream).  A state that fails turns the mode off for good on
+// this handle.
+int lpl_product_update(svils_handle *h) {
+  if (!h->epi_lpl) return 0;
+  DeviceState &d = h->d;
+  if (h->prod_gate && h->have_graph && h->have_state) {
+    DeviceState dv = d;
+    dv.epi = nullptr;                         // Elogpi rows of the arrived state (k_dir_exp writes them whatever the mode)
+    launch_dir_exp(h->geo, dv, h->stream);
+    launch_lambda_exp(h->geo, d, h->stream);
+    unsigned long long w[4] = {0ull, 0ull, 0ull, 0ull};
+    HIPCHK(hipMemsetAsync(h->prod_state, 0, sizeof w, h->stream));
+    const uint64_t nl = d.nlinks;
+    const uint32_t nb = (uint32_t)std::min<uint64_t>((nl + 255u) / 256u, 4096u);
+    hipLaunchKernelGGL(k_state_links, dim3(nb ? nb : 1u), dim3(256), 0, h->stream, nl, h->geo.K, h->geo.ld, d.links, d.elogpi,
+                       d.elogbeta, h->prod_state);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(w, h->prod_state, sizeof w, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double v[3];
+    memcpy(v, w, sizeof v);
+    const double M = -v[0], X = -v[1], B = std::min(-v[2], ln_b_min(h));
+    if (w[3] || !(M + B >= kProdFloor) || !(X + ln_e_min(h->prod_gmin) + B >= kProdFloor)) h->prod_gate = false;
+  }
+  const bool on = h->prod_gate;
+  if (on != (d.epi != nullptr)) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    drop_graphs(h);   // captured launches hold the other pointers
+    d.epi = on ? h->epi_lpl : nullptr;
+    d.skip_elogpi = on ? 1 : 0;
+  }
+  h->opt.lpl_product = on ? 1 : 0;
+  return 0;
+}
+
 // chunk a row segment [off, off+len) of node p into items of <= ch neighbours
 void chunk_row(std::vector<Item> &items, uint32_t p, uint32_t off, uint32_t len, uint32_t ch,
                int32_t *next_slot, int32_t *first_slot, uint32_t *nsplit) {
@@ -437,6 +548,9 @@ int svils_set_graph(svils_handle *h, const uint32_t *links, uint64_t nlinks) {
     if (h->opt.wt >= 0) d.wt = (d.lpl && h->opt.wt != 0) ? 1 : 0;                                     // A/B knob
   }
   d.nlinks = nlinks;
+  // product mode (lpl_product_gate, above): -1 follows the gate, 0 / 1 force; a forced 1 still needs the gate
+  h->prod_gate = h->opt.lpl_product != 0 && lpl_product_gate(h, nlinks, &h->prod_gmin);
+  h->opt.lpl_product = 0;   // (reads back the decision: lpl_product_update sets 1 once the buffers exist)
   d.ent_begin = rowptr[g.node_begin];
   d.ent_end = rowptr[g.node_end];
   d.lpl_w0 = 0;
@@ -520,6 +634,10 @@ int svils_set_graph(svils_handle *h, const uint32_t *links, uint64_t nlinks) {
     guard(dalloc(h, &d.tbase, tiles_all));
     guard(dalloc(h, &d.tpoll, tiles_all));
     if (g.K <= 32) guard(dalloc(h, &d.gacc0, (size_t)g.n_alloc * g.ld));   // three-launch sweeps accumulate beside gamma
+    if (h->prod_gate) {   // exp(Elogpi) rows beside the Elogpi buffer, which a state outside the bound falls back to
+      guard(dalloc(h, &h->epi_lpl, (size_t)g.n_alloc * g.ld));
+      guard(dalloc(h, &h->prod_state, 4));
+    }
     {
       // co-residency of the in-launch hand-off: the s3 launch's 64 + 1 role blocks next to whatever s3 blocks are still
       // running.  Not met on a partition of a few CUs; not knowable under a CU mask (the attribute still counts every
@@ -581,6 +699,12 @@ int svils_set_graph(svils_handle *h, const uint32_t *links, uint64_t nlinks) {
   h->h_rowptr.swap(rowptr);
   h->h_upper.swap(upper);
   h->have_graph = true;
+  if (int rc_ = lpl_product_update(h)) return rc_;
+  if (d.epi && d.lpl && h->have_state) {   // the state came first: its exp(Elogpi) rows
+    launch_dir_exp(g, d, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
   return apply_s3_split(h);
 }
 
@@ -645,6 +769,8 @@ int state_arrived(svils_handle *h, const double *lambda, const uint32_t *converg
   uint32_t *cur = d.conv + (size_t)c.parity * g.n_alloc;
   if (converged) HIPCHK(hipMemcpyAsync(cur, converged, g.n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   else HIPCHK(hipMemsetAsync(cur, 0, g.n * sizeof(uint32_t), h->stream));
+  h->have_state = true;
+  if (int rc_ = lpl_product_update(h)) return rc_;   // (before the expectations: it decides which rows they are)
   if (!d.ksh) launch_dir_exp(g, d, h->stream);   // K-sharded: the row sums cross ranks (svils_ksh_init_state)
   launch_lambda_exp(g, d, h->stream);
   HIPCHK(hipGetLastError());

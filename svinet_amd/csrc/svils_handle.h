@@ -148,6 +148,14 @@ struct svils_handle {
   GraphLadder whole_graphs{eager_sweeps, hipStreamCaptureModeThreadLocal, true};
   GraphLadder block_graphs{sharded_sweeps, hipStreamCaptureModeRelaxed, false};
   uint32_t graph_after = 128;           // sweeps a handle runs eagerly before it captures graphs (svils_sweep, svils_sweep_sharded)
+  // Product mode of the lane-per-link layout (K <= 32, svils_api.hip: lpl_product_gate): d.epi = epi_lpl, d.skip_elogpi = 1 while it is
+  // on.  The gate is decided with the graph; every state that ARRIVES from outside (svils_set_state, svils_init_gamma) is measured
+  // on the device (lpl_product_update) and turns the mode off for the handle if a link of it could underflow -- the Elogpi
+  // buffer stays allocated, so the exp kernels take over as they are.
+  bool prod_gate = false;
+  double prod_gmin = 0.0;          // lower bound of every gamma entry a sweep writes
+  double *epi_lpl = nullptr;
+  unsigned long long *prod_state = nullptr;   // device: what k_state_links measures (four words)
   double *elogpi_view = nullptr;   // DeviceState::skip_elogpi: where svils_get_aux(0) / SVILS_BUF_ELOGPI get their Elogpi rows computed
   std::vector<void *> allocs;
   // pipelined reports (svils_report_enqueue): staging slots, a copy stream, per-slot events
@@ -315,6 +323,7 @@ int open_device(int device, const char *bad_args = nullptr);
 int drain_timing(svils_handle *h);
 int fault_error(uint32_t code);
 int elogpi_rows(svils_handle *h, double **rows);
+int lpl_product_update(svils_handle *h);   // product mode of the lane-per-link layout: on / off by the gate and the state on the device
 int state_arrived(svils_handle *h, const double *lambda, const uint32_t *converged);   // the tail of svils_set_state   // the Elogpi rows of the state as it stands (computed now where a handle does not store them)
 void chunk_row(std::vector<Item> &items, uint32_t p, uint32_t off, uint32_t len, uint32_t ch,
                int32_t *next_slot, int32_t *first_slot, uint32_t *nsplit);

@@ -213,7 +213,12 @@ __global__ __launch_bounds__(256) void k_validate_lpl(Geometry geo, DeviceState 
 #ifndef LPL_MID_KC   // smallest KC that takes the LPL_MID_* shape
 #define LPL_MID_KC 12
 #endif
-template <int KC, int NW, bool PIPE>
+// PROD (K <= 32, DeviceState::epi set: product mode, svils_api.hip: lpl_product_gate): the rows are exp(Elogpi) and eb[] holds
+// exp(Elogbeta[.][0]), so a term is t_k = (e_p[k] e_q[k]) b[k] -- two multiplies instead of two adds, a max pass, an argmax pass,
+// a subtraction and an exponential -- and phi_k = t_k / sum_j t_j (j ascending).  No log-domain fall-back: the gate's bound
+// keeps every t_k above 1e-250.  A link tags column k iff t_k > link_thresh * sum (link_thresh >= 1/2: at most one column
+// passes).  Everything behind the row -- staging, column walk, flush rules, sumfx, role blocks -- is shared.
+template <int KC, int NW, bool PIPE, bool PROD = false>
 __global__ __launch_bounds__(64 * NW, (PIPE || KC >= 18 ? 2 : KC >= LPL_MID_KC ? LPL_MID_OCC : 4)) void k_phi_lpl(Geometry geo, DeviceState d, Params prm) {
   STAMP(0, 0);
   DevCtrl *ctrl = d.ctrl;
@@ -238,15 +243,16 @@ __global__ __launch_bounds__(64 * NW, (PIPE || KC >= 18 ? 2 : KC >= LPL_MID_KC ?
   // (k >= K) get -inf, which masks them in the softmax without any select.
   __shared__ double eb[KR];
   const uint32_t K = geo.K, ld = geo.ld;
-  double ebv = NEG_INF;
-  if (threadIdx.x < K) ebv = d.elogbeta[2 * threadIdx.x];
+  // (PROD: exp(Elogbeta[.][0]), once per block; padding columns 0.0, which masks them in the product)
+  double ebv = PROD ? 0.0 : NEG_INF;
+  if (threadIdx.x < K) ebv = PROD ? exp_neg(fmin(d.elogbeta[2 * threadIdx.x], 0.0)) : d.elogbeta[2 * threadIdx.x];
   if (stopped) return;
   STAMP(0, 1);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool write_comm = wcomm != 0;
   const uint32_t tot0 = cpar ? t10 : t00, tot1 = cpar ? t11 : t01;
   const uint32_t n0 = (tot0 + 63u) >> 6, n1 = (tot1 + 63u) >> 6, nit = n0 + n1;
-  const double *__restrict__ elogpi = d.elogpi;
+  const double *__restrict__ elogpi = PROD ? d.epi : d.elogpi;   // PROD: rows of exp(Elogpi)
   double *mylds = lds[wave];
   const uint32_t step = d.nb_a * NW;
   uint32_t it = blockIdx.x * NW + wave;
@@ -315,13 +321,34 @@ __global__ __launch_bounds__(64 * NW, (PIPE || KC >= 18 ? 2 : KC >= LPL_MID_KC ?
             xb[u] = rq[k];
           }
         }
+        if constexpr (PROD) {
+          if (ku[0] >= 0) {   // the same products over the union's columns, ascending k
+            dense_row = true;
+            double ssum = 0.0;
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+              su[u] = ku[u] >= 0 ? (xa[u] * xb[u]) * eb[ku[u] >= 0 ? ku[u] : 0] : 0.0;
+              ssum += su[u];
+            }
+            const double inv = fast_rcp(ssum);
+            if (write_comm) {
+              const double thr = prm.link_thresh * ssum;
+#pragma unroll
+              for (int u = 0; u < NU; ++u) tagk = (su[u] > thr) ? ku[u] : tagk;
+            }
+#pragma unroll
+            for (int u = 0; u < NU; ++u) su[u] *= inv;
+          }
+        }
         double m = NEG_INF;
+        if constexpr (!PROD) {
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
           if (ku[u] >= 0) su[u] = (xa[u] + xb[u]) + eb[ku[u]];   // the reference's order (:686)
           m = max_f64(m, su[u]);
         }
-        if (m != NEG_INF) {
+        }
+        if (!PROD && m != NEG_INF) {
           dense_row = true;
           int best = 0;
 #pragma unroll
@@ -358,8 +385,8 @@ __global__ __launch_bounds__(64 * NW, (PIPE || KC >= 18 ? 2 : KC >= LPL_MID_KC ?
       if constexpr (PIPE) {
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
-          phi[2 * c] = (ra[c].x + rb[c].x) + eb[2 * c];
-          phi[2 * c + 1] = (ra[c].y + rb[c].y) + eb[2 * c + 1];
+          phi[2 * c] = PROD ? (ra[c].x * rb[c].x) * eb[2 * c] : (ra[c].x + rb[c].x) + eb[2 * c];
+          phi[2 * c + 1] = PROD ? (ra[c].y * rb[c].y) * eb[2 * c + 1] : (ra[c].y + rb[c].y) + eb[2 * c + 1];
         }
       } else {
         const double *rp = elogpi + (size_t)p * ld, *rq = elogpi + (size_t)q * ld;
@@ -367,8 +394,8 @@ __global__ __launch_bounds__(64 * NW, (PIPE || KC >= 18 ? 2 : KC >= LPL_MID_KC ?
         for (int c = 0; c < KC; ++c) {
           const double2 a = *reinterpret_cast<const double2 *>(rp + 2 * c);
           const double2 b = *reinterpret_cast<const double2 *>(rq + 2 * c);
-          phi[2 * c] = (a.x + b.x) + eb[2 * c];
-          phi[2 * c + 1] = (a.y + b.y) + eb[2 * c + 1];
+          phi[2 * c] = PROD ? (a.x * b.x) * eb[2 * c] : (a.x + b.x) + eb[2 * c];
+          phi[2 * c + 1] = PROD ? (a.y * b.y) * eb[2 * c + 1] : (a.y + b.y) + eb[2 * c + 1];
         }
       }
     }
@@ -378,7 +405,21 @@ __global__ __launch_bounds__(64 * NW, (PIPE || KC >= 18 ? 2 : KC >= LPL_MID_KC ?
     }
     uint32_t pnn = 0xffffffffu, qnn = 0;
     if constexpr (PIPE) fetch_idx(it + 2 * step, pnn, qnn);
-    if (valid && !list) {
+    if (PROD && valid && !list) {
+      dense_row = true;
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < KR; ++k) s += phi[k];   // ascending k; padding columns are 0 via eb[]
+      const double inv = fast_rcp(s);
+      if (write_comm) {   // (wave-uniform)
+        const double thr = prm.link_thresh * s;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) tagk = (phi[k] > thr) ? k : tagk;
+      }
+#pragma unroll
+      for (int k = 0; k < KR; ++k) phi[k] *= inv;
+    }
+    if (!PROD && valid && !list) {
       dense_row = true;
       // branch-free from here so the KR independent exp chains interleave
       double m = NEG_INF;
@@ -583,9 +624,36 @@ __device__ __forceinline__ FinIdx fin_load_idx(const DeviceState &d, uint32_t p,
   return x;
 }
 
+// exp_neg (svils_devutil.h), same operations and constants, for the tail of k_finalize_lpl's node loop: there the compiler
+// hoists the nine polynomial constants out of the loop into 18 VGPRs that stay live through the whole body (v_fmac wants its
+// addend in a register) -- 4 VGPRs more than the 168 of a 9-wave block, i.e. scratch.  An empty asm on each constant keeps
+// it a scalar pair formed where it is used.
+__device__ __forceinline__ double exp_neg_tail(double t) {
+  auto C = [](double c) { asm volatile("" : "+s"(c)); return c; };
+  t = fmax(t, -750.0);
+  const double n = rint(t * 1.4426950408889634);
+  double r = fma(n, -6.93147180369123816490e-01, t);
+  r = fma(n, -1.90821492927058770002e-10, r);
+  double p = 2.51100376059637769e-08;
+  p = fma(p, r, C(2.76326396390410286e-07));
+  p = fma(p, r, C(2.75572409185789696e-06));
+  p = fma(p, r, C(2.48014854823284939e-05));
+  p = fma(p, r, C(1.98412698900471131e-04));
+  p = fma(p, r, C(1.38888889523147751e-03));
+  p = fma(p, r, C(8.33333333331960115e-03));
+  p = fma(p, r, C(4.16666666664880989e-02));
+  p = fma(p, r, C(1.66666666666666796e-01));
+  p = fma(p, r, C(5.00000000000001887e-01));
+  p = fma(p, r, 1.0);
+  p = fma(p, r, 1.0);
+  return ldexp(p, (int)n);
+}
+
 // LIGHT: the node-block form (see k_finalize in svils_device.hip): mean indicators, s1 / s2, tags and the unscaled row into
 // the exchange staging; scale, Elogpi and prune() follow in k_expand_all behind the exchange.
-template <int FW, int NC, bool STOCH, bool LIGHT = false, int NTH = fin_threads(NC)>
+// PROD (product mode, K <= 32): the row written for the phi pass is exp(Elogpi) into d.epi instead of Elogpi -- NC interleaved
+// exp_neg chains on values that are live anyway; nothing else in a small-K sweep reads Elogpi rows.
+template <int FW, int NC, bool STOCH, bool LIGHT = false, int NTH = fin_threads(NC), bool PROD = false>
 __global__ __launch_bounds__(NTH, (NTH >= 768 ? 3 : 2)) void k_finalize_lpl(Geometry geo, DeviceState d, Params prm) {
   STAMP(1, 0);
   DevCtrl *ctrl = d.ctrl;
@@ -870,7 +938,9 @@ __global__ __launch_bounds__(NTH, (NTH >= 768 ? 3 : 2)) void k_finalize_lpl(Geom
     unsigned long long bits = 0ull;
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-      if (ST(j)) row_store(&d.elogpi[rowoff + j * FW], kv[j] ? ps[j] - psi_rs : 0.0, d.wt != 0);
+      if constexpr (!PROD) {
+        if (ST(j)) row_store(&d.elogpi[rowoff + j * FW], kv[j] ? ps[j] - psi_rs : 0.0, d.wt != 0);
+      }
       // prune / check_and_set_converged, src/linksampling.cc:455-475
       bits |= ((__ballot(kv[j] && (gn[j] - prm.alpha >= 1.0)) >> (g * FW)) & group_mask<FW>()) << (j * FW);
     }
@@ -889,6 +959,15 @@ __global__ __launch_bounds__(NTH, (NTH >= 768 ? 3 : 2)) void k_finalize_lpl(Geom
       if (nown < geo.n) {   // node-block handles only: the same flags, packed for the exchange (nobody reads them otherwise)
         uint32_t *xf = d.xflags + (size_t)p * d.xf_ld;
         xf[0] = cnew; xf[1] = active; xf[2] = (uint32_t)am; xf[3] = (uint32_t)(am >> 32);
+      }
+    }
+    if constexpr (PROD) {
+      // the row for the phi pass, last: by now only the NC differences are live beside the loop's own state.
+      // psi(gamma_k) - psi(row sum) <= 0 by construction (the clamp takes the last bit of the two digamma evaluations)
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const double e = exp_neg_tail(kv[j] ? fmin(ps[j] - psi_rs, 0.0) : 0.0);
+        if (ST(j)) row_store(&d.epi[rowoff + j * FW], e, d.wt != 0);   // padding columns stay 0
       }
     }
     ix = ix_next;
@@ -1178,25 +1257,30 @@ __global__ __launch_bounds__(NTH) void k_s3_lpl(Geometry geo, DeviceState d, Par
       if (threadIdx.x < 128) logtab[threadIdx.x] = ltv;
       double s1 = 0.0, s2 = 0.0;
       {
-        constexpr uint32_t RG = NTH / 32, NL = 256 / RG;   // row groups x 32 columns; nb_c <= 192 rows
+        // The order of k_tail's fold of the same rows (FoldRows<32, 256>, svils_devutil.h: eight row groups r0, r0 + 8, ...,
+        // each added in row order, then the groups in order), by the first 256 threads: a three-launch and a four-launch
+        // sweep then leave the same bits in lambda.  With one row group per 32 threads of the block (16 or 32 groups) the two
+        // forms differed in the last bit of s3, which 40 sweeps amplify to 1e-12 of gamma.  nb_c <= 192 rows: 24 loads.
+        constexpr uint32_t RG = 8, NL = 192 / RG;
         const uint32_t c = threadIdx.x & 31u, r0 = threadIdx.x >> 5;
         double v[NL];
 #pragma unroll
         for (uint32_t i = 0; i < NL; ++i) {
           const uint32_t r = r0 + RG * i;
-          v[i] = (c < K && r < d.nb_c) ? ld_agent(&d.part_c[(size_t)r * K + c]) : 0.0;
+          v[i] = (r0 < RG && c < K && r < d.nb_c) ? ld_agent(&d.part_c[(size_t)r * K + c]) : 0.0;
         }
         if (threadIdx.x < K) { s1 = ld_agent(&d.kvec_c[threadIdx.x]); s2 = ld_agent(&d.kvec_c[K + threadIdx.x]); }   // same wait
         double t = 0.0;
 #pragma unroll
-        for (uint32_t i = 0; i < NL; ++i) t += v[i];
-        tmp[r0 * 32 + c] = t;
+        for (uint32_t i = 0; i < NL; ++i)
+          if (RG * i < d.nb_c) t += v[i];   // (uniform; past the last row only zeros follow, which change no bit)
+        if (r0 < RG) tmp[r0 * 32 + c] = t;
       }
       __syncthreads();
       if (threadIdx.x < 32) {
         double t = 0.0;
 #pragma unroll
-        for (uint32_t i = 0; i < NTH / 32; ++i) t += tmp[i * 32 + threadIdx.x];
+        for (uint32_t i = 0; i < 8; ++i) t += tmp[i * 32 + threadIdx.x];
         s3tot[threadIdx.x] = t;
       }
       __syncthreads();
@@ -1344,9 +1428,14 @@ uint32_t lpl_scatter_blocks(const DeviceState &d) {
   return nb ? nb : 1u;
 }
 void launch_phi_lpl(const Geometry &g, const DeviceState &d, const Params &p, hipStream_t s) {
+  // (product mode exists for KC <= 16 alone: beyond, the flag below is false and both arms are the one instantiation)
 #define CALL(KC_)                                                                                   \
-  hipLaunchKernelGGL((k_phi_lpl<KC_, lpl_waves(KC_), lpl_pipe(KC_)>), dim3(d.nb_a + (d.fused3 ? d.nvb : 0u)),      \
-                     dim3(64 * lpl_waves(KC_)), 0, s, g, d, p)
+  do {                                                                                              \
+    if (d.epi) hipLaunchKernelGGL((k_phi_lpl<KC_, lpl_waves(KC_), lpl_pipe(KC_), (KC_ <= 16)>), dim3(d.nb_a + (d.fused3 ? d.nvb : 0u)), \
+                                  dim3(64 * lpl_waves(KC_)), 0, s, g, d, p);                        \
+    else hipLaunchKernelGGL((k_phi_lpl<KC_, lpl_waves(KC_), lpl_pipe(KC_)>), dim3(d.nb_a + (d.fused3 ? d.nvb : 0u)), \
+                            dim3(64 * lpl_waves(KC_)), 0, s, g, d, p);                              \
+  } while (0)
   LPL_DISPATCH(g.K, CALL);
 #undef CALL
 }
@@ -1375,8 +1464,14 @@ uint32_t lpl_finalize_resident_blocks(uint32_t K, int device) {
 void launch_finalize_lpl(const Geometry &g, const DeviceState &d, const Params &p, hipStream_t s) {
 #define FIN(W_, NC_)                                                                                \
   do {                                                                                              \
-    if (p.stoch) hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, true>), dim3(d.nb_b), dim3(fin_threads(NC_)), 0, s, g, d, p); \
-    else if (d.light && NC_ == 4 && d.fin_waves == 12u)                                             \
+    if (d.epi && !d.light) {   /* product mode (FW = 8 alone: beyond, the flag is false and these are the instantiations below) */ \
+      if (p.stoch) hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, true, false, fin_threads(NC_), (W_ == 8)>), dim3(d.nb_b), dim3(fin_threads(NC_)), 0, s, g, d, p); \
+      else if (NC_ == 4 && d.fin_waves == 12u)                                                      \
+        hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, false, false, (NC_ == 4 ? 768 : fin_threads(NC_)), (W_ == 8)>), dim3(d.nb_b), dim3(768), 0, s, g, d, p); \
+      else hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, false, false, fin_threads(NC_), (W_ == 8)>), dim3(d.nb_b), dim3(fin_threads(NC_)), 0, s, g, d, p); \
+    }                                                                                               \
+    else if (p.stoch) hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, true>), dim3(d.nb_b), dim3(fin_threads(NC_)), 0, s, g, d, p); \
+    else if (d.light && NC_ == 4 && d.fin_waves == 12u)                                           \
       hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, false, true, (NC_ == 4 ? 768 : fin_threads(NC_))>), dim3(d.nb_b), dim3(768), 0, s, g, d, p); \
     else if (d.light) hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, false, true>), dim3(d.nb_b), dim3(fin_threads(NC_)), 0, s, g, d, p); \
     else if (NC_ == 4 && d.fin_waves == 12u)                                                        \

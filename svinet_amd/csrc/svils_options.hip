@@ -43,6 +43,10 @@ const Row kRows[] = {
      "write-through row stores of the lane-per-link finalise / phi passes: -1 when the n-by-k state is 1 - 8 MB, 0 / 1 forced"},
     {"fused3", "SVILS_FUSED3", "-1", GRAPH, I32, OFF(fused3), -1, 1,
      "three-launch sweeps (in-launch hand-offs between role blocks): -1 by the static co-residency check, 0 / 1 forced"},
+    {"lpl_product", "SVILS_LPL_PRODUCT", "-1", GRAPH, I32, OFF(lpl_product), -1, 1,
+     "K <= 32, lane-per-link layout, whole-graph handle, link_thresh >= 1/2: the finalise pass stores exp(Elogpi) rows instead of Elogpi "
+     "and the phi pass multiplies (no exponentials per link): -1 where the static underflow bound holds, 0 / 1 forced (a forced 1 that "
+     "fails a condition falls back to 0); after svils_set_graph the option reads back the decision taken"},
     {"one_comm", "SVILS_ONE_COMM", "0", ANY, I32, OFF(one_comm), 0, 1,
      "1: the chunked row exchange of node-block sweeps shares the first communicator instead of forming a second one"},
     {"xchunks", "SVILS_XCHUNKS", "0", ANY, U32, OFF(xchunks), 0, 64,
