@@ -657,6 +657,18 @@ typedef struct svils_batch svils_batch;
  * SVILS_ERR_UNSUPPORTED: k > SVILS_BATCH_MAX_K or n > SVILS_BATCH_MAX_N (checked before any device call) */
 int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double eta0, double eta1, double epsilon,
                        svils_batch **out);
+/* The same handle in SPARSE FORM, for the sampled engines (-rnode / -rpair / -infset / -snode) on graphs of any n the
+ * memory holds: same arguments, contract and k limit, no SVILS_BATCH_MAX_N check (n < 2: SVILS_ERR_ARG; no room on the
+ * device: SVILS_ERR_NOMEM, naming the buffer).  svils_batch_set_graph then keeps the links and the skip pairs as two
+ * symmetric CSRs with ascending rows and 64-bit row offsets, on the host and on the device -- 8 (n + 1) + 8 * pairs bytes
+ * each, nothing n x n anywhere -- with the same refusals in the same order.  The step kernels look a pair up by a
+ * lower-bound search in a sorted row where the dense form reads a bit; everything else is the same code, and the two
+ * forms give the same bits.  Every entry point works as on the dense form except the all-pairs
+ * passes: svils_batch_sweep, svils_batch_elbo and svils_batch_set_elbo_tiles answer SVILS_ERR_UNSUPPORTED and touch
+ * nothing.  State: 3 * n * k * 8 bytes at creation, and [ceil(n / G)][k] * 3 doubles (G = 64 / W pairs per wavefront)
+ * from the first node step on (either form) */
+int svils_batch_create_sparse(int device, uint32_t n, uint32_t k, double alpha, double eta0, double eta1, double epsilon,
+                              svils_batch **out);
 int svils_batch_destroy(svils_batch *h);
 /* links [nlinks][2]: y(p, q) = 1 (Network::y); skip [nskip][2]: the held-out and validation pairs batch_infer leaves out
  * (:851-853).  Every pair has p < q < n; a self pair, p > q, a node >= n or a pair repeated inside its list: SVILS_ERR_ARG */

@@ -44,7 +44,7 @@ EXPORTS = (
     "svils_batch_sweep", "svils_batch_pair_loglik", "svils_batch_get_stats", "svils_batch_get_timing", "svils_batch_variant",
     "svils_batch_step_node", "svils_batch_step_pairs", "svils_batch_step_star", "svils_batch_set_star_chain",
     "svils_batch_get_expectations", "svils_batch_elbo", "svils_batch_set_elbo_tiles",
-    "svils_batch_step_strat", "svils_batch_get_lag",
+    "svils_batch_step_strat", "svils_batch_get_lag", "svils_batch_create_sparse",
     "svils_orig_create", "svils_orig_destroy", "svils_orig_set_graph", "svils_orig_set_state", "svils_orig_get_state",
     "svils_orig_sweep", "svils_orig_pair_loglik", "svils_orig_get_stats", "svils_orig_get_timing", "svils_orig_variant",
     "svils_orig_set_launch_rows", "svils_orig_link_prob", "svils_orig_predict_links", "svils_orig_rank_links",
@@ -204,6 +204,7 @@ def load():
     L.svils_lc_get_gml.argtypes = [vp, C.POINTER(C.c_uint64), vp]
     L.svils_lc_get_timing.argtypes = [vp, vp]
     L.svils_batch_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(vp)]
+    L.svils_batch_create_sparse.argtypes = L.svils_batch_create.argtypes
     L.svils_batch_destroy.argtypes = [vp]
     L.svils_batch_set_graph.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
     L.svils_batch_set_state.argtypes = [vp, vp, vp]
@@ -695,12 +696,14 @@ def batch_variant(k):
 
 
 class Batch:
-    """One svils_batch handle: the body of MMSBInfer::batch_infer (all pairs) on the device."""
+    """One svils_batch handle: the body of MMSBInfer::batch_infer (all pairs) on the device.  sparse=True:
+    svils_batch_create_sparse, the form of the sampled steps without a cap on n (no sweep, no elbo)."""
 
-    def __init__(self, n, k, alpha, eta, epsilon=1e-30, device=0):
+    def __init__(self, n, k, alpha, eta, epsilon=1e-30, device=0, sparse=False):
         self._h = C.c_void_p()
-        self.n, self.k = n, k
-        _chk(load().svils_batch_create(device, n, k, alpha, eta[0], eta[1], epsilon, C.byref(self._h)))
+        self.n, self.k, self.sparse = n, k, bool(sparse)
+        create = load().svils_batch_create_sparse if sparse else load().svils_batch_create
+        _chk(create(device, n, k, alpha, eta[0], eta[1], epsilon, C.byref(self._h)))
 
     def set_graph(self, links, skip=()):
         links = np.ascontiguousarray(links, dtype=np.uint32).reshape(-1, 2)

@@ -574,9 +574,49 @@ __device__ __forceinline__ void wave_partial(double pa, double pj, bool y, bool 
 // a stored row value at its true value (strat steps, below): f == 1 exactly (a row that is not behind) keeps its bits
 __device__ __forceinline__ double caught_up(double g, double alpha, double f) { return f == 1.0 ? g : alpha + (g - alpha) * f; }
 
-struct StepArgs {
-  uint32_t n, K, nw;
+// ---- the graph of the step kernels: one policy per form of the handle (svils_batch_create / svils_batch_create_sparse),
+// in the style of BitRows / CsrRows (svils_pairtiles.h).  star(a, j): the pair of a node step, looked up from a's side -- is
+// it left out, and its y; link(p, q), p < q: y of a listed pair
+
+// dense form: bit q of row p (p < q) of two [n][nw] bit matrices, one word read each
+struct DenseGraph {
   const uint32_t *adj, *skip;
+  uint32_t nw;
+  __device__ __forceinline__ void star(uint32_t a, uint32_t j, bool &skipped, bool &y) const {
+    const uint32_t p = min(a, j), q = max(a, j);
+    const size_t wd = (size_t)p * nw + (q >> 5);
+    const uint32_t bit = 1u << (q & 31);
+    skipped = (skip[wd] & bit) != 0;
+    y = (adj[wd] & bit) != 0;
+  }
+  __device__ __forceinline__ bool link(uint32_t p, uint32_t q) const { return (adj[(size_t)p * nw + (q >> 5)] & (1u << (q & 31))) != 0; }
+};
+
+// sparse form: the links and the skip pairs as two symmetric CSRs with ascending rows and 64-bit row offsets.  A lookup is
+// a lower-bound search without a branch in its loop: at most ceil(log2(row length)) probes, none in an empty row.  A node
+// step searches the rows of a: ONE row per list, read by every group of the grid and resident in L2, a hub's included
+struct SparseGraph {
+  const uint64_t *lrow, *srow;      // [n + 1]
+  const uint32_t *lcol, *scol;
+  // q among col[b .. e), ascending and without repeats: what lies right of the window is > q, so q is there iff it ends the search
+  static __device__ __forceinline__ bool has(const uint32_t *__restrict__ col, uint64_t b, uint64_t e, uint32_t q) {
+    uint64_t len = e - b;
+    while (len > 1) {
+      const uint64_t half = len >> 1;
+      b += col[b + half - 1] < q ? half : 0;
+      len -= half;
+    }
+    return len != 0 && col[b] == q;
+  }
+  __device__ __forceinline__ void star(uint32_t a, uint32_t j, bool &skipped, bool &y) const {
+    skipped = has(scol, srow[a], srow[a + 1], j);
+    y = has(lcol, lrow[a], lrow[a + 1], j);
+  }
+  __device__ __forceinline__ bool link(uint32_t p, uint32_t q) const { return has(lcol, lrow[p], lrow[p + 1], q); }
+};
+
+struct StepArgs {
+  uint32_t n, K;
   double *gamma, *elogpi;           // [n][K]: the kernel that owns a row writes both
   const double *elogbeta;
   double logeps, alpha, scale, rho;
@@ -594,8 +634,8 @@ struct StepArgs {
 
 // Node step, first launch: group j holds the pair (a, j).  Row a and Elogpi_a are only read; row j belongs to its group,
 // which blends it and writes Elogpi_j (a skipped pair: with phi = 0).  phi_a and the lambda terms leave per wavefront.
-template <int W, int V>
-__global__ __launch_bounds__(256) void k_batch_step_node(StepArgs x) {
+template <int W, int V, class Graph>
+__global__ __launch_bounds__(256) void k_batch_step_node(StepArgs x, Graph gr) {
   constexpr int G = 64 / W;
   __shared__ double2 logtab[128];
   load_logtab(logtab, x.gtab);
@@ -606,11 +646,9 @@ __global__ __launch_bounds__(256) void k_batch_step_node(StepArgs x) {
   const bool row_ok = j < n && j != a;
   bool valid = row_ok, y = false;
   if (row_ok) {
-    const uint32_t p = min(a, j), q = max(a, j);
-    const size_t wd = (size_t)p * x.nw + (q >> 5);
-    const uint32_t bit = 1u << (q & 31);
-    valid = (x.skip[wd] & bit) == 0;
-    y = (x.adj[wd] & bit) != 0;
+    bool skipped;
+    gr.star(a, j, skipped, y);
+    valid = !skipped;
   }
   bool kval[V];
   double ela[V], elj[V], ef[V], pa[V], pj[V];
@@ -638,8 +676,8 @@ __global__ __launch_bounds__(256) void k_batch_step_node(StepArgs x) {
 }
 
 // Pair step, first launch: group e holds the e-th listed pair; phi goes to the step's buffer, the lambda terms leave per wavefront
-template <int W, int V>
-__global__ __launch_bounds__(256) void k_batch_step_phi(StepArgs x) {
+template <int W, int V, class Graph>
+__global__ __launch_bounds__(256) void k_batch_step_phi(StepArgs x, Graph gr) {
   constexpr int G = 64 / W;
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / W, lw = lane % W;
   const uint32_t K = x.K, wv = blockIdx.x * 4 + wave, e = wv * G + g;
@@ -649,7 +687,7 @@ __global__ __launch_bounds__(256) void k_batch_step_phi(StepArgs x) {
   if (valid) {
     p = x.pairs[2 * (size_t)e];
     q = x.pairs[2 * (size_t)e + 1];
-    y = (x.adj[(size_t)p * x.nw + (q >> 5)] & (1u << (q & 31))) != 0;
+    y = gr.link(p, q);
   }
   bool kval[V];
   double elp[V], elq[V], ef[V], p1[V], p2[V];
@@ -983,8 +1021,21 @@ __global__ __launch_bounds__(STAR_THREADS) void k_batch_star_chain(StarArgs x) {
 
 // events: ev[0] sweep begin, ev[1] Elogpi / Elogbeta done, then per launch of the pair kernel ev[2 + 2 b] (pairs done) and
 // ev[3 + 2 b] (reduced)
+// a list of pairs as a symmetric CSR with ascending rows: the host copy of the sparse form, for the checks of the step calls
+struct HostCsr {
+  std::vector<uint64_t> row;   // [n + 1]
+  std::vector<uint32_t> col;
+  bool has(uint32_t p, uint32_t q) const { return std::binary_search(col.begin() + row[p], col.begin() + row[p + 1], q); }
+  void clear() {
+    std::vector<uint64_t>().swap(row);
+    std::vector<uint32_t>().swap(col);
+  }
+};
+
 struct svils_batch : ToolHandle {
   uint32_t n = 0, k = 0, w = 0, ta = 0, nw = 0;
+  bool sparse = false;                                            // svils_batch_create_sparse: no n x n structure anywhere
+  HostCsr h_links, h_skips;                                       // sparse form: what h_adj / h_skip are to the dense form
   double alpha = 0, eta0 = 0, eta1 = 0, epsilon = 0;
   // HANDLE scope
   double *gamma = nullptr, *gnext = nullptr, *elogpi = nullptr;   // [n][k]
@@ -992,7 +1043,9 @@ struct svils_batch : ToolHandle {
   double *gtab = nullptr;                                         // [128][2] log_tab's table
   unsigned long long *ctr = nullptr;                              // [5]
   // GRAPH scope
-  uint32_t *adj = nullptr, *skip = nullptr;                       // [n][nw]
+  uint32_t *adj = nullptr, *skip = nullptr;                       // [n][nw] (dense form)
+  uint64_t *lrow = nullptr, *srow = nullptr;                      // sparse form: the links and the skip pairs as symmetric
+  uint32_t *lcol = nullptr, *scol = nullptr;                      // CSRs, [n + 1] offsets and ascending rows
   uint32_t *tiles = nullptr, *rowoff = nullptr, *jfirst = nullptr;
   double *pa = nullptr, *pb = nullptr, *pl = nullptr;
   uint32_t *ll_pairs = nullptr;                                   // svils_batch_pair_loglik: grown on demand
@@ -1039,6 +1092,35 @@ void free_graph(svils_batch *h) {
   h->have_graph = false;
   std::vector<uint32_t>().swap(h->h_skip);   // the host copies of the graph's bits go with it
   std::vector<uint32_t>().swap(h->h_adj);
+  h->h_links.clear();
+  h->h_skips.clear();
+}
+
+// the host's answer to "is (p, q), p < q, in the skip set" / "is it a link", in either form
+bool host_skipped(const svils_batch *h, uint32_t p, uint32_t q) {
+  return h->sparse ? h->h_skips.has(p, q) : (h->h_skip[(size_t)p * h->nw + (q >> 5)] & (1u << (q & 31))) != 0;
+}
+bool host_link(const svils_batch *h, uint32_t p, uint32_t q) {
+  return h->sparse ? h->h_links.has(p, q) : (h->h_adj[(size_t)p * h->nw + (q >> 5)] & (1u << (q & 31))) != 0;
+}
+
+// the all-pairs passes walk the tiles of the bit matrices
+int dense_only(const svils_batch *h, const char *name) {
+  if (h->sparse)
+    return fail(SVILS_ERR_UNSUPPORTED, "%s: the all-pairs passes need the dense form (svils_batch_create), this handle is in sparse form", name);
+  return 0;
+}
+
+DenseGraph dense_graph(const svils_batch *h) { return DenseGraph{h->adj, h->skip, h->nw}; }
+SparseGraph sparse_graph(const svils_batch *h) { return SparseGraph{h->lrow, h->srow, h->lcol, h->scol}; }
+
+// *p = count elements, as ToolHandle::reserve (for a pointer the scope does not hold yet: a plain allocation); where the
+// device has no room, the message the allocation left is replaced by one that names the buffer
+template <class T>
+int reserve_named(svils_batch *h, ToolHandle::Scope s, T **p, size_t count, const char *name, const char *what) {
+  const int rc = h->reserve(s, p, count);
+  if (rc == SVILS_ERR_NOMEM) return fail(SVILS_ERR_NOMEM, "%s: out of device memory for %s (%zu bytes)", name, what, count * sizeof(T));
+  return rc;
 }
 
 // The launch table, the one place that maps the handle's lane width to an instantiation: launch(Width<W>()) for W = h->w.
@@ -1169,7 +1251,7 @@ int end_steps(svils_batch *h) {
 int check_star_entries(svils_batch *h, const char *name, uint32_t nsteps, const uint32_t *start, const uint64_t *off,
                        const uint32_t *partner, const uint8_t *y, const double *rho_partner) {
   const uint32_t n = h->n;
-  if (off[nsteps] && h->h_adj.empty()) {
+  if (off[nsteps] && !h->sparse && h->h_adj.empty()) {
     std::vector<uint32_t> bits((size_t)n * h->nw);
     HIPCHK(hipStreamSynchronize(h->st));
     HIPCHK(hipMemcpy(bits.data(), h->adj, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1183,10 +1265,9 @@ int check_star_entries(svils_batch *h, const char *name, uint32_t nsteps, const 
       if (j >= n || j == a) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u pairs node %u with %u (n = %u)", name, x, s, a, j, n);
       if (seen[j] == s + 1) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u lists partner %u twice", name, x, s, j);
       seen[j] = s + 1;
-      const uint32_t p = std::min(a, j), q = std::max(a, j), bit = 1u << (q & 31);
-      const size_t wd = (size_t)p * h->nw + (q >> 5);
-      if (h->h_skip[wd] & bit) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) is in the skip set", name, x, s, p, q);
-      if (((h->h_adj[wd] & bit) != 0) != (y[e] != 0))
+      const uint32_t p = std::min(a, j), q = std::max(a, j);
+      if (host_skipped(h, p, q)) return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) is in the skip set", name, x, s, p, q);
+      if (host_link(h, p, q) != (y[e] != 0))
         return fail(SVILS_ERR_ARG, "%s: entry %llu of step %u (%u, %u) has y = %u, the graph says otherwise", name, x, s, p, q, (unsigned)y[e]);
       if (rho_partner && !(rho_partner[e] > 0.0 && rho_partner[e] <= 1.0))
         return fail(SVILS_ERR_ARG, "%s: rho_partner of entry %llu of step %u is not in (0, 1]", name, x, s);
@@ -1260,13 +1341,74 @@ class Staging {
   size_t nwords_ = 0, elem_ = sizeof(double);
 };
 
+// Sparse form: one list of svils_batch_set_graph as a symmetric CSR with ascending rows.  The refusals are the dense form's,
+// in its order -- the first entry that is no pair p < q < n or repeats an earlier one -- with the repeat found after a sort
+// of the entries before the first that is no pair.  The sorted list fills the rows in order: row r takes its partners
+// below r while their rows are walked and those above r in its own, so no row is sorted again
+int build_csr(uint32_t n, const uint32_t *list, uint64_t cnt, const char *what, HostCsr &out) {
+  uint64_t bad = cnt;
+  for (uint64_t x = 0; x < cnt && bad == cnt; ++x)
+    if (list[2 * x] >= list[2 * x + 1] || list[2 * x + 1] >= n) bad = x;
+  std::vector<std::pair<uint64_t, uint64_t>> key((size_t)bad);   // (p, q) in one word, then the entry
+  for (uint64_t x = 0; x < bad; ++x) key[x] = {((uint64_t)list[2 * x] << 32) | list[2 * x + 1], x};
+  std::sort(key.begin(), key.end());
+  uint64_t rep = cnt;   // equal pairs stand together in entry order: the first repeat is the least second of two neighbours
+  for (uint64_t i = 1; i < bad; ++i)
+    if (key[i].first == key[i - 1].first) rep = std::min(rep, key[i].second);
+  if (rep < cnt)
+    return fail(SVILS_ERR_ARG, "svils_batch_set_graph: %s %llu (%u, %u) is repeated", what, (unsigned long long)rep, list[2 * rep], list[2 * rep + 1]);
+  if (bad < cnt)
+    return fail(SVILS_ERR_ARG, "svils_batch_set_graph: %s %llu (%u, %u) is not a pair p < q < n = %u", what, (unsigned long long)bad,
+                list[2 * bad], list[2 * bad + 1], n);
+  out.row.assign((size_t)n + 1, 0);
+  out.col.assign(2 * (size_t)cnt, 0);
+  for (uint64_t x = 0; x < cnt; ++x) {
+    ++out.row[list[2 * x] + 1];
+    ++out.row[list[2 * x + 1] + 1];
+  }
+  for (uint32_t i = 0; i < n; ++i) out.row[i + 1] += out.row[i];
+  std::vector<uint64_t> at(out.row.begin(), out.row.end() - 1);
+  for (const auto &kx : key) {
+    const uint32_t p = (uint32_t)(kx.first >> 32), q = (uint32_t)kx.first;
+    out.col[at[p]++] = q;
+    out.col[at[q]++] = p;
+  }
+  return 0;
+}
+
+// svils_batch_set_graph of a sparse-form handle: the two CSRs, on the host for the checks of the step calls and on the
+// device for the step kernels.  No tile list, no tile partials, no bit copies: nothing here is n x n
+int set_graph_sparse(svils_batch *h, const uint32_t *links, uint64_t nlinks, const uint32_t *skip, uint64_t nskip) {
+  HostCsr lk, sk;
+  if (int rc = build_csr(h->n, links, nlinks, "link", lk)) return rc;
+  if (int rc = build_csr(h->n, skip, nskip, "skipped pair", sk)) return rc;
+  HIPCHK(hipStreamSynchronize(h->st));
+  free_graph(h);
+  const auto scope = ToolHandle::GRAPH;
+  int rc = h->upload(scope, &h->lrow, lk.row);
+  if (!rc) rc = h->upload(scope, &h->lcol, lk.col);   // an empty list: a null pointer no search reads
+  if (!rc) rc = h->upload(scope, &h->srow, sk.row);
+  if (!rc) rc = h->upload(scope, &h->scol, sk.col);
+  if (!rc && hipStreamSynchronize(h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "svils_batch_set_graph: upload failed");
+  if (rc) {
+    free_graph(h);
+    return rc;
+  }
+  h->h_links.row.swap(lk.row);
+  h->h_links.col.swap(lk.col);
+  h->h_skips.row.swap(sk.row);
+  h->h_skips.col.swap(sk.col);
+  std::vector<uint32_t>().swap(h->h_tiles);
+  h->ntiles = h->nrb = h->batch = 0;
+  h->have_graph = true;
+  h->timed = svils_batch::Timed::NONE;
+  return 0;
+}
+
 StepArgs step_args(svils_batch *h, double scale, double rho) {
   StepArgs x{};
   x.n = h->n;
   x.K = h->k;
-  x.nw = h->nw;
-  x.adj = h->adj;
-  x.skip = h->skip;
   x.gamma = h->gamma;
   x.elogpi = h->elogpi;
   x.elogbeta = h->elogbeta;
@@ -1294,13 +1436,15 @@ int svils_batch_variant(uint32_t k, uint32_t *w, uint32_t *v) {
   return 0;
 }
 
-int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double eta0, double eta1, double epsilon, svils_batch **out) {
-  if (!out) return fail(SVILS_ERR_ARG, "svils_batch_create: null argument");
+// both forms of the handle: the dense form (sparse = false) keeps the n cap of its bit matrices, the sparse form has none
+static int create_batch(const char *name, bool sparse, int device, uint32_t n, uint32_t k, double alpha, double eta0, double eta1,
+                        double epsilon, svils_batch **out) {
+  if (!out) return fail(SVILS_ERR_ARG, "%s: null argument", name);
   *out = nullptr;
   if (n < 2 || k < 2 || !(alpha > 0) || !(eta0 > 0) || !(eta1 > 0) || !(epsilon > 0) || !(epsilon < 1))
-    return fail(SVILS_ERR_ARG, "svils_batch_create: need n >= 2, k >= 2, alpha, eta0, eta1 > 0 and 0 < epsilon < 1");
-  if (k > SVILS_BATCH_MAX_K) return fail(SVILS_ERR_UNSUPPORTED, "svils_batch_create: k = %u exceeds SVILS_BATCH_MAX_K = %d", k, SVILS_BATCH_MAX_K);
-  if (n > SVILS_BATCH_MAX_N) return fail(SVILS_ERR_UNSUPPORTED, "svils_batch_create: n = %u exceeds SVILS_BATCH_MAX_N = %d", n, SVILS_BATCH_MAX_N);
+    return fail(SVILS_ERR_ARG, "%s: need n >= 2, k >= 2, alpha, eta0, eta1 > 0 and 0 < epsilon < 1", name);
+  if (k > SVILS_BATCH_MAX_K) return fail(SVILS_ERR_UNSUPPORTED, "%s: k = %u exceeds SVILS_BATCH_MAX_K = %d", name, k, SVILS_BATCH_MAX_K);
+  if (!sparse && n > SVILS_BATCH_MAX_N) return fail(SVILS_ERR_UNSUPPORTED, "%s: n = %u exceeds SVILS_BATCH_MAX_N = %d", name, n, SVILS_BATCH_MAX_N);
   if (int rc = open_device(device)) return rc;
   svils_batch *h = new (std::nothrow) svils_batch();
   if (!h) return fail(SVILS_ERR_NOMEM, "out of host memory");
@@ -1308,7 +1452,8 @@ int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double 
   h->k = k;
   h->w = variant_w(k);
   h->ta = 4 * (uint32_t)rows_per_wave((int)(h->w * VARIANT_V));
-  h->nw = (n + 31) / 32;
+  h->sparse = sparse;
+  h->nw = sparse ? 0 : (n + 31) / 32;
   h->alpha = alpha;
   h->eta0 = eta0;
   h->eta1 = eta1;
@@ -1317,22 +1462,31 @@ int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double 
   const auto scope = ToolHandle::HANDLE;
   const size_t nk = (size_t)n * k;
   int rc = h->open(device, 2);
-  if (!rc) rc = h->dalloc(scope, &h->gamma, nk);
-  if (!rc) rc = h->dalloc(scope, &h->gnext, nk);
-  if (!rc) rc = h->dalloc(scope, &h->elogpi, nk);
-  if (!rc) rc = h->dalloc(scope, &h->lam, 2 * (size_t)k);
-  if (!rc) rc = h->dalloc(scope, &h->lnext, 2 * (size_t)k);
-  if (!rc) rc = h->dalloc(scope, &h->elogbeta, 2 * (size_t)k);
-  if (!rc) rc = h->dalloc(scope, &h->ctr, 5);
+  if (!rc) rc = reserve_named(h, scope, &h->gamma, nk, name, "gamma");
+  if (!rc) rc = reserve_named(h, scope, &h->gnext, nk, name, "gamma_next");
+  if (!rc) rc = reserve_named(h, scope, &h->elogpi, nk, name, "Elogpi");
+  if (!rc) rc = reserve_named(h, scope, &h->lam, 2 * (size_t)k, name, "lambda");
+  if (!rc) rc = reserve_named(h, scope, &h->lnext, 2 * (size_t)k, name, "lambda_next");
+  if (!rc) rc = reserve_named(h, scope, &h->elogbeta, 2 * (size_t)k, name, "Elogbeta");
+  if (!rc) rc = reserve_named(h, scope, &h->ctr, (size_t)5, name, "the counters");
   if (!rc) rc = h->upload(scope, &h->gtab, log_table());
-  if (!rc && hipMemsetAsync(h->ctr, 0, 5 * sizeof(unsigned long long), h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "svils_batch_create: memset failed");
-  if (!rc && hipStreamSynchronize(h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "svils_batch_create: upload failed");
+  if (!rc && hipMemsetAsync(h->ctr, 0, 5 * sizeof(unsigned long long), h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "%s: memset failed", name);
+  if (!rc && hipStreamSynchronize(h->st) != hipSuccess) rc = fail(SVILS_ERR_DEVICE, "%s: upload failed", name);
   if (rc) {
     svils_batch_destroy(h);
     return rc;
   }
   *out = h;
   return 0;
+}
+
+int svils_batch_create(int device, uint32_t n, uint32_t k, double alpha, double eta0, double eta1, double epsilon, svils_batch **out) {
+  return create_batch("svils_batch_create", false, device, n, k, alpha, eta0, eta1, epsilon, out);
+}
+
+int svils_batch_create_sparse(int device, uint32_t n, uint32_t k, double alpha, double eta0, double eta1, double epsilon,
+                              svils_batch **out) {
+  return create_batch("svils_batch_create_sparse", true, device, n, k, alpha, eta0, eta1, epsilon, out);
 }
 
 int svils_batch_destroy(svils_batch *h) {
@@ -1351,6 +1505,7 @@ int svils_batch_destroy(svils_batch *h) {
 int svils_batch_set_graph(svils_batch *h, const uint32_t *links, uint64_t nlinks, const uint32_t *skip, uint64_t nskip) {
   if (int rc = check(h, "svils_batch_set_graph")) return rc;
   if ((nlinks && !links) || (nskip && !skip)) return fail(SVILS_ERR_ARG, "svils_batch_set_graph: null argument");
+  if (h->sparse) return set_graph_sparse(h, links, nlinks, skip, nskip);
   const uint32_t n = h->n, nw = h->nw;
   std::vector<uint32_t> adj((size_t)n * nw, 0), skp((size_t)n * nw, 0);
   for (int which = 0; which < 2; ++which) {
@@ -1442,6 +1597,7 @@ int svils_batch_get_state(svils_batch *h, double *gamma, double *lambda) {
 
 int svils_batch_sweep(svils_batch *h, uint32_t nsweeps) {
   if (int rc = check(h, "svils_batch_sweep")) return rc;
+  if (int rc = dense_only(h, "svils_batch_sweep")) return rc;
   if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "svils_batch_sweep: set the graph and the state first");
   if (int rc = catch_up(h)) return rc;
   for (uint32_t s = 0; s < nsweeps; ++s)
@@ -1461,15 +1617,19 @@ int svils_batch_step_node(svils_batch *h, uint32_t nsteps, const uint32_t *nodes
   if (!nsteps) return 0;
   if (int rc = catch_up(h)) return rc;
   const uint32_t n = h->n, K = h->k, G = 64 / h->w, nb = blocks(n, 4 * G), nwv = 4 * nb;
-  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_part, (size_t)nwv * K)) return rc;
-  if (int rc = h->reserve(ToolHandle::HANDLE, &h->st_pl, (size_t)nwv * K * 2)) return rc;
+  // the per-wavefront partials grow with n ([ceil(n / G)][K] and twice that): allocated by the first node step, not at creation
+  if (int rc = reserve_named(h, ToolHandle::HANDLE, &h->st_part, (size_t)nwv * K, name, "the node steps' phi partials")) return rc;
+  if (int rc = reserve_named(h, ToolHandle::HANDLE, &h->st_pl, (size_t)nwv * K * 2, name, "the node steps' lambda partials")) return rc;
   if (int rc = begin_steps(h)) return rc;
   for (uint32_t s = 0; s < nsteps; ++s) {
     StepArgs x = step_args(h, scale, rho_gamma[s]);
     x.a = nodes[s];
-    if (int rc = launch_for_width(h, name, [&](auto w) {
-          hipLaunchKernelGGL((k_batch_step_node<decltype(w)::value, (int)VARIANT_V>), dim3(nb), dim3(256), 0, h->st, x);
-        }))
+    const auto launch = [&](auto gr) {
+      return launch_for_width(h, name, [&](auto w) {
+        hipLaunchKernelGGL((k_batch_step_node<decltype(w)::value, (int)VARIANT_V, decltype(gr)>), dim3(nb), dim3(256), 0, h->st, x, gr);
+      });
+    };
+    if (int rc = h->sparse ? launch(sparse_graph(h)) : launch(dense_graph(h)))
       return rc;
     double *ga = h->gamma + (size_t)x.a * K;
     hipLaunchKernelGGL(k_batch_step_tail, dim3(K), dim3(256), 0, h->st, K, nwv, h->st_part, h->st_pl, ga, h->alpha, h->eta0, h->eta1,
@@ -1496,7 +1656,7 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
       const uint32_t p = pairs[2 * e], q = pairs[2 * e + 1];
       if (p >= q || q >= n)
         return fail(SVILS_ERR_ARG, "%s: pair %llu of step %u (%u, %u) is not a pair p < q < n = %u", name, (unsigned long long)(e - off[s]), s, p, q, n);
-      if (h->h_skip[(size_t)p * h->nw + (q >> 5)] & (1u << (q & 31)))
+      if (host_skipped(h, p, q))
         return fail(SVILS_ERR_ARG, "%s: pair %llu of step %u (%u, %u) is in the skip set", name, (unsigned long long)(e - off[s]), s, p, q);
     }
   if (int rc = catch_up(h)) return rc;
@@ -1538,11 +1698,14 @@ int svils_batch_step_pairs(svils_batch *h, uint32_t nsteps, const uint64_t *off,
     x.noff = lists.device(s_noff) + (size_t)s * (n + 1);
     x.phi = h->st_phi;
     const uint32_t nb = blocks(m, 4 * G);
-    if (int rc = launch_for_width(h, name, [&](auto w) {
-          constexpr int W = decltype(w)::value, V = (int)VARIANT_V;
-          if (m) hipLaunchKernelGGL((k_batch_step_phi<W, V>), dim3(nb), dim3(256), 0, h->st, x);
-          hipLaunchKernelGGL((k_batch_step_rows<W, V>), dim3(blocks(n, 4 * G)), dim3(256), 0, h->st, x);
-        }))
+    const auto launch = [&](auto gr) {
+      return launch_for_width(h, name, [&](auto w) {
+        constexpr int W = decltype(w)::value, V = (int)VARIANT_V;
+        if (m) hipLaunchKernelGGL((k_batch_step_phi<W, V, decltype(gr)>), dim3(nb), dim3(256), 0, h->st, x, gr);
+        hipLaunchKernelGGL((k_batch_step_rows<W, V>), dim3(blocks(n, 4 * G)), dim3(256), 0, h->st, x);
+      });
+    };
+    if (int rc = h->sparse ? launch(sparse_graph(h)) : launch(dense_graph(h)))
       return rc;
     if (rho_lambda[s] >= 0.0)
       hipLaunchKernelGGL(k_batch_step_tail, dim3(K), dim3(256), 0, h->st, K, 4 * nb, (const double *)nullptr, h->st_pl, (double *)nullptr,
@@ -1740,6 +1903,7 @@ int svils_batch_pair_loglik(svils_batch *h, const uint32_t *pairs, const uint8_t
 
 int svils_batch_set_elbo_tiles(svils_batch *h, uint32_t tiles_per_launch) {
   if (int rc = check(h, "svils_batch_set_elbo_tiles")) return rc;
+  if (int rc = dense_only(h, "svils_batch_set_elbo_tiles")) return rc;
   if (tiles_per_launch > BATCH_TILES)
     return fail(SVILS_ERR_ARG, "svils_batch_set_elbo_tiles: %u tiles per launch exceed the most, %u", tiles_per_launch, BATCH_TILES);
   h->elbo_tiles = tiles_per_launch ? tiles_per_launch : BATCH_TILES;
@@ -1749,6 +1913,7 @@ int svils_batch_set_elbo_tiles(svils_batch *h, uint32_t tiles_per_launch) {
 int svils_batch_elbo(svils_batch *h, double parts[4], uint64_t *pairs_done, uint64_t *rounds_total) {
   const char *name = "svils_batch_elbo";
   if (int rc = check(h, name)) return rc;
+  if (int rc = dense_only(h, name)) return rc;
   if (!parts) return fail(SVILS_ERR_ARG, "%s: null argument", name);
   if (!h->have_graph || !h->have_state) return fail(SVILS_ERR_ARG, "%s: set the graph and the state first", name);
   if (int rc = catch_up(h)) return rc;

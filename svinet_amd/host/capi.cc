@@ -47,6 +47,7 @@ typedef struct {
   double tau0, kappa, nodetau0, nodekappa;   // their step sizes (svih_options_default: 1024, 0.9, 1024, 0.5)
   double inf_epsilon;      // svih_infset_from_file: the chance of a non-informative step (svih_options_default: 1e-4)
   int32_t logl;            // svih_batch_from_file / svih_infset_from_file: -logl, a row of the lower bound after the constructor and at every report
+  int32_t sparse_graph;    // the sampled engines on the device: -sparse-graph (svils_batch_create_sparse, no cap on n)
 } svih_options;
 
 struct svih_setup {
@@ -202,6 +203,7 @@ static svih_batch *make_batch(const char *path, const svih_options *o, const cha
   }
   a.device = o->device;
   a.logl = o->logl != 0;
+  a.sparse_graph = o->sparse_graph != 0;   // (the all-pairs passes of such a handle answer SVILS_ERR_UNSUPPORTED: a sweep, the lower bound)
   a.rand_seed = o->seed;
   a.hol_ratio = o->heldout_ratio;
   a.eta_type = eta_names[(o->eta_type >= 0 && o->eta_type < 4) ? o->eta_type : 0];

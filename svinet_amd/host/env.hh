@@ -30,6 +30,9 @@ class Env {
     // -snode: stratified random node SVI (FastAMM2::infer, src/fastamm2.cc:535-702; the reference starts it with
     // -stratified -rnode).  The constructor is -infset's; the chance of a non-link step is inf_epsilon, 0.5 there (:15)
     bool snode = false;
+    // -sparse-graph (with -rnode / -rpair / -infset / -snode on the device): the handle keeps the graph as sorted adjacency
+    // rows (svils_batch_create_sparse) and -n has no cap
+    bool sparse_graph = false;
     // -orig: the full K x K blockmodel (MMSBInferOrig::batch_infer, src/mmsbinferorig.cc:212-294); -itype: its beta start
     // (0: init_beta1, > 0: init_beta2).  On the device unless -host-loops is given
     bool orig = false;
@@ -138,6 +141,7 @@ class Env {
   bool infset, preprocess;           // -infset / -preprocess (src/env.hh:325, :436)
   double inf_epsilon;                // the chance of a non-informative step (-snode: of a non-link step)
   bool snode;                        // -snode (FastAMM2)
+  bool sparse_graph;                 // -sparse-graph: the device handle in sparse form; the number of pairs counted in 64 bits
   bool fastamm() const { return infset || snode; }   // the constructor both engines share (src/fastamm.cc:64-97)
   bool orig, orig_device;            // -orig; without -host-loops MMSBInferOrig drives a svils_orig handle
   int itype;                         // -itype (src/main.cc:193-194), read by -orig alone

@@ -111,6 +111,11 @@ static const ToolMode kOrig = {
         F_MINIBATCH | F_ADAMIC,
     "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
 
+static const ToolMode kSparseGraph = {       // -sparse-graph: the sparse form of the device graph of -rnode / -rpair / -infset / -snode
+    F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS,
+    "error: %1$s is not available with %2$s (it is the graph form of the sampled engines on the GPU: -rnode, -rpair, -infset, -snode; "
+    "the all-pairs passes and the other tools keep the dense form)\n"};
+
 // true (the refusal printed) when a flag `mode` refuses is set
 static bool refused(const Env::Args &a, const ToolMode &mode, const char *flag) {
   const struct { unsigned bit; bool set; const char *name; } flags[] = {
@@ -176,20 +181,24 @@ static void usage() {
           "\t-batch-gpu\t-batch with every sweep and pair likelihood on the GPU: same output directory and files, -k <= 256,\n"
           "\t\t\t-n <= 32768.  Single GPU; without one the run fails (no fall-back to the host engine)\n\n"
           "\t-rnode\t\tstochastic variational inference of the model of -batch, one random node per iteration: the\n"
-          "\t\t\tn - 1 pairs of the node are the mini-batch.  On the GPU (-k <= 256, -n <= 32768; without one the run fails);\n"
+          "\t\t\tn - 1 pairs of the node are the mini-batch.  On the GPU (-k <= 256, -n <= 32768 unless -sparse-graph; without one the run fails);\n"
           "\t\t\ta report every 100 iterations unless -rfreq came before it; step sizes -tau0 -kappa -nodetau0 -nodekappa\n\n"
           "\t-rpair\t\tthe same with n / 2 random pairs per iteration; not with -rnode\n\n"
           "\t-stratified\twith -rpair: mini-batches alternate between non-links and links (with -rnode or alone: refused)\n\n"
           "\t-nodelay\twith -rnode / -rpair: learn lambda from the first iteration (default: once iterations x n / 2 exceed the\n"
           "\t\t\tnumber of pairs)\n\n"
           "\t-host-loops\twith -rnode / -rpair / -infset / -snode: the host CPU loops instead of the GPU (small graphs)\n\n"
+          "\t-sparse-graph\twith -rnode / -rpair / -infset / -snode on the GPU: the device keeps the links and the held-out pairs as\n"
+          "\t\t\tsorted adjacency rows, not as n x n bit matrices, and -n has no limit but the memory (-k <= 256 stays).\n"
+          "\t\t\tThe same results bit for bit where both forms run.  Refused beside -batch, -batch-gpu, -logl, -orig, -ppc,\n"
+          "\t\t\t-ppc-orig, -gen, -link-sampling, -findk, -gml, -lcstats, -preprocess and -host-loops, and without an engine\n\n"
           "\t-snode\t\tinference using stratified random node sampling (the reference's -stratified -rnode): an iteration\n"
           "\t\t\ttakes a random node with its links or, as often, with n / 10 of its non-links, and moves every row.\n"
-          "\t\t\tOn the GPU (-k <= 256, -n <= 32768; without one the run fails); a report every 100 iterations unless\n"
+          "\t\t\tOn the GPU (-k <= 256, -n <= 32768 unless -sparse-graph; without one the run fails); a report every 100 iterations unless\n"
           "\t\t\t-rfreq came before it; step sizes -tau0 -kappa -nodetau0 -nodekappa\n\n"
           "\t-infset\t\tinference using informative set sampling: an iteration takes a random node, its links and the\n"
           "\t\t\tnon-links -preprocess chose for it (rarely: 200 other non-links) and moves only their rows.  Reads neighbors.bin\n"
-          "\t\t\tof the working directory.  On the GPU, a report interval per launch chain (-k <= 256, -n <= 32768; without\n"
+          "\t\t\tof the working directory.  On the GPU, a report interval per launch chain (-k <= 256, -n <= 32768 unless -sparse-graph; without\n"
           "\t\t\tone the run fails); give -rfreq (default 1: a report after every iteration)\n\n"
           "\t-preprocess\tpreprocess to run informative set sampling: writes neighbors.bin (per node up to 100 two-hop\n"
           "\t\t\tnon-neighbours) into the run's output directory and exits; host CPU, threaded\n\n"
@@ -313,6 +322,7 @@ int main(int argc, char **argv) {
     else if (is("-rpair")) { a.rpair = true; if (a.rfreq == 1) a.rfreq = 100; }
     else if (is("-stratified")) { a.stratified = true; if (a.rfreq == 1) a.rfreq = 100; }
     else if (is("-host-loops")) { a.host_loops = true; }
+    else if (is("-sparse-graph")) { a.sparse_graph = true; }
     else if (is("-scale")) { need(i); a.scale = atof(argv[++i]); }
     else if (is("-file")) { need(i); a.datfname = argv[++i]; }
     else if (is("-batch")) { a.batch = true; a.link_sampling = false; a.rfreq = 1; }
@@ -397,6 +407,21 @@ int main(int argc, char **argv) {
   const bool infset = a.infset || a.preprocess;
   const bool ppc_plain = a.ppc;
   if (a.ppc_orig) a.ppc = true;                          // -ppc-orig: the -ppc mode plus the K x K kind (it does not set -orig)
+  if (a.sparse_graph && !unsupported) {                  // -sparse-graph: refusals before anything is read or created
+    const struct { bool set; const char *name; } more[] = {   // (-batch-gpu first: it sets -batch too, and is the flag to name)
+        {a.batch_gpu, "-batch-gpu"}, {a.logl, "-logl"}, {a.orig, "-orig"}, {a.ppc_orig, "-ppc-orig"}, {a.ppc, "-ppc"}, {a.gen, "-gen"},
+        {a.preprocess, "-preprocess"}, {a.host_loops, "-host-loops"}};
+    for (const auto &m : more)
+      if (m.set) {
+        fprintf(stderr, kSparseGraph.fmt, "-sparse-graph", m.name);
+        return 2;
+      }
+    if (refused(a, kSparseGraph, "-sparse-graph")) return 2;
+    if (!(sampled || a.infset || a.snode)) {
+      fprintf(stderr, "error: -sparse-graph belongs to -rnode, -rpair, -infset or -snode runs (alone it selects no engine)\n");
+      return 2;
+    }
+  }
   if (a.ppc_hops && !unsupported) {                      // -ppc-hops: beside -ppc alone; refusals before anything is read or created
     if (refused(a, kHops, "-ppc-hops")) return 2;
     const struct { bool set; const char *name; } more[] = {
@@ -482,8 +507,8 @@ int main(int argc, char **argv) {
       fprintf(stderr, "error: -snode holds -k <= %d (SVILS_BATCH_MAX_K); -k %u is refused\n", SVILS_BATCH_MAX_K, a.k);
       return 2;
     }
-    if (!a.host_loops && a.n > SVILS_BATCH_MAX_N) {
-      fprintf(stderr, "error: -snode holds -n <= %d (SVILS_BATCH_MAX_N); -n %u is refused\n", SVILS_BATCH_MAX_N, a.n);
+    if (!a.host_loops && !a.sparse_graph && a.n > SVILS_BATCH_MAX_N) {
+      fprintf(stderr, "error: -snode holds -n <= %d (SVILS_BATCH_MAX_N) unless -sparse-graph is given; -n %u is refused\n", SVILS_BATCH_MAX_N, a.n);
       return 2;
     }
     a.inf_epsilon = 0.5;                                 // _inf_epsilon of FastAMM2 (src/fastamm2.cc:15)
@@ -499,8 +524,8 @@ int main(int argc, char **argv) {
       fprintf(stderr, "error: -infset holds -k <= %d (SVILS_BATCH_MAX_K); -k %u is refused\n", SVILS_BATCH_MAX_K, a.k);
       return 2;
     }
-    if (!a.preprocess && !a.host_loops && a.n > SVILS_BATCH_MAX_N) {
-      fprintf(stderr, "error: -infset holds -n <= %d (SVILS_BATCH_MAX_N); -n %u is refused\n", SVILS_BATCH_MAX_N, a.n);
+    if (!a.preprocess && !a.host_loops && !a.sparse_graph && a.n > SVILS_BATCH_MAX_N) {
+      fprintf(stderr, "error: -infset holds -n <= %d (SVILS_BATCH_MAX_N) unless -sparse-graph is given; -n %u is refused\n", SVILS_BATCH_MAX_N, a.n);
       return 2;
     }
   }
@@ -562,8 +587,8 @@ int main(int argc, char **argv) {
       fprintf(stderr, "error: %s holds -k <= %d (SVILS_BATCH_MAX_K); -k %u is refused\n", flag, SVILS_BATCH_MAX_K, a.k);
       return 2;
     }
-    if (!a.host_loops && a.n > SVILS_BATCH_MAX_N) {
-      fprintf(stderr, "error: %s holds -n <= %d (SVILS_BATCH_MAX_N); -n %u is refused\n", flag, SVILS_BATCH_MAX_N, a.n);
+    if (!a.host_loops && !a.sparse_graph && a.n > SVILS_BATCH_MAX_N) {
+      fprintf(stderr, "error: %s holds -n <= %d (SVILS_BATCH_MAX_N) unless -sparse-graph is given; -n %u is refused\n", flag, SVILS_BATCH_MAX_N, a.n);
       return 2;
     }
   }

@@ -92,8 +92,11 @@ void MMSBBatch::device_failed(const char *what, int rc) {
 }
 
 void MMSBBatch::attach_device() {
-  if (int rc = svils_batch_create(env_.device, n_, k_, env_.alpha, env_.eta0, env_.eta1, env_.epsilon, &dev_))
-    device_failed("svils_batch_create", rc);
+  // -sparse-graph: the handle's sparse form, without a cap on n (no sweep, no lower bound: main() refuses those beside it)
+  const char *create = env_.sparse_graph ? "svils_batch_create_sparse" : "svils_batch_create";
+  if (int rc = (env_.sparse_graph ? svils_batch_create_sparse : svils_batch_create)(env_.device, n_, k_, env_.alpha, env_.eta0, env_.eta1,
+                                                                                     env_.epsilon, &dev_))
+    device_failed(create, rc);
   std::set<Edge> links(network_.edges().begin(), network_.edges().end()), skip;
   for (const auto &it : heldout_map_) skip.insert(it.first);
   for (const auto &it : validation_map_) skip.insert(it.first);
@@ -877,7 +880,7 @@ void MMSBBatch::compute_and_log_groups() {
   }
   for (uint32_t k = 0; k < k_; ++k) beta[k] = lambda_[2 * k] / (lambda_[2 * k] + lambda_[2 * k + 1]);
   std::map<uint32_t, std::vector<uint32_t> > communities;
-  std::vector<uint32_t> groups(n_, 0);
+  std::vector<uint32_t> groups(n_, 0), nbrs;
   uint32_t unlikely = 0;
   for (uint32_t i = 0; i < n_; ++i) {
     const double *pi = &epi[(size_t)i * k_];
@@ -888,8 +891,13 @@ void MMSBBatch::compute_and_log_groups() {
       if (pi[j] > max) { max = pi[j]; groups[i] = j; }
     }
     fprintf(groupsf, "%d\n", groups[i]);
-    for (uint32_t m = i + 1; m < n_; ++m) {
-      if (!network_.y(i, m)) continue;
+    // the links (i, m), m > i, in ascending m, from the adjacency list where the reference asks y(i, m) of all n: the same
+    // links in the same order, each once -- the reader drops repeated pairs, so get_edges() lists a neighbour once
+    nbrs.clear();
+    for (uint32_t m : network_.get_edges(i))
+      if (m > i) nbrs.push_back(m);
+    std::sort(nbrs.begin(), nbrs.end());
+    for (uint32_t m : nbrs) {
       const double *pm = &epi[(size_t)m * k_];
       // inner_prod_max (src/matrix.hh:459-476): largest term of sum_k pi_i pi_m beta over the sum
       double u = .0, s = .0;

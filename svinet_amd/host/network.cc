@@ -252,8 +252,11 @@ void Network::set_env_variables() {
   // the reference and wraps for n >= 65537; kept for parity.
   const uint32_t n = env_.n;
   env_.total_pairs = (uint32_t)(n * (n - 1u)) / 2u;
+  // -sparse-graph runs past 65536 nodes and counts in 64 bits; every other mode keeps the wrapped count.  Above 65536
+  // nodes the scale of -rpair, the delayed-learning switch and -eta-type fromdata therefore differ between the two
+  if (env_.sparse_graph) env_.total_pairs = (uint64_t)n * (n - 1) / 2;
   if ((uint64_t)n * (n - 1) / 2 != env_.total_pairs)
-    fprintf(stderr, "warning: n(n-1)/2 wraps in 32 bits (%u nodes): total_pairs=%llu as in the reference\n",
+    fprintf(stderr, "warning: n(n-1)/2 wraps in 32 bits (%u nodes): total_pairs=%llu as in the reference (-sparse-graph, where it applies, counts in 64 bits)\n",
             n, (unsigned long long)env_.total_pairs);
   Env::plog("total pairs", env_.total_pairs);
   env_.ones_prob = (double)ones() / env_.total_pairs;

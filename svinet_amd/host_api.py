@@ -23,7 +23,7 @@ class Options(C.Structure):
                 ("lt_min_deg", C.c_uint32), ("eta_type", C.c_int32), ("accuracy", C.c_int32), ("defer_gamma", C.c_int32),
                 ("batch_device", C.c_int32), ("device", C.c_int32), ("sampled", C.c_int32), ("nodelay", C.c_int32),
                 ("tau0", C.c_double), ("kappa", C.c_double), ("nodetau0", C.c_double), ("nodekappa", C.c_double),
-                ("inf_epsilon", C.c_double), ("logl", C.c_int32)]
+                ("inf_epsilon", C.c_double), ("logl", C.c_int32), ("sparse_graph", C.c_int32)]
 
 
 _lib = None
@@ -209,7 +209,9 @@ class BatchEngine:
     """The `-batch` engine of the host library (svinet_amd/host/mmsbbatch.cc): the reference's
     all-pairs engine MMSBInfer::batch_infer (src/mmsbinfer.cc:833-930).  on_device=False: its host loops (plumbing only);
     on_device=True: the sweeps and pair likelihoods run through svils_batch_* on `device` (-batch-gpu) -- SvilsError
-    without a HIP device, never the host loops instead."""
+    without a HIP device, never the host loops instead.  sparse_graph=True (-sparse-graph): the sampled engines built on
+    this class (SampledEngine, InfsetEngine, StratNodeEngine) on the device with the handle of svils_batch_create_sparse --
+    no cap on n, no sweep and no lower bound; ValueError with on_device=False, logl=True or the all-pairs engine itself."""
 
     _SAMPLED = 0
     _STEP_SIZES = ("tau0", "kappa", "nodetau0", "nodekappa")   # the keyword arguments beyond the named ones
@@ -219,7 +221,11 @@ class BatchEngine:
         return L.svih_batch_from_file(os.fsencode(path), C.byref(o))
 
     def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, eta_type="uniform", on_device=False, device=0, nodelay=False,
-                 logl=False, **step_sizes):
+                 logl=False, sparse_graph=False, **step_sizes):
+        if sparse_graph and (type(self) is BatchEngine or not on_device or logl):
+            raise ValueError("sparse_graph belongs to the sampled engines on the device: the all-pairs passes (a sweep, "
+                             "the lower bound) need the dense form, and the host loops have no device graph")
+        self.sparse_graph = bool(sparse_graph)
         L = load()
         vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
         if not hasattr(L, "_batch_ready"):
@@ -260,6 +266,7 @@ class BatchEngine:
         o.batch_device, o.device = int(bool(on_device)), device
         o.sampled, o.nodelay = self._SAMPLED, int(bool(nodelay))
         o.logl = int(bool(logl))
+        o.sparse_graph = int(bool(sparse_graph))
         for key, value in step_sizes.items():
             if key not in self._STEP_SIZES:
                 raise TypeError("unexpected argument %r" % key)
