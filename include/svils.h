@@ -47,6 +47,7 @@ extern "C" {
                                     (additive, same version) svils_batch_elbo / svils_batch_set_elbo_tiles: -logl, the variational lower bound;
                                     (additive, same version) svils_batch_step_strat / svils_batch_get_lag: -snode, stratified random node steps;
                                     (additive, same version) svils_orig_*: -orig, the full K x K blockmodel over all ordered pairs;
+                                    (additive, same version) svils_sbm_*: -single, the single-membership stochastic blockmodel;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_ppc_*: -ppc / -gen, networks drawn from a model and their statistics;
                                     (additive, same version) svils_ppc_hops / svils_ppc_get_hop*: -ppc-hops, the exact hop plot and components;
@@ -930,6 +931,66 @@ int svils_orig_get_query_timing(svils_orig *h, double *ms);
 /* host only: the instantiation of the pair kernel for k -- padded K, pairs per wavefront, 1 if the log tables live in LDS
  * (0: in registers).  SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_ORIG_MAX_K */
 int svils_orig_variant(uint32_t k, uint32_t *padded_k, uint32_t *pairs_per_wave, uint32_t *tables_in_lds);
+
+/* ---- -single: the single-membership stochastic blockmodel (an ADDITION of ABI 8; a handle of its own) --------------------
+ * The reference's SBM::batch_infer (src/sbm.cc:457-543, src/sbm.hh).  State: phi [n][k] (rows sum to 1), gamma [k],
+ * lambda [k + 1][2] (row k: the rate between different groups; column 0 counts links, column 1 non-links).  The trained
+ * pairs T are all unordered pairs p != q that are not in the skip list.  One iteration:
+ *   E-step   at most 10 passes; a pass takes p = 0 .. n - 1 in order (Gauss-Seidel: p reads the rows 0 .. p - 1 wrote in
+ *            the same pass): a_k = Elogpi_k + sum over (p, q) in T of (1 - phi_qk) Elogbeta[K][y'] + phi_qk Elogbeta[k][y'],
+ *            y' = 0 for a link and 1 for a non-link; phi_p = exp(a - logsumexp a); msum = sum_p sum_k |old - new|; the
+ *            E-step ends after the first pass with msum < 0.01
+ *   M-step   gamma_k = alpha + sum_i phi_ik; lambda_k0 = eta_k0 + sum over links of T of phi_ik phi_jk, lambda_k1 = eta_k1 +
+ *            the same over non-links; row K: eta_K0 + sum over links sum_k (1 - phi_ik phi_jk), and over non-links; then
+ *            Elogpi = psi(gamma_k) - psi(sum gamma), Elogbeta = psi(lambda_kt) - psi(lambda_k0 + lambda_k1)
+ * The device never walks the n^2 pairs: with S the column sums of phi, the sum over all partners of p is S - phi_p, and
+ * the links and the skipped pairs of p correct it, so a pass costs O((links + skips) k) and runs at
+ * any n the memory holds.  All sums are fp64 in a fixed order (ascending partner within a row, ascending wavefront / block
+ * across partials) and no floating-point atomic is used: results are bitwise equal from run to run, on two handles, for
+ * every svils_sbm_set_launch_nodes value and for both chain forms, and svils_sbm_sweep(h, 3) equals three
+ * svils_sbm_sweep(h, 1).  Without a HIP device svils_sbm_create answers SVILS_ERR_DEVICE ("no CPU path"); every other
+ * entry point answers SVILS_ERR_DEVICE for a null handle there, SVILS_ERR_ARG where a device exists. */
+#define SVILS_SBM_MAX_K 256
+#define SVILS_SBM_MAX_PASSES 10               /* passes of one E-step (src/sbm.cc:470) */
+typedef struct svils_sbm svils_sbm;
+/* eta [k + 1][2], every entry > 0.  SVILS_ERR_ARG: n < 2, k < 2, alpha <= 0, a null pointer, an eta entry not > 0;
+ * SVILS_ERR_UNSUPPORTED: k > SVILS_SBM_MAX_K (all checked before any device call) */
+int svils_sbm_create(int device, uint32_t n, uint32_t k, double alpha, const double *eta, svils_sbm **out);
+int svils_sbm_destroy(svils_sbm *h);
+/* links [nlinks][2] with p < q < n, each once; skip [nskip][2]: pairs p < q < n left out of training, each once (a skipped
+ * pair is a link exactly when it is listed in links).  Both are kept as symmetric CSRs with ascending rows and 64-bit
+ * offsets.  The refusals (SVILS_ERR_ARG, the graph the handle had stays) are svils_batch_set_graph's */
+int svils_sbm_set_graph(svils_sbm *h, const uint32_t *links, uint64_t nlinks, const uint32_t *skip, uint64_t nskip);
+/* phi [n][k]: finite, >= 0, every row summing to 1 within 1e-9; gamma [k] > 0; lambda [k + 1][2] > 0.  Elogpi and Elogbeta
+ * are formed on the device.  SVILS_ERR_ARG otherwise (the state the handle had stays) */
+int svils_sbm_set_state(svils_sbm *h, const double *phi, const double *gamma, const double *lambda);
+/* any pointer may be NULL.  Waits for the device */
+int svils_sbm_get_state(svils_sbm *h, double *phi, double *gamma, double *lambda);
+/* The E-step alone, from the stored gamma and lambda: at most max_passes (1 .. SVILS_SBM_MAX_PASSES) passes.  *passes:
+ * the passes run; msum [max_passes]: msum of every pass run (the rest 0).  Either may be NULL.  Waits for the device */
+int svils_sbm_estep(svils_sbm *h, uint32_t max_passes, uint32_t *passes, double *msum);
+/* niter whole iterations (E-step of at most SVILS_SBM_MAX_PASSES passes, M-step, Elogpi / Elogbeta), queued without a
+ * host round trip: the launches of all passes are queued, and those behind the end of an E-step return at once */
+int svils_sbm_sweep(svils_sbm *h, uint32_t niter);
+/* edge_likelihood2 (src/sbm.hh:284-308) of the current state: out[x] = log max(s, 1e-30), s = sum_k phi_pk phi_qk f_k +
+ * (1 - sum_k phi_pk phi_qk) f_K, f = r or 1 - r by y[x], r_k = lambda_k0 / (lambda_k0 + lambda_k1).  Waits for the device */
+int svils_sbm_pair_loglik(svils_sbm *h, const uint32_t *pairs, const uint8_t *y, uint64_t m, double *out);
+/* passes of the last E-step; passes over the last svils_sbm_estep / svils_sbm_sweep call; msum [SVILS_SBM_MAX_PASSES] of
+ * every pass of the last E-step (0 past its end).  Any pointer may be NULL.  Waits for the device */
+int svils_sbm_get_stats(svils_sbm *h, uint32_t *passes_last, uint64_t *passes_call, double *msum);
+/* device ms of the last call: the whole call; the chain launches of its last E-step (those behind its end included); the
+ * M-step of its last iteration (-1 after svils_sbm_estep).  -1 before the first call */
+int svils_sbm_get_timing(svils_sbm *h, double ms[3]);
+/* nodes per launch of the chain kernel from the next call on; 0: the default, 2048 -- a launch stays a few milliseconds on
+ * a shared device (DESIGN.md section 4r has the measurement).  The results do not depend on it, bit for bit */
+int svils_sbm_set_launch_nodes(svils_sbm *h, uint32_t nodes);
+/* plain != 0: the plain chain -- one wavefront, one node per turn, no look-ahead -- instead of the blocked one.  The same
+ * bits; kept for the measurement of DESIGN.md section 4r */
+int svils_sbm_set_plain_chain(svils_sbm *h, int plain);
+/* host only: the lane mapping of the chain kernel for k -- a lane holds the columns lane, lane + 64, .. (*cols_per_lane of
+ * them) of a row -- and *block_nodes = B, the consecutive nodes (= wavefronts of the workgroup) whose gathers overlap.
+ * SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_SBM_MAX_K */
+int svils_sbm_variant(uint32_t k, uint32_t *cols_per_lane, uint32_t *block_nodes);
 
 /* ---- -ppc / -gen: networks drawn from a model and their statistics (an ADDITION of ABI 8; a handle of its own) -----------
  * The device side of the reference's MMSBGen::gen (src/mmsbgen.cc:43-71) and MMSBGen::ppc (draw_and_save, :662-697, with

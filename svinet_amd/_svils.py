@@ -49,6 +49,9 @@ EXPORTS = (
     "svils_orig_sweep", "svils_orig_pair_loglik", "svils_orig_get_stats", "svils_orig_get_timing", "svils_orig_variant",
     "svils_orig_set_launch_rows", "svils_orig_link_prob", "svils_orig_predict_links", "svils_orig_rank_links",
     "svils_orig_get_query_timing", "svils_orig_elbo", "svils_orig_get_elbo_stats", "svils_orig_get_elbo_timing",
+    "svils_sbm_create", "svils_sbm_destroy", "svils_sbm_set_graph", "svils_sbm_set_state", "svils_sbm_get_state", "svils_sbm_estep",
+    "svils_sbm_sweep", "svils_sbm_pair_loglik", "svils_sbm_get_stats", "svils_sbm_get_timing", "svils_sbm_set_launch_nodes",
+    "svils_sbm_set_plain_chain", "svils_sbm_variant",
     "svils_ppc_create", "svils_ppc_destroy", "svils_ppc_set_params", "svils_ppc_draw", "svils_ppc_set_links", "svils_ppc_stats",
     "svils_ppc_get_draw_counts", "svils_ppc_get_links", "svils_ppc_get_nodes", "svils_ppc_get_summary", "svils_ppc_get_communities",
     "svils_ppc_get_timing", "svils_ppc_set_tile_batch",
@@ -59,6 +62,7 @@ EXPORTS = (
 PPC_MAX_N, PPC_MAX_K = 32768, 2048      # SVILS_PPC_MAX_N, SVILS_PPC_MAX_K
 ORIG_MAX_K, ORIG_MAX_N = 64, 32768      # SVILS_ORIG_MAX_K, SVILS_ORIG_MAX_N
 BATCH_MAX_K, BATCH_MAX_N = 256, 32768   # SVILS_BATCH_MAX_K, SVILS_BATCH_MAX_N
+SBM_MAX_K, SBM_MAX_PASSES = 256, 10     # SVILS_SBM_MAX_K, SVILS_SBM_MAX_PASSES
 BATCH_STAR_CHAIN_MAX = 1024             # SVILS_BATCH_STAR_CHAIN_MAX
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
 NBR_CN, NBR_AA, NBR_RA = range(3)   # svils_nbr_measure
@@ -242,6 +246,19 @@ def load():
     L.svils_orig_get_elbo_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.svils_orig_get_elbo_timing.argtypes = [vp, vp]
     L.svils_orig_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.svils_sbm_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_double, vp, C.POINTER(vp)]
+    L.svils_sbm_destroy.argtypes = [vp]
+    L.svils_sbm_set_graph.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+    L.svils_sbm_set_state.argtypes = [vp, vp, vp, vp]
+    L.svils_sbm_get_state.argtypes = [vp, vp, vp, vp]
+    L.svils_sbm_estep.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), vp]
+    L.svils_sbm_sweep.argtypes = [vp, C.c_uint32]
+    L.svils_sbm_pair_loglik.argtypes = [vp, vp, vp, C.c_uint64, vp]
+    L.svils_sbm_get_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), vp]
+    L.svils_sbm_get_timing.argtypes = [vp, vp]
+    L.svils_sbm_set_launch_nodes.argtypes = [vp, C.c_uint32]
+    L.svils_sbm_set_plain_chain.argtypes = [vp, C.c_int]
+    L.svils_sbm_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.svils_ppc_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(vp)]
     L.svils_ppc_destroy.argtypes = [vp]
     L.svils_ppc_set_params.argtypes = [vp, vp, vp]
@@ -957,6 +974,85 @@ class Orig:
     def close(self):
         if getattr(self, "_h", None) and not getattr(self, "_borrowed", False):
             load().svils_orig_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+
+def sbm_variant(k):
+    """svils_sbm_variant: (columns of a row per lane, B = the nodes of a block of the chain kernel) for k; no device needed"""
+    v, b = C.c_uint32(), C.c_uint32()
+    _chk(load().svils_sbm_variant(k, C.byref(v), C.byref(b)))
+    return v.value, b.value
+
+
+class Sbm:
+    """One svils_sbm handle: the body of SBM::batch_infer (the single-membership stochastic blockmodel) on the device."""
+
+    def __init__(self, n, k, alpha, eta, device=0):
+        self._h = C.c_void_p()
+        self.n, self.k = n, k
+        eta = np.ascontiguousarray(eta, dtype=np.float64).reshape(k + 1, 2)
+        _chk(load().svils_sbm_create(device, n, k, alpha, eta.ctypes.data, C.byref(self._h)))
+
+    def set_graph(self, links, skip=()):
+        """links [m][2] with p < q; skip [s][2] with p < q: the pairs left out of training"""
+        links = np.ascontiguousarray(links, dtype=np.uint32).reshape(-1, 2)
+        skip = np.ascontiguousarray(skip, dtype=np.uint32).reshape(-1, 2)
+        _chk(load().svils_sbm_set_graph(self._h, links.ctypes.data, links.shape[0], skip.ctypes.data, skip.shape[0]))
+
+    def set_state(self, phi, gamma, lam):
+        phi = np.ascontiguousarray(phi, dtype=np.float64).reshape(self.n, self.k)
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64).reshape(self.k)
+        lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(self.k + 1, 2)
+        _chk(load().svils_sbm_set_state(self._h, phi.ctypes.data, gamma.ctypes.data, lam.ctypes.data))
+
+    def state(self):
+        """(phi [n][k], gamma [k], lambda [k + 1][2])"""
+        p, g, l = np.empty((self.n, self.k)), np.empty(self.k), np.empty((self.k + 1, 2))
+        _chk(load().svils_sbm_get_state(self._h, p.ctypes.data, g.ctypes.data, l.ctypes.data))
+        return p, g, l
+
+    def estep(self, max_passes=SBM_MAX_PASSES):
+        """the E-step alone -> (passes run, msum of every pass run)"""
+        np_, ms = C.c_uint32(), np.zeros(max(int(max_passes), 1))
+        _chk(load().svils_sbm_estep(self._h, max_passes, C.byref(np_), ms.ctypes.data))
+        return np_.value, ms[:np_.value].copy()
+
+    def sweep(self, niter=1):
+        _chk(load().svils_sbm_sweep(self._h, niter))
+
+    def pair_loglik(self, pairs, y):
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        y = np.ascontiguousarray(y, dtype=np.uint8).reshape(-1)
+        assert y.shape[0] == pairs.shape[0]
+        out = np.empty(pairs.shape[0])
+        _chk(load().svils_sbm_pair_loglik(self._h, pairs.ctypes.data, y.ctypes.data, pairs.shape[0], out.ctypes.data))
+        return out
+
+    def stats(self):
+        """(passes of the last E-step, passes over the last estep() / sweep() call, msum of every pass of the last E-step)"""
+        a, b, ms = C.c_uint32(), C.c_uint64(), np.zeros(SBM_MAX_PASSES)
+        _chk(load().svils_sbm_get_stats(self._h, C.byref(a), C.byref(b), ms.ctypes.data))
+        return a.value, b.value, ms[:a.value].copy()
+
+    def timing(self):
+        """device ms of the last call: the whole call, the chain launches of its last E-step, the M-step of its last iteration"""
+        ms = np.zeros(3)
+        _chk(load().svils_sbm_get_timing(self._h, ms.ctypes.data))
+        return ms
+
+    def set_launch_nodes(self, nodes):
+        """nodes per launch of the chain kernel (0: the library's default); the results do not depend on it"""
+        _chk(load().svils_sbm_set_launch_nodes(self._h, nodes))
+
+    def set_plain_chain(self, plain):
+        """the plain chain (one wavefront, no look-ahead) instead of the blocked one; the same bits"""
+        _chk(load().svils_sbm_set_plain_chain(self._h, int(bool(plain))))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().svils_sbm_destroy(self._h)
         self._h = None
 
     __del__ = close

@@ -54,6 +54,7 @@
 //   k_batch_elbo_reduce     one block: the lambda terms, and the three sums in a fixed order
 #include <cassert>
 
+#include "svils_csr.h"
 #include "svils_devutil.h"
 #include "svils_elbo.h"
 #include "svils_steplists.h"
@@ -1021,21 +1022,10 @@ __global__ __launch_bounds__(STAR_THREADS) void k_batch_star_chain(StarArgs x) {
 
 // events: ev[0] sweep begin, ev[1] Elogpi / Elogbeta done, then per launch of the pair kernel ev[2 + 2 b] (pairs done) and
 // ev[3 + 2 b] (reduced)
-// a list of pairs as a symmetric CSR with ascending rows: the host copy of the sparse form, for the checks of the step calls
-struct HostCsr {
-  std::vector<uint64_t> row;   // [n + 1]
-  std::vector<uint32_t> col;
-  bool has(uint32_t p, uint32_t q) const { return std::binary_search(col.begin() + row[p], col.begin() + row[p + 1], q); }
-  void clear() {
-    std::vector<uint64_t>().swap(row);
-    std::vector<uint32_t>().swap(col);
-  }
-};
-
 struct svils_batch : ToolHandle {
   uint32_t n = 0, k = 0, w = 0, ta = 0, nw = 0;
   bool sparse = false;                                            // svils_batch_create_sparse: no n x n structure anywhere
-  HostCsr h_links, h_skips;                                       // sparse form: what h_adj / h_skip are to the dense form
+  HostCsr h_links, h_skips;                                       // sparse form (svils_csr.h): what h_adj / h_skip are to the dense form
   double alpha = 0, eta0 = 0, eta1 = 0, epsilon = 0;
   // HANDLE scope
   double *gamma = nullptr, *gnext = nullptr, *elogpi = nullptr;   // [n][k]
@@ -1341,47 +1331,12 @@ class Staging {
   size_t nwords_ = 0, elem_ = sizeof(double);
 };
 
-// Sparse form: one list of svils_batch_set_graph as a symmetric CSR with ascending rows.  The refusals are the dense form's,
-// in its order -- the first entry that is no pair p < q < n or repeats an earlier one -- with the repeat found after a sort
-// of the entries before the first that is no pair.  The sorted list fills the rows in order: row r takes its partners
-// below r while their rows are walked and those above r in its own, so no row is sorted again
-int build_csr(uint32_t n, const uint32_t *list, uint64_t cnt, const char *what, HostCsr &out) {
-  uint64_t bad = cnt;
-  for (uint64_t x = 0; x < cnt && bad == cnt; ++x)
-    if (list[2 * x] >= list[2 * x + 1] || list[2 * x + 1] >= n) bad = x;
-  std::vector<std::pair<uint64_t, uint64_t>> key((size_t)bad);   // (p, q) in one word, then the entry
-  for (uint64_t x = 0; x < bad; ++x) key[x] = {((uint64_t)list[2 * x] << 32) | list[2 * x + 1], x};
-  std::sort(key.begin(), key.end());
-  uint64_t rep = cnt;   // equal pairs stand together in entry order: the first repeat is the least second of two neighbours
-  for (uint64_t i = 1; i < bad; ++i)
-    if (key[i].first == key[i - 1].first) rep = std::min(rep, key[i].second);
-  if (rep < cnt)
-    return fail(SVILS_ERR_ARG, "svils_batch_set_graph: %s %llu (%u, %u) is repeated", what, (unsigned long long)rep, list[2 * rep], list[2 * rep + 1]);
-  if (bad < cnt)
-    return fail(SVILS_ERR_ARG, "svils_batch_set_graph: %s %llu (%u, %u) is not a pair p < q < n = %u", what, (unsigned long long)bad,
-                list[2 * bad], list[2 * bad + 1], n);
-  out.row.assign((size_t)n + 1, 0);
-  out.col.assign(2 * (size_t)cnt, 0);
-  for (uint64_t x = 0; x < cnt; ++x) {
-    ++out.row[list[2 * x] + 1];
-    ++out.row[list[2 * x + 1] + 1];
-  }
-  for (uint32_t i = 0; i < n; ++i) out.row[i + 1] += out.row[i];
-  std::vector<uint64_t> at(out.row.begin(), out.row.end() - 1);
-  for (const auto &kx : key) {
-    const uint32_t p = (uint32_t)(kx.first >> 32), q = (uint32_t)kx.first;
-    out.col[at[p]++] = q;
-    out.col[at[q]++] = p;
-  }
-  return 0;
-}
-
 // svils_batch_set_graph of a sparse-form handle: the two CSRs, on the host for the checks of the step calls and on the
 // device for the step kernels.  No tile list, no tile partials, no bit copies: nothing here is n x n
 int set_graph_sparse(svils_batch *h, const uint32_t *links, uint64_t nlinks, const uint32_t *skip, uint64_t nskip) {
   HostCsr lk, sk;
-  if (int rc = build_csr(h->n, links, nlinks, "link", lk)) return rc;
-  if (int rc = build_csr(h->n, skip, nskip, "skipped pair", sk)) return rc;
+  if (int rc = build_csr("svils_batch_set_graph", h->n, links, nlinks, "link", lk)) return rc;
+  if (int rc = build_csr("svils_batch_set_graph", h->n, skip, nskip, "skipped pair", sk)) return rc;
   HIPCHK(hipStreamSynchronize(h->st));
   free_graph(h);
   const auto scope = ToolHandle::GRAPH;

@@ -16,6 +16,7 @@
 #include "network.hh"
 #include "nmi.hh"
 #include "ppc.hh"
+#include "sbm.hh"
 
 using namespace svinet;
 
@@ -374,6 +375,63 @@ const uint32_t *svih_orig_edges(const svih_orig *b) { return &b->net->edges()[0]
 uint32_t svih_orig_ones(const svih_orig *b) { return b->net->ones(); }
 // the engine's svils_orig handle, for the link queries of include/svils.h (null: host loops); the engine keeps owning it
 void *svih_orig_device(const svih_orig *b) { return b->eng->device(); }
+
+// ---- the -single engine (SBM): on_device 0 = the host loops, 1 = svils_sbm_* on `device` ----
+struct svih_sbm {
+  std::unique_ptr<Env> env;
+  std::unique_ptr<Network> net;
+  std::unique_ptr<SBM> eng;
+};
+svih_sbm *svih_sbm_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t on_device,
+                             int32_t device) {
+  Env::Args a;
+  a.n = n;
+  a.k = k;
+  a.single = true;
+  a.host_loops = on_device == 0;
+  a.device = device;
+  a.rand_seed = seed;
+  a.hol_ratio = heldout_ratio;
+  a.write_files = false;
+  svih_sbm *b = new svih_sbm();
+  b->env.reset(new Env(a));
+  b->net.reset(new Network(*b->env));
+  if (b->net->read(path) < 0) { delete b; return nullptr; }
+  b->env->n = b->net->n() - b->net->singles();
+  if (svils_rc([&] { b->eng.reset(new SBM(*b->env, *b->net)); return 0; })) {   // svils_last_error() keeps the library's text
+    delete b;
+    return nullptr;
+  }
+  return b;
+}
+void svih_sbm_free(svih_sbm *b) { delete b; }
+uint32_t svih_sbm_n(const svih_sbm *b) { return b->eng->n(); }
+uint32_t svih_sbm_iter(const svih_sbm *b) { return b->eng->iter(); }
+uint32_t svih_sbm_passes(const svih_sbm *b) { return b->eng->passes(); }
+const double *svih_sbm_msums(const svih_sbm *b) { return b->eng->msums().data(); }   // [passes]
+// which 0: phi [n][k]; 1: gamma [k]; 2: lambda [k + 1][2]; 3: eta [k + 1][2]
+int svih_sbm_state(svih_sbm *b, int32_t which, double *out) {
+  return svils_rc([&] {
+    const std::vector<double> &v = which == 0 ? b->eng->phi() : which == 1 ? b->eng->gamma() : which == 2 ? b->eng->lambda() : b->eng->eta();
+    memcpy(out, v.data(), v.size() * sizeof(double));
+    return 0;
+  });
+}
+// which 0: the held-out pairs; 1: the validation pairs; 2: the precision pairs -- [count][2], p < q, as drawn
+uint64_t svih_sbm_npairs(const svih_sbm *b, int32_t which) {
+  return (which == 0 ? b->eng->heldout_pairs() : which == 1 ? b->eng->validation_pairs() : b->eng->precision_pairs()).size() / 2;
+}
+const uint32_t *svih_sbm_pairs(const svih_sbm *b, int32_t which) {
+  return (which == 0 ? b->eng->heldout_pairs() : which == 1 ? b->eng->validation_pairs() : b->eng->precision_pairs()).data();
+}
+uint64_t svih_sbm_nrows(const svih_sbm *b) { return b->eng->rows().size() / 8; }
+const double *svih_sbm_rows(const svih_sbm *b) { return b->eng->rows().data(); }
+int svih_sbm_sweep(svih_sbm *b) { return svils_rc([&] { b->eng->sweep(); return 0; }); }   // < 0: a svils_error of the device backend
+int svih_sbm_set_state(svih_sbm *b, const double *phi, const double *gamma, const double *lambda) {
+  return svils_rc([&] { b->eng->set_state(phi, gamma, lambda); return 0; });
+}
+const uint32_t *svih_sbm_edges(const svih_sbm *b) { return &b->net->edges()[0].first; }
+uint32_t svih_sbm_ones(const svih_sbm *b) { return b->net->ones(); }
 
 // tests: how many of `count` values differ between the writers' fixed-point formatter (fixedfmt.hh) and printf's
 // "%.5f" / "%.3f" -- the values come as they are, the test chooses them

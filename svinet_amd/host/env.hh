@@ -39,7 +39,10 @@ class Env {
     // -clean-holdout (with -orig): both orientations of every held-out and validation pair are left out of training
     bool clean_holdout = false;
     int itype = 0;
-    bool findk = false;                 // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
+    // -single: the single-membership stochastic blockmodel (SBM::batch_infer, src/sbm.cc:457-543).  On the device unless
+    // -host-loops is given
+    bool single = false;
+    bool findk = false;                // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
     bool ppc = false, gen = false;      // -ppc / -gen: posterior predictive checks, a network from the prior (MMSBGen, src/main.cc:268-303)
     int ppc_draws = 100;                // -ppc-draws (ppc_ndraws, src/env.hh:452)
@@ -146,6 +149,8 @@ class Env {
   bool orig, orig_device;            // -orig; without -host-loops MMSBInferOrig drives a svils_orig handle
   int itype;                         // -itype (src/main.cc:193-194), read by -orig alone
   bool clean_holdout;                // -clean-holdout: -orig trains on no orientation of a held-out or validation pair
+  bool single, single_device;        // -single; without -host-loops SBM drives a svils_sbm handle
+  double sbm_alpha;                  // the Dirichlet prior of -single (src/env.hh:345)
   uint32_t s;                        // their mini-batch size n / 2 (src/env.hh:321; -rpair only)
   bool gml, lcstats;
   bool strid;

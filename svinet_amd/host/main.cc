@@ -8,7 +8,8 @@
 // reference's small all-pairs CPU engine -batch (plumbing only), with
 // -batch-gpu, -rnode, -rpair, -rpair -stratified, -infset (with its -preprocess pass) and -snode the same model on the device, and
 // -orig, the blockmodel with a full K x K matrix of block rates (MMSBInferOrig), on the device as well (with -clean-holdout
-// it answers the link-prediction flags too); the
+// it answers the link-prediction flags too), and -single, the single-membership stochastic blockmodel (SBM), on the device
+// too; the
 // flags that select the reference's other engines are recognised and rejected
 // with a message instead of being silently ignored.  -adamic-adar (src/main.cc:173), which
 // the reference wires to two of those engines, is here an option of the link-prediction
@@ -29,6 +30,7 @@
 #include "findk.hh"
 #include "lcstats.hh"
 #include "ppc.hh"
+#include "sbm.hh"
 #include "linksampling.hh"
 #include "mmsbbatch.hh"
 #include "mmsbinferorig.hh"
@@ -111,6 +113,12 @@ static const ToolMode kOrig = {
         F_MINIBATCH | F_ADAMIC,
     "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
 
+// -single: an engine of its own on one GPU; its graph form is always the sparse one
+static const ToolMode kSingle = {
+    F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS | F_RNODE | F_RPAIR | F_STRATIFIED | F_GPUS | F_KSHARD | F_SHARDED |
+        F_MINIBATCH | F_PAIRS | F_RECOMMEND | F_RANKPAIRS | F_RANKHELDOUT | F_ADAMIC,
+    "error: %1$s is not available with %2$s (an engine of its own: single GPU, its own output directory)\n"};
+
 static const ToolMode kSparseGraph = {       // -sparse-graph: the sparse form of the device graph of -rnode / -rpair / -infset / -snode
     F_BATCH | F_LINKSAMPLING | F_FINDK | F_GML | F_LCSTATS,
     "error: %1$s is not available with %2$s (it is the graph form of the sampled engines on the GPU: -rnode, -rpair, -infset, -snode; "
@@ -187,7 +195,7 @@ static void usage() {
           "\t-stratified\twith -rpair: mini-batches alternate between non-links and links (with -rnode or alone: refused)\n\n"
           "\t-nodelay\twith -rnode / -rpair: learn lambda from the first iteration (default: once iterations x n / 2 exceed the\n"
           "\t\t\tnumber of pairs)\n\n"
-          "\t-host-loops\twith -rnode / -rpair / -infset / -snode: the host CPU loops instead of the GPU (small graphs)\n\n"
+          "\t-host-loops\twith -rnode / -rpair / -infset / -snode / -orig / -single: the host CPU loops instead of the GPU (small graphs)\n\n"
           "\t-sparse-graph\twith -rnode / -rpair / -infset / -snode on the GPU: the device keeps the links and the held-out pairs as\n"
           "\t\t\tsorted adjacency rows, not as n x n bit matrices, and -n has no limit but the memory (-k <= 256 stays).\n"
           "\t\t\tThe same results bit for bit where both forms run.  Refused beside -batch, -batch-gpu, -logl, -orig, -ppc,\n"
@@ -206,6 +214,11 @@ static void usage() {
           "\t\t\tvariational inference over all ordered pairs, on the GPU (-k <= 64, -n <= 32768; without one the run fails,\n"
           "\t\t\t-host-loops runs the host CPU loops).  Needs -max-iterations N: N sweeps, then gamma.txt and beta.txt.\n"
           "\t\t\t-itype 0 (default) starts beta at random, -itype 1 from the link density\n\n"
+          "\t-single\t\tthe single-membership stochastic blockmodel (a node belongs to one of K groups): batch variational\n"
+          "\t\t\tinference, on the GPU in O((links + held-out pairs) K) per pass (-k <= 256, any -n the memory holds; without a GPU\n"
+          "\t\t\tthe run fails, -host-loops runs the host CPU loops over all pairs).  Needs -max-iterations N: N iterations, then\n"
+          "\t\t\tphi.txt, lambda.txt and gamma.txt.  Refused beside every other engine or tool flag, -infset (the sampled variant\n"
+          "\t\t\tis not implemented), -sparse-graph (the engine is always sparse), -logl, -gpus N > 1, -scale and the link queries\n\n"
           "\t-clean-holdout\twith -orig: leave both orientations of every held-out and every validation pair out of training\n"
           "\t\t\t(the reference leaves out the held-out pairs alone, and only in the orientation drawn).  With it -orig answers\n"
           "\t\t\t-predict-pairs, -recommend, -rank-pairs and -rank-heldout from its final state, on the GPU: the score of\n"
@@ -395,8 +408,8 @@ int main(int argc, char **argv) {
     else if (is("-ppc-mean")) { a.ppc_mean = true; }
     else if (is("-ppc-hops")) { a.ppc_hops = true; }
     else if (is("-ppc-orig")) { a.ppc_orig = true; }
-    else if (is("-single") ||
-             is("-gp") || is("-disjoint") ||
+    else if (is("-single")) { a.single = true; }               // src/main.cc:191-192
+    else if (is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
       unsupported = true;
       unsupported_flag = f;
@@ -407,6 +420,26 @@ int main(int argc, char **argv) {
   const bool infset = a.infset || a.preprocess;
   const bool ppc_plain = a.ppc;
   if (a.ppc_orig) a.ppc = true;                          // -ppc-orig: the -ppc mode plus the K x K kind (it does not set -orig)
+  if (a.single && !unsupported) {                        // -single (SBM::batch_infer): an engine of its own; refusals before anything is read
+    if (refused(a, kSingle, "-single")) return 2;
+    const struct { bool set; const char *name; } more[] = {
+        {a.batch_gpu, "-batch-gpu"}, {a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.snode, "-snode"}, {a.orig, "-orig"},
+        {a.ppc_orig, "-ppc-orig"}, {a.ppc, "-ppc"}, {a.gen, "-gen"}, {a.sparse_graph, "-sparse-graph"}, {a.logl, "-logl"}, {a.load, "-load"},
+        {a.val_load, "-load-validation"}, {a.test_load, "-load-test"}, {a.init_comm, "-init-communities"}, {a.scale != 1, "-scale"}};
+    for (const auto &m : more)
+      if (m.set) {
+        fprintf(stderr, kSingle.fmt, "-single", m.name);
+        return 2;
+      }
+    if (a.max_iterations == 0) {
+      fprintf(stderr, "error: -single needs -max-iterations N: the reference's loop never ends and its stop rule cannot fire\n");
+      return 2;
+    }
+    if (!a.host_loops && a.k > SVILS_SBM_MAX_K) {        // the limit of svils_sbm_create
+      fprintf(stderr, "error: -single holds -k <= %d (SVILS_SBM_MAX_K) unless -host-loops is given; -k %u is refused\n", SVILS_SBM_MAX_K, a.k);
+      return 2;
+    }
+  }
   if (a.sparse_graph && !unsupported) {                  // -sparse-graph: refusals before anything is read or created
     const struct { bool set; const char *name; } more[] = {   // (-batch-gpu first: it sets -batch too, and is the flag to name)
         {a.batch_gpu, "-batch-gpu"}, {a.logl, "-logl"}, {a.orig, "-orig"}, {a.ppc_orig, "-ppc-orig"}, {a.ppc, "-ppc"}, {a.gen, "-gen"},
@@ -561,7 +594,7 @@ int main(int argc, char **argv) {
     unsupported = true;
     unsupported_flag = "-stratified";
   }
-  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || a.ppc || sampled || infset || a.orig || a.snode)) {
+  if (unsupported || !(a.batch || a.link_sampling || a.findk || a.gml || a.lcstats || a.ppc || sampled || infset || a.orig || a.snode || a.single)) {
     fprintf(stderr,
             "svinet (MI355X build): only the -link-sampling and -batch engines are implemented here (and -findk, -gml, -lcstats)%s%s.\n"
             "Use the reference build for the other engines.\n",
@@ -830,6 +863,17 @@ run:
     try {                                    // the device backend: a failed svils_orig_* call ends the run (no host fall-back)
       MMSBInferOrig mmsb(env, network, a.itype);
       mmsb.batch_infer();
+    } catch (const SvilsError &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return -1;
+    }
+    exit(0);
+  }
+  if (a.single) {                            // src/main.cc:344-352
+    printf("+ running stochastic blockmodel inference\n");
+    try {                                    // the device backend: a failed svils_sbm_* call ends the run (no host fall-back)
+      SBM sbm(env, network);
+      sbm.batch_infer();
     } catch (const SvilsError &e) {
       fprintf(stderr, "error: %s\n", e.what());
       return -1;

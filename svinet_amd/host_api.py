@@ -496,6 +496,111 @@ class OrigEngine:
     __del__ = close
 
 
+class SbmEngine:
+    """The `-single` engine of the host library (svinet_amd/host/sbm.cc): the reference's SBM::batch_infer (src/sbm.cc:457-543),
+    the single-membership stochastic blockmodel.  on_device=True: every iteration and pair likelihood runs through svils_sbm_*
+    on `device` -- SvilsError without a HIP device, never the host loops instead; on_device=False: the host loops
+    (-host-loops).  heldout / validation / precision: the three samples [m][2], p < q, as drawn; skip: all of them, the pairs
+    left out of training."""
+
+    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, on_device=True, device=0):
+        L = load()
+        vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
+        if not hasattr(L, "_sbm_ready"):
+            L.svih_sbm_from_file.argtypes = [C.c_char_p, u32, u32, dbl, dbl, C.c_int32, C.c_int32]
+            L.svih_sbm_from_file.restype = vp
+            for name, res in (("free", None), ("n", u32), ("iter", u32), ("passes", u32), ("msums", P(dbl)), ("nrows", u64),
+                              ("rows", P(dbl)), ("sweep", C.c_int), ("edges", P(u32)), ("ones", u32)):
+                f = getattr(L, "svih_sbm_" + name)
+                f.argtypes = [vp]
+                f.restype = res
+            L.svih_sbm_state.argtypes = [vp, C.c_int32, vp]
+            L.svih_sbm_state.restype = C.c_int
+            L.svih_sbm_npairs.argtypes = [vp, C.c_int32]
+            L.svih_sbm_npairs.restype = u64
+            L.svih_sbm_pairs.argtypes = [vp, C.c_int32]
+            L.svih_sbm_pairs.restype = P(u32)
+            L.svih_sbm_set_state.argtypes = [vp, vp, vp, vp]
+            L.svih_sbm_set_state.restype = C.c_int
+            L._sbm_ready = True
+        self._h = L.svih_sbm_from_file(os.fsencode(path), n, k, seed, heldout_ratio, int(bool(on_device)), device)
+        if not self._h:
+            if on_device:
+                err = _svils.load().svils_last_error().decode("utf-8", "replace")
+                raise _svils.SvilsError(-2 if "no HIP device" in err else -1,
+                                        "SbmEngine: cannot read %r or the device backend failed: %s" % (path, err))
+            raise IOError("cannot read network %r" % (path,))
+        self.n, self.k = L.svih_sbm_n(self._h), k
+        self.heldout, self.validation, self.precision = (
+            _arr(L.svih_sbm_pairs(self._h, w), (L.svih_sbm_npairs(self._h, w), 2), np.uint32) for w in range(3))
+        self.skip = np.concatenate([self.heldout, self.validation, self.precision])
+        self.edges = _arr(L.svih_sbm_edges(self._h), (L.svih_sbm_ones(self._h), 2), np.uint32)
+
+    def _state(self, which, shape):
+        out = np.empty(shape)
+        rc = load().svih_sbm_state(self._h, which, out.ctypes.data)
+        if rc < 0:
+            _svils._chk(rc)
+        return out
+
+    @property
+    def phi(self):
+        return self._state(0, (self.n, self.k))
+
+    @property
+    def gamma(self):
+        return self._state(1, (self.k,))
+
+    @property
+    def lam(self):
+        return self._state(2, (self.k + 1, 2))
+
+    @property
+    def eta(self):
+        return self._state(3, (self.k + 1, 2))
+
+    @property
+    def rows(self):
+        """[rows][8]: which (0 held-out, 1 validation), iter, mean, count, mean of the non-links, count, mean of the links, count;
+        two rows after the constructor and two after every sweep()"""
+        return _arr(load().svih_sbm_rows(self._h), (load().svih_sbm_nrows(self._h), 8), np.float64)
+
+    @property
+    def iter(self):
+        return load().svih_sbm_iter(self._h)
+
+    @property
+    def passes(self):
+        """passes of the last iteration's E-step"""
+        return load().svih_sbm_passes(self._h)
+
+    @property
+    def msums(self):
+        """msum of every pass of the last iteration's E-step"""
+        return _arr(load().svih_sbm_msums(self._h), (self.passes,), np.float64)
+
+    def set_state(self, phi, gamma, lam):
+        phi = np.ascontiguousarray(phi, dtype=np.float64).reshape(self.n, self.k)
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64).reshape(self.k)
+        lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(self.k + 1, 2)
+        rc = load().svih_sbm_set_state(self._h, phi.ctypes.data, gamma.ctypes.data, lam.ctypes.data)
+        if rc < 0:
+            _svils._chk(rc)
+
+    def sweep(self):
+        """one iteration: the E-step (at most 10 passes), the M-step, a held-out and a validation row"""
+        rc = load().svih_sbm_sweep(self._h)
+        if rc < 0:
+            _svils._chk(rc)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().svih_sbm_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 class SampledEngine(BatchEngine):
     """The sampled-pair engines of the host library: the reference's MMSBInfer::infer (src/mmsbinfer.cc:459-740) for
     mode "rnode", "rpair" or "rpair-stratified".  on_device=False: its host loops (-host-loops); on_device=True: the steps
