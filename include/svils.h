@@ -305,7 +305,8 @@ int svils_get_community_tags(svils_handle *h, uint32_t *tags, uint64_t cap, uint
 
 /* Derived device arrays for parity tests and integrators:
  * which = 0 Elogpi [n][k], 1 Elogbeta [k][2], 2 mphi [n][k],
- *         3 active_comms [n] (uint32), 4 training_links [n] (double). */
+ *         3 active_comms [n] (uint32), 4 training_links [n] (double),
+ *         6 exp(Elogpi) [n][k] as the product-form phi pass reads it (handles on which option lpl_product reads 1). */
 int svils_get_aux(svils_handle *h, int which, void *out);
 
 /* ---- link prediction from the current state (an ADDITION of ABI 8; nothing on the sweep path changes) --------------------

@@ -508,7 +508,7 @@ class Engine:
     def aux(self, which):
         shapes = {0: ((self.n, self.k), np.float64), 1: ((self.k, 2), np.float64),
                   2: ((self.n, self.k), np.float64), 3: ((self.n,), np.uint32),
-                  4: ((self.n,), np.float64)}
+                  4: ((self.n,), np.float64), 6: ((self.n, self.k), np.float64)}
         shape, dt = shapes[which]
         out = np.zeros(shape, dtype=dt)
         _chk(load().svils_get_aux(self._h, which, out.ctypes.data))

@@ -188,7 +188,14 @@ int lpl_product_update(svils_handle *h) {
     d.skip_elogpi = on ? 1 : 0;
   }
   h->opt.lpl_product = on ? 1 : 0;
+  if (h->have_graph) h->opt.lpl_defer_epi = defer_epi_now(h) ? 1 : 0;
   return 0;
+}
+// the deferred-rows form applies to whole sweeps of this handle as it stands (run_phase: the same conditions as fused3, on top of
+// product mode and the decision taken with the graph)
+bool defer_epi_now(svils_handle *h) {
+  const DeviceState &d = h->d;
+  return h->defer_ok && d.lpl && d.epi && d.epi_q && d.gacc0 && h->geo.K <= 32u && d.cls_ntiles <= 512u && !h->nt && h->fused3_ok;
 }
 
 // chunk a row segment [off, off+len) of node p into items of <= ch neighbours
@@ -651,6 +658,14 @@ int svils_set_graph(svils_handle *h, const uint32_t *links, uint64_t nlinks) {
       h->fused3_ok = res >= 2u * 65u && !masked;
       if (h->opt.fused3 >= 0) h->fused3_ok = h->opt.fused3 != 0;
     }
+    {
+      // deferred rows (DeviceState::defer_epi): -1 takes the form where it measured faster, 0 / 1 force; a forced 1 still needs an
+      // s3 instantiation that carries the role, product mode and three-launch sweeps (defer_epi_now)
+      guard(dalloc(h, &d.epi_q, 4));
+      d.epi_cus = cu_count(h->cfg.device);
+      const bool auto_on = g.K <= 32u;   // profiles/r30a_defer_epi.txt
+      h->defer_ok = lpl_s3_carries_defer(g.K, d.s3_threads) && (h->opt.lpl_defer_epi == 1 || (h->opt.lpl_defer_epi < 0 && auto_on));
+    }
     // ltot [2][8] u32 | shist [2][K] u64, cleared together before a stand-alone classification
     const size_t shist_bytes = ((2 * (size_t)g.K * sizeof(unsigned long long)) + 63) / 64 * 64;
     h->cls_zero_bytes = 64 + shist_bytes + 2 * 8 * 2 * 64 * sizeof(long long);   // ... | sumfx [2][8][hi|lo][64] i64
@@ -700,6 +715,7 @@ int svils_set_graph(svils_handle *h, const uint32_t *links, uint64_t nlinks) {
   h->h_upper.swap(upper);
   h->have_graph = true;
   if (int rc_ = lpl_product_update(h)) return rc_;
+  h->opt.lpl_defer_epi = defer_epi_now(h) ? 1 : 0;   // (reads back the decision, also where the handle has no product mode at all)
   if (d.epi && d.lpl && h->have_state) {   // the state came first: its exp(Elogpi) rows
     launch_dir_exp(g, d, h->stream);
     HIPCHK(hipGetLastError());
@@ -769,6 +785,7 @@ int state_arrived(svils_handle *h, const double *lambda, const uint32_t *converg
   uint32_t *cur = d.conv + (size_t)c.parity * g.n_alloc;
   if (converged) HIPCHK(hipMemcpyAsync(cur, converged, g.n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   else HIPCHK(hipMemsetAsync(cur, 0, g.n * sizeof(uint32_t), h->stream));
+  if (d.epi_q) HIPCHK(hipMemsetAsync(d.epi_q, 0, sizeof(uint32_t), h->stream));   // (every finalise launch that defers the rows clears it too)
   h->have_state = true;
   if (int rc_ = lpl_product_update(h)) return rc_;   // (before the expectations: it decides which rows they are)
   if (!d.ksh) launch_dir_exp(g, d, h->stream);   // K-sharded: the row sums cross ranks (svils_ksh_init_state)
@@ -813,6 +830,7 @@ int svils_set_control(svils_handle *h, const svils_control *in) {
   c.iter = in->iter; c.annealing = in->annealing; c.write_comm = in->write_comm; c.nh = in->nh;
   c.prev_h = in->prev_h; c.max_h = in->max_h;
   HIPCHK(hipMemcpy(h->d.ctrl, &c, sizeof c, hipMemcpyHostToDevice));
+  if (h->d.epi_q) HIPCHK(hipMemset(h->d.epi_q, 0, sizeof(uint32_t)));
   h->frozen = false;      // the loop state is the caller's again: getters wait for the stream until a stop is seen anew
   h->cls_valid = false;   // _iter decides between the dense and the active-set class
   return 0;
@@ -962,6 +980,10 @@ int svils_get_aux(svils_handle *h, int which, void *out) {
     }
     case 5:   // profiling stamps (zeros unless the library was built with -DSVILS_STAMPS)
       HIPCHK(hipMemcpy(out, h->d.stamps, 4 * 1024 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      return 0;
+    case 6:   // the exp(Elogpi) rows the product-form phi pass reads, as they stand (lane-per-link layout, K <= 32)
+      if (!h->d.lpl || !h->d.epi) return fail(SVILS_ERR_ARG, "svils_get_aux: the handle keeps no exp(Elogpi) rows (option lpl_product reads 0)");
+      HIPCHK(hipMemcpy2D(out, g.K * sizeof(double), h->d.epi, g.ld * sizeof(double), g.K * sizeof(double), g.n, hipMemcpyDeviceToHost));
       return 0;
     default:
       return fail(SVILS_ERR_ARG, "svils_get_aux: unknown selector %d", which);

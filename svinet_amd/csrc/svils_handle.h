@@ -156,6 +156,9 @@ struct svils_handle {
   double prod_gmin = 0.0;          // lower bound of every gamma entry a sweep writes
   double *epi_lpl = nullptr;
   unsigned long long *prod_state = nullptr;   // device: what k_state_links measures (four words)
+  // Deferred rows (option lpl_defer_epi, decided with the graph): product-mode sweeps that run as three launches leave the exp(Elogpi)
+  // rows to the s3 launch (DeviceState::defer_epi, set per sweep by run_phase while the conditions hold: defer_epi_now)
+  bool defer_ok = false;
   double *elogpi_view = nullptr;   // DeviceState::skip_elogpi: where svils_get_aux(0) / SVILS_BUF_ELOGPI get their Elogpi rows computed
   std::vector<void *> allocs;
   // pipelined reports (svils_report_enqueue): staging slots, a copy stream, per-slot events
@@ -323,6 +326,7 @@ int open_device(int device, const char *bad_args = nullptr);
 int drain_timing(svils_handle *h);
 int fault_error(uint32_t code);
 int elogpi_rows(svils_handle *h, double **rows);
+bool defer_epi_now(svils_handle *h);   // the deferred-rows form applies to whole sweeps of this handle as it stands; option lpl_defer_epi reads it back
 int lpl_product_update(svils_handle *h);   // product mode of the lane-per-link layout: on / off by the gate and the state on the device
 int state_arrived(svils_handle *h, const double *lambda, const uint32_t *converged);   // the tail of svils_set_state   // the Elogpi rows of the state as it stands (computed now where a handle does not store them)
 void chunk_row(std::vector<Item> &items, uint32_t p, uint32_t off, uint32_t len, uint32_t ch,

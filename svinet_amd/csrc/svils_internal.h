@@ -171,6 +171,13 @@ struct DeviceState {
   // cache-resident and the second launch's ~2 us outweigh the write saved; option skip_elogpi forces either way).
   // svils_get_aux(0) / SVILS_BUF_ELOGPI compute a view on demand (k_dir_exp).
   int skip_elogpi;
+  // Deferred rows (K <= 32, product mode, three-launch sweeps; set per sweep by run_phase): the finalise
+  // launch stores no exp(Elogpi) rows; the s3 launch forms them from gamma in the blocks that have nothing else left to do
+  // (svils_lpl.hip: lpl_epi_rows_role), chunk by chunk off a queue.
+  int defer_epi;
+  uint32_t *epi_q;      // [1] next chunk (8 nodes) of that queue: cleared by the finalise launch, only incremented by the s3 launch
+  uint32_t epi_cus;     // CUs of the device: the s3 launch adds helper blocks of the role up to this many blocks in all
+  uint32_t epi_nhelp;   // ... that many of them in this launch (launch_s3_lpl)
   // K-sharded sweeps (svils_ksh.h): what crosses ranks, each buffer summed over the ranks between two phases
   int ksh;              // 1: the handle holds a column slice
   uint32_t *elink;      // [2L]  training-link index of every CSR entry
@@ -286,6 +293,7 @@ int lpl_finalize_group(uint32_t K);
 uint32_t lpl_finalize_resident_blocks(uint32_t K, int device);
 uint32_t lpl_scatter_blocks(const DeviceState &d);
 uint32_t lpl_s3_resident_blocks(uint32_t K, int device, uint32_t threads, int assume_cus);
+bool lpl_s3_carries_defer(uint32_t K, uint32_t threads);   // the s3 instantiation for this shape carries the deferred-rows role
 void launch_carry_flags(const Geometry &g, const DeviceState &d, hipStream_t s);
 void launch_expand_window(const Geometry &g, const DeviceState &d, const Params &p, uint32_t wb, uint32_t we,
                           uint32_t block, uint32_t my_rank, uint32_t world, hipStream_t s);

@@ -649,11 +649,49 @@ __device__ __forceinline__ double exp_neg_tail(double t) {
   return ldexp(p, (int)n);
 }
 
+// psi of one gamma row in the (FW, NC) lane layout of k_finalize_lpl: lane lw of a group holds gn[j] = gamma[lw + j * FW]
+// (padding columns 0).  -> ps[j] = psi(gamma_k) per community, psi_rs = psi(row sum).  Shared by the finalise pass and by the
+// deferred-rows role of the s3 launch (lpl_epi_rows_role), which feeds it the stored doubles: the same operations in the
+// same order, hence the same bits.
+// A slot above K is idle when K < FW * NC: lane FW - 1 evaluates psi(row sum) in its last slot, in the same
+// digamma call as the last community of the other lanes; a full row (K == FW * NC) takes one more call
+template <int FW, int NC>
+__device__ __forceinline__ void lpl_row_psi(const double (&gn)[NC], const bool (&kv)[NC], uint32_t K, int g, int lw,
+                                            const double2 *logtab, double (&ps)[NC], double &psi_rs) {
+  double rsl = 0.0;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) rsl += gn[j];
+  const double rs = group_sum<FW>(rsl);
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    double arg = kv[j] ? gn[j] : 1.0;
+    if (j == NC - 1 && lw == FW - 1 && K < (uint32_t)(FW * NC)) arg = rs;
+    ps[j] = digamma(arg, logtab);
+  }
+  if (K < (uint32_t)(FW * NC)) psi_rs = __shfl(ps[NC - 1], g * FW + FW - 1, 64);
+  else psi_rs = digamma(rs, logtab);
+}
+// ... and the row for the product-form phi pass from them: exp(psi(gamma_k) - psi(row sum)) into d.epi.
+// psi(gamma_k) - psi(row sum) <= 0 by construction (the clamp takes the last bit of the two digamma evaluations)
+template <int FW, int NC>
+__device__ __forceinline__ void lpl_row_epi_store(const DeviceState &d, const double (&ps)[NC], double psi_rs,
+                                                  const bool (&kv)[NC], bool ok, size_t rowoff) {
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const double e = exp_neg_tail(kv[j] ? fmin(ps[j] - psi_rs, 0.0) : 0.0);
+    if (kv[j] && ok) row_store(&d.epi[rowoff + j * FW], e, d.wt != 0);   // padding columns stay 0
+  }
+}
+
 // LIGHT: the node-block form (see k_finalize in svils_device.hip): mean indicators, s1 / s2, tags and the unscaled row into
 // the exchange staging; scale, Elogpi and prune() follow in k_expand_all behind the exchange.
 // PROD (product mode, K <= 32): the row written for the phi pass is exp(Elogpi) into d.epi instead of Elogpi -- NC interleaved
 // exp_neg chains on values that are live anyway; nothing else in a small-K sweep reads Elogpi rows.
-template <int FW, int NC, bool STOCH, bool LIGHT = false, int NTH = fin_threads(NC), bool PROD = false>
+// PROD == 2 (three-launch sweeps in product mode, DeviceState::defer_epi): the pass stops after the flags.  Nothing it writes
+// besides that row depends on psi, so no digamma, no exponential, no row sum and no epi store here: the s3 launch forms the
+// rows from the gamma rows stored below, in blocks that would otherwise idle (lpl_epi_rows_role).  Block 0 clears that
+// role's chunk counter: this launch precedes the one that consumes it.
+template <int FW, int NC, bool STOCH, bool LIGHT = false, int NTH = fin_threads(NC), int PROD = 0>
 __global__ __launch_bounds__(NTH, (NTH >= 768 ? 3 : 2)) void k_finalize_lpl(Geometry geo, DeviceState d, Params prm) {
   STAMP(1, 0);
   DevCtrl *ctrl = d.ctrl;
@@ -688,9 +726,12 @@ __global__ __launch_bounds__(NTH, (NTH >= 768 ? 3 : 2)) void k_finalize_lpl(Geom
     if (threadIdx.x < K) { sh0 = d.shist[threadIdx.x]; sh1 = d.shist[(size_t)K + threadIdx.x]; }
   }
   const uint32_t c_cpar = ctrl->cls_par, c_epoch = ctrl->sweeps_done + 1u;
-  load_logtab(logtab, d.logtab);
+  if constexpr (PROD != 2 || STOCH) load_logtab(logtab, d.logtab);
   if (stopped) return;
   STAMP(1, 1);
+  if constexpr (PROD == 2) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *d.epi_q = 0u;
+  }
   const bool annealing = !LIGHT && c_ann != 0;
   const bool write_comm = c_wc != 0;
   const uint32_t *__restrict__ conv_old = d.conv + (size_t)c_par * geo.n_alloc;
@@ -916,29 +957,15 @@ __global__ __launch_bounds__(NTH, (NTH >= 768 ? 3 : 2)) void k_finalize_lpl(Geom
       ix = ix_next;
       continue;
     }
-    double rsl = 0.0;
 #pragma unroll
-    for (int j = 0; j < NC; ++j) {
+    for (int j = 0; j < NC; ++j)
       if (ST(j)) row_store(&d.gamma[rowoff + j * FW], gn[j], d.wt != 0);   // padding columns stay 0
-      rsl += gn[j];
-    }
-    const double rs = group_sum<FW>(rsl);
-    // A slot above K is idle when K < FW * NC: lane FW - 1 evaluates psi(row sum) in its last slot, in the same
-    // digamma call as the last community of the other lanes; a full row (K == FW * NC) takes one more call
-    double ps[NC];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-      double arg = kv[j] ? gn[j] : 1.0;
-      if (j == NC - 1 && lw == FW - 1 && K < (uint32_t)(FW * NC)) arg = rs;
-      ps[j] = digamma(arg, logtab);
-    }
-    double psi_rs;
-    if (K < (uint32_t)(FW * NC)) psi_rs = __shfl(ps[NC - 1], g * FW + FW - 1, 64);
-    else psi_rs = digamma(rs, logtab);
+    double ps[NC], psi_rs = 0.0;
+    if constexpr (PROD != 2) lpl_row_psi<FW, NC>(gn, kv, K, g, lw, logtab, ps, psi_rs);
     unsigned long long bits = 0ull;
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-      if constexpr (!PROD) {
+      if constexpr (PROD == 0) {
         if (ST(j)) row_store(&d.elogpi[rowoff + j * FW], kv[j] ? ps[j] - psi_rs : 0.0, d.wt != 0);
       }
       // prune / check_and_set_converged, src/linksampling.cc:455-475
@@ -961,15 +988,8 @@ __global__ __launch_bounds__(NTH, (NTH >= 768 ? 3 : 2)) void k_finalize_lpl(Geom
         xf[0] = cnew; xf[1] = active; xf[2] = (uint32_t)am; xf[3] = (uint32_t)(am >> 32);
       }
     }
-    if constexpr (PROD) {
-      // the row for the phi pass, last: by now only the NC differences are live beside the loop's own state.
-      // psi(gamma_k) - psi(row sum) <= 0 by construction (the clamp takes the last bit of the two digamma evaluations)
-#pragma unroll
-      for (int j = 0; j < NC; ++j) {
-        const double e = exp_neg_tail(kv[j] ? fmin(ps[j] - psi_rs, 0.0) : 0.0);
-        if (ST(j)) row_store(&d.epi[rowoff + j * FW], e, d.wt != 0);   // padding columns stay 0
-      }
-    }
+    // the row for the phi pass, last: by now only the NC differences are live beside the loop's own state
+    if constexpr (PROD == 1) lpl_row_epi_store<FW, NC>(d, ps, psi_rs, kv, ok, rowoff);
     ix = ix_next;
   }
   STAMP(1, 3);
@@ -1008,18 +1028,90 @@ __global__ __launch_bounds__(NTH, (NTH >= 768 ? 3 : 2)) void k_finalize_lpl(Geom
 // (profiles/r06a_*, r06b_*, r06c_*) -- lpl_s3_threads decides by the link count.
 constexpr int s3_threads(int kc) { return kc >= 12 ? 512 : 1024; }
 
-template <int KC, int NTH = s3_threads(KC)>
+// Deferred rows (three-launch sweeps in product mode, DeviceState::defer_epi): the exp(Elogpi) rows of the sweep, which
+// k_finalize_lpl<..., PROD = 2> did not form, as a spin-free work queue for the blocks of this launch that have nothing
+// else left to do.  A chunk is the 8 nodes one wavefront of the finalise pass handles, in its (FW = 8, NC) lane layout; a
+// block draws tickets for as many chunks as it has wavefronts with one integer atomic on d.epi_q, every wavefront reads
+// the gamma rows of its chunk, which the finalise launch stored, and runs the finalise pass's own arithmetic on them
+// (lpl_row_psi, lpl_row_epi_store).  Nobody waits for another block; nothing read here is written in this launch (gamma:
+// the finalise launch; the counter: cleared there, only incremented here), and the rows are first read by the next phi
+// launch.  Which wavefront forms a row does not show in it.  Called by all threads of the block.
+// LOAD_TAB: the block has not put the log table into LDS yet; it does so once its first ticket names a chunk (a block that
+// finds the queue empty leaves at the price of that one atomic).
+template <int NC, bool LOAD_TAB = false>
+__device__ __forceinline__ void lpl_epi_rows_role(const Geometry &geo, const DeviceState &d, double2 *logtab) {
+  constexpr int FW = 8, G = 64 / FW;
+  const int lane = threadIdx.x & 63, g = lane / FW, lw = lane % FW;
+  const uint32_t K = geo.K, ld = geo.ld;
+  const uint32_t nown = geo.node_end - geo.node_begin, nchunks = (nown + G - 1u) / G;
+  bool kv[NC];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) kv[j] = (uint32_t)(lw + j * FW) < K;
+  // One ticket per BLOCK and round, for as many chunks as the block has wavefronts: thread 0 draws it, the block reads it
+  // from LDS (two slots in turn: one barrier per round), and the ticket of the next round travels while this one's rows
+  // are formed.  (A ticket per wavefront was measured first: ~6 000 atomics on one word retire at ~10 ns each whatever
+  // the number of CUs asking, and the s3 launch took 76 us instead of 16; profiles/r30a_defer_epi.txt.)
+  __shared__ uint32_t ticket[2];
+  const uint32_t nwv = blockDim.x >> 6, wave = threadIdx.x >> 6;
+  uint32_t next = 0;
+  if (threadIdx.x == 0) next = atomicAdd(d.epi_q, nwv);
+#pragma unroll 1
+  for (uint32_t round = 0;; ++round) {
+    if (threadIdx.x == 0) ticket[round & 1u] = next;
+    __syncthreads();
+    const uint32_t base = ticket[round & 1u];
+    if (base >= nchunks) break;   // (uniform over the block)
+    if constexpr (LOAD_TAB) {
+      if (round == 0) { load_logtab(logtab, d.logtab); __syncthreads(); }
+    }
+    const uint32_t c = base + wave;
+    const bool work = c < nchunks;   // (uniform over the wavefront; one without a chunk still meets the next barrier)
+    const uint32_t i = c * G + (uint32_t)g;
+    const bool ok = work && i < nown;
+    const size_t rowoff = (size_t)(geo.node_begin + (ok ? i : 0u)) * ld + lw;
+    double gn[NC], ps[NC], psi_rs;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) gn[j] = kv[j] ? (ok ? d.gamma[rowoff + j * FW] : 1.0) : 0.0;   // (a group without a node: any valid row)
+    if (threadIdx.x == 0) next = atomicAdd(d.epi_q, nwv);   // behind the row loads: they do not wait for it
+    if (work) {
+      lpl_row_psi<FW, NC>(gn, kv, K, g, lw, logtab, ps, psi_rs);
+      lpl_row_epi_store<FW, NC>(d, ps, psi_rs, kv, ok, rowoff);
+    }
+  }
+}
+// The instantiations of k_s3_lpl that carry the role: those where its presence costs neither scratch nor a wave per SIMD
+// (profiles/r30a_defer_epi.txt has the table); the others keep their code, and the finalise pass keeps forming the rows.
+// The three 12-wave shapes sit on their 168 registers: with the role KC = 12 starts to spill (12 VGPRs) and KC = 14 / 16 gain
+// 12 bytes of scratch each.  The 8- and 16-wave shapes take it with the occupancy and the (absent) scratch they had.
+constexpr bool s3_defer_ok(int kc, int nth) { return kc <= 16 && nth != 768; }
+
+template <int KC, int NTH = s3_threads(KC), bool DEFER = false>
 __global__ __launch_bounds__(NTH) void k_s3_lpl(Geometry geo, DeviceState d, Params prm) {
   DevCtrl *ctrl = d.ctrl;
   constexpr int KR = LplCfg<KC>::KR, SROW = LplCfg<KC>::SROW;
   constexpr int NWV = NTH / 64, NWORK = NTH / 256;
+  constexpr int DNC = (2 * KC + 7) / 8;   // communities per lane of the finalise pass's layout at this K (FIN_DISPATCH)
   constexpr bool PEEL = KC >= 12 && KC <= 20;   // see below
   if constexpr (!PEEL) {
     if (ctrl->stopped) return;   // (the instantiations without the first-link form keep the order of accesses they had)
   }
-  // three-launch sweeps: the very last block only folds s1, s2 from k_finalize_lpl's partial rows, from the
+  __shared__ double2 logtab[128];
+  // DEFER: the last d.epi_nhelp blocks of the grid are helpers of the deferred-rows role and do nothing else.  They follow
+  // every block that takes part in a hand-off, so they never keep one of those from starting.
+  const uint32_t nhelp = DEFER ? d.epi_nhelp : 0u;
+  if constexpr (DEFER) {
+    if (blockIdx.x >= gridDim.x - nhelp) {
+      if constexpr (PEEL) {
+        if (ctrl->stopped) return;
+      }
+      lpl_epi_rows_role<DNC, true>(geo, d, logtab);
+      STAMP(2, 6);
+      return;
+    }
+  }
+  // three-launch sweeps: the last block before the helpers only folds s1, s2 from k_finalize_lpl's partial rows, from the
   // start of the launch, so that nobody on the critical path has to (it arrives on the s3 ticket like an s3 block)
-  const bool fold_role = d.fused3 && blockIdx.x == gridDim.x - 1u;
+  const bool fold_role = d.fused3 && blockIdx.x == gridDim.x - nhelp - 1u;
   // The s3 blocks' path through this launch is a chain of dependent misses: control block -> link -> converged flags ->
   // rows -> (block partial, ticket) -> the last block's serial stage.  On three-launch sweeps (graphs of a few hundred
   // thousand links: about ONE link per lane) the first link of a lane, whose address depends on nothing, is requested
@@ -1051,7 +1143,7 @@ __global__ __launch_bounds__(NTH) void k_s3_lpl(Geometry geo, DeviceState d, Par
   STAMP(2, 0);
   __shared__ uint32_t hflag;
   if (blockIdx.x >= d.nb_c && !fold_role) {   // the blocks after the s3 blocks: link classes of the NEXT sweep
-    const uint32_t rb = blockIdx.x - d.nb_c, nrb = gridDim.x - d.nb_c - (d.fused3 ? 1u : 0u);
+    const uint32_t rb = blockIdx.x - d.nb_c, nrb = gridDim.x - nhelp - d.nb_c - (d.fused3 ? 1u : 0u);
     if (d.fused3) {
       // three-launch sweeps: both passes here, handed over inside the launch (the scatter pass has no
       // later launch to ride on before the next phi pass needs its lists)
@@ -1061,6 +1153,10 @@ __global__ __launch_bounds__(NTH) void k_s3_lpl(Geometry geo, DeviceState d, Par
       cls_count_tiles<NWORK>(geo, d, prm, shw, rb, nrb, true);   // count pass; the scatter pass rides on k_tail
     }
     STAMP(2, 7);
+    if constexpr (DEFER) {   // the role is done (at once when no flag changed): deferred rows
+      lpl_epi_rows_role<DNC, true>(geo, d, logtab);
+      STAMP(2, 6);
+    }
     return;
   }
   // the log table for the serial stage of a three-launch sweep: fetched ahead of its use, used by the last block only
@@ -1181,6 +1277,9 @@ __global__ __launch_bounds__(NTH) void k_s3_lpl(Geometry geo, DeviceState d, Par
     for (int pp = 0; pp < NP; ++pp) tot += __shfl(acc, pp * KR + kcol, 64);
     if (lane < KR) red[wave][lane] = tot;
   }
+  if constexpr (DEFER) {   // every block needs the log table now, not the last one alone
+    if (threadIdx.x < 128) logtab[threadIdx.x] = ltv;
+  }
   __syncthreads();
   if (threadIdx.x < K && !fold_role) {
     double t = 0.0;
@@ -1249,12 +1348,26 @@ __global__ __launch_bounds__(NTH) void k_s3_lpl(Geometry geo, DeviceState d, Par
       // (src/linksampling.cc:748-759); write_comm for the next sweep (:768-774), _iter++ (:787).  The
       // likelihood row, stop rule and annealing switch of this sweep follow as a role of the next launch.
       STAMP(2, 3);
-      if (!last_block_arrives(d.s3_ctl, d.nb_c + 1u, &hflag)) return;
+      if (!last_block_arrives(d.s3_ctl, d.nb_c + 1u, &hflag)) {
+        if constexpr (DEFER) {   // not the last: nothing left to do here but deferred rows
+          lpl_epi_rows_role<DNC>(geo, d, logtab);
+          STAMP(2, 6);
+        }
+        return;
+      }
       STAMP(2, 4);
-      __shared__ double2 logtab[128];
       __shared__ double s3tot[32];
       double *tmp = &lds[0][0];
-      if (threadIdx.x < 128) logtab[threadIdx.x] = ltv;
+      if constexpr (!DEFER) {
+        if (threadIdx.x < 128) logtab[threadIdx.x] = ltv;
+      }
+      // DEFER: a look at the queue now, where the answer travels beside the partial rows.  The counter only grows: if every
+      // chunk has been drawn by now (the rule), this block need not ask again behind its serial stage, at the end of the launch.
+      __shared__ uint32_t q_seen;
+      uint32_t q_now = 0;
+      if constexpr (DEFER) {
+        if (threadIdx.x == 0) q_now = ld_agent(d.epi_q);
+      }
       double s1 = 0.0, s2 = 0.0;
       {
         // The order of k_tail's fold of the same rows (FoldRows<32, 256>, svils_devutil.h: eight row groups r0, r0 + 8, ...,
@@ -1275,6 +1388,9 @@ __global__ __launch_bounds__(NTH) void k_s3_lpl(Geometry geo, DeviceState d, Par
         for (uint32_t i = 0; i < NL; ++i)
           if (RG * i < d.nb_c) t += v[i];   // (uniform; past the last row only zeros follow, which change no bit)
         if (r0 < RG) tmp[r0 * 32 + c] = t;
+      }
+      if constexpr (DEFER) {
+        if (threadIdx.x == 0) q_seen = q_now;   // (same wait as the rows)
       }
       __syncthreads();
       if (threadIdx.x < 32) {
@@ -1325,6 +1441,10 @@ __global__ __launch_bounds__(NTH) void k_s3_lpl(Geometry geo, DeviceState d, Par
       }
       for (uint32_t i = threadIdx.x; i < 1024u; i += NTH) d.sumfx[(size_t)cpar0 * 1024 + i] = 0;   // (blocks of 512 or 1024 threads)
       STAMP(2, 5);
+      if constexpr (DEFER) {   // the serial stage is over: whatever is left of the queue (normally nothing, and known since q_seen)
+        if (q_seen < (geo.node_end - geo.node_begin + 7u) / 8u) lpl_epi_rows_role<DNC>(geo, d, logtab);
+        STAMP(2, 6);
+      }
     }
   }
 }
@@ -1466,6 +1586,9 @@ void launch_finalize_lpl(const Geometry &g, const DeviceState &d, const Params &
   do {                                                                                              \
     if (d.epi && !d.light) {   /* product mode (FW = 8 alone: beyond, the flag is false and these are the instantiations below) */ \
       if (p.stoch) hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, true, false, fin_threads(NC_), (W_ == 8)>), dim3(d.nb_b), dim3(fin_threads(NC_)), 0, s, g, d, p); \
+      else if (d.defer_epi && NC_ == 4 && d.fin_waves == 12u)   /* the rows follow in the s3 launch (lpl_epi_rows_role) */ \
+        hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, false, false, (NC_ == 4 ? 768 : fin_threads(NC_)), (W_ == 8 ? 2 : 0)>), dim3(d.nb_b), dim3(768), 0, s, g, d, p); \
+      else if (d.defer_epi) hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, false, false, fin_threads(NC_), (W_ == 8 ? 2 : 0)>), dim3(d.nb_b), dim3(fin_threads(NC_)), 0, s, g, d, p); \
       else if (NC_ == 4 && d.fin_waves == 12u)                                                      \
         hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, false, false, (NC_ == 4 ? 768 : fin_threads(NC_)), (W_ == 8)>), dim3(d.nb_b), dim3(768), 0, s, g, d, p); \
       else hipLaunchKernelGGL((k_finalize_lpl<W_, NC_, false, false, fin_threads(NC_), (W_ == 8)>), dim3(d.nb_b), dim3(fin_threads(NC_)), 0, s, g, d, p); \
@@ -1500,15 +1623,36 @@ uint32_t lpl_s3_resident_blocks(uint32_t K, int device, uint32_t threads, int as
   if (per_cu <= 0 || cus <= 0) return 0;
   return (uint32_t)per_cu * (uint32_t)cus;
 }
-void launch_s3_lpl(const Geometry &g, const DeviceState &d, const Params &p, hipStream_t s) {
-  const dim3 grid(d.nb_c + lpl_cls_blocks(d) + (d.fused3 ? 1u : 0u));
+// helper blocks of the deferred-rows role: as many as the launch leaves CUs free (they come last in dispatch order and never
+// wait, so neither lpl_s3_resident_blocks nor the fused3 decision counts them)
+bool lpl_s3_carries_defer(uint32_t K, uint32_t threads) {
+  if (K > 32) return false;
+  if (threads == 768u) return K <= 20 ? false : K <= 24 ? s3_defer_ok(12, 768) : K <= 28 ? s3_defer_ok(14, 768) : s3_defer_ok(16, 768);
+  bool ok = false;
+#define CALL(KC_) ok = s3_defer_ok(KC_, s3_threads(KC_))
+  LPL_DISPATCH(K, CALL);
+#undef CALL
+  return ok;
+}
+template <int KC, int NTH>
+static void launch_s3_one(dim3 grid, const Geometry &g, const DeviceState &d, const Params &p, hipStream_t s) {
+  if constexpr (s3_defer_ok(KC, NTH)) {
+    if (d.defer_epi) { hipLaunchKernelGGL((k_s3_lpl<KC, NTH, true>), grid, dim3(NTH), 0, s, g, d, p); return; }
+  }
+  hipLaunchKernelGGL((k_s3_lpl<KC, NTH>), grid, dim3(NTH), 0, s, g, d, p);
+}
+void launch_s3_lpl(const Geometry &g, const DeviceState &d0, const Params &p, hipStream_t s) {
+  DeviceState d = d0;
+  const uint32_t nblocks = d.nb_c + lpl_cls_blocks(d) + (d.fused3 ? 1u : 0u);
+  d.epi_nhelp = (d.defer_epi && d.epi_cus > nblocks) ? d.epi_cus - nblocks : 0u;
+  const dim3 grid(nblocks + d.epi_nhelp);
   if (d.s3_threads == 768u && g.K > 20 && g.K <= 32) {   // the 12-wave shape of KC = 12 / 14 / 16 (lpl_s3_threads)
-    if (g.K <= 24) hipLaunchKernelGGL((k_s3_lpl<12, 768>), grid, dim3(768), 0, s, g, d, p);
-    else if (g.K <= 28) hipLaunchKernelGGL((k_s3_lpl<14, 768>), grid, dim3(768), 0, s, g, d, p);
-    else hipLaunchKernelGGL((k_s3_lpl<16, 768>), grid, dim3(768), 0, s, g, d, p);
+    if (g.K <= 24) launch_s3_one<12, 768>(grid, g, d, p, s);
+    else if (g.K <= 28) launch_s3_one<14, 768>(grid, g, d, p, s);
+    else launch_s3_one<16, 768>(grid, g, d, p, s);
     return;
   }
-#define CALL(KC_) hipLaunchKernelGGL((k_s3_lpl<KC_>), grid, dim3(s3_threads(KC_)), 0, s, g, d, p)
+#define CALL(KC_) launch_s3_one<KC_, s3_threads(KC_)>(grid, g, d, p, s)
   LPL_DISPATCH(g.K, CALL);
 #undef CALL
 }

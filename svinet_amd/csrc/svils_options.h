@@ -23,6 +23,9 @@ struct Options {
   int fused3 = -1;              // three-launch sweeps: -1 by the co-residency check, 0 / 1 forced
   int lpl_product = -1;         // K <= 32, lane-per-link: product-form phi on exp(Elogpi) rows (svils_api.hip: lpl_product_gate); -1 auto, 0 / 1
                                 // forced; a forced 1 that fails a condition falls back to 0, and the field reads back the decision taken
+  int lpl_defer_epi = -1;       // product mode on three-launch sweeps: the exp(Elogpi) rows are formed in the s3 launch's idle blocks instead of
+                                // by the finalise pass (DeviceState::defer_epi); -1 auto, 0 / 1 forced; a forced 1 that fails a condition falls
+                                // back to 0, and the field reads back the decision taken
   // ---- node-block runs (read at every svils_sweep_sharded from the handle, never from the environment)
   int one_comm = 0;             // 1: the chunked row exchange shares the first communicator
   uint32_t xchunks = 0;         // chunks of the pipelined row exchange; 0: by payload (one below 256 MB, then one per 128 MB, <= 8)

@@ -47,6 +47,11 @@ const Row kRows[] = {
      "K <= 32, lane-per-link layout, whole-graph handle, link_thresh >= 1/2: the finalise pass stores exp(Elogpi) rows instead of Elogpi "
      "and the phi pass multiplies (no exponentials per link): -1 where the static underflow bound holds, 0 / 1 forced (a forced 1 that "
      "fails a condition falls back to 0); after svils_set_graph the option reads back the decision taken"},
+    {"lpl_defer_epi", "SVILS_LPL_DEFER_EPI", "-1", GRAPH, I32, OFF(lpl_defer_epi), -1, 1,
+     "product mode (lpl_product) on three-launch sweeps of a whole-graph handle without a test set: the finalise pass stops after the "
+     "flags and the exp(Elogpi) rows are formed from gamma by the blocks of the s3 launch that have nothing else left to do: -1 where "
+     "it measured faster (profiles/r30a_defer_epi.txt), 0 / 1 forced (a forced 1 that fails a condition falls back to 0); after "
+     "svils_set_graph the option reads back the decision taken"},
     {"one_comm", "SVILS_ONE_COMM", "0", ANY, I32, OFF(one_comm), 0, 1,
      "1: the chunked row exchange of node-block sweeps shares the first communicator instead of forming a second one"},
     {"xchunks", "SVILS_XCHUNKS", "0", ANY, U32, OFF(xchunks), 0, 64,

@@ -120,6 +120,7 @@ int svils_set_test(svils_handle *h, const uint32_t *pairs_y, uint64_t nt) {
       return fail(SVILS_ERR_ARG, "svils_set_test: pair %llu names node %u / %u (n = %u)", (unsigned long long)i, pairs_y[3 * i], pairs_y[3 * i + 1], h->geo.n);
   drop_graphs(h);            // the captured sweeps do not know about the test launches (or still carry them)
   h->nt = 0;
+  if (h->have_graph) h->opt.lpl_defer_epi = defer_epi_now(h) ? 1 : 0;
   if (!nt) return 0;
   int rc;
   if (nt > h->t_cap) {          // a larger set than any before: the old buffers go back (the stream is idle here)
@@ -138,6 +139,7 @@ int svils_set_test(svils_handle *h, const uint32_t *pairs_y, uint64_t nt) {
   HIPCHK(hipMemcpyAsync(h->t_pairs, pairs_y, 3 * (size_t)nt * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->nt = (uint32_t)nt;
+  if (h->have_graph) h->opt.lpl_defer_epi = 0;   // a handle with a test set keeps four launches, hence the rows in the finalise pass
   return 0;
 }
 

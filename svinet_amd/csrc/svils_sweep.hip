@@ -54,6 +54,7 @@ int run_phase(svils_handle *h, svils_phase ph, const Geometry &g, const DeviceSt
     d.gacc = d.gacc0;
     d.nvb = lpl_validation_blocks(g, d.nv, g.K);
   }
+  d.defer_epi = (d.fused3 && d.epi && h->defer_ok) ? 1 : 0;   // product mode: the s3 launch forms the exp(Elogpi) rows (svils_lpl.hip)
   d.cls_next = (d.lpl && !prm.stoch) ? 1 : 0;
   switch (ph) {
     case SVILS_PHASE_A: {

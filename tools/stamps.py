@@ -21,7 +21,7 @@ from svinet_amd import _svils
 out = np.zeros(4 * 1024 * 8, dtype=np.uint64)
 _svils._chk(_svils.load().svils_get_aux(eng._h, 5, out.ctypes.data))
 st = out.reshape(4, 1024, 8).astype(np.float64)
-names = ["phi", "finalize", "s3(+count role: slots 0,7)", "tail(+scatter role: slots 0,7)"]
+names = ["phi", "finalize", "s3(+count role: slots 0,7; slot 6: deferred-rows queue found empty)", "tail(+scatter role: slots 0,7)"]
 t00 = None
 for kk in range(4):
     a = st[kk]
