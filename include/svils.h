@@ -48,6 +48,7 @@ extern "C" {
                                     (additive, same version) svils_batch_step_strat / svils_batch_get_lag: -snode, stratified random node steps;
                                     (additive, same version) svils_orig_*: -orig, the full K x K blockmodel over all ordered pairs;
                                     (additive, same version) svils_sbm_*: -single, the single-membership stochastic blockmodel;
+                                    (additive, same version) svils_sbmelbo / svils_sbmelbo_get_timing: -single-logl, its variational lower bound;
                                     (additive, same version) svils_lc_*: -gml / -lcstats, the link communities of a fitted model;
                                     (additive, same version) svils_ppc_*: -ppc / -gen, networks drawn from a model and their statistics;
                                     (additive, same version) svils_ppc_hops / svils_ppc_get_hop*: -ppc-hops, the exact hop plot and components;
@@ -992,6 +993,29 @@ int svils_sbm_set_plain_chain(svils_sbm *h, int plain);
  * them) of a row -- and *block_nodes = B, the consecutive nodes (= wavefronts of the workgroup) whose gathers overlap.
  * SVILS_ERR_ARG: k < 2 or a null pointer; SVILS_ERR_UNSUPPORTED: k > SVILS_SBM_MAX_K */
 int svils_sbm_variant(uint32_t k, uint32_t *cols_per_lane, uint32_t *block_nodes);
+/* -single-logl: the variational lower bound of the handle's CURRENT state -- phi, gamma, lambda and the Elogpi / Elogbeta
+ * the handle keeps current (SBM::approx_log_likelihood, src/sbm.cc:1133-1239, compiled out there).
+ * (An ADDITION of ABI 8.  The two names do not begin with svils_sbm_: that family's count is pinned.)
+ * out = total, P, N, G with total = P + N + G.  E_1[k] = Elogbeta[k][0], E_0[k] = Elogbeta[k][1], k = 0 .. K:
+ *   P  the sum over every trained pair p < q, y its link bit, of sum_k phi_pk phi_qk E_y[k] + (1 - sum_k phi_pk phi_qk) E_y[K]
+ *      (the proper 1 - sum_k, not the M-step's row-K sum of 1 - phi_pk phi_qk over k)
+ *   N  sum_p sum_k phi_pk (Elogpi_k - log phi_pk); an entry of phi that is exactly 0 adds 0 (the reference gives NaN)
+ *   G  for k = 0 .. K: lnGamma(eta_k0 + eta_k1) - lnGamma(eta_k0) - lnGamma(eta_k1) + sum_t (eta_kt - 1) Elogbeta[k][t] minus
+ *      the same expression in lambda_k; plus lnGamma(K alpha) - K lnGamma(alpha) + (alpha - 1) sum_k Elogpi_k -
+ *      [lnGamma(sum gamma) - sum_k lnGamma(max(gamma_k, 1e-30))] - sum_k (gamma_k - 1) Elogpi_k
+ * The device forms P from the sums a_k, b_k of phi_ik phi_jk over the trained links and non-links exactly as the M-step
+ * forms them (P = sum_k D1_k a_k + sum_k D0_k b_k + n1 E_1[K] + n0 E_0[K], D_y,k = E_y[k] - E_y[K]) and N in a row kernel
+ * that leaves one partial per piece of SVILS_SBMELBO_PIECE_ROWS rows (more where n exceeds 4096 pieces: the extent of a
+ * piece depends on n alone); one block adds all partials in ascending order.  G is formed on the host inside the call,
+ * from gamma, lambda, Elogpi and Elogbeta copied back.  O((n + links + skipped pairs) k).  All sums fp64 in a fixed order,
+ * no floating-point atomic: the four outputs are bitwise equal from run to run, on two handles, for every
+ * svils_sbm_set_launch_nodes value and for both chain forms.  The call changes nothing that a pass, an M-step,
+ * svils_sbm_get_stats or svils_sbm_get_timing reads.  Waits for the device.
+ * SVILS_ERR_ARG: a null handle, a null out, no graph or no state */
+#define SVILS_SBMELBO_PIECE_ROWS 16
+int svils_sbmelbo(svils_sbm *h, double out[4]);
+/* device ms of the last svils_sbmelbo pass (its four kernels); -1 before the first */
+int svils_sbmelbo_get_timing(svils_sbm *h, double ms[1]);
 
 /* ---- -ppc / -gen: networks drawn from a model and their statistics (an ADDITION of ABI 8; a handle of its own) -----------
  * The device side of the reference's MMSBGen::gen (src/mmsbgen.cc:43-71) and MMSBGen::ppc (draw_and_save, :662-697, with

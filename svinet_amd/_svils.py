@@ -51,7 +51,7 @@ EXPORTS = (
     "svils_orig_get_query_timing", "svils_orig_elbo", "svils_orig_get_elbo_stats", "svils_orig_get_elbo_timing",
     "svils_sbm_create", "svils_sbm_destroy", "svils_sbm_set_graph", "svils_sbm_set_state", "svils_sbm_get_state", "svils_sbm_estep",
     "svils_sbm_sweep", "svils_sbm_pair_loglik", "svils_sbm_get_stats", "svils_sbm_get_timing", "svils_sbm_set_launch_nodes",
-    "svils_sbm_set_plain_chain", "svils_sbm_variant",
+    "svils_sbm_set_plain_chain", "svils_sbm_variant", "svils_sbmelbo", "svils_sbmelbo_get_timing",
     "svils_ppc_create", "svils_ppc_destroy", "svils_ppc_set_params", "svils_ppc_draw", "svils_ppc_set_links", "svils_ppc_stats",
     "svils_ppc_get_draw_counts", "svils_ppc_get_links", "svils_ppc_get_nodes", "svils_ppc_get_summary", "svils_ppc_get_communities",
     "svils_ppc_get_timing", "svils_ppc_set_tile_batch",
@@ -63,6 +63,9 @@ PPC_MAX_N, PPC_MAX_K = 32768, 2048      # SVILS_PPC_MAX_N, SVILS_PPC_MAX_K
 ORIG_MAX_K, ORIG_MAX_N = 64, 32768      # SVILS_ORIG_MAX_K, SVILS_ORIG_MAX_N
 BATCH_MAX_K, BATCH_MAX_N = 256, 32768   # SVILS_BATCH_MAX_K, SVILS_BATCH_MAX_N
 SBM_MAX_K, SBM_MAX_PASSES = 256, 10     # SVILS_SBM_MAX_K, SVILS_SBM_MAX_PASSES
+# SVILS_SBMELBO_PIECE_ROWS: the rows of a piece of svils_sbmelbo's row kernel (one partial sum per piece), while n stays below
+# SBMELBO_MAX_PIECES of them; above, a piece takes ceil(n / SBMELBO_MAX_PIECES) rows
+SBMELBO_PIECE_ROWS, SBMELBO_MAX_PIECES = 16, 4096
 BATCH_STAR_CHAIN_MAX = 1024             # SVILS_BATCH_STAR_CHAIN_MAX
 PREDICT_MAX_TOPK = 256   # SVILS_PREDICT_MAX_TOPK
 NBR_CN, NBR_AA, NBR_RA = range(3)   # svils_nbr_measure
@@ -259,6 +262,8 @@ def load():
     L.svils_sbm_set_launch_nodes.argtypes = [vp, C.c_uint32]
     L.svils_sbm_set_plain_chain.argtypes = [vp, C.c_int]
     L.svils_sbm_variant.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.svils_sbmelbo.argtypes = [vp, vp]
+    L.svils_sbmelbo_get_timing.argtypes = [vp, vp]
     L.svils_ppc_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(vp)]
     L.svils_ppc_destroy.argtypes = [vp]
     L.svils_ppc_set_params.argtypes = [vp, vp, vp]
@@ -1041,6 +1046,18 @@ class Sbm:
         ms = np.zeros(3)
         _chk(load().svils_sbm_get_timing(self._h, ms.ctypes.data))
         return ms
+
+    def elbo(self):
+        """svils_sbmelbo: the variational lower bound of the current state -> (total, P, N, G), total = P + N + G"""
+        out = np.zeros(4)
+        _chk(load().svils_sbmelbo(self._h, out.ctypes.data))
+        return tuple(out)
+
+    def elbo_timing(self):
+        """device ms of the last elbo() pass; -1 before the first"""
+        ms = np.zeros(1)
+        _chk(load().svils_sbmelbo_get_timing(self._h, ms.ctypes.data))
+        return float(ms[0])
 
     def set_launch_nodes(self, nodes):
         """nodes per launch of the chain kernel (0: the library's default); the results do not depend on it"""

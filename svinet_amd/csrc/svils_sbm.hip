@@ -29,6 +29,10 @@
 //   k_sbm_mstep         one block: folds the partials in ascending order; gamma, lambda, Elogpi, Elogbeta
 //   k_sbm_elog          Elogpi, Elogbeta of a state that arrives from the host
 //   k_sbm_pair_ll       edge_likelihood2 (src/sbm.hh:284-308): one wavefront per pair
+//   k_sbm_elbo_rows     svils_sbmelbo (-single-logl): sum phi (Elogpi - log phi) per piece of the rows,
+//                       rows packed into a wavefront as k_sbm_links packs pairs
+//   k_sbm_elbo_fold     one block: the pair part of the bound from the colsum and link partials as the M-step folds them,
+//                       and the sum of the row partials, in ascending order
 //
 // No floating-point atomics; all sums fp64 in a fixed order.
 #include "svils_csr.h"
@@ -408,10 +412,79 @@ __global__ __launch_bounds__(256) void k_sbm_pair_ll(uint64_t m, uint32_t K, con
   if (lane == 0) out[x] = log(s < 1e-30 ? 1e-30 : s);
 }
 
+// ---- svils_sbmelbo: the lower bound of the current state ------------------------------------------
+// epart[piece] = sum over the piece's rows i and all k of phi_ik (Elogpi_k - log phi_ik), an exact 0 of phi adding 0.  One
+// wavefront per piece of `per` consecutive rows; lanes as in k_sbm_links: W lanes hold a row, the 64 / W lane groups take
+// every (64 / W)th row of the piece, a lane adds its entries in ascending row (and column), the lanes by the fixed butterfly
+__global__ __launch_bounds__(256) void k_sbm_elbo_rows(uint32_t n, uint32_t K, uint32_t W, uint32_t per, uint32_t pieces,
+                                                       const double *__restrict__ phi, const double *__restrict__ elogpi,
+                                                       double *__restrict__ epart) {
+  const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, g = lane / W, lw = lane % W, G = 64 / W;
+  if (wave >= pieces) return;   // whole wavefronts leave together
+  const uint32_t r0 = wave * per, r1 = min(n, r0 + per);
+  double ep[MAX_V];
+#pragma unroll
+  for (int v = 0; v < MAX_V; ++v) ep[v] = lw + 64 * v < K ? elogpi[lw + 64 * v] : 0.0;
+  double acc = 0.0;
+  for (uint32_t i = r0 + g; i < r1; i += G) {
+#pragma unroll
+    for (int v = 0; v < MAX_V; ++v) {
+      const uint32_t k = lw + 64 * v;
+      if (k < K) {
+        const double x = phi[(size_t)i * K + k];
+        acc += x > 0.0 ? x * (ep[v] - log(x)) : 0.0;
+      }
+    }
+  }
+  acc = wave_sum_f64(acc);
+  if (lane == 0) epart[wave] = acc;
+}
+
+struct ElboArgs {
+  uint32_t K, nb, pieces;
+  double n1, n0;
+  const double *elogbeta, *cpart, *lpart, *epart;
+  double *eout;                               // [2]: P, N
+};
+
+// one block: a_k and b_k from the partials exactly as k_sbm_mstep forms them, then P (thread 0) and N (thread 64), every
+// sum in ascending order
+__global__ __launch_bounds__(256) void k_sbm_elbo_fold(ElboArgs x) {
+  __shared__ double sa[256], sb[256];
+  const uint32_t t = threadIdx.x, K = x.K;
+  if (t < K) {
+    const double S = fold_colsum(x.cpart, x.nb, K, 0, t), Q = fold_colsum(x.cpart, x.nb, K, 1, t);
+    double X = 0.0, Y1 = 0.0, Y0 = 0.0;
+    for (uint32_t wv = 0; wv < LINK_WAVES; ++wv) {
+      X += x.lpart[((size_t)wv * 3 + 0) * K + t];
+      Y1 += x.lpart[((size_t)wv * 3 + 1) * K + t];
+      Y0 += x.lpart[((size_t)wv * 3 + 2) * K + t];
+    }
+    const double a = X - Y1;                                    // over the trained links
+    const double b = (0.5 * fma(S, S, -Q) - X) - Y0;            // over the trained non-links
+    sa[t] = (x.elogbeta[2 * t] - x.elogbeta[2 * K]) * a;
+    sb[t] = (x.elogbeta[2 * t + 1] - x.elogbeta[2 * K + 1]) * b;
+  }
+  __syncthreads();
+  if (t == 0) {
+    double pa = 0.0, pb = 0.0;
+    for (uint32_t k = 0; k < K; ++k) {
+      pa += sa[k];
+      pb += sb[k];
+    }
+    x.eout[0] = ((pa + pb) + x.n1 * x.elogbeta[2 * K]) + x.n0 * x.elogbeta[2 * K + 1];
+  }
+  if (t == 64) {
+    double s = 0.0;
+    for (uint32_t p = 0; p < x.pieces; ++p) s += x.epart[p];
+    x.eout[1] = s;
+  }
+}
+
 }  // namespace
 
 // events: ev[0] .. ev[1] the call; ev[2 + 2 b] .. ev[3 + 2 b] the chain launches of pass b of the last E-step; ev[22] .. ev[23]
-// the M-step of the last iteration
+// the M-step of the last iteration; ev[24] .. ev[25] the last svils_sbmelbo pass
 struct svils_sbm : ToolHandle {
   uint32_t n = 0, k = 0;
   double alpha = 0;
@@ -422,6 +495,9 @@ struct svils_sbm : ToolHandle {
   double *carry = nullptr, *msums = nullptr;                      // [k + 1], [SVILS_SBM_MAX_PASSES]
   double *cpart = nullptr, *lpart = nullptr;                      // [nb][2][k], [LINK_WAVES][3][k]
   double *gtab = nullptr;                                         // [128][2] log_tab's table
+  double *epart = nullptr, *eout = nullptr;                       // svils_sbmelbo: [pieces] row partials; [2] P, N
+  std::vector<double> eta_h;                                      // eta on the host (the G part of svils_sbmelbo)
+  uint32_t eper = 0, epieces = 0;                                 // rows per piece of k_sbm_elbo_rows, pieces
   u64 *ctl = nullptr;                                             // [CTL_COUNT]
   // GRAPH scope
   uint64_t *lrow = nullptr, *srow = nullptr;                      // the links and the skipped pairs as symmetric CSRs
@@ -436,12 +512,13 @@ struct svils_sbm : ToolHandle {
   uint32_t nb = 0, per = 0;                                       // colsum blocks, nodes per block
   uint32_t launch_nodes = 0;
   bool plain = false;
-  bool have_graph = false, have_state = false, timed = false, timed_m = false;
+  bool have_graph = false, have_state = false, timed = false, timed_m = false, timed_e = false;
 };
 
 namespace {
 
-constexpr int EV_PASS = 2, EV_MSTEP = 2 + 2 * SVILS_SBM_MAX_PASSES, EV_COUNT = EV_MSTEP + 2;
+constexpr int EV_PASS = 2, EV_MSTEP = 2 + 2 * SVILS_SBM_MAX_PASSES, EV_ELBO = EV_MSTEP + 2, EV_COUNT = EV_ELBO + 2;
+constexpr uint32_t ELBO_PIECE_ROWS = SVILS_SBMELBO_PIECE_ROWS, ELBO_MAX_PIECES = 4096;   // the fold adds the pieces one by one
 
 template <int B>
 int launch_chain(svils_sbm *h, const ChainArgs &a) {
@@ -453,6 +530,13 @@ int launch_chain(svils_sbm *h, const ChainArgs &a) {
     default: return fail(SVILS_ERR_UNSUPPORTED, "svils_sbm: no chain kernel for k = %u", h->k);   // a missing kernel is an error
   }
   return 0;
+}
+
+// the power of two >= min(k, 64) lanes that hold a row in k_sbm_links and k_sbm_elbo_rows
+uint32_t row_lanes(uint32_t k) {
+  uint32_t W = 2;
+  while (W < 64 && W < k) W <<= 1;
+  return W;
 }
 
 void launch_colsum(svils_sbm *h, int guard) {
@@ -481,8 +565,7 @@ int queue_estep(svils_sbm *h, uint32_t max_passes) {
 int queue_mstep(svils_sbm *h) {
   HIPCHK(hipEventRecord(h->ev[EV_MSTEP], h->st));
   launch_colsum(h, 0);
-  uint32_t W = 2;
-  while (W < 64 && W < h->k) W <<= 1;
+  const uint32_t W = row_lanes(h->k);
   hipLaunchKernelGGL(k_sbm_links, dim3(LINK_WAVES / 4), dim3(256), 0, h->st, h->k, W, (uint64_t)h->nlinks, (uint64_t)h->nskip, h->edges,
                      h->spairs, h->py, h->phi, h->lpart);
   const MstepArgs a{h->k, h->nb, h->alpha, h->n1, h->n0, h->eta, h->cpart, h->lpart, h->gtab, h->gamma, h->lam, h->elogpi, h->elogbeta};
@@ -533,6 +616,9 @@ int svils_sbm_create(int device, uint32_t n, uint32_t k, double alpha, const dou
   h->nb = std::min(COLSUM_BLOCKS, (n + 63) / 64);
   h->per = (n + h->nb - 1) / h->nb;
   h->nb = (n + h->per - 1) / h->per;   // no empty block
+  h->eper = std::max(ELBO_PIECE_ROWS, (n + ELBO_MAX_PIECES - 1) / ELBO_MAX_PIECES);
+  h->epieces = (n + h->eper - 1) / h->eper;
+  h->eta_h.assign(eta, eta + 2 * ((size_t)k + 1));
   const auto scope = ToolHandle::HANDLE;
   const size_t kk = 2 * ((size_t)k + 1);
   int rc = h->open(device, EV_COUNT);
@@ -547,6 +633,8 @@ int svils_sbm_create(int device, uint32_t n, uint32_t k, double alpha, const dou
   if (!rc) rc = h->dalloc(scope, &h->cpart, (size_t)h->nb * 2 * k);
   if (!rc) rc = h->dalloc(scope, &h->lpart, (size_t)LINK_WAVES * 3 * k);
   if (!rc) rc = h->dalloc(scope, &h->ctl, (size_t)CTL_COUNT);
+  if (!rc) rc = h->dalloc(scope, &h->epart, (size_t)h->epieces);
+  if (!rc) rc = h->dalloc(scope, &h->eout, (size_t)2);
   if (!rc) rc = h->upload(scope, &h->gtab, log_table());
   if (!rc && (hipMemsetAsync(h->ctl, 0, CTL_COUNT * sizeof(u64), h->st) != hipSuccess ||
               hipMemsetAsync(h->msums, 0, SVILS_SBM_MAX_PASSES * sizeof(double), h->st) != hipSuccess))
@@ -724,6 +812,66 @@ int svils_sbm_get_timing(svils_sbm *h, double ms[3]) {
   ms[0] = h->elapsed_ms(0, 1, h->timed);
   ms[1] = h->launches_ms(EV_PASS, SVILS_SBM_MAX_PASSES, h->timed);
   ms[2] = h->elapsed_ms(EV_MSTEP, EV_MSTEP + 1, h->timed_m);
+  return 0;
+}
+
+// The bound of the current state.  cpart and lpart are scratch here as in the M-step (every reader rewrites them first); the
+// row partials, eout and the two events are this call's own; ctl, msums, carry and the state are only read
+int svils_sbmelbo(svils_sbm *h, double out[4]) {
+  if (!h) return fail(SVILS_ERR_ARG, "svils_sbmelbo: null handle");
+  if (!out) return fail(SVILS_ERR_ARG, "svils_sbmelbo: null argument");
+  if (int rc = ready(h, "svils_sbmelbo")) return rc;
+  const uint32_t K = h->k, W = row_lanes(K);
+  HIPCHK(hipEventRecord(h->ev[EV_ELBO], h->st));
+  launch_colsum(h, 0);
+  hipLaunchKernelGGL(k_sbm_links, dim3(LINK_WAVES / 4), dim3(256), 0, h->st, K, W, (uint64_t)h->nlinks, (uint64_t)h->nskip, h->edges,
+                     h->spairs, h->py, h->phi, h->lpart);
+  hipLaunchKernelGGL(k_sbm_elbo_rows, dim3(blocks(h->epieces, 4)), dim3(256), 0, h->st, h->n, K, W, h->eper, h->epieces, h->phi, h->elogpi,
+                     h->epart);
+  const ElboArgs a{K, h->nb, h->epieces, h->n1, h->n0, h->elogbeta, h->cpart, h->lpart, h->epart, h->eout};
+  hipLaunchKernelGGL(k_sbm_elbo_fold, dim3(1), dim3(256), 0, h->st, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev[EV_ELBO + 1], h->st));
+  h->timed_e = true;
+  const size_t kk = 2 * ((size_t)K + 1);
+  std::vector<double> gamma(K), elogpi(K), lam(kk), elogbeta(kk);
+  double pn[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(pn, h->eout, sizeof pn, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(gamma.data(), h->gamma, K * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(elogpi.data(), h->elogpi, K * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(lam.data(), h->lam, kk * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(elogbeta.data(), h->elogbeta, kk * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  // G on the host: 4 (K + 1) + 2 K + 2 lnGamma (src/sbm.cc:1144-1164, :1193-1213)
+  auto beta_term = [&](const double *p, uint32_t k) {
+    return std::lgamma(p[2 * k] + p[2 * k + 1]) - std::lgamma(p[2 * k]) - std::lgamma(p[2 * k + 1]) +
+           ((p[2 * k] - 1) * elogbeta[2 * k] + (p[2 * k + 1] - 1) * elogbeta[2 * k + 1]);
+  };
+  double G = 0.0;
+  for (uint32_t k = 0; k <= K; ++k) G += beta_term(h->eta_h.data(), k) - beta_term(lam.data(), k);
+  double se = 0.0, sg = 0.0, slg = 0.0, sge = 0.0;
+  for (uint32_t k = 0; k < K; ++k) {
+    se += elogpi[k];
+    sg += gamma[k];
+    slg += std::lgamma(gamma[k] < 1e-30 ? 1e-30 : gamma[k]);
+    sge += (gamma[k] - 1) * elogpi[k];
+  }
+  G += std::lgamma(K * h->alpha) - K * std::lgamma(h->alpha) + (h->alpha - 1) * se;
+  G -= std::lgamma(sg) - slg;
+  G -= sge;
+  out[1] = pn[0];
+  out[2] = pn[1];
+  out[3] = G;
+  out[0] = (pn[0] + pn[1]) + G;
+  return 0;
+}
+
+int svils_sbmelbo_get_timing(svils_sbm *h, double ms[1]) {
+  if (!h) return fail(SVILS_ERR_ARG, "svils_sbmelbo_get_timing: null handle");
+  if (!ms) return fail(SVILS_ERR_ARG, "svils_sbmelbo_get_timing: null argument");
+  if (int rc = check(h, "svils_sbmelbo_get_timing")) return rc;
+  HIPCHK(hipStreamSynchronize(h->st));
+  ms[0] = h->elapsed_ms(EV_ELBO, EV_ELBO + 1, h->timed_e);
   return 0;
 }
 

@@ -382,12 +382,14 @@ struct svih_sbm {
   std::unique_ptr<Network> net;
   std::unique_ptr<SBM> eng;
 };
-svih_sbm *svih_sbm_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t on_device,
-                             int32_t device) {
+static svih_sbm *sbm_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t on_device,
+                               int32_t device, int32_t logl, int32_t stop) {
   Env::Args a;
   a.n = n;
   a.k = k;
   a.single = true;
+  a.single_logl = logl != 0;
+  a.use_validation_stop = stop != 0;
   a.host_loops = on_device == 0;
   a.device = device;
   a.rand_seed = seed;
@@ -403,6 +405,39 @@ svih_sbm *svih_sbm_from_file(const char *path, uint32_t n, uint32_t k, double se
     return nullptr;
   }
   return b;
+}
+svih_sbm *svih_sbm_from_file(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t on_device,
+                             int32_t device) {
+  return sbm_from_file(path, n, k, seed, heldout_ratio, on_device, device, 0, 1);
+}
+// logl: -single-logl (a row of the lower bound after the M-step of every sweep: svih_sbm_logl_rows); stop 0: -no-stop
+svih_sbm *svih_sbm_from_file_logl(const char *path, uint32_t n, uint32_t k, double seed, double heldout_ratio, int32_t on_device,
+                                  int32_t device, int32_t logl, int32_t stop) {
+  return sbm_from_file(path, n, k, seed, heldout_ratio, on_device, device, logl, stop);
+}
+// the variational lower bound of the current state: out = total, P, N, G
+int svih_sbm_elbo(svih_sbm *b, double *out) { return svils_rc([&] { b->eng->elbo(out); return 0; }); }
+uint64_t svih_sbm_nlogl_rows(const svih_sbm *b) { return b->eng->logl_rows().size() / 2; }
+const double *svih_sbm_logl_rows(const svih_sbm *b) { return b->eng->logl_rows().data(); }   // [rows][2]: iter, total
+int32_t svih_sbm_stop_rule_verdict(const svih_sbm *b) { return (int32_t)b->eng->stop_rule_verdict(); }   // 0 go on, 1 drop, 2 gain
+// tests: the engine's own stop rule (enabled unless -no-stop) fed a made-up row; the verdict.  Not a row of logl_rows
+int32_t svih_sbm_feed_stop_rule(svih_sbm *b, uint32_t iter, double s) { return (int32_t)b->eng->stop_rule().update(iter, s); }
+// compute_precision of the current state: out = c10, c100, c1000 (cumulative)
+int svih_sbm_precision(svih_sbm *b, uint32_t *out) {
+  return svils_rc([&] {
+    const SbmPrecision r = b->eng->compute_precision();
+    out[0] = r.c10; out[1] = r.c100; out[2] = r.c1000;
+    return 0;
+  });
+}
+// tests: the ranking of compute_precision on its own.  out = c10, c100, c1000; curve [2 * curve_cap]: (rank, links so far)
+// rows; returns the curve's rows
+uint64_t svih_sbm_rank_precision(const uint32_t *pairs, const double *score, const uint8_t *y, uint64_t m, uint32_t *out, uint32_t *curve,
+                                 uint64_t curve_cap) {
+  const SbmPrecision r = sbm_rank_precision(pairs, score, y, m);
+  out[0] = r.c10; out[1] = r.c100; out[2] = r.c1000;
+  for (size_t i = 0; i < r.curve.size() && i < 2 * curve_cap; ++i) curve[i] = r.curve[i];
+  return r.curve.size() / 2;
 }
 void svih_sbm_free(svih_sbm *b) { delete b; }
 uint32_t svih_sbm_n(const svih_sbm *b) { return b->eng->n(); }

@@ -67,7 +67,7 @@ Env::Env(const Args &a)
       nmi(a.nmi), ground_truth_fname(a.ground_truth_fname),
       datfname(a.datfname), label(a.label), gpus(a.gpus), rank(a.rank), kshard(a.kshard), sharded((a.sharded || a.gpus > 1) && !a.kshard), comm_rfd(a.comm_rfd), comm_wfds(a.comm_wfds),
       batch_mode(a.batch), link_sampling(a.link_sampling), findk(a.findk), batch_device((a.batch && a.batch_gpu) || ((a.rnode || a.rpair || a.infset || a.snode) && !a.host_loops)),
-      randomnode(a.rnode), randompair(a.rpair), stratified(a.stratified), delaylearn((a.rnode || a.rpair) && !a.nodelay), infset(a.infset || a.preprocess), preprocess(a.preprocess), inf_epsilon(a.inf_epsilon), snode(a.snode), sparse_graph(a.sparse_graph), orig(a.orig), orig_device(a.orig && !a.host_loops), itype(a.itype), clean_holdout(a.clean_holdout), single(a.single), single_device(a.single && !a.host_loops), sbm_alpha(0.5), s(a.n / 2), gml(a.gml), lcstats(a.lcstats), strid(a.strid),
+      randomnode(a.rnode), randompair(a.rpair), stratified(a.stratified), delaylearn((a.rnode || a.rpair) && !a.nodelay), infset(a.infset || a.preprocess), preprocess(a.preprocess), inf_epsilon(a.inf_epsilon), snode(a.snode), sparse_graph(a.sparse_graph), orig(a.orig), orig_device(a.orig && !a.host_loops), itype(a.itype), clean_holdout(a.clean_holdout), single(a.single), single_device(a.single && !a.host_loops), single_logl(a.single_logl), sbm_alpha(0.5), s(a.n / 2), gml(a.gml), lcstats(a.lcstats), strid(a.strid),
       terminate(0), total_pairs(0), ones_prob(0), zeros_prob(1),
       device(a.device), sweep_batch(a.sweep_batch), write_files(a.write_files),
       minibatch(a.minibatch), tau0(a.tau0), kappa(a.kappa), nodetau0(a.nodetau0), nodekappa(a.nodekappa),

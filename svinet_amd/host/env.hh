@@ -42,7 +42,9 @@ class Env {
     // -single: the single-membership stochastic blockmodel (SBM::batch_infer, src/sbm.cc:457-543).  On the device unless
     // -host-loops is given
     bool single = false;
-    bool findk = false;                // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
+    // -single-logl: -single with the lower bound after every iteration (logl.txt) and its two stop rules (sbm.hh)
+    bool single_logl = false;
+    bool findk = false;               // -findk: estimate the number of communities (FastInit, src/main.cc:321-327)
     bool gml = false, lcstats = false;  // -gml / -lcstats: link communities of a fitted model (MMSBGen, src/main.cc:307-318)
     bool ppc = false, gen = false;      // -ppc / -gen: posterior predictive checks, a network from the prior (MMSBGen, src/main.cc:268-303)
     int ppc_draws = 100;                // -ppc-draws (ppc_ndraws, src/env.hh:452)
@@ -150,6 +152,7 @@ class Env {
   int itype;                         // -itype (src/main.cc:193-194), read by -orig alone
   bool clean_holdout;                // -clean-holdout: -orig trains on no orientation of a held-out or validation pair
   bool single, single_device;        // -single; without -host-loops SBM drives a svils_sbm handle
+  bool single_logl;                  // -single-logl: SBM writes the lower bound after every iteration and heeds its stop rules
   double sbm_alpha;                  // the Dirichlet prior of -single (src/env.hh:345)
   uint32_t s;                        // their mini-batch size n / 2 (src/env.hh:321; -rpair only)
   bool gml, lcstats;

@@ -219,6 +219,12 @@ static void usage() {
           "\t\t\tthe run fails, -host-loops runs the host CPU loops over all pairs).  Needs -max-iterations N: N iterations, then\n"
           "\t\t\tphi.txt, lambda.txt and gamma.txt.  Refused beside every other engine or tool flag, -infset (the sampled variant\n"
           "\t\t\tis not implemented), -sparse-graph (the engine is always sparse), -logl, -gpus N > 1, -scale and the link queries\n\n"
+          "\t-single-logl\t-single with its variational lower bound, on the GPU in O((n + links + held-out pairs) K): a row of logl.txt\n"
+          "\t\t\tafter the M-step of every iteration, and two stop rules on it: the bound below its maximum at more than 3\n"
+          "\t\t\titerations past iteration 10 (writes max.txt), or a relative gain below 1e-5 (writes done.txt).  Either ends\n"
+          "\t\t\tthe run with the model saved, precision.txt and hitcurve_0.txt written, so -max-iterations is optional (if\n"
+          "\t\t\tgiven it still caps the run); -no-stop turns both rules off and needs -max-iterations.  Refused with\n"
+          "\t\t\teverything -single is refused with\n\n"
           "\t-clean-holdout\twith -orig: leave both orientations of every held-out and every validation pair out of training\n"
           "\t\t\t(the reference leaves out the held-out pairs alone, and only in the orientation drawn).  With it -orig answers\n"
           "\t\t\t-predict-pairs, -recommend, -rank-pairs and -rank-heldout from its final state, on the GPU: the score of\n"
@@ -409,6 +415,7 @@ int main(int argc, char **argv) {
     else if (is("-ppc-hops")) { a.ppc_hops = true; }
     else if (is("-ppc-orig")) { a.ppc_orig = true; }
     else if (is("-single")) { a.single = true; }               // src/main.cc:191-192
+    else if (is("-single-logl")) { a.single = a.single_logl = true; }   // -single with the lower bound and its stop rules
     else if (is("-gp") || is("-disjoint") ||
              is("-load-test-sets")) {
       unsupported = true;
@@ -421,17 +428,18 @@ int main(int argc, char **argv) {
   const bool ppc_plain = a.ppc;
   if (a.ppc_orig) a.ppc = true;                          // -ppc-orig: the -ppc mode plus the K x K kind (it does not set -orig)
   if (a.single && !unsupported) {                        // -single (SBM::batch_infer): an engine of its own; refusals before anything is read
-    if (refused(a, kSingle, "-single")) return 2;
+    const char *flag = a.single_logl ? "-single-logl" : "-single";   // the same table for both
+    if (refused(a, kSingle, flag)) return 2;
     const struct { bool set; const char *name; } more[] = {
         {a.batch_gpu, "-batch-gpu"}, {a.infset, "-infset"}, {a.preprocess, "-preprocess"}, {a.snode, "-snode"}, {a.orig, "-orig"},
         {a.ppc_orig, "-ppc-orig"}, {a.ppc, "-ppc"}, {a.gen, "-gen"}, {a.sparse_graph, "-sparse-graph"}, {a.logl, "-logl"}, {a.load, "-load"},
         {a.val_load, "-load-validation"}, {a.test_load, "-load-test"}, {a.init_comm, "-init-communities"}, {a.scale != 1, "-scale"}};
     for (const auto &m : more)
       if (m.set) {
-        fprintf(stderr, kSingle.fmt, "-single", m.name);
+        fprintf(stderr, kSingle.fmt, flag, m.name);
         return 2;
       }
-    if (a.max_iterations == 0) {
+    if (a.max_iterations == 0 && !(a.single_logl && a.use_validation_stop)) {   // -single-logl: the stop rules of the bound end the run
       fprintf(stderr, "error: -single needs -max-iterations N: the reference's loop never ends and its stop rule cannot fire\n");
       return 2;
     }

@@ -61,7 +61,9 @@ SBM::SBM(Env &env, Network &network)
       fclose(open_or_die(Env::file_str(f), f + 1));
     hf_ = open_or_die(Env::file_str("/heldout.txt"), "heldout");
     vf_ = open_or_die(Env::file_str("/validation.txt"), "validation");
+    if (env_.single_logl) lf_ = open_or_die(Env::file_str("/logl.txt"), "logl");
   }
+  rule_.enabled = env_.use_validation_stop;
   Env::plog("network ones", network_.ones());
   Env::plog("network singles", network_.singles());
   printf("+ sbm initialization end\n");
@@ -74,6 +76,7 @@ SBM::SBM(Env &env, Network &network)
 SBM::~SBM() {
   if (hf_) fclose(hf_);
   if (vf_) fclose(vf_);
+  if (lf_) fclose(lf_);
   if (dev_) svils_sbm_destroy(dev_);
 }
 
@@ -299,9 +302,162 @@ void SBM::sweep() {
     estep_host();
     mstep_host();
   }
+  const OrigStopRule::Verdict v = env_.single_logl ? approx_log_likelihood() : OrigStopRule::GO_ON;   // :528-530
   likelihood_row(heldout_map_, hf_, 0);       // :532-534
   likelihood_row(validation_map_, vf_, 1);
+  if (v != OrigStopRule::GO_ON) {             // a rule ends the run (:914-936, :1222-1225)
+    const SbmPrecision pr = compute_precision();
+    const double s = logl_rows_.back();
+    if (env_.write_files && v == OrigStopRule::STOP_DROP) {
+      FILE *f = open_or_die(Env::file_str("/max.txt"), "max");   // a, t, v, max: the bound, 0, the validation mean, its maximum
+      fprintf(f, "%d\t%d\t%.5f\t%.5f\t%.5f\t%.5f\t%d\t%d\t%d\t%d\n", iter_, duration(), s, 0.0, rows_[rows_.size() - 6], rule_.max, pr.c10,
+              pr.c100, pr.c1000, 1);
+      fclose(f);
+    } else if (env_.write_files) {
+      FILE *f = open_or_die(Env::file_str("/done.txt"), "done");
+      fprintf(f, "%d\t%d\t%.5f\n", iter_, duration(), s);
+      fclose(f);
+    }
+  }
   iter_++;
+}
+
+// ---------------------------------------------------------------------------
+// the lower bound (:1133-1239) and its stop rules
+// ---------------------------------------------------------------------------
+void SBM::elbo_host(double out[4]) {
+  const uint32_t K = k_;
+  auto beta_term = [&](const std::vector<double> &p, uint32_t k) {   // :1144-1164
+    return lgamma(p[2 * k] + p[2 * k + 1]) - (lgamma(p[2 * k]) + lgamma(p[2 * k + 1])) +
+           ((p[2 * k] - 1) * elogbeta_[2 * k] + (p[2 * k + 1] - 1) * elogbeta_[2 * k + 1]);
+  };
+  double G = 0;
+  for (uint32_t k = 0; k <= K; ++k) G += beta_term(eta_, k) - beta_term(lambda_, k);
+  double P = 0;                                                      // :1166-1185
+  std::vector<uint8_t> yv((size_t)n_), ok((size_t)n_);
+  for (uint32_t p = 0; p < n_; ++p) {
+    std::fill(yv.begin(), yv.end(), 0);
+    std::fill(ok.begin(), ok.end(), 1);
+    for (uint32_t q : skipped_[p]) ok[q] = 0;
+    for (uint32_t q : network_.get_edges(p)) yv[q] = 1;
+    const double *pp = &phi_[(size_t)p * K];
+    for (uint32_t q = p + 1; q < n_; ++q) {
+      if (!ok[q]) continue;
+      const int t = yv[q] ? 0 : 1;
+      const double *pq = &phi_[(size_t)q * K];
+      double sum = 0;
+      for (uint32_t k = 0; k < K; ++k) {
+        sum += pp[k] * pq[k];
+        P += pp[k] * pq[k] * elogbeta_[2 * k + t];
+      }
+      P += (1 - sum) * elogbeta_[2 * K + t];
+    }
+  }
+  double N = 0;                                                      // :1187-1191 (an exact 0 adds 0)
+  for (uint32_t i = 0; i < n_; ++i)
+    for (uint32_t k = 0; k < K; ++k) {
+      const double x = phi_[(size_t)i * K + k];
+      if (x > 0) N += x * (elogpi_[k] - log(x));
+    }
+  double se = 0, sg = 0, slg = 0, sge = 0;                           // :1193-1213
+  for (uint32_t k = 0; k < K; ++k) {
+    se += elogpi_[k];
+    sg += gamma_[k];
+    slg += lgamma(gamma_[k] < 1e-30 ? 1e-30 : gamma_[k]);
+    sge += (gamma_[k] - 1) * elogpi_[k];
+  }
+  G += lgamma(K * env_.sbm_alpha) - K * lgamma(env_.sbm_alpha) + (env_.sbm_alpha - 1) * se;
+  G -= lgamma(sg) - slg;
+  G -= sge;
+  out[0] = (P + N) + G;
+  out[1] = P;
+  out[2] = N;
+  out[3] = G;
+}
+
+void SBM::elbo(double out[4]) {
+  if (dev_) {
+    if (int rc = svils_sbmelbo(dev_, out)) throw_svils("svils_sbmelbo", rc);
+  } else {
+    elbo_host(out);
+  }
+}
+
+OrigStopRule::Verdict SBM::approx_log_likelihood() {
+  double o[4];
+  elbo(o);
+  const double s = o[0];
+  printf("approx. log likelihood = %f\n", s);
+  if (lf_) {
+    fprintf(lf_, "%d\t%d\t%.5f\n", iter_, duration(), s);   // :1216
+    fflush(lf_);
+  }
+  logl_rows_.push_back((double)iter_);
+  logl_rows_.push_back(s);
+  return verdict_ = rule_.update(iter_, s);
+}
+
+// ---------------------------------------------------------------------------
+// compute_precision (:991-1060)
+// ---------------------------------------------------------------------------
+SbmPrecision sbm_rank_precision(const uint32_t *pairs, const double *score, const uint8_t *y, size_t m) {
+  std::vector<size_t> order(m);
+  for (size_t i = 0; i < m; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    if (score[a] != score[b]) return score[a] > score[b];
+    if (pairs[2 * a] != pairs[2 * b]) return pairs[2 * a] < pairs[2 * b];
+    return pairs[2 * a + 1] < pairs[2 * b + 1];
+  });
+  SbmPrecision r;
+  uint32_t hits = 0;
+  for (size_t i = 0; i < m; ++i) {
+    if (y[order[i]]) {
+      hits++;
+      if (i < 10) r.c10++;
+      else if (i < 100) r.c100++;
+      else if (i < 1000) r.c1000++;
+    }
+    if (i == 0 || (i + 1) % 1000 == 0) {
+      r.curve.push_back((uint32_t)(i + 1));
+      r.curve.push_back(hits);
+    }
+  }
+  r.c100 += r.c10;
+  r.c1000 += r.c100;
+  return r;
+}
+
+SbmPrecision SBM::compute_precision() {
+  const size_t m = precision_map_.size();
+  std::vector<uint32_t> pq;
+  std::vector<uint8_t> y, ones(m, 1);
+  std::vector<double> u(m);
+  for (const auto &it : precision_map_) {
+    pq.push_back(it.first.first);
+    pq.push_back(it.first.second);
+    y.push_back(network_.y(it.first.first, it.first.second) ? 1 : 0);
+  }
+  if (dev_) {
+    if (int rc = svils_sbm_pair_loglik(dev_, pq.data(), ones.data(), m, u.data())) throw_svils("svils_sbm_pair_loglik", rc);
+  } else {
+    for (size_t i = 0; i < m; ++i) u[i] = edge_likelihood2(pq[2 * i], pq[2 * i + 1], 1);
+  }
+  const SbmPrecision r = sbm_rank_precision(pq.data(), u.data(), y.data(), m);
+  if (env_.write_files) {
+    char buf[64];
+    snprintf(buf, sizeof buf, "/hitcurve_%u.txt", hitcurve_id_++);
+    FILE *hc = open_or_die(Env::file_str(buf), "hitcurve");
+    for (size_t i = 0; i + 1 < r.curve.size(); i += 2) fprintf(hc, "%d\t%d\n", r.curve[i], r.curve[i + 1]);
+    fclose(hc);
+    FILE *pf = fopen(Env::file_str("/precision.txt").c_str(), "a");   // opened (and emptied) by the constructor
+    if (!pf) {
+      fprintf(stderr, "cannot open precision file\n");
+      exit(-1);
+    }
+    fprintf(pf, "%d\t%d\t%d\t%d\t%d\n", iter_, duration(), r.c10, r.c100, r.c1000);
+    fclose(pf);
+  }
+  return r;
 }
 
 // ---------------------------------------------------------------------------
@@ -356,11 +512,13 @@ void SBM::likelihood_row(const SampleMap &pairs, FILE *f, int which) {
 
 int SBM::batch_infer() {
   printf("Running batch inference\n");
-  while (iter_ < env_.max_iterations && !env_.terminate) {
+  const bool open_end = env_.max_iterations == 0 && env_.single_logl && rule_.enabled;   // a stop rule ends the run
+  while ((open_end || iter_ < env_.max_iterations) && !env_.terminate && verdict_ == OrigStopRule::GO_ON) {
     sweep();
     printf("iteration = %d took %d secs (%u E-step passes)\n", iter_, duration(), passes_);
     fflush(stdout);
   }
+  if (env_.single_logl && verdict_ == OrigStopRule::GO_ON) compute_precision();   // the run ended at -max-iterations
   fetch_state();
   if (env_.write_files) save_model();
   return 0;

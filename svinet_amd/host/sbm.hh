@@ -27,10 +27,18 @@
 // Departures, all forced:
 //   - the reference's loop never ends, and its stop rule needs iter > 5000 on a value that is always 0 (src/sbm.cc:895): here
 //     -single requires -max-iterations N, runs N iterations, then writes phi.txt, lambda.txt and gamma.txt in save_model's
-//     formats (src/sbm.cc:297-338);
+//     formats (src/sbm.cc:297-338) -- unless -single-logl is given: then the variational lower bound (elbo(), DESIGN.md
+//     section 4s: approx_log_likelihood, :1133-1239, compiled out there under GLOBALPHIS) is appended to logl.txt after the
+//     M-step of every iteration, and the two rules of OrigStopRule (mmsbinferorig.hh) on it end the run: the bound below
+//     its maximum at more than 3 reports with iter > 10 (max.txt in the ten columns of :926-932, t = 0, the bound in the
+//     place of the held-out value that is always 0 there), or a relative gain below 1e-5 (done.txt).  -max-iterations is
+//     then optional and still caps the run; -no-stop turns both rules off;
+//   - compute_precision (:991-1060) is reached from the stop rule alone there; here a -single-logl run calls it when a rule
+//     ends the run and when the run ends at -max-iterations: edge_likelihood2(p, q, 1) of the precision sample, ranked in
+//     descending order -- ties by ascending pair, so the files are defined -- into precision.txt and hitcurve_<id>.txt;
+//     an exact 0 of phi adds 0 to the bound's entropy (the reference gives NaN);
 //   - a graph with too few links or non-links for the three samples is refused with a message (the reference draws for ever);
-//   - network.gml and the lower bound (GLOBALPHIS, compiled out there) are not written; precision.txt and the hit curves
-//     (compute_precision, only reached from the stop rule) neither;
+//   - network.gml is not written; without -single-logl neither are the lower bound, precision.txt and the hit curves;
 //   - gsl_ran_gamma: the same Marsaglia-Tsang recipe as mmsbbatch.cc over the same MT19937 stream with a polar Box-Muller
 //     Gaussian, so the distribution matches and the stream does not.
 #pragma once
@@ -41,20 +49,42 @@
 #include <vector>
 
 #include "env.hh"
+#include "mmsbinferorig.hh"   // OrigStopRule
 #include "network.hh"
 #include "rng.hh"
 #include "svils.h"
 
 namespace svinet {
 
+// compute_precision's ranking (src/sbm.cc:1022-1056) on its own: pairs [m][2] with their scores and true y, ranked by
+// descending score, ties by ascending pair.  c10 / c100 / c1000: the links among the first 10 / 100 / 1000 ranks
+// (cumulative); curve: (rank, links so far) at rank 1 and at every 1000th
+struct SbmPrecision {
+  uint32_t c10 = 0, c100 = 0, c1000 = 0;
+  std::vector<uint32_t> curve;   // [rows][2]
+};
+SbmPrecision sbm_rank_precision(const uint32_t *pairs, const double *score, const uint8_t *y, size_t m);
+
 class SBM {
  public:
   SBM(Env &env, Network &network);
   ~SBM();
 
-  // env.max_iterations iterations, a heldout.txt and a validation.txt row after each, then the model files; returns 0
+  // env.max_iterations iterations (0 with -single-logl: until a stop rule fires), a heldout.txt and a validation.txt row
+  // after each, then the model files; returns 0
   int batch_infer();
-  void sweep();   // one iteration (E-step, M-step, Elogpi / Elogbeta) and its two rows; iter() advances
+  // one iteration (E-step, M-step, Elogpi / Elogbeta) and its two rows; with -single-logl the bound's row after the M-step
+  // and, where a rule answers a stop, max.txt / done.txt and compute_precision; iter() advances
+  void sweep();
+  // The variational lower bound of the current state: total, P, N, G.  Device backend:
+  // svils_sbmelbo; -host-loops: the reference's O(n^2 K) loops restated
+  void elbo(double out[4]);
+  // approx_log_likelihood (:1133-1239): prints the bound, appends a row of logl.txt, drives the stop rules; the verdict
+  OrigStopRule::Verdict approx_log_likelihood();
+  const std::vector<double> &logl_rows() const { return logl_rows_; }   // [rows][2]: iter, total
+  OrigStopRule::Verdict stop_rule_verdict() const { return verdict_; }  // of the last row
+  OrigStopRule &stop_rule() { return rule_; }                           // enabled unless -no-stop
+  SbmPrecision compute_precision();                                     // :991-1060; with files: precision.txt, hitcurve_<id>.txt
 
   uint32_t n() const { return n_; }
   uint32_t k() const { return k_; }
@@ -88,6 +118,7 @@ class SBM {
   void estep_host();
   void mstep_host();
   void likelihood_row(const SampleMap &pairs, FILE *f, int which);
+  void elbo_host(double out[4]);
   void save_model();
   uint32_t duration() const { return (uint32_t)(time(0) - start_time_); }
 
@@ -103,7 +134,11 @@ class SBM {
   std::vector<double> phi_, gamma_, lambda_, eta_, elogpi_, elogbeta_, rows_, msums_;
   uint32_t passes_ = 0;
   time_t start_time_;
-  FILE *hf_ = nullptr, *vf_ = nullptr;
+  FILE *hf_ = nullptr, *vf_ = nullptr, *lf_ = nullptr;
+  std::vector<double> logl_rows_;
+  OrigStopRule rule_;
+  OrigStopRule::Verdict verdict_ = OrigStopRule::GO_ON;
+  uint32_t hitcurve_id_ = 0;
   svils_sbm *dev_ = nullptr;
   bool host_stale_ = false;   // the device has swept since phi_ / gamma_ / lambda_ were fetched
 };

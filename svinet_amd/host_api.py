@@ -496,14 +496,33 @@ class OrigEngine:
     __del__ = close
 
 
+def sbm_rank_precision(pairs, score, y):
+    """compute_precision's ranking (svinet_amd/host/sbm.cc: sbm_rank_precision) on its own: descending score, ties by
+    ascending pair -> ((c10, c100, c1000) cumulative, curve [rows][2] of (rank, links so far))"""
+    L = load()
+    L.svih_sbm_rank_precision.argtypes = [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.svih_sbm_rank_precision.restype = C.c_uint64
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    score = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+    y = np.ascontiguousarray(y, dtype=np.uint8).reshape(-1)
+    assert score.shape[0] == y.shape[0] == pairs.shape[0]
+    cap = pairs.shape[0] // 1000 + 2
+    out, curve = np.zeros(3, dtype=np.uint32), np.zeros((cap, 2), dtype=np.uint32)
+    rows = L.svih_sbm_rank_precision(pairs.ctypes.data, score.ctypes.data, y.ctypes.data, pairs.shape[0], out.ctypes.data,
+                                     curve.ctypes.data, cap)
+    return tuple(int(v) for v in out), curve[:rows].copy()
+
+
 class SbmEngine:
     """The `-single` engine of the host library (svinet_amd/host/sbm.cc): the reference's SBM::batch_infer (src/sbm.cc:457-543),
     the single-membership stochastic blockmodel.  on_device=True: every iteration and pair likelihood runs through svils_sbm_*
     on `device` -- SvilsError without a HIP device, never the host loops instead; on_device=False: the host loops
     (-host-loops).  heldout / validation / precision: the three samples [m][2], p < q, as drawn; skip: all of them, the pairs
-    left out of training."""
+    left out of training.  logl=True (-single-logl): every sweep() appends (iter, lower bound) to logl_rows after its M-step and
+    sets stop_rule_verdict (0 go on, 1 the drop rule, 2 the gain rule; always 0 with stop=False, -no-stop); elbo() is the
+    bound of the current state with or without it."""
 
-    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, on_device=True, device=0):
+    def __init__(self, path, n, k, seed=0, heldout_ratio=0.01, on_device=True, device=0, logl=False, stop=True):
         L = load()
         vp, u32, u64, dbl, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double, C.POINTER
         if not hasattr(L, "_sbm_ready"):
@@ -522,8 +541,21 @@ class SbmEngine:
             L.svih_sbm_pairs.restype = P(u32)
             L.svih_sbm_set_state.argtypes = [vp, vp, vp, vp]
             L.svih_sbm_set_state.restype = C.c_int
+            L.svih_sbm_from_file_logl.argtypes = L.svih_sbm_from_file.argtypes + [C.c_int32, C.c_int32]
+            L.svih_sbm_from_file_logl.restype = vp
+            L.svih_sbm_elbo.argtypes = [vp, vp]
+            L.svih_sbm_elbo.restype = C.c_int
+            L.svih_sbm_precision.argtypes = [vp, vp]
+            L.svih_sbm_precision.restype = C.c_int
+            L.svih_sbm_nlogl_rows.argtypes = [vp]
+            L.svih_sbm_nlogl_rows.restype = u64
+            L.svih_sbm_logl_rows.argtypes = [vp]
+            L.svih_sbm_logl_rows.restype = P(dbl)
+            L.svih_sbm_stop_rule_verdict.argtypes = [vp]
+            L.svih_sbm_stop_rule_verdict.restype = C.c_int32
             L._sbm_ready = True
-        self._h = L.svih_sbm_from_file(os.fsencode(path), n, k, seed, heldout_ratio, int(bool(on_device)), device)
+        self._h = L.svih_sbm_from_file_logl(os.fsencode(path), n, k, seed, heldout_ratio, int(bool(on_device)), device,
+                                            int(bool(logl)), int(bool(stop)))
         if not self._h:
             if on_device:
                 err = _svils.load().svils_last_error().decode("utf-8", "replace")
@@ -592,6 +624,47 @@ class SbmEngine:
         rc = load().svih_sbm_sweep(self._h)
         if rc < 0:
             _svils._chk(rc)
+
+    def elbo(self):
+        """the variational lower bound of the current state (approx_log_likelihood, src/sbm.cc:1133-1239): (total, P, N, G).
+        on_device=True: svils_sbmelbo; else the host loops over all pairs"""
+        out = np.empty(4)
+        rc = load().svih_sbm_elbo(self._h, out.ctypes.data)
+        if rc < 0:
+            _svils._chk(rc)
+        return tuple(out)
+
+    @property
+    def logl_rows(self):
+        """[rows][2] (iter, lower bound): with logl=True one row per sweep(), taken after its M-step"""
+        return _arr(load().svih_sbm_logl_rows(self._h), (load().svih_sbm_nlogl_rows(self._h), 2), np.float64)
+
+    @property
+    def stop_rule_verdict(self):
+        """the stop rules' answer to the last row: 0 go on, 1 the drop rule (max.txt), 2 the gain rule (done.txt)"""
+        return int(load().svih_sbm_stop_rule_verdict(self._h))
+
+    def feed_stop_rule(self, seq):
+        """tests: the engine's own stop rule fed made-up rows seq = [(iter, s), ...] -> the verdict of every row, up to the first
+        stop.  The rows do not enter logl_rows"""
+        L = load()
+        L.svih_sbm_feed_stop_rule.argtypes = [C.c_void_p, C.c_uint32, C.c_double]
+        L.svih_sbm_feed_stop_rule.restype = C.c_int32
+        out = []
+        for it, s in seq:
+            out.append(int(L.svih_sbm_feed_stop_rule(self._h, int(it), float(s))))
+            if out[-1]:
+                break
+        return out
+
+    def precision_counts(self):
+        """compute_precision of the current state: the links among the first 10 / 100 / 1000 of the precision sample ranked by
+        edge_likelihood2(p, q, 1) -> (c10, c100, c1000), cumulative"""
+        out = np.zeros(3, dtype=np.uint32)
+        rc = load().svih_sbm_precision(self._h, out.ctypes.data)
+        if rc < 0:
+            _svils._chk(rc)
+        return tuple(int(v) for v in out)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1,7 +1,8 @@
 """The -single engine on the device: device milliseconds per E-step pass and per whole iteration from
 the hipEvent brackets of svils_sbm_get_timing, for the blocked chain (B consecutive nodes gather at once) and the plain chain
 (B = 1) on the same handle, alternating, the median of --repeats runs after one warm-up run each; the time of one chain launch
-at the nodes-per-launch cap; and, on LFR, the seconds per pass of the host loops (-host-loops: one iteration through the host
+at the nodes-per-launch cap; the device ms of a bound pass of -single-logl (svils_sbmelbo) and the wall ms
+of the whole call beside an E-pass, the median of --repeats passes after a warm-up; and, on LFR, the seconds per pass of the host loops (-host-loops: one iteration through the host
 library, over its passes; on ca-AstroPh they are not run).  One JSON line per workload:
 
     LFR (n = 1 000) at K = 28, ca-AstroPh (n = 17 903) at K = 20
@@ -69,6 +70,17 @@ def run(name, gz, k, a):
     h.estep(1)
     cap = a.launch_nodes or 2048
     out["launch_ms_at_cap"] = h.timing()[1] / -(-n // cap)
+    # the bound pass of -single-logl (svils_sbmelbo) beside an E-pass: device ms of its four kernels and
+    # the wall ms of the whole call (with the copies back and the host's lnGamma terms), on the state the E-pass left
+    h.elbo()
+    ems, wall, vals = [], [], set()
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        vals.add(h.elbo())
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ems.append(h.elbo_timing())
+    out["elbo"] = {"device_ms": float(np.median(ems)), "device_ms_min_max": [min(ems), max(ems)], "call_wall_ms": float(np.median(wall)),
+                   "same_bits": len(vals) == 1, "over_e_pass": float(np.median(ems)) / out["blocked"]["ms_per_pass"]}
     h.close()
     if a.host and name == "lfr":
         from svinet_amd.host_api import SbmEngine
