@@ -213,6 +213,120 @@ EARLY = (61, 4, 1)                      # peaked: the E-step ends after 2 passes
 LFR_SEED = 6
 
 
+# ---- the instantiation matrix and the loop-shape cases of tests/test_gpu_sbm_matrix.py -----------------------------------------
+# (K, seed) at n = 61: both edges of every (V, W) class of K = 2 .. 256 -- V = ceil(K / 64) columns per lane of k_sbm_chain, W the
+# row lanes of k_sbm_links and k_sbm_elbo_rows.  The seeds keep every msum of the E-step and of three iterations outside
+# [0.009, 0.011] (seed 1 does not at K = 5, 16, 32 and 128); tests/test_sbm.py asserts it
+MATRIX_N = 61
+MATRIX = ((2, 1), (3, 1), (4, 1), (5, 2), (8, 1), (9, 1), (16, 2), (17, 1), (32, 3), (33, 1), (64, 1), (65, 1), (128, 4), (129, 1),
+          (192, 1), (193, 1), (256, 1))
+MATRIX_ITERS = 3
+HUBS = ((150, 4), (150, 65))            # (n, K): rows longer than a wavefront
+HUB_SEED, HUB_SKIPS = 21, 100
+DENSE = ((260, 4, 0.9, 0.45, 3000, 31), (200, 20, 0.9, 0.4, 3000, 32))   # (n, K, p_in, p_out, nskip, seed): long link and skip lists
+LOOP_ITERS = 2                          # iterations the hub and dense cases are compared over
+RINGS = ((16500, 3, 41), (65553, 3, 42))   # (n, K, seed): partition sizes above the floor; no O(n^2) restatement at these sizes
+RING_SKIPS = 2000
+
+
+def row_lanes(K):
+    """the lanes that hold a row in k_sbm_links and k_sbm_elbo_rows: the power of two >= min(K, 64), at least 2"""
+    W = 2
+    while W < min(K, 64):
+        W *= 2
+    return W
+
+
+def matrix_cases():
+    return [planted_case(MATRIX_N, K, seed) for K, seed in MATRIX]
+
+
+def hub_nodes(n, B):
+    """the first node, a node in the middle of a block of B near n / 2, the last node"""
+    return 0, (n // (2 * B)) * B + (B - 1) // 2, n - 1
+
+
+@functools.lru_cache(maxsize=None)
+def hub_case(n, K, B):
+    """a planted graph (p_in 0.3, p_out 0.02) whose three hubs are linked to every other node -- all partners later, partners
+    on both sides and inside the block, all partners earlier -- and node 1, in hub 0's block, skipped against HUB_SKIPS random
+    partners: a skip row longer than a wavefront, of both y values, on both sides of the node"""
+    links, _ = planted(n, K, HUB_SEED, 0.3, 0.02)
+    have = {(int(p), int(q)) for p, q in links}
+    for h in hub_nodes(n, B):
+        have |= {(min(h, q), max(h, q)) for q in range(n) if q != h}
+    rng = np.random.RandomState(3000 + HUB_SEED)
+    others = np.array([q for q in range(n) if q != 1])
+    skip = [(min(1, int(q)), max(1, int(q))) for q in np.sort(rng.choice(others, HUB_SKIPS, replace=False))]
+    return Case("hub-n%d-k%d" % (n, K), n, K, sorted(have), skip, plain_state(n, K, HUB_SEED))
+
+
+@functools.lru_cache(maxsize=None)
+def dense_case(n, K, p_in, p_out, nskip, seed):
+    """planted groups; the skip list is nskip pairs drawn uniformly from all pairs"""
+    links, _ = planted(n, K, seed, p_in, p_out)
+    rng = np.random.RandomState(4000 + seed)
+    i, j = np.triu_indices(n, 1)
+    pick = np.sort(rng.choice(i.shape[0], nskip, replace=False))
+    return Case("dense-n%d-k%d" % (n, K), n, K, links, np.stack([i[pick], j[pick]], axis=1), plain_state(n, K, seed))
+
+
+def loop_cases(B):
+    return [hub_case(n, K, B) for n, K in HUBS] + [dense_case(*d) for d in DENSE]
+
+
+@functools.lru_cache(maxsize=None)
+def ring_case(n, K, seed):
+    """a ring of n links, and about RING_SKIPS skipped pairs: half of them links of the ring, half non-links"""
+    rng = np.random.RandomState(5000 + seed)
+    links = np.concatenate([path_graph(n), np.array([(0, n - 1)], dtype=np.uint32)])
+    s1 = links[np.sort(rng.choice(n, RING_SKIPS // 2, replace=False))]
+    p = np.sort(rng.randint(0, n, (2 * RING_SKIPS, 2)), axis=1)
+    d = p[:, 1] - p[:, 0]
+    s0 = np.unique(p[(d >= 2) & (d != n - 1)], axis=0)[:RING_SKIPS // 2]
+    return Case("ring-n%d-k%d" % (n, K), n, K, links, np.concatenate([s1, s0]), plain_state(n, K, seed))
+
+
+def iters_compared(case):
+    """the whole iterations a device test compares the case over with the restatement (0: its E-step alone)"""
+    if case in matrix_cases() or ((case.n, case.K) in [(n, K) for n, K, _ in ITER_CASES] and case.name.endswith("plain")):
+        return MATRIX_ITERS
+    return LOOP_ITERS if case.name.startswith(("hub-", "dense-")) else 0
+
+
+# ---- a second restatement for sizes the masks cannot reach: O(n K) ----------------------------------------------------------------
+def pair_sums_prefix(phi, links, skip):
+    """-> (a [K], b [K], n1, n0): the sums of phi_ik phi_jk over the trained links and the trained non-links, and their counts.
+    The sum over ALL pairs i < j is formed as sum_j phi_jk (sum of the rows below j), in np.longdouble; the listed links and the
+    skipped pairs are then taken off pair by pair.  A direct pair sum: not the (S^2 - Q) / 2 of the device"""
+    n, K = phi.shape
+    P = phi.astype(np.longdouble)
+    below = np.cumsum(P, axis=0)                         # below[j - 1] = the sum of the rows 0 .. j - 1
+    every = (P[1:] * below[:-1]).sum(axis=0)
+    links = np.asarray(links, dtype=np.int64).reshape(-1, 2)
+    skip = np.asarray(skip, dtype=np.int64).reshape(-1, 2)
+    is_link = {(int(p), int(q)) for p, q in links}
+    y = np.array([(int(p), int(q)) in is_link for p, q in skip], dtype=bool)
+    X = (P[links[:, 0]] * P[links[:, 1]]).sum(axis=0)    # one product per listed pair
+    V = P[skip[:, 0]] * P[skip[:, 1]]
+    Y1, Y0 = V[y].sum(axis=0), V[~y].sum(axis=0)
+    n1 = links.shape[0] - int(y.sum())
+    n0 = n * (n - 1) // 2 - links.shape[0] - int((~y).sum())
+    return X - Y1, (every - X) - Y0, n1, n0
+
+
+def mstep_prefix(phi, eta, links, skip, alpha=ALPHA):
+    """-> (gamma, lambda) of phi from pair_sums_prefix"""
+    K = phi.shape[1]
+    a, b, n1, n0 = pair_sums_prefix(phi, links, skip)
+    lam = eta.astype(np.longdouble)
+    lam[:K, 0] += a
+    lam[:K, 1] += b
+    lam[K, 0] += K * n1 - a.sum()                        # sum over the pairs and over k of 1 - phi_ik phi_jk
+    lam[K, 1] += K * n0 - b.sum()
+    return (alpha + phi.astype(np.longdouble).sum(axis=0)).astype(np.float64), lam.astype(np.float64)
+
+
 def estep_cases(B):
     """every E-step case of the device tests: K over ESTEP_K at n = 61; n over the block edges at K = 4 and K = 65"""
     out = [planted_case(61, K, 1) for K in ESTEP_K]
@@ -223,5 +337,6 @@ def estep_cases(B):
 
 def all_cases(B):
     """every case any SBM test uses (the case conditions of tests/test_sbm.py are asserted on all of them)"""
-    return (estep_cases(B) + block_cases(B) + [planted_case(n, K, s) for n, K, s in ITER_CASES] +
-            [planted_case(*EARLY, state="peaked")] + [planted_case(n, K, s) for n, K, s in ((61, 4, 1), (97, 7, 2), (130, 3, 3))])
+    out = (estep_cases(B) + block_cases(B) + [planted_case(n, K, s) for n, K, s in ITER_CASES] +
+           [planted_case(*EARLY, state="peaked")] + [planted_case(n, K, s) for n, K, s in ((61, 4, 1), (97, 7, 2), (130, 3, 3))])
+    return out + [c for c in matrix_cases() if c not in out] + loop_cases(B)

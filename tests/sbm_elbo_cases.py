@@ -45,6 +45,28 @@ def elbo(phi, gamma, lam, eta, T, Y, alpha=S.ALPHA):
     return P + N + G, P, N, G, A
 
 
+def elbo_prefix(phi, gamma, lam, eta, links, skip, alpha=S.ALPHA):
+    """-> (total, P, N, G, A) as elbo returns them, for sizes the masks cannot reach: the pair part from the direct pair sums of
+    sbm_cases.pair_sums_prefix (np.longdouble), N and G as above.  phi_ik phi_jk >= 0, 1 - sum_k phi_ik phi_jk >= 0 and
+    Elogbeta < 0, so all addends of P are <= 0: their absolute values sum to -P"""
+    n, K = phi.shape
+    elogpi, elogbeta = S.elog(gamma, lam)
+    a, b, n1, n0 = S.pair_sums_prefix(phi, links, skip)
+    P = float((a * elogbeta[:K, 0]).sum() + (b * elogbeta[:K, 1]).sum() + (n1 - a.sum()) * elogbeta[K, 0] + (n0 - b.sum()) * elogbeta[K, 1])
+    assert np.all(elogbeta < 0) and np.all(a >= 0) and np.all(b >= 0) and n1 >= a.sum() and n0 >= b.sum()
+    ne, nh = phi * elogpi, -xlogy(phi, phi)
+    N = ne.sum() + nh.sum()
+    g = []
+    for par, sign in ((eta, 1.0), (lam, -1.0)):
+        g += [sign * gammaln(par.sum(axis=1)), -sign * gammaln(par[:, 0]), -sign * gammaln(par[:, 1]),
+              sign * (par[:, 0] - 1.0) * elogbeta[:, 0], sign * (par[:, 1] - 1.0) * elogbeta[:, 1]]
+    g += [np.array([gammaln(K * alpha)]), np.full(K, -gammaln(alpha)), (alpha - 1.0) * elogpi,
+          np.array([-gammaln(gamma.sum())]), gammaln(np.maximum(gamma, 1e-30)), -(gamma - 1.0) * elogpi]
+    g = np.concatenate(g)
+    G = g.sum()
+    return P + N + G, P, N, G, -P + np.abs(ne).sum() + np.abs(nh).sum() + np.abs(g).sum()
+
+
 def entropy(phi):
     """the entropy part of N alone: - sum phi log phi"""
     return -xlogy(phi, phi).sum()

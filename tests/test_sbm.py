@@ -47,9 +47,10 @@ def planted_files(tmp_path_factory):
 
 # ---- the case conditions, on the restatement alone -------------------------------------------------------------------------
 def _msums_of(case):
+    """the msums of the E-step and of every whole iteration a device test compares the case over"""
     ms = list(case.estep()[2])
-    if (case.n, case.K) in [(n, K) for n, K, _ in S.ITER_CASES] and case.name.endswith("plain"):
-        for m in case.iterate(3)[4]:
+    if S.iters_compared(case):
+        for m in case.iterate(S.iters_compared(case))[4]:
             ms += list(m)
     return np.array(ms)
 
@@ -72,6 +73,100 @@ def test_estep_does_not_amplify_a_perturbation(case):
     ref, rpass, _ = case.estep()
     assert npass == rpass
     np.testing.assert_allclose(got, ref, rtol=1e-9, atol=1e-200)
+
+
+@pytest.mark.parametrize("case", [c for c in S.all_cases(B) if S.iters_compared(c)], ids=lambda c: c.name)
+def test_iterations_do_not_amplify_a_perturbation(case):
+    """the same over the whole iterations the device tests compare: the same pass counts, phi, gamma and lambda within 1e-9"""
+    niter = S.iters_compared(case)
+    rng = np.random.RandomState(5)
+    phi = case.phi * (1.0 + 1e-13 * rng.uniform(-1, 1, case.phi.shape))
+    phi /= phi.sum(axis=1, keepdims=True)
+    T, Y = case.masks()
+    got = S.iterate(phi, case.gamma, case.lam, case.eta, T, Y, niter)
+    ref = case.iterate(niter)
+    assert got[3] == ref[3]
+    for g, r in zip(got[:3], ref[:3]):
+        np.testing.assert_allclose(g, r, rtol=1e-9, atol=1e-200)
+
+
+def test_the_matrix_has_both_edges_of_every_class():
+    """the (V, W) classes of K = 2 .. SBM_MAX_K by the documented rules (no device library asked): nine classes, both edges of
+    each in S.MATRIX"""
+    by = {}
+    for k in range(2, _svils.SBM_MAX_K + 1):
+        by.setdefault(((k + 63) // 64, S.row_lanes(k)), []).append(k)
+    assert sorted(by) == [(1, 2), (1, 4), (1, 8), (1, 16), (1, 32), (1, 64), (2, 64), (3, 64), (4, 64)]
+    ks = [k for k, _ in S.MATRIX]
+    assert sorted({k for v in by.values() for k in (v[0], v[-1])}) == ks
+    assert [c.n for c in S.matrix_cases()] == [S.MATRIX_N] * len(ks) and S.MATRIX_N > 7 * B
+
+
+@pytest.mark.parametrize("n,K", S.HUBS)
+def test_hub_cases_are_what_they_claim(n, K):
+    case = S.hub_case(n, K, B)
+    T, Y = case.masks()
+    hubs = S.hub_nodes(n, B)
+    assert hubs[0] == 0 and hubs[2] == n - 1 and 0 < hubs[1] % B < B - 1 and B <= hubs[1] < n - B   # mid-block, blocks on both sides
+    for h in hubs:
+        assert Y[h].sum() == n - 1 > 2 * 64                           # split_row: three trips of 64 entries
+    assert Y.sum(axis=1).max() == n - 1 and np.array_equal(Y, Y.T)
+    srow = np.flatnonzero(~T[1] & (np.arange(n) != 1))                # node 1's skip row: in hub 0's block
+    assert 1 < B and srow.shape[0] == S.HUB_SKIPS > 64
+    assert 0 < Y[1, srow].sum() < srow.shape[0]                       # both y values
+    assert (srow >= B).sum() > 64 and ((srow > 1) & (srow < B)).any()   # beyond the block (a second trip of the gather), and in it
+    assert (~T).sum() == 2 * S.HUB_SKIPS + n                          # nothing else is skipped
+    assert case.iterate(S.LOOP_ITERS)[3] == {4: [4, 10], 65: [5, 4]}[K]
+
+
+@pytest.mark.parametrize("d", S.DENSE, ids=lambda d: "n%d-k%d" % d[:2])
+def test_dense_cases_are_what_they_claim(d):
+    case = S.dense_case(*d)
+    T, Y = case.masks()
+    assert case.skip.shape[0] == d[4] == len({tuple(p) for p in case.skip.tolist()}) and np.all(case.skip[:, 0] < case.skip[:, 1])
+    y = case.y_of(case.skip)
+    assert min(y.sum(), (1 - y).sum()) > 500                          # both y values, many of each
+    assert abs(case.links.shape[0] - {260: 18900, 200: 10500}[case.n]) < 500
+    rpasses = case.iterate(S.LOOP_ITERS)[3]
+    assert rpasses == {260: [4, 3], 200: [10, 3]}[case.n]
+    assert case.iterate(S.LOOP_ITERS)[2].min() > 0.9                  # lambda stays away from 0: rtol on it means something
+
+
+@pytest.mark.parametrize("n,K,seed", S.RINGS)
+def test_ring_cases_are_what_they_claim(n, K, seed):
+    case = S.ring_case(n, K, seed)
+    assert case.links.shape == (n, 2) and np.all(case.links[:, 0] < case.links[:, 1])
+    deg = np.bincount(case.links.ravel(), minlength=n)
+    assert np.all(deg == 2)
+    sk = [tuple(p) for p in case.skip.tolist()]
+    links = {tuple(p) for p in case.links.tolist()}
+    y = np.array([p in links for p in sk])
+    assert len(set(sk)) == len(sk) and np.all(case.skip[:, 0] < case.skip[:, 1])
+    assert y.sum() == S.RING_SKIPS // 2 and 0.9 * S.RING_SKIPS // 2 <= (~y).sum() <= S.RING_SKIPS // 2
+    np.testing.assert_allclose(case.phi.sum(axis=1), 1.0, rtol=1e-12)
+
+
+@pytest.mark.parametrize("n,K,seed", [(61, 7, 1), (130, 4, 2), (61, 256, 1)])
+def test_prefix_sum_restatement_against_the_masks(n, K, seed):
+    """pair_sums_prefix, mstep_prefix and elbo_prefix (the references at sizes the masks cannot reach) against the mask-based
+    M-step and bound, at the start and after one iteration"""
+    import sbm_elbo_cases as E
+    case = S.planted_case(n, K, seed)
+    T, Y = case.masks()
+    for phi, gamma, lam in ((case.phi, case.gamma, case.lam), case.iterate(1)[:3]):
+        rgamma, rlam = S.mstep(phi, case.eta, T, Y)
+        ggamma, glam = S.mstep_prefix(phi, case.eta, case.links, case.skip)
+        np.testing.assert_allclose(ggamma, rgamma, rtol=1e-12)
+        np.testing.assert_allclose(glam, rlam, rtol=1e-12)
+        a, b, n1, n0 = S.pair_sums_prefix(phi, case.links, case.skip)
+        tri = np.triu(T, 1)
+        assert n1 == (tri & Y).sum() and n0 == (tri & ~Y).sum()
+        ref = E.elbo(phi, gamma, lam, case.eta, T, Y)
+        got = E.elbo_prefix(phi, gamma, lam, case.eta, case.links, case.skip)
+        np.testing.assert_allclose(got[1], ref[1], rtol=1e-12)        # P: addends of one sign
+        np.testing.assert_allclose(got[4], ref[4], rtol=1e-12)        # A
+        for g, r in zip(got[:4], ref[:4]):
+            assert abs(g - r) <= 1e-12 * ref[4]
 
 
 def test_restatement_split_algebra_is_not_what_it_uses():
